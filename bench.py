@@ -10,10 +10,14 @@ A "step" is one full training iteration of BASELINE.json configs[1] on every ran
 coordinated-advantage HIP reduction, 5 PPO epochs of 512-row minibatches and 5 LCF meta-update passes (the
 reference's hyper-parameters, algo_ippo.py:22-42 / algo_copo.py:66-72).  `value` = agent rows that acted,
 summed over all ranks, divided by the wall time of the K timed steps (barrier + synchronize on both sides,
-max over ranks).  Weak scaling: every rank owns 256 scenes and a 512-row minibatch; gradients / advantage
-statistics / meta gradients are all-reduced over RCCL.
+max over ranks); `ms_per_step` = that wall time / K.  Weak scaling: every rank owns 256 scenes and a 512-row
+minibatch; gradients / advantage statistics / meta gradients are all-reduced over RCCL.
 
-Extra objects on the JSON line:
+A plain run sets up, warms up, times the K steps and prints the line.  `--dump-outputs DIR` then also writes what the
+last timed step computed as DIR/<name>.npy (see dump_outputs).  `--full` adds every side measurement below (each takes
+runs of its own, on a second trainer brought to the same point when there is one process).
+
+Extra objects on the JSON line with --full:
   roofline      the simulator step kernel (the path's dominant custom kernel): algorithmic bytes
                 (202 + 4*O per present agent slot) / mean launch time measured with HIP events
                 on the launch stream, against the 8 TB/s HBM peak.  At the workload's 256 scenes a launch is one
@@ -24,7 +28,9 @@ Extra objects on the JSON line:
                 time (HIP events over the trainer's captured 16-step graphs), against the dense fp32 MFMA peak.  The step is a chain of two latency-bound launches
                 on a 512-row minibatch, not a throughput GEMM; the fraction says how far from the matrix peak that leaves it.
   cpu_baseline  the same iteration on the host: scalar C oracle simulator + oracle ops + the same torch code
-                on CPU threads ("port"), on a bounded sample.
+                on CPU threads ("port"), on a bounded sample (one process only; --no-cpu-baseline leaves it out).
+  phases        synchronised wall clock of the phases of a few extra iterations (one process only).
+  config.collective  the data-parallel gradient all-reduce alone (several ranks only).
 """
 import argparse
 import json
@@ -292,6 +298,58 @@ def _capi_build_info():
     """What the loaded libcopo_hip.so says about itself (copo_build_info: ABI, profiling mask, environment variables it reads)."""
     from copo_amd import _capi
     return _capi.lib.copo_build_info().decode("utf-8", "replace")
+
+
+DUMP_MAX_ELEMENTS = 1 << 18      # per array; larger arrays are written as a fixed sample of this many elements
+DUMP_MAX_BYTES = 64 << 20
+
+
+def _dump_array(x):
+    """float32 for fp32 / narrower data and small integers, float64 for fp64 and wide integers (exact in both cases)."""
+    a = x.detach().cpu().numpy() if torch.is_tensor(x) else np.asarray(x)
+    if a.dtype == np.float64 or (a.dtype.kind in "iu" and a.dtype.itemsize > 2):
+        a = a.astype(np.float64)
+    else:
+        a = a.astype(np.float32)
+    if a.size > DUMP_MAX_ELEMENTS:      # seeded by the size alone: the same elements in every run
+        pick = np.sort(np.random.RandomState(0).choice(a.size, DUMP_MAX_ELEMENTS, replace=False))
+        a = a.reshape(-1)[pick]
+    return a
+
+
+def dump_outputs(trainer, res, out_dir):
+    """`--dump-outputs DIR`: what the last timed `train()` computed, as DIR/<name>.npy --
+      result.<path>   every number of its result dict (learner statistics, LCF meta update, episode metrics, counters),
+                      wall-clock times left out;
+      weights.<name>  the policy's parameters after the step (policy / value nets, LCF parameters);
+      batch.<name>    the step's rollout batch after postprocess (observations, actions, rewards, advantages, targets, ...).
+    The inputs are seeded (scenes, policy population, torch seed), so that two builds given the same arguments can be
+    compared array for array.  Returns the number of bytes written."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {}
+
+    def walk(prefix, d):
+        for k in sorted(d):
+            v = d[k]
+            if k == "timers" or k.endswith(("_s", "_ms")):      # wall-clock times
+                continue
+            if isinstance(v, dict):
+                walk(prefix + k + ".", v)
+            elif isinstance(v, (bool, int, float, np.integer, np.floating)) or (torch.is_tensor(v) and v.numel() == 1):
+                arrays[prefix + k] = np.asarray(float(v), np.float64)
+    walk("result.", res)
+    for k, v in trainer.policy.model.state_dict().items():
+        arrays["weights." + k] = _dump_array(v)
+    batch = trainer._last_batch
+    for k in sorted(batch.keys()):
+        v = batch[k]
+        if not k.startswith("_") and torch.is_tensor(v):
+            arrays["batch." + k] = _dump_array(v)
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_MAX_BYTES, "outputs of %d bytes exceed the %d-byte bound" % (total, DUMP_MAX_BYTES)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name.replace("/", "_") + ".npy"), a)
+    return total
 
 
 def cpu_baseline(num_envs, num_agents, iters=1):
@@ -573,6 +631,109 @@ def cpu_sim_only(num_agents, threads, scenes_per_thread=16, steps=40):
     return sum(counts) / dt
 
 
+def side_measurements(line, trainer, args, world, warm):
+    """`--full`, rank 0, after the timed steps: the simulator-kernel and learner rooflines, the phases and the CPU baselines,
+    added to `line`."""
+    side = trainer
+    if world == 1:
+        side = make_trainer(args.num_envs, args.num_agents, graphs=not args.no_graphs, pretrained=not args.untrained)
+        for _ in range(warm):
+            side.train()
+        torch.cuda.synchronize()
+    sim = side.env.sim
+    k_s, present = measure_sim_kernel(side)
+    bytes_per_unit = 202 + 4 * sim.O
+    achieved = present * bytes_per_unit / k_s * 1e-9
+    # HBM bytes per launch from the PMC counters are taken in a separate rocprofv3 pass (scripts/sim_traffic.sh writes
+    # profiles/sim_traffic.json); quoted only if that pass ran on exactly this kernel source
+    traffic, traffic_units = None, None
+    tfile = os.path.join(ROOT, "profiles", "sim_traffic.json")
+    if os.path.exists(tfile):
+        tj = json.load(open(tfile))
+        if tj.get("kernel_source_sha1") == kernel_source_hash():
+            traffic = tj.get("bytes_per_launch")
+            traffic_units = tj.get("units_per_launch")        # present slots of the launches the counters saw
+    # VALU roofline of the saturated launch (the kernel is bound by the vector ALUs' issue rate, not by HBM): wave-level VALU
+    # instructions per launch from the PMC pass of scripts/prof_sim_round.sh (profiles/sim_valu.json, same source-hash rule)
+    valu = None
+    vfile = os.path.join(ROOT, "profiles", "sim_valu.json")
+    if os.path.exists(vfile):
+        vj = json.load(open(vfile))
+        if vj.get("kernel_source_sha1") == kernel_source_hash() and vj.get("valu_wave_instructions_per_launch"):
+            valu = vj
+    learner = None     # (after `phases`: it walks the trainer's SGD plan tables)
+    sat_s, sat_present, sat_slots = measure_sim_kernel_saturated(side, policy="cruise")
+    rnd_s, rnd_present, _ = measure_sim_kernel_saturated(side, policy="random")
+    line["roofline"] = {
+        "bound": "hbm", "kernel": "copo::sim_step_kernel", "achieved": round(achieved, 2),
+        "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBPS, 5),
+        "traffic": traffic, "traffic_units_per_launch": traffic_units,
+        "us_per_launch": round(k_s * 1e6, 2),
+        "units_per_launch": round(present, 1), "bytes_per_unit": bytes_per_unit,
+        "neighbour_lists": measure_sim_kernel.lists,
+        "state": "the trainer's own scenes and policy: actions of 200 env steps recorded closed-loop, scenes put "
+                 "back, actions replayed (timed loop = simulator launches only); `traffic` = PMC FETCH_SIZE + "
+                 "WRITE_SIZE per launch from rocprofv3 passes over `bench.py --roofline-only` (the same replay), "
+                 "with the present slots those launches had",
+        "saturated": {"scenes": sat_slots // sim.N, "actions": "lane-keeping controller (recorded, replayed)",
+                      "us_per_launch": round(sat_s * 1e6, 1),
+                      "present_slots": round(sat_present), "slots_stepped": sat_slots,
+                      "achieved": round(sat_present * bytes_per_unit / sat_s * 1e-9, 1),
+                      "frac": round(sat_present * bytes_per_unit / sat_s * 1e-9 / HBM_PEAK_GBPS, 4),
+                      "random_actions": {"us_per_launch": round(rnd_s * 1e6, 1), "present_slots": round(rnd_present),
+                                         "frac": round(rnd_present * bytes_per_unit / rnd_s * 1e-9 / HBM_PEAK_GBPS, 4)}},
+        "timing": "HIP events around back-to-back launches on the launch stream; rocprofv3 --kernel-trace reports "
+                  "~10 % longer per-kernel durations at 16 384 scenes because traced dispatches do not overlap "
+                  "the previous launch's drain with their own ramp-up",
+        "library_build": _capi_build_info()}
+    if valu is not None:
+        # peak: 1024 SIMDs x 2.4 GHz / 4 cycles per wave64 VALU instruction (MI355X_MICROARCH.md); issued: this launch's
+        # instructions / its duration measured live above
+        issued = valu["valu_wave_instructions_per_launch"] / sat_s * 1e-9
+        line["roofline"]["valu"] = {
+            "bound": "valu-issue", "issued": round(issued, 1), "peak": VALU_PEAK_GINST, "unit": "G wave-instructions/s",
+            "frac": round(issued / VALU_PEAK_GINST, 4),
+            "instructions_per_launch": round(valu["valu_wave_instructions_per_launch"]),
+            "instructions_per_present_slot": round(valu["valu_wave_instructions_per_launch"] * 64 / max(sat_present, 1.0), 1),
+            "what": "copo::sim_step_kernel on %d populated scenes: SQ_INSTS_VALU per launch (profiles/sim_valu.json, rocprofv3 --pmc on "
+                    "`bench.py --saturated-only`) / the launch time measured here; `instructions_per_present_slot` counts lane-"
+                    "instructions (x 64).  The HBM fraction of this launch can only rise by deleting instructions" % valu["scenes"]}
+    if world == 1:
+        line["phases"] = measure_phases(side)
+    learner = measure_learner_step(side)
+    if learner is not None:
+        l_s, l_flops = learner
+        line["learner_roofline"] = {
+            "bound": "mfma", "kernel": "copo::rowpass_kernel + copo::wgrad_adam_kernel (one 512-row SGD step, 4 nets)",
+            "achieved": round(l_flops / l_s * 1e-12, 2), "peak": MFMA_F32_PEAK_TFLOPS, "unit": "TFLOP/s",
+            "frac": round(l_flops / l_s * 1e-12 / MFMA_F32_PEAK_TFLOPS, 4), "traffic": None,
+            "us_per_step": round(l_s * 1e6, 2), "flops_per_step": int(l_flops)}
+    if side is not trainer:
+        side.stop()
+    if world == 1 and not args.no_cpu_baseline:
+        v, cdt, n, used = cpu_baseline(args.num_envs, args.num_agents)
+        host = os.cpu_count() or 1
+        va, adt, an, aw, at, asplit = cpu_baseline_all_cores(args.num_envs, args.num_agents)
+        sim1 = cpu_sim_only(args.num_agents, 1)
+        simn = cpu_sim_only(args.num_agents, host)
+        line["cpu_baseline"] = {"value": round(v, 1), "unit": "agent-steps/s", "cores": used, "kind": "port",
+                                "sample": "1 iteration of the same workload on a steady-state population (%d agent-steps, "
+                                          "%.1f s): scalar C oracle simulator on 1 thread + the build's torch learner on %d "
+                                          "CPU threads (host has %d)" % (n, cdt, used, host),
+                                "all_cores": {"value": round(va, 1), "unit": "agent-steps/s", "sim_threads": aw, "learner_threads": at,
+                                              "sample": "the same iteration (%d agent-steps, %.1f s): one C oracle instance per host thread "
+                                                        "for the scenes, batched torch inference, torch learner at its fastest thread "
+                                                        "count for 512-row minibatches (candidates 4, 8, 16, 32, 64 threads, 8 kept unless another is 15 %% faster; "
+                                                        "per-candidate times in split.learner_thread_sweep_ms_per_step)" % (an, adt),
+                                              "split": asplit},
+                                "sim_only": {"threads_1": round(sim1, 1), "threads_%d" % host: round(simn, 1),
+                                             "unit": "agent-steps/s, simulator half alone (C oracle, one instance per thread)"},
+                                "live_reference": live_reference(),
+                                "recorded_reference": {"value": 1500.0, "unit": "agent-steps/s",
+                                                       "what": "the reference itself: MetaDrive + RLlib on 4 rollout workers, 60 env-steps/s "
+                                                               "(BASELINE.md; cited, not re-measured: MetaDrive and Ray are not installable here)"}}
+
+
 def _free_port():
     import socket
     s = socket.socket()
@@ -654,7 +815,12 @@ def main():
     ap.add_argument("--mb-per-rank", type=int, default=512,
                     help="rows per SGD minibatch and rank (512 = the reference's sgd_minibatch_size; 1024 halves the data-parallel steps of an "
                          "iteration at 1.73 x the step time, DESIGN.md section 6 -- recorded in config.sgd_minibatch_size_per_rank)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, every side measurement too: simulator-kernel and learner rooflines, phases, the "
+                         "collective alone (several ranks), the CPU baselines (one process)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baselines out")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32 / float64, at most 64 MB)")
     ap.add_argument("--untrained", action="store_true",
                     help="random-init policy net instead of the reference's published population (the scenes then empty during the run)")
     ap.add_argument("--roofline-only", action="store_true",
@@ -672,6 +838,8 @@ def main():
                     help="start the ranks of --gpus N, let them meet over gloo on the host and print the head of the line: "
                          "checks the launcher where there is no GPU")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     global MB_PER_RANK
     MB_PER_RANK = int(args.mb_per_rank)
 
@@ -748,8 +916,11 @@ def main():
     agent_steps = trainer._counters["num_agent_steps_sampled"] - a0      # already summed over ranks
     value = agent_steps / dt
 
+    if args.dump_outputs and rank == 0:
+        dump_outputs(trainer, res, args.dump_outputs)
+
     coll = None
-    if world > 1:
+    if args.full and world > 1:
         # what the data-parallel step adds: one all-reduce of the flat gradient bucket per SGD minibatch (every rank takes
         # part; HIP events on this rank's stream, barrier-separated from the timed region above)
         fz = trainer.policy.fused
@@ -786,40 +957,7 @@ def main():
 
     line = None
     if rank == 0:
-        # Side measurements refer to the state the timed region STARTED from: training moves the policy (the value nets start
-        # untrained, their advantages perturb the loaded driver) and with it the population, so with one process a second trainer
-        # is built with the same seed and brought to the same point (`warm` iterations); several ranks keep the trainer they
-        # have (building one on rank 0 alone would leave the other ranks' collectives without a partner)
-        side = trainer
-        if world == 1:
-            side = make_trainer(args.num_envs, args.num_agents, graphs=not args.no_graphs, pretrained=not args.untrained)
-            for _ in range(warm):
-                side.train()
-            torch.cuda.synchronize()
-        sim = side.env.sim
-        k_s, present = measure_sim_kernel(side)
-        bytes_per_unit = 202 + 4 * sim.O
-        achieved = present * bytes_per_unit / k_s * 1e-9
-        # HBM bytes per launch from the PMC counters are taken in a separate rocprofv3 pass (scripts/sim_traffic.sh writes
-        # profiles/sim_traffic.json); quoted only if that pass ran on exactly this kernel source
-        traffic, traffic_units = None, None
-        tfile = os.path.join(ROOT, "profiles", "sim_traffic.json")
-        if os.path.exists(tfile):
-            tj = json.load(open(tfile))
-            if tj.get("kernel_source_sha1") == kernel_source_hash():
-                traffic = tj.get("bytes_per_launch")
-                traffic_units = tj.get("units_per_launch")        # present slots of the launches the counters saw
-        # VALU roofline of the saturated launch (the kernel is bound by the vector ALUs' issue rate, not by HBM): wave-level VALU
-        # instructions per launch from the PMC pass of scripts/prof_sim_round.sh (profiles/sim_valu.json, same source-hash rule)
-        valu = None
-        vfile = os.path.join(ROOT, "profiles", "sim_valu.json")
-        if os.path.exists(vfile):
-            vj = json.load(open(vfile))
-            if vj.get("kernel_source_sha1") == kernel_source_hash() and vj.get("valu_wave_instructions_per_launch"):
-                valu = vj
-        learner = None     # (after `phases`: it walks the trainer's SGD plan tables)
-        sat_s, sat_present, sat_slots = measure_sim_kernel_saturated(side, policy="cruise")
-        rnd_s, rnd_present, _ = measure_sim_kernel_saturated(side, policy="random")
+        sim = trainer.env.sim
         line = {
             "metric": "agent-env-steps/sec (sim+learn), Intersection 40-agent", "value": round(value, 1),
             "unit": "agent-steps/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -842,76 +980,11 @@ def main():
                        "dp_step": getattr(trainer.policy, "_dp_mode", None),
                        "dp_step_reason": getattr(trainer.policy, "dp_reason", None)},
             "data_parallel": data_parallel,
-            "roofline": {"bound": "hbm", "kernel": "copo::sim_step_kernel", "achieved": round(achieved, 2),
-                         "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBPS, 5),
-                         "traffic": traffic, "traffic_units_per_launch": traffic_units,
-                         "us_per_launch": round(k_s * 1e6, 2),
-                         "units_per_launch": round(present, 1), "bytes_per_unit": bytes_per_unit,
-                         "neighbour_lists": measure_sim_kernel.lists,
-                         "state": "the trainer's own scenes and policy: actions of 200 env steps recorded closed-loop, scenes put "
-                                  "back, actions replayed (timed loop = simulator launches only); `traffic` = PMC FETCH_SIZE + "
-                                  "WRITE_SIZE per launch from rocprofv3 passes over `bench.py --roofline-only` (the same replay), "
-                                  "with the present slots those launches had",
-                         "saturated": {"scenes": sat_slots // sim.N, "actions": "lane-keeping controller (recorded, replayed)",
-                                       "us_per_launch": round(sat_s * 1e6, 1),
-                                       "present_slots": round(sat_present), "slots_stepped": sat_slots,
-                                       "achieved": round(sat_present * bytes_per_unit / sat_s * 1e-9, 1),
-                                       "frac": round(sat_present * bytes_per_unit / sat_s * 1e-9 / HBM_PEAK_GBPS, 4),
-                                       "random_actions": {"us_per_launch": round(rnd_s * 1e6, 1), "present_slots": round(rnd_present),
-                                                          "frac": round(rnd_present * bytes_per_unit / rnd_s * 1e-9 / HBM_PEAK_GBPS, 4)}},
-                         "timing": "HIP events around back-to-back launches on the launch stream; rocprofv3 --kernel-trace reports "
-                                   "~10 % longer per-kernel durations at 16 384 scenes because traced dispatches do not overlap "
-                                   "the previous launch's drain with their own ramp-up",
-                         "library_build": _capi_build_info()},
         }
-        if valu is not None:
-            # peak: 1024 SIMDs x 2.4 GHz / 4 cycles per wave64 VALU instruction (MI355X_MICROARCH.md); issued: this launch's
-            # instructions / its duration measured live above
-            issued = valu["valu_wave_instructions_per_launch"] / sat_s * 1e-9
-            line["roofline"]["valu"] = {
-                "bound": "valu-issue", "issued": round(issued, 1), "peak": VALU_PEAK_GINST, "unit": "G wave-instructions/s",
-                "frac": round(issued / VALU_PEAK_GINST, 4),
-                "instructions_per_launch": round(valu["valu_wave_instructions_per_launch"]),
-                "instructions_per_present_slot": round(valu["valu_wave_instructions_per_launch"] * 64 / max(sat_present, 1.0), 1),
-                "what": "copo::sim_step_kernel on %d populated scenes: SQ_INSTS_VALU per launch (profiles/sim_valu.json, rocprofv3 --pmc on "
-                        "`bench.py --saturated-only`) / the launch time measured here; `instructions_per_present_slot` counts lane-"
-                        "instructions (x 64).  The HBM fraction of this launch can only rise by deleting instructions" % valu["scenes"]}
-        if world == 1:
-            line["phases"] = measure_phases(side)
-        learner = measure_learner_step(side)
-        if learner is not None:
-            l_s, l_flops = learner
-            line["learner_roofline"] = {
-                "bound": "mfma", "kernel": "copo::rowpass_kernel + copo::wgrad_adam_kernel (one 512-row SGD step, 4 nets)",
-                "achieved": round(l_flops / l_s * 1e-12, 2), "peak": MFMA_F32_PEAK_TFLOPS, "unit": "TFLOP/s",
-                "frac": round(l_flops / l_s * 1e-12 / MFMA_F32_PEAK_TFLOPS, 4), "traffic": None,
-                "us_per_step": round(l_s * 1e6, 2), "flops_per_step": int(l_flops)}
         if coll is not None:
             line["config"]["collective"] = coll
-        if side is not trainer:
-            side.stop()
-        if world == 1 and not args.no_cpu_baseline:
-            v, cdt, n, used = cpu_baseline(args.num_envs, args.num_agents)
-            host = os.cpu_count() or 1
-            va, adt, an, aw, at, asplit = cpu_baseline_all_cores(args.num_envs, args.num_agents)
-            sim1 = cpu_sim_only(args.num_agents, 1)
-            simn = cpu_sim_only(args.num_agents, host)
-            line["cpu_baseline"] = {"value": round(v, 1), "unit": "agent-steps/s", "cores": used, "kind": "port",
-                                    "sample": "1 iteration of the same workload on a steady-state population (%d agent-steps, "
-                                              "%.1f s): scalar C oracle simulator on 1 thread + the build's torch learner on %d "
-                                              "CPU threads (host has %d)" % (n, cdt, used, host),
-                                    "all_cores": {"value": round(va, 1), "unit": "agent-steps/s", "sim_threads": aw, "learner_threads": at,
-                                                  "sample": "the same iteration (%d agent-steps, %.1f s): one C oracle instance per host thread "
-                                                            "for the scenes, batched torch inference, torch learner at its fastest thread "
-                                                            "count for 512-row minibatches (candidates 4, 8, 16, 32, 64 threads, 8 kept unless another is 15 %% faster; "
-                                                            "per-candidate times in split.learner_thread_sweep_ms_per_step)" % (an, adt),
-                                                  "split": asplit},
-                                    "sim_only": {"threads_1": round(sim1, 1), "threads_%d" % host: round(simn, 1),
-                                                 "unit": "agent-steps/s, simulator half alone (C oracle, one instance per thread)"},
-                                    "live_reference": live_reference(),
-                                    "recorded_reference": {"value": 1500.0, "unit": "agent-steps/s",
-                                                           "what": "the reference itself: MetaDrive + RLlib on 4 rollout workers, 60 env-steps/s "
-                                                                   "(BASELINE.md; cited, not re-measured: MetaDrive and Ray are not installable here)"}}
+        if args.full:
+            side_measurements(line, trainer, args, world, warm)
     trainer.stop()
     if rank == 0:
         # libraries that write through C stdio (RCCL's start-up banner) sit in a buffer when stdout is a pipe and would

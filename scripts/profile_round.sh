@@ -5,9 +5,9 @@ TAG=$1
 ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOT/gpurun_out/profile_$TAG
 mkdir -p $OUT; cd /tmp; export TMPDIR=/tmp
-python $ROOT/bench.py --steps 10 --warmup 5 > $OUT/bench_plain.json 2> $OUT/bench_plain.err
-rocprofv3 --kernel-trace --stats -d $OUT/trace -o trace -- python $ROOT/bench.py --steps 10 --warmup 5 --no-cpu-baseline > $OUT/bench_traced.json 2> $OUT/trace.err
-{ echo "# rocprofv3 --kernel-trace --stats -- python bench.py --steps 10 --warmup 5 --no-cpu-baseline"; echo "# bench line (traced run):"; tail -n 1 $OUT/bench_traced.json; echo "# bench line (plain run):"; tail -n 1 $OUT/bench_plain.json; python $ROOT/scripts/top_kernels.py $OUT/trace/trace_results.db 30; } > $OUT/kernel_stats.txt
+python $ROOT/bench.py --full --steps 10 --warmup 5 > $OUT/bench_plain.json 2> $OUT/bench_plain.err
+rocprofv3 --kernel-trace --stats -d $OUT/trace -o trace -- python $ROOT/bench.py --full --steps 10 --warmup 5 --no-cpu-baseline > $OUT/bench_traced.json 2> $OUT/trace.err
+{ echo "# rocprofv3 --kernel-trace --stats -- python bench.py --full --steps 10 --warmup 5 --no-cpu-baseline"; echo "# bench line (traced run):"; tail -n 1 $OUT/bench_traced.json; echo "# bench line (plain run):"; tail -n 1 $OUT/bench_plain.json; python $ROOT/scripts/top_kernels.py $OUT/trace/trace_results.db 30; } > $OUT/kernel_stats.txt
 for ctr in FETCH_SIZE WRITE_SIZE; do
   rocprofv3 --kernel-trace --pmc $ctr -d $OUT/pmc_$ctr -o pmc -- python $ROOT/scripts/bench_sim.py --E 256 --blocks 1024 > $OUT/pmc_$ctr.log 2>&1
 done

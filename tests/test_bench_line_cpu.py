@@ -87,3 +87,25 @@ def test_bench_refuses_to_run_on_fewer_gpus_than_asked():
     r = _run_bench("--gpus", "8", "--steps", "1", "--warmup", "0",
                    env=dict(RANK="0", LOCAL_RANK="0", WORLD_SIZE="1", MASTER_ADDR="127.0.0.1", MASTER_PORT="29599"))
     assert r.returncode != 0 and "WORLD_SIZE=1" in r.stderr, (r.returncode, r.stderr[-500:])
+
+
+def test_dump_arrays_are_float_and_a_fixed_sample():
+    """`--dump-outputs` writes float32 / float64 only, exact for the integer and fp64 data of a step, and an array above the
+    per-array bound as the same seeded sample of elements in every run."""
+    import sys
+    sys.path.insert(0, ROOT)
+    import numpy as np
+    import torch
+    import bench
+    assert bench._dump_array(torch.arange(5, dtype=torch.uint8)).dtype == np.float32
+    assert bench._dump_array(torch.arange(5, dtype=torch.int64)).dtype == np.float64
+    assert bench._dump_array(torch.ones(3, dtype=torch.float64)).dtype == np.float64
+    x = torch.arange(bench.DUMP_MAX_ELEMENTS + 1000, dtype=torch.float32)
+    a, b = bench._dump_array(x), bench._dump_array(x.clone())
+    assert a.dtype == np.float32 and a.size == bench.DUMP_MAX_ELEMENTS and np.array_equal(a, b)
+    assert np.all(np.diff(a) > 0)            # sorted picks of distinct elements
+
+
+def test_bench_refuses_zero_steps():
+    r = _run_bench("--gpus", "1", "--steps", "0")
+    assert r.returncode != 0 and "--steps" in r.stderr

@@ -59,7 +59,7 @@ def test_dense_postprocess_vs_reference(golden_dir, kind, fuse):
 
 @pytest.mark.parametrize("algo,extra", [("ippo", {}), ("ccppo", dict(fuse_mode="mf")), ("ccppo", dict(fuse_mode="concat")),
                                         ("copo", {}), ("copo", dict(use_fused_learner=False, use_hip_graphs=False))])
-def test_trainers_run_and_report(algo, extra):
+def test_trainers_run_and_report(algo, extra, tmp_path):
     from copo_amd.torch_copo.algo_ccppo import CCPPOTrainer, get_ccppo_env
     from copo_amd.torch_copo.algo_copo import CoPOTrainer
     from copo_amd.torch_copo.algo_ippo import IPPOTrainer
@@ -91,7 +91,7 @@ def test_trainers_run_and_report(algo, extra):
         assert abs(a.env.current_lcf_mean - mu["lcf"]) < 1e-9        # pushed to the envs (algo_copo.py:608-611)
         tgt, cur = a.policy.target_model.state_dict(), a.policy.model.state_dict()
         assert all(torch.equal(tgt[k], cur[k]) for k in cur)          # update_old_policy
-    path = a.save_checkpoint("/tmp/copo_ckpt_test")
+    path = a.save_checkpoint(str(tmp_path / "ckpt"))
     w0 = {k: v.clone() for k, v in a.policy.model.state_dict().items()}
     fz = a.policy.fused
     adam0 = None if fz is None else (fz.adam_m.clone(), fz.adam_v.clone(), fz.step_count.clone())
@@ -655,8 +655,8 @@ def test_bench_harness_with_two_ranks_on_one_gpu():
     for rank in range(2):
         env = dict(os.environ, RANK=str(rank), LOCAL_RANK="0", WORLD_SIZE="2", MASTER_ADDR="127.0.0.1", MASTER_PORT="29571",
                    COPO_DIST_BACKEND="gloo", COPO_FORCE_DIST="0")
-        procs.append(subprocess.Popen([sys.executable, "bench.py", "--gpus", "2", "--steps", "2", "--warmup", "1", "--num-envs", "32"],
-                                      env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, cwd=root))
+        procs.append(subprocess.Popen([sys.executable, "bench.py", "--gpus", "2", "--steps", "2", "--warmup", "1", "--num-envs", "32",
+                                       "--full"], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, cwd=root))
     outs = [p.communicate(timeout=900) for p in procs]
     for p, (so, se) in zip(procs, outs):
         assert p.returncode == 0, se[-3000:]
@@ -691,6 +691,38 @@ def test_bench_gpus_2_as_one_command_on_a_shared_device():
     assert d["n_gpus"] == 2 and d["config"]["parallelism"] == "dp2" and d["scaling"] == "weak"
     per_rank_iter = d["config"]["agent_steps_per_iter"]
     assert abs(d["value"] * d["ms_per_step"] * 1e-3 - 2 * per_rank_iter) <= 1e-3 * 2 * per_rank_iter
+
+
+@pytest.mark.timeout(900)
+def test_bench_plain_run_dumps_its_last_step(tmp_path):
+    """A plain `bench.py` run prints the headline line only (no side measurement) and `--dump-outputs DIR` writes what the last
+    timed step computed: result numbers, policy weights and the rollout batch, float32 / float64, at most 64 MB."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+    out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1", "--num-envs", "32",
+                        "--dump-outputs", str(out)], env=env, cwd=root, capture_output=True, text=True, timeout=800)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d["steps"] == 3 and d["higher_is_better"] is True and d["dtype"] == "f32" and d["unit"] == "agent-steps/s"
+    assert abs(d["value"] * d["ms_per_step"] * 1e-3 - d["config"]["agent_steps_per_iter"]) <= 1e-3 * d["config"]["agent_steps_per_iter"]
+    for k in ("roofline", "learner_roofline", "phases", "cpu_baseline"):
+        assert k not in d, k
+    files = sorted(os.listdir(out))
+    total = 0
+    for f in files:
+        a = np.load(out / f)
+        assert f.endswith(".npy") and a.dtype in (np.float32, np.float64), (f, a.dtype)
+        total += a.nbytes
+    assert total <= 64 << 20
+    for want in ("result.info.learner.default.learner_stats.total_loss.npy", "batch.obs.npy", "weights.lcf_parameters.npy"):
+        assert want in files, (want, files[:40])
+    assert not [f for f in files if f.startswith("result.") and f.endswith(("_s.npy", "_ms.npy"))]      # no wall-clock times
 
 
 
