@@ -7,7 +7,12 @@
 #include <algorithm>
 #include <vector>
 
+#include <array>
+#include <cmath>
+#include <set>
+
 #include "sim_common.h"
+#include "render_common.h"
 
 using namespace copo;
 
@@ -38,6 +43,10 @@ struct copo_sim {
     float lcf_host[4];         // {mean, std, capacity, 0}: what the kernels read from p.lcf_dist
     bool lcf_dirty;
     std::vector<void*> allocs;
+    // host copies of the map tables for copo_render_create: road records [n_routes][seg_rows][COPO_SEG_STRIDE], route_meta,
+    // lane lines (on the device only when a detector reads them) and static boxes
+    std::vector<float> h_segs, h_meta, h_lines, h_boxes;
+    bool boxes_hidden;
 };
 
 extern "C" int copo_version(void) { return COPO_ABI_VERSION; }
@@ -265,6 +274,11 @@ extern "C" int copo_sim_create(const copo_sim_cfg* cfg, int device, copo_sim** o
             memcpy(compact.data() + (size_t)r * rows * COPO_SEG_STRIDE,
                    cfg->route_segs + (size_t)r * (COPO_MAX_SEGS + 1) * COPO_SEG_STRIDE, sizeof(float) * rows * COPO_SEG_STRIDE);
         rc = upload(s, compact.data(), compact.size(), &p.route_segs);
+        s->h_segs = std::move(compact);
+        s->h_meta.assign(cfg->route_meta, cfg->route_meta + (size_t)cfg->n_routes * 4);
+        if (cfg->n_lines > 0 && cfg->lines) s->h_lines.assign(cfg->lines, cfg->lines + (size_t)cfg->n_lines * COPO_LINE_STRIDE);
+        if (cfg->n_boxes > 0) s->h_boxes.assign(cfg->boxes, cfg->boxes + (size_t)cfg->n_boxes * COPO_BOX_STRIDE);
+        s->boxes_hidden = cfg->boxes_hidden != 0;
     }
     if (rc == COPO_OK) rc = upload(s, cfg->route_meta, (size_t)cfg->n_routes * 4, &p.route_meta);
     if (rc == COPO_OK) rc = upload(s, cfg->spawn_tab, (size_t)cfg->n_spawns * 4, &p.spawn_tab);
@@ -528,5 +542,167 @@ extern "C" int copo_lcf_mix_apply_f32(const float* mixed, const float* glob_adv,
     if (B < 0) return fail(COPO_ERR_DIM, "copo_lcf_mix_apply_f32: B=%lld", (long long)B);
     if (B == 0) return COPO_OK;
     HIP_TRY(launch_lcf_mix_apply(mixed, glob_adv, valid, B, stats, norm_adv, glob_adv_std, static_cast<hipStream_t>(stream)));
+    return COPO_OK;
+}
+
+// ---- top-down renderer (render_kernels.hip) ----------------------------------------------------------------
+
+struct copo_render {
+    copo_sim* sim;
+    int W, H, cap, head, count;
+    int n_roads, n_lines;
+    uint32_t box_rgba;
+    const float* roads;        // [n_roads][RENDER_ROAD_STRIDE] deduplicated road records + world boxes
+    const float* lines;        // [n_lines][RENDER_LINE_STRIDE]
+    const uint32_t* palette;   // [12]
+    int32_t* ring;             // [cap][RENDER_RING_FIELDS][E][N]
+    int32_t* ring_ep;          // [cap][E]
+    std::vector<void*> allocs;
+};
+
+static void free_render(copo_render* r) {
+    for (void* a : r->allocs) (void)hipFree(a);
+    delete r;
+}
+
+template <typename T>
+static int render_upload(copo_render* r, const T* host, size_t count, const T** dev) {
+    void* d = nullptr;
+    HIP_TRY(hipMalloc(&d, count ? count * sizeof(T) : sizeof(T)));
+    r->allocs.push_back(d);
+    if (count && host) HIP_TRY(hipMemcpy(d, host, count * sizeof(T), hipMemcpyHostToDevice));
+    else HIP_TRY(hipMemset(d, 0, count ? count * sizeof(T) : sizeof(T)));      // (no host table: zeros)
+    *dev = static_cast<const T*>(d);
+    return COPO_OK;
+}
+
+// world box {x0, x1, y0, y1} of the points at lateral offsets lat0 and lat1 (left +) of a straight or arc of `len` metres starting at
+// (x0, y0) with heading (c, s) and curvature kap; sampled finely enough that 0.5 m of padding covers the chords
+static void prim_box(double x0, double y0, double c, double s, double len, double kap, double lat0, double lat1, float* bb) {
+    double lo_x = 1e30, hi_x = -1e30, lo_y = 1e30, hi_y = -1e30;
+    const int n = 129;
+    for (int k = 0; k < n; ++k) {
+        const double sl = len * k / (n - 1), a = kap * sl;
+        double px, py, hc, hs;
+        if (kap == 0.0) {
+            px = x0 + c * sl; py = y0 + s * sl; hc = c; hs = s;
+        } else {
+            const double r = 1.0 / kap;       // signed
+            hc = c * std::cos(a) - s * std::sin(a);
+            hs = s * std::cos(a) + c * std::sin(a);
+            px = x0 + r * (hs - s); py = y0 - r * (hc - c);
+        }
+        for (double lat : {lat0, lat1}) {
+            const double qx = px - hs * lat, qy = py + hc * lat;
+            lo_x = std::min(lo_x, qx); hi_x = std::max(hi_x, qx); lo_y = std::min(lo_y, qy); hi_y = std::max(hi_y, qy);
+        }
+    }
+    bb[0] = (float)(lo_x - 0.5); bb[1] = (float)(hi_x + 0.5); bb[2] = (float)(lo_y - 0.5); bb[3] = (float)(hi_y + 0.5);
+}
+
+extern "C" int copo_render_create(copo_sim* sim, int32_t width, int32_t height, int32_t trail, const uint8_t* palette_rgb,
+                                  copo_render** out) {
+    if (!sim || !palette_rgb || !out) return fail(COPO_ERR_NULL, "copo_render_create: NULL argument");
+    *out = nullptr;
+    if (width < 1 || width > RENDER_MAX_SIZE || height < 1 || height > RENDER_MAX_SIZE || trail < 0 || trail > RENDER_MAX_TRAIL)
+        return fail(COPO_ERR_DIM, "copo_render_create: %d x %d pixels (1..%d each), trail %d (0..%d)", width, height, RENDER_MAX_SIZE,
+                    trail, RENDER_MAX_TRAIL);
+    HIP_TRY(hipSetDevice(sim->device));
+    copo_render* r = new (std::nothrow) copo_render();
+    if (!r) return fail(COPO_ERR_DEVICE, "out of host memory");
+    r->sim = sim; r->W = width; r->H = height; r->cap = trail; r->head = 0; r->count = 0;
+    const SimParams& p = sim->p;
+    const double w = p.lane_width;
+    // road records of every route, deduplicated on the fields the road rule reads (routes share their roads)
+    std::vector<float> roads;
+    std::set<std::array<float, 10>> seen;
+    for (int q = 0; q < p.n_routes; ++q) {
+        const int nseg = (int)sim->h_meta[(size_t)q * 4 + 1];
+        for (int k = 0; k < nseg; ++k) {
+            const float* g = sim->h_segs.data() + ((size_t)q * p.seg_rows + k) * COPO_SEG_STRIDE;
+            const std::array<float, 10> key = {g[0], g[1], g[2], g[3], g[4], g[5], floorf(g[COPO_SEG_LANES]), g[12], g[14], g[15]};
+            if (!seen.insert(key).second) continue;
+            const size_t o = roads.size();
+            roads.resize(o + RENDER_ROAD_STRIDE);
+            std::copy(g, g + COPO_SEG_STRIDE, roads.begin() + o);
+            const double lanes = std::floor((double)g[COPO_SEG_LANES]);
+            const double funnel = (g[5] == 0.0f && g[12] != 0.0f) ? std::fabs((double)g[14]) : 0.0;
+            prim_box(g[0], g[1], g[2], g[3], g[4], g[5], 0.5 * w, -((lanes - 0.5) * w + funnel), roads.data() + o + 16);
+        }
+    }
+    std::vector<float> lines;
+    const int nl = (int)(sim->h_lines.size() / COPO_LINE_STRIDE);
+    for (int k = 0; k < nl; ++k) {
+        const float* L = sim->h_lines.data() + (size_t)k * COPO_LINE_STRIDE;
+        const size_t o = lines.size();
+        lines.resize(o + RENDER_LINE_STRIDE);
+        std::copy(L, L + COPO_LINE_STRIDE, lines.begin() + o);
+        prim_box(L[1], L[2], L[3], L[4], L[5], L[6], 0.0, 0.0, lines.data() + o + 12);
+    }
+    uint32_t pal[12];
+    for (int k = 0; k < 12; ++k)
+        pal[k] = (uint32_t)palette_rgb[3 * k] | ((uint32_t)palette_rgb[3 * k + 1] << 8) | ((uint32_t)palette_rgb[3 * k + 2] << 16) | 0xff000000u;
+    r->n_roads = (int)(roads.size() / RENDER_ROAD_STRIDE);
+    r->n_lines = nl;
+    r->box_rgba = sim->boxes_hidden ? (190u | (150u << 8) | (110u << 16) | 0xff000000u) : (120u | (80u << 8) | (50u << 16) | 0xff000000u);
+    const size_t EN = (size_t)p.E * p.N;
+    const int32_t* ring = nullptr;
+    const int32_t* ring_ep = nullptr;
+    int rc = render_upload(r, roads.data(), roads.size(), &r->roads);
+    if (rc == COPO_OK) rc = render_upload(r, lines.data(), lines.size(), &r->lines);
+    if (rc == COPO_OK) rc = render_upload(r, pal, 12, &r->palette);
+    if (rc == COPO_OK) rc = render_upload<int32_t>(r, nullptr, (size_t)std::max(trail, 1) * RENDER_RING_FIELDS * EN, &ring);
+    if (rc == COPO_OK) rc = render_upload<int32_t>(r, nullptr, (size_t)std::max(trail, 1) * p.E, &ring_ep);
+    if (rc != COPO_OK) {
+        free_render(r);
+        return rc;
+    }
+    r->ring = const_cast<int32_t*>(ring);
+    r->ring_ep = const_cast<int32_t*>(ring_ep);
+    *out = r;
+    return COPO_OK;
+}
+
+extern "C" int copo_render_destroy(copo_render* r) {
+    if (!r) return fail(COPO_ERR_NULL, "copo_render_destroy: NULL handle");
+    (void)hipSetDevice(r->sim->device);
+    free_render(r);
+    return COPO_OK;
+}
+
+extern "C" int copo_render_record(copo_render* r, void* stream) {
+    if (!r) return fail(COPO_ERR_NULL, "copo_render_record: NULL handle");
+    if (r->cap == 0) return COPO_OK;
+    const SimParams& p = r->sim->p;
+    HIP_TRY(launch_render_record(p.state, p.env, p.E, p.N, r->ring, r->ring_ep, r->head, static_cast<hipStream_t>(stream)));
+    r->head = (r->head + 1) % r->cap;
+    r->count = std::min(r->count + 1, r->cap);
+    return COPO_OK;
+}
+
+extern "C" int copo_render_clear(copo_render* r, void* stream) {
+    (void)stream;
+    if (!r) return fail(COPO_ERR_NULL, "copo_render_clear: NULL handle");
+    r->head = 0;
+    r->count = 0;
+    return COPO_OK;
+}
+
+extern "C" int copo_render_frames(copo_render* r, const int32_t* scenes, int32_t S, const float* views, int32_t trail, uint32_t* rgba,
+                                  void* stream) {
+    if (!r || !scenes || !views || !rgba) return fail(COPO_ERR_NULL, "copo_render_frames: NULL argument");
+    const SimParams& p = r->sim->p;
+    if (S < 1 || S > p.E) return fail(COPO_ERR_DIM, "copo_render_frames: S=%d scenes (1..%d)", S, p.E);
+    if (trail < 0 || trail > r->cap) return fail(COPO_ERR_DIM, "copo_render_frames: trail=%d (0..%d, the capacity at create)", trail, r->cap);
+    RenderArgs a;
+    a.state = p.state; a.env = p.env; a.E = p.E; a.N = p.N;
+    a.roads = r->roads; a.lines = r->lines; a.boxes = p.boxes;
+    a.n_roads = r->n_roads; a.n_lines = r->n_lines; a.n_boxes = p.n_boxes;
+    a.box_rgba = r->box_rgba; a.palette = r->palette;
+    a.ring = r->ring; a.ring_ep = r->ring_ep; a.cap = r->cap; a.head = r->head;
+    a.K = trail; a.Kd = std::min(trail, r->count);
+    a.hl = p.hl; a.hw = p.hw; a.lane_w = p.lane_width;
+    a.scenes = scenes; a.views = views; a.S = S; a.W = r->W; a.H = r->H; a.out = rgba;
+    HIP_TRY(launch_render_frames(a, static_cast<hipStream_t>(stream)));
     return COPO_OK;
 }

@@ -19,11 +19,10 @@ _SCENES = {"round": ("MultiAgentRoundaboutEnv", 40), "inter": ("MultiAgentInters
 
 def get_make_env(env, wrap_with_svo_env=False, render=False):
     """`make_env()` for one of "round" / "inter" / "parking" / "bottle" / "tollgate".  `wrap_with_svo_env` selects the LCF
-    env (the torch reference's successor of the SVO env) so that the observation carries the LCF column; rendering does
-    not exist in this build."""
+    env (the torch reference's successor of the SVO env) so that the observation carries the LCF column.  `render=True`:
+    every step also renders one top-down frame (`env.render(mode="top_down", num_stack=25)`) into the list `env.frames`."""
     if env not in _SCENES:
         raise ValueError()
-    assert not render, "no renderer in this build"
     cls_name, n = _SCENES[env]
 
     def make_env(env_id=None):
@@ -31,9 +30,32 @@ def get_make_env(env, wrap_with_svo_env=False, render=False):
         cls = getattr(W, cls_name)
         if wrap_with_svo_env:
             cls = W.get_lcf_env(cls)
-        return RecorderEnv(cls(dict(num_agents=n, crash_done=True)))
+        e = RecorderEnv(cls(dict(num_agents=n, crash_done=True)))
+        return _RenderingEnv(e) if render else e
 
     return make_env
+
+
+class _RenderingEnv:
+    """A wrapped env that renders one top-down frame per step into `frames` (numpy uint8 [H, W, 3] each)."""
+
+    def __init__(self, env):
+        self.env = env
+        self.frames = []
+
+    def __getattr__(self, name):
+        return getattr(self.env, name)
+
+    def reset(self, *args, **kwargs):
+        return self.env.reset(*args, **kwargs)
+
+    def step(self, *args, **kwargs):
+        out = self.env.step(*args, **kwargs)
+        self.frames.append(self.env.render(mode="top_down", num_stack=25))
+        return out
+
+    def close(self):
+        return self.env.close()
 
 
 def evaluate_once(model_name, make_env, num_episodes=10, use_distributional_svo=False, suffix="", auto_add_svo_to_obs=True,

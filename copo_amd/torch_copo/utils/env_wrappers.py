@@ -137,10 +137,47 @@ class MultiAgentMetaDrive:
 
     # ---- vector API ----------------------------------------------------------------------------------------
     def vec_reset(self, seeds=None):
-        return self.sim.reset(seeds)
+        out = self.sim.reset(seeds)
+        self._restart_trail()
+        return out
 
     def vec_step(self, actions):
-        return self.sim.step(actions)
+        out = self.sim.step(actions)
+        self._record_trail()
+        return out
+
+    # ---- top-down rendering (copo/vis.py: env.render(mode="top_down", num_stack=25)) ------------------------------------------
+    def render(self, mode="top_down", num_stack=25, film_size=(512, 512), track_agent=None, **kwargs):
+        """numpy uint8 [H, W, 3] top-down frame of scene 0 (`film_size` = (width, height)): the whole map, or centred on agent
+        `track_agent` ("agent3") at 0.2 m per pixel while that agent drives.  The last `num_stack - 1` recorded poses are drawn as
+        a fading trail (at most 32).  The renderer is created on the first call -- trails start there -- and from then on
+        every step records a snapshot; an env that never renders does no rendering work."""
+        if mode != "top_down":
+            raise NotImplementedError("only mode='top_down' is built (no 3D renderer)")
+        from copo_amd.render import MAX_TRAIL, TopDownRenderer, to_numpy_rgb
+        W, H = int(film_size[0]), int(film_size[1])
+        r = getattr(self, "_renderer", None)
+        if r is None or (r.W, r.H) != (W, H):
+            if r is not None:
+                r.close()
+            self._renderer = r = TopDownRenderer(self.sim, W, H, trail=MAX_TRAIL)
+            r.record()
+        trail = max(0, min(int(num_stack) - 1, MAX_TRAIL))
+        ids = self._slot_ids or []
+        if track_agent is not None and track_agent in ids:
+            f = r.frames(scenes=[0], view="follow", follow_slot=ids.index(track_agent), trail=trail)
+        else:
+            f = r.frames(scenes=[0], view="map", trail=trail)
+        return to_numpy_rgb(f)[0]
+
+    def _record_trail(self):
+        if getattr(self, "_renderer", None) is not None:
+            self._renderer.record()
+
+    def _restart_trail(self):
+        if getattr(self, "_renderer", None) is not None:
+            self._renderer.clear()
+            self._renderer.record()
 
     def set_lcf_dist(self, mean, std):
         assert self.ENABLE_LCF, "set_lcf_dist needs an LCF env (get_lcf_env)"
@@ -184,6 +221,7 @@ class MultiAgentMetaDrive:
         assert self.num_envs == 1, "the dict API serves one scene; use vec_reset/vec_step for num_envs > 1"
         seed = self.config.get("start_seed", 5000) if force_seed is None else force_seed
         out = self.sim.reset(np.array([seed], np.uint64))
+        self._restart_trail()
         ids = self._ids(out)
         self._slot_ids = ["agent%d" % a for a in ids]
         self._just_terminated = {}
@@ -202,6 +240,7 @@ class MultiAgentMetaDrive:
             if a is not None:
                 act[0, s] = np.asarray(actions[a], np.float32)[:self.sim.A]
         out = self.sim.step(torch.from_numpy(act).to(self.sim.device))
+        self._record_trail()
         h = {k: v[0].cpu().numpy() for k, v in out.items() if v is not None}
         flags = h["flags"]
         env_reset = bool((flags & F.F_ENV_RESET).any())
@@ -277,6 +316,9 @@ class MultiAgentMetaDrive:
         return o, r, d, i
 
     def close(self):
+        if getattr(self, "_renderer", None) is not None:
+            self._renderer.close()
+            self._renderer = None
         self.sim.close()
 
 

@@ -273,6 +273,24 @@ int copo_sim_set_chunk(copo_sim* sim, int32_t fans);
  * (NULL switches it off; results of the step do not depend on it); row [7]: which formulation of the neighbour lists ran */
 int copo_sim_set_debug(copo_sim* sim, int64_t* stamps);
 
+/* ---- top-down renderer: the reference's env.render(mode="top_down", num_stack=25) (copo/vis.py), drawn from the simulator's own
+ *      device state.  A handle reads its simulator's state and map tables and must be destroyed before it.
+ * Pixel (row i from the top = north, column j) of a view {cx, cy, m metres per pixel} is the world point
+ * (cx + (j + 0.5 - W/2) m, cy - (i + 0.5 - H/2) m); layers in paint order: background, road surface (the step kernel's lateral road
+ * rule), lane lines, static boxes, the trail of the last `trail` snapshots, vehicles.  Pixels are packed RGBA8
+ * words (R in the low byte). ---- */
+typedef struct copo_render copo_render;
+/* width, height 1..4096; trail = snapshot capacity 0..32; palette_rgb: HOST [12][3], the vehicle colours by agent id % 12 */
+int copo_render_create(copo_sim* sim, int32_t width, int32_t height, int32_t trail, const uint8_t* palette_rgb, copo_render** out);
+/* push every slot's current pose, status and agent id and each scene's episode counter into the trail ring */
+int copo_render_record(copo_render* r, void* stream);
+/* empty the trail ring (after a manual reset or set_state) */
+int copo_render_clear(copo_render* r, void* stream);
+/* scenes: device [S] indices into 0..E-1 (not checked on the device), 1 <= S <= E; views: device [S][3]; trail 0..capacity; rgba:
+ * device [S][H][W] */
+int copo_render_frames(copo_render* r, const int32_t* scenes, int32_t S, const float* views, int32_t trail, uint32_t* rgba, void* stream);
+int copo_render_destroy(copo_render* r);
+
 /* ---- stateless ops ---- */
 
 /* CCEnv._update_distance_map + _find_in_range (env_wrappers.py:125-158) + LCFEnv reward block (:313-326).
