@@ -58,6 +58,11 @@ class PpoCfg(C.Structure):
     ]
 
 
+class InteractCfg(C.Structure):
+    """Mirror of `copo_interact_cfg`."""
+    _fields_ = [("horizon_s", C.c_float), ("ttc_crit_s", C.c_float), ("gap_near_m", C.c_float), ("brake_mps2", C.c_float)]
+
+
 HEAD_PPO, HEAD_META_NEW, HEAD_META_OLD = 0, 1, 2
 OPERAND_F32, OPERAND_BF16 = 0, 1
 PPO_STATS = 8
@@ -122,6 +127,11 @@ _SIGS = {
     "copo_render_clear": (C.c_int, [C.c_void_p, C.c_void_p]),
     "copo_render_frames": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     "copo_render_destroy": (C.c_int, [C.c_void_p]),
+    "copo_interact_create": (C.c_int, [C.c_void_p, C.POINTER(InteractCfg), C.POINTER(C.c_void_p)]),
+    "copo_interact_record": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "copo_interact_totals": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
+    "copo_interact_reset": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "copo_interact_destroy": (C.c_int, [C.c_void_p]),
     "copo_neighbours_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_float,
                                       C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                       C.c_void_p, C.c_void_p]),

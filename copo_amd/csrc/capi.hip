@@ -13,6 +13,7 @@
 
 #include "sim_common.h"
 #include "render_common.h"
+#include "interact_common.h"
 
 using namespace copo;
 
@@ -705,4 +706,96 @@ extern "C" int copo_render_frames(copo_render* r, const int32_t* scenes, int32_t
     a.scenes = scenes; a.views = views; a.S = S; a.W = r->W; a.H = r->H; a.out = rgba;
     HIP_TRY(launch_render_frames(a, static_cast<hipStream_t>(stream)));
     return COPO_OK;
+}
+
+// ---- interaction meter (interact_kernels.hip) ----------------------------------------------------------------
+
+struct copo_interact {
+    copo_sim* sim;
+    copo_interact_cfg cfg;
+    int32_t* acc;              // [INTERACT_ACC_WORDS][E][N]
+    double* tit;               // [E][N]
+    long long* counts;         // [E][INTERACT_COUNTS]
+    double* sums;              // [E][INTERACT_SUMS]
+    size_t acc_bytes, tit_bytes, counts_bytes, sums_bytes;
+};
+
+static void free_interact(copo_interact* h) {
+    for (void* a : {(void*)h->acc, (void*)h->tit, (void*)h->counts, (void*)h->sums})
+        if (a) (void)hipFree(a);
+    delete h;
+}
+
+static InteractArgs interact_args(const copo_interact* h) {
+    const SimParams& p = h->sim->p;
+    InteractArgs a;
+    a.state = p.state; a.env = p.env; a.E = p.E; a.N = p.N;
+    a.hl = p.hl; a.hw = p.hw; a.dt = p.dt;
+    a.horizon_s = h->cfg.horizon_s; a.ttc_crit_s = h->cfg.ttc_crit_s; a.gap_near_m = h->cfg.gap_near_m; a.brake_mps2 = h->cfg.brake_mps2;
+    a.acc = h->acc; a.tit = h->tit; a.counts = h->counts; a.sums = h->sums;
+    return a;
+}
+
+static int interact_clear(copo_interact* h, hipStream_t stream) {
+    HIP_TRY(hipMemsetAsync(h->acc, 0, h->acc_bytes, stream));
+    HIP_TRY(hipMemsetAsync(h->tit, 0, h->tit_bytes, stream));
+    HIP_TRY(hipMemsetAsync(h->counts, 0, h->counts_bytes, stream));
+    HIP_TRY(hipMemsetAsync(h->sums, 0, h->sums_bytes, stream));
+    return COPO_OK;
+}
+
+extern "C" int copo_interact_create(copo_sim* sim, const copo_interact_cfg* cfg, copo_interact** out) {
+    if (!sim || !cfg || !out) return fail(COPO_ERR_NULL, "copo_interact_create: NULL argument");
+    *out = nullptr;
+    if (!(cfg->horizon_s > 0.0f) || !(cfg->brake_mps2 > 0.0f) || !(cfg->ttc_crit_s >= 0.0f) || !(cfg->gap_near_m >= 0.0f) ||
+        !std::isfinite(cfg->horizon_s) || !std::isfinite(cfg->brake_mps2) || !std::isfinite(cfg->ttc_crit_s) || !std::isfinite(cfg->gap_near_m))
+        return fail(COPO_ERR_CONFIG, "copo_interact_create: horizon_s=%g brake_mps2=%g (> 0), ttc_crit_s=%g gap_near_m=%g (>= 0), all finite",
+                    (double)cfg->horizon_s, (double)cfg->brake_mps2, (double)cfg->ttc_crit_s, (double)cfg->gap_near_m);
+    HIP_TRY(hipSetDevice(sim->device));
+    copo_interact* h = new (std::nothrow) copo_interact();
+    if (!h) return fail(COPO_ERR_DEVICE, "out of host memory");
+    h->sim = sim; h->cfg = *cfg;
+    const size_t E = (size_t)sim->p.E, EN = E * sim->p.N;
+    h->acc_bytes = (size_t)INTERACT_ACC_WORDS * EN * sizeof(int32_t); h->tit_bytes = EN * sizeof(double);
+    h->counts_bytes = E * INTERACT_COUNTS * sizeof(long long); h->sums_bytes = E * INTERACT_SUMS * sizeof(double);
+    hipError_t err = hipMalloc((void**)&h->acc, h->acc_bytes);
+    if (err == hipSuccess) err = hipMalloc((void**)&h->tit, h->tit_bytes);
+    if (err == hipSuccess) err = hipMalloc((void**)&h->counts, h->counts_bytes);
+    if (err == hipSuccess) err = hipMalloc((void**)&h->sums, h->sums_bytes);
+    if (err == hipSuccess) err = hipMemset(h->acc, 0, h->acc_bytes);
+    if (err == hipSuccess) err = hipMemset(h->tit, 0, h->tit_bytes);
+    if (err == hipSuccess) err = hipMemset(h->counts, 0, h->counts_bytes);
+    if (err == hipSuccess) err = hipMemset(h->sums, 0, h->sums_bytes);
+    if (err != hipSuccess) {
+        free_interact(h);
+        return fail(COPO_ERR_DEVICE, "copo_interact_create: %s", hipGetErrorString(err));
+    }
+    *out = h;
+    return COPO_OK;
+}
+
+extern "C" int copo_interact_destroy(copo_interact* h) {
+    if (!h) return fail(COPO_ERR_NULL, "copo_interact_destroy: NULL handle");
+    (void)hipSetDevice(h->sim->device);
+    free_interact(h);
+    return COPO_OK;
+}
+
+extern "C" int copo_interact_record(copo_interact* h, float* gap, float* ttc, void* stream) {
+    if (!h) return fail(COPO_ERR_NULL, "copo_interact_record: NULL handle");
+    HIP_TRY(launch_interact_record(interact_args(h), gap, ttc, static_cast<hipStream_t>(stream)));
+    return COPO_OK;
+}
+
+extern "C" int copo_interact_totals(copo_interact* h, int64_t* counts_i64, double* sums_f64, int32_t flush_open, void* stream) {
+    if (!h || !counts_i64 || !sums_f64) return fail(COPO_ERR_NULL, "copo_interact_totals: NULL argument");
+    if (flush_open != 0 && flush_open != 1) return fail(COPO_ERR_DIM, "copo_interact_totals: flush_open=%d (0 or 1)", flush_open);
+    HIP_TRY(launch_interact_totals(interact_args(h), reinterpret_cast<long long*>(counts_i64), sums_f64, flush_open,
+                                   static_cast<hipStream_t>(stream)));
+    return COPO_OK;
+}
+
+extern "C" int copo_interact_reset(copo_interact* h, void* stream) {
+    if (!h) return fail(COPO_ERR_NULL, "copo_interact_reset: NULL handle");
+    return interact_clear(h, static_cast<hipStream_t>(stream));
 }

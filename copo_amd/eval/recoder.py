@@ -3,7 +3,8 @@
 `reset() / step(dict)` surface -- here `get_lcf_env(MultiAgent*Env)` & co. of `copo_amd.torch_copo.utils.env_wrappers` --
 and turns the info stream into the per-episode evaluation row of `eval/evaluate_population.py` (success / crash / out rates,
 velocity / energy step means, episode reward / cost / length statistics, neighbour counts, the agent-level SVO estimate).
-Host-side bookkeeping only; nothing here touches the device.
+Host-side bookkeeping only; nothing here touches the device.  When the wrapped env measures interactions (`interaction_metrics`), the episode row
+also carries its `interaction_*` columns (copo_amd/interact.py).
 """
 import math
 from collections import defaultdict
@@ -227,4 +228,7 @@ class RecorderEnv:
         ret["svo_estimate_deg_mean"], ret["svo_estimate_deg_min"] = np.mean(svos), np.min(svos)
         ret["svo_estimate_deg_max"] = np.max(svos)
         ret["svo_reward"] = np.sum(svo_rewards) / n
+        if getattr(self.unwrapped, "_meter", None) is not None:      # env config `interaction_metrics`: the agents that ended since reset()
+            for k, v in self.unwrapped.interaction_summary().items():
+                ret["interaction_" + k] = v
         return ret

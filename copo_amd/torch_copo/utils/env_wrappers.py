@@ -62,7 +62,7 @@ class MultiAgentMetaDrive:
     @classmethod
     def default_config(cls):
         return dict(map=cls.MAP, num_envs=1, num_agents=None, start_seed=5000, horizon=1000, num_lasers=72,
-                    device=0, crash_done=True, out_of_road_done=True, allow_respawn=True, delay_done=25)
+                    device=0, crash_done=True, out_of_road_done=True, allow_respawn=True, delay_done=25, interaction_metrics=False)
 
     def __init__(self, config=None):
         cfg = type(self).default_config()
@@ -85,6 +85,10 @@ class MultiAgentMetaDrive:
             self.sim_config.nbr_k = max(1, self.sim_config.resolved()[1] - 1)
         self.sim = VecSim(self.sim_config, device=int(cfg.get("device", 0) or 0))
         self.num_envs, self.num_agents = self.sim.E, self.sim.N
+        self._meter = None         # `interaction_metrics`: gaps, time to collision, near misses of every step (copo_amd/interact.py)
+        if cfg.get("interaction_metrics", False):
+            from copo_amd.interact import InteractionMeter
+            self._meter = InteractionMeter(self.sim)
         self._slot_ids = None      # dict API state (num_envs == 1)
         self._next_obs = None
         self.current_lcf_mean, self.current_lcf_std = self.sim_config.lcf_mean, self.sim_config.lcf_std
@@ -139,11 +143,13 @@ class MultiAgentMetaDrive:
     def vec_reset(self, seeds=None):
         out = self.sim.reset(seeds)
         self._restart_trail()
+        self._restart_interaction()
         return out
 
     def vec_step(self, actions):
         out = self.sim.step(actions)
         self._record_trail()
+        self._record_interaction()
         return out
 
     # ---- top-down rendering (copo/vis.py: env.render(mode="top_down", num_stack=25)) ------------------------------------------
@@ -178,6 +184,21 @@ class MultiAgentMetaDrive:
         if getattr(self, "_renderer", None) is not None:
             self._renderer.clear()
             self._renderer.record()
+
+    # ---- interaction metrics (config key `interaction_metrics`): one measurement of the state after reset and after every step ----
+    def _record_interaction(self):
+        if self._meter is not None:
+            self._meter.record()
+
+    def _restart_interaction(self):
+        if self._meter is not None:
+            self._meter.reset()
+            self._meter.record()
+
+    def interaction_summary(self, flush_open=False):
+        """`InteractionMeter.summary` over the agents that ended since the last reset (`flush_open`: and those still driving)."""
+        assert self._meter is not None, "set interaction_metrics=True in the env config"
+        return self._meter.summary(flush_open)
 
     def set_lcf_dist(self, mean, std):
         assert self.ENABLE_LCF, "set_lcf_dist needs an LCF env (get_lcf_env)"
@@ -222,6 +243,7 @@ class MultiAgentMetaDrive:
         seed = self.config.get("start_seed", 5000) if force_seed is None else force_seed
         out = self.sim.reset(np.array([seed], np.uint64))
         self._restart_trail()
+        self._restart_interaction()
         ids = self._ids(out)
         self._slot_ids = ["agent%d" % a for a in ids]
         self._just_terminated = {}
@@ -241,7 +263,10 @@ class MultiAgentMetaDrive:
                 act[0, s] = np.asarray(actions[a], np.float32)[:self.sim.A]
         out = self.sim.step(torch.from_numpy(act).to(self.sim.device))
         self._record_trail()
+        self._record_interaction()
         h = {k: v[0].cpu().numpy() for k, v in out.items() if v is not None}
+        if self._meter is not None:      # of the state after the step: +inf for an agent that ended in it
+            h["min_gap"], h["ttc"] = self._meter.gap[0].cpu().numpy(), self._meter.ttc[0].cpu().numpy()
         flags = h["flags"]
         env_reset = bool((flags & F.F_ENV_RESET).any())
         self._episode_over = False
@@ -279,6 +304,8 @@ class MultiAgentMetaDrive:
             self._episode_energy[a] = self._episode_energy.get(a, 0.0) + e_step
             info.update(step_energy=e_step, episode_energy=self._episode_energy[a],
                         raw_action=np.asarray(actions.get(a, (0.0, 0.0)), np.float32)[:2].copy())
+            if self._meter is not None:      # (a slot whose agent ended may already hold the next one: that one's figures are not this agent's)
+                info.update(min_gap=math.inf if d[a] else float(h["min_gap"][s]), ttc=math.inf if d[a] else float(h["ttc"][s]))
             if self.ENABLE_LCF:
                 lcf, nei_r = float(h["lcf"][s]), float(h["nei_rew"][s])
                 coord = math.cos(lcf * math.pi / 2) * r[a] + math.sin(lcf * math.pi / 2) * nei_r
@@ -319,6 +346,9 @@ class MultiAgentMetaDrive:
         if getattr(self, "_renderer", None) is not None:
             self._renderer.close()
             self._renderer = None
+        if getattr(self, "_meter", None) is not None:
+            self._meter.close()
+            self._meter = None
         self.sim.close()
 
 

@@ -2,10 +2,13 @@
 top-down frames written to disk.
 
     python -m copo_amd.vis --env inter --algo copo --weights FILE.npz [--key copo_inter] --steps 300 --out DIR [--gif] [--follow SLOT]
+                           [--interaction]
 
 `--weights` is a population file (`{ALGO}_{ENV}.npz` with the reference's key layout); `--key NAME` takes the arrays stored under
 `NAME/w/` of a bundle instead.  One PPM per step (`DIR/frame_00000.ppm`, ...), plus `DIR/vis.gif` with `--gif` (needs Pillow).
-At the end of every scene episode the reference's summary dict is printed.
+At the end of every scene episode the reference's summary dict is printed; with `--interaction` the interaction metrics of that
+episode's agents (gaps, time to collision, near misses, harsh braking: copo_amd/interact.py) are printed next to it, and those of all
+agents of the run, finished or not, at the end.
 """
 import argparse
 import os
@@ -35,18 +38,18 @@ def load_policy(algo, env, weights_path, key=None):
     return pf
 
 
-def make_env(env):
+def make_env(env, interaction=False):
     from copo_amd.torch_copo.utils import env_wrappers as W
     cls_name, n = _SCENES[env]
-    return getattr(W, cls_name)(dict(num_agents=n))
+    return getattr(W, cls_name)(dict(num_agents=n, interaction_metrics=bool(interaction)))
 
 
-def run(env_name, algo, weights, steps, out, key=None, gif=False, follow=None, film_size=(512, 512), seed=0, fps=10):
+def run(env_name, algo, weights, steps, out, key=None, gif=False, follow=None, film_size=(512, 512), seed=0, fps=10, interaction=False):
     """Roll `steps` env steps, writing one frame per step; returns the list of frame paths."""
     from copo_amd.render import write_gif, write_ppm
     np.random.seed(seed)
     policy = load_policy(algo, env_name, weights, key)
-    env = make_env(env_name)
+    env = make_env(env_name, interaction)
     paths, kept = [], []
     try:
         o, d = env.reset(), {"__all__": False}
@@ -60,7 +63,8 @@ def run(env_name, algo, weights, steps, out, key=None, gif=False, follow=None, f
                     ep_agent += 1
             if d["__all__"]:
                 print({"total agents": ep_agent, "existing agents": len(o),
-                       "success rate": ep_success / ep_agent if ep_agent > 0 else None, "ep step": ep_step})
+                       "success rate": ep_success / ep_agent if ep_agent > 0 else None, "ep step": ep_step},
+                      *([{"interaction": env.interaction_summary()}] if interaction else []))
                 ep_success = ep_step = ep_agent = 0
                 o, d = env.reset(), {"__all__": False}
                 policy.reset()
@@ -70,6 +74,8 @@ def run(env_name, algo, weights, steps, out, key=None, gif=False, follow=None, f
             paths += write_ppm(frame, out, start=t)
             if gif:
                 kept.append(frame)
+        if interaction:
+            print({"interaction, agents still driving included": env.interaction_summary(flush_open=True)})
     finally:
         env.close()
     if gif and kept:
@@ -89,8 +95,10 @@ def main(argv=None):
     ap.add_argument("--follow", type=int, default=None, help="centre the view on this agent slot")
     ap.add_argument("--size", type=int, nargs=2, default=(512, 512), metavar=("W", "H"))
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--interaction", action="store_true", help="measure and print the interaction metrics")
     a = ap.parse_args(argv)
-    paths = run(a.env, a.algo, a.weights, a.steps, a.out, key=a.key, gif=a.gif, follow=a.follow, film_size=tuple(a.size), seed=a.seed)
+    paths = run(a.env, a.algo, a.weights, a.steps, a.out, key=a.key, gif=a.gif, follow=a.follow, film_size=tuple(a.size), seed=a.seed,
+                interaction=a.interaction)
     print("wrote %d frames to %s" % (len(paths), a.out))
 
 

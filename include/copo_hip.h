@@ -291,6 +291,33 @@ int copo_render_clear(copo_render* r, void* stream);
 int copo_render_frames(copo_render* r, const int32_t* scenes, int32_t S, const float* views, int32_t trail, uint32_t* rgba, void* stream);
 int copo_render_destroy(copo_render* r);
 
+/* ---- interaction meter: surrogate safety measures of the driving agents, computed from the simulator's own device state (DESIGN.md
+ *      section 8b).  A handle reads its simulator's state and must be destroyed before it.
+ * Bodies are the rectangles veh_half_len x veh_half_wid of the ALIVE (velocity speed x heading) and WRECK (velocity 0) slots of a scene;
+ * static boxes take no part.  Per ALIVE slot and record, over the other bodies of its scene: gap = 0 when the rectangles overlap, else
+ * the smallest of the eight vertex-to-rectangle distances; TTC = first time of overlap under constant velocities and fixed headings
+ * (swept separating axes), +inf beyond horizon_s or when the pair never meets.  Per agent (slot + agent id + episode counter) the
+ * meter accumulates steps, minimum gap, minimum TTC, steps with TTC < ttc_crit_s (tet), sum of (ttc_crit_s - TTC) dt over them (tit),
+ * entries into the near state (TTC < ttc_crit_s or gap < gap_near_m) and steps that follow a record of the same agent with
+ * (previous speed - speed) / dt > brake_mps2; an agent that left its slot is folded into the scene totals by the next record. ---- */
+typedef struct copo_interact_cfg {
+    float horizon_s, ttc_crit_s, gap_near_m, brake_mps2;
+} copo_interact_cfg;
+typedef struct copo_interact copo_interact;
+/* horizon_s, brake_mps2 > 0 and ttc_crit_s, gap_near_m >= 0, all finite (COPO_ERR_CONFIG otherwise); every accumulator starts empty */
+int copo_interact_create(copo_sim* sim, const copo_interact_cfg* cfg, copo_interact** out);
+/* measure the current state: gap, ttc device [E][N] fp32 (+inf for a slot that is not ALIVE or has no partner), either may be NULL;
+ * updates the accumulators and totals.  One launch, no allocation, no host synchronisation. */
+int copo_interact_record(copo_interact* h, float* gap, float* ttc, void* stream);
+/* counts_i64: device [E][6] = {agents, steps, tet steps, near events, brake events, agents with a finite minimum TTC}; sums_f64: device
+ * [E][3] = {sum of minimum gaps (+inf once an agent never had a partner), sum of the finite minimum TTCs, sum of tit}, over the agents
+ * folded so far, added up in slot order (reproducible bit for bit).  flush_open = 1: as if every agent still driving ended now
+ * (the accumulators themselves are left as they are). */
+int copo_interact_totals(copo_interact* h, int64_t* counts_i64, double* sums_f64, int32_t flush_open, void* stream);
+/* empty every accumulator and the totals (after a manual reset or set_state) */
+int copo_interact_reset(copo_interact* h, void* stream);
+int copo_interact_destroy(copo_interact* h);
+
 /* ---- stateless ops ---- */
 
 /* CCEnv._update_distance_map + _find_in_range (env_wrappers.py:125-158) + LCFEnv reward block (:313-326).
