@@ -63,6 +63,14 @@ class InteractCfg(C.Structure):
     _fields_ = [("horizon_s", C.c_float), ("ttc_crit_s", C.c_float), ("gap_near_m", C.c_float), ("brake_mps2", C.c_float)]
 
 
+class ClipCfg(C.Structure):
+    """Mirror of `copo_clip_cfg`."""
+    _fields_ = [("pre", C.c_int32), ("post", C.c_int32), ("max_clips", C.c_int32), ("flag_mask", C.c_uint32), ("ttc_below", C.c_float),
+                ("gap_below", C.c_float)]
+
+
+CLIP_MAX_CAP, CLIP_WORDS, CLIP_HEADER = 256, 6, 8
+
 HEAD_PPO, HEAD_META_NEW, HEAD_META_OLD = 0, 1, 2
 OPERAND_F32, OPERAND_BF16 = 0, 1
 PPO_STATS = 8
@@ -132,6 +140,14 @@ _SIGS = {
     "copo_interact_totals": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
     "copo_interact_reset": (C.c_int, [C.c_void_p, C.c_void_p]),
     "copo_interact_destroy": (C.c_int, [C.c_void_p]),
+    "copo_clip_create": (C.c_int, [C.c_void_p, C.POINTER(ClipCfg), C.POINTER(C.c_void_p)]),
+    "copo_clip_record": (C.c_int, [C.c_void_p] * 5),
+    "copo_clip_flush": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "copo_clip_count": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_void_p]),
+    "copo_clip_read": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "copo_clip_reset": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "copo_clip_destroy": (C.c_int, [C.c_void_p]),
+    "copo_clip_scatter": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
     "copo_neighbours_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_float,
                                       C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                       C.c_void_p, C.c_void_p]),

@@ -14,6 +14,7 @@
 #include "sim_common.h"
 #include "render_common.h"
 #include "interact_common.h"
+#include "clip_common.h"
 
 using namespace copo;
 
@@ -798,4 +799,153 @@ extern "C" int copo_interact_totals(copo_interact* h, int64_t* counts_i64, doubl
 extern "C" int copo_interact_reset(copo_interact* h, void* stream) {
     if (!h) return fail(COPO_ERR_NULL, "copo_interact_reset: NULL handle");
     return interact_clear(h, static_cast<hipStream_t>(stream));
+}
+
+// ---- event clips (clip_kernels.hip) ----------------------------------------------------------------------------
+
+struct copo_clip {
+    copo_sim* sim;
+    copo_clip_cfg cfg;
+    int32_t cap;
+    uint32_t *ring, *pool;
+    int32_t *ring_env, *scene, *ready, *cid, *counters, *pool_env, *header;
+    size_t ring_bytes, ring_env_bytes, scene_bytes, ready_bytes, pool_bytes, pool_env_bytes, header_bytes;
+};
+
+static void free_clip(copo_clip* h) {
+    for (void* a : {(void*)h->ring, (void*)h->pool, (void*)h->ring_env, (void*)h->scene, (void*)h->ready, (void*)h->cid, (void*)h->counters,
+                    (void*)h->pool_env, (void*)h->header})
+        if (a) (void)hipFree(a);
+    delete h;
+}
+
+static ClipArgs clip_args(const copo_clip* h) {
+    const SimParams& p = h->sim->p;
+    ClipArgs a;
+    a.state = p.state; a.env = p.env; a.E = p.E; a.N = p.N;
+    a.pre = h->cfg.pre; a.post = h->cfg.post; a.cap = h->cap; a.max_clips = h->cfg.max_clips;
+    a.flag_mask = h->cfg.flag_mask; a.ttc_below = h->cfg.ttc_below; a.gap_below = h->cfg.gap_below;
+    a.ring = h->ring; a.ring_env = h->ring_env; a.scene = h->scene; a.ready = h->ready; a.cid = h->cid; a.counters = h->counters;
+    a.pool = h->pool; a.pool_env = h->pool_env; a.header = h->header;
+    return a;
+}
+
+// idle state machines, no clip, record 0; the pool is zeroed so that frames beyond a clip's length read 0 (the ring needs no clearing:
+// a clip never reaches back beyond the records made since)
+static int clip_clear(copo_clip* h, hipStream_t stream) {
+    HIP_TRY(hipMemsetAsync(h->scene, 0, h->scene_bytes, stream));
+    HIP_TRY(hipMemsetAsync(h->ready, 0, h->ready_bytes, stream));
+    HIP_TRY(hipMemsetAsync(h->cid, 0, h->ready_bytes, stream));
+    HIP_TRY(hipMemsetAsync(h->counters, 0, CLIP_COUNTERS * sizeof(int32_t), stream));
+    HIP_TRY(hipMemsetAsync(h->pool, 0, h->pool_bytes, stream));
+    HIP_TRY(hipMemsetAsync(h->pool_env, 0, h->pool_env_bytes, stream));
+    HIP_TRY(hipMemsetAsync(h->header, 0, h->header_bytes, stream));
+    return COPO_OK;
+}
+
+extern "C" int copo_clip_create(copo_sim* sim, const copo_clip_cfg* cfg, copo_clip** out) {
+    if (!sim || !cfg || !out) return fail(COPO_ERR_NULL, "copo_clip_create: NULL argument");
+    *out = nullptr;
+    if (cfg->pre < 0 || cfg->post < 0 || cfg->pre > COPO_CLIP_MAX_CAP || cfg->post > COPO_CLIP_MAX_CAP || cfg->pre + cfg->post + 1 > COPO_CLIP_MAX_CAP)
+        return fail(COPO_ERR_DIM, "copo_clip_create: pre=%d post=%d (>= 0, pre + post + 1 <= %d)", cfg->pre, cfg->post, COPO_CLIP_MAX_CAP);
+    if (cfg->max_clips < 1) return fail(COPO_ERR_DIM, "copo_clip_create: max_clips=%d (>= 1)", cfg->max_clips);
+    if (!(cfg->ttc_below >= 0.0f) || !(cfg->gap_below >= 0.0f) || !std::isfinite(cfg->ttc_below) || !std::isfinite(cfg->gap_below) ||
+        cfg->flag_mask > 0xffu)
+        return fail(COPO_ERR_CONFIG, "copo_clip_create: ttc_below=%g gap_below=%g (>= 0, finite; 0 = off), flag_mask=0x%x (COPO_F_* bits)",
+                    (double)cfg->ttc_below, (double)cfg->gap_below, cfg->flag_mask);
+    static_assert(COPO_CLIP_MAX_CAP == CLIP_MAX_CAP && COPO_CLIP_WORDS == CLIP_WORDS && COPO_CLIP_HEADER == CLIP_HEADER, "copo_hip.h / clip_common.h");
+    HIP_TRY(hipSetDevice(sim->device));
+    copo_clip* h = new (std::nothrow) copo_clip();
+    if (!h) return fail(COPO_ERR_DEVICE, "out of host memory");
+    h->sim = sim; h->cfg = *cfg; h->cap = cfg->pre + cfg->post + 1;
+    const size_t E = (size_t)sim->p.E, N = (size_t)sim->p.N, cap = (size_t)h->cap, C = (size_t)cfg->max_clips;
+    h->ring_bytes = E * cap * CLIP_WORDS * N * 4; h->ring_env_bytes = E * cap * CLIP_ENV_WORDS * 4;
+    h->scene_bytes = E * CLIP_SCENE_WORDS * 4; h->ready_bytes = E * 4;
+    h->pool_bytes = C * cap * CLIP_WORDS * N * 4; h->pool_env_bytes = C * cap * CLIP_ENV_WORDS * 4; h->header_bytes = C * CLIP_HEADER * 4;
+    hipError_t err = hipMalloc((void**)&h->ring, h->ring_bytes);
+    if (err == hipSuccess) err = hipMalloc((void**)&h->ring_env, h->ring_env_bytes);
+    if (err == hipSuccess) err = hipMalloc((void**)&h->scene, h->scene_bytes);
+    if (err == hipSuccess) err = hipMalloc((void**)&h->ready, h->ready_bytes);
+    if (err == hipSuccess) err = hipMalloc((void**)&h->cid, h->ready_bytes);
+    if (err == hipSuccess) err = hipMalloc((void**)&h->counters, CLIP_COUNTERS * sizeof(int32_t));
+    if (err == hipSuccess) err = hipMalloc((void**)&h->pool, h->pool_bytes);
+    if (err == hipSuccess) err = hipMalloc((void**)&h->pool_env, h->pool_env_bytes);
+    if (err == hipSuccess) err = hipMalloc((void**)&h->header, h->header_bytes);
+    if (err == hipSuccess) err = hipMemset(h->ring, 0, h->ring_bytes);
+    if (err == hipSuccess) err = hipMemset(h->ring_env, 0, h->ring_env_bytes);
+    if (err != hipSuccess) {
+        (void)hipGetLastError();               // (a refused request must not show up as the next launch's error)
+        free_clip(h);
+        return fail(COPO_ERR_DEVICE, "copo_clip_create: %s (ring %zu bytes, pool %zu bytes)", hipGetErrorString(err), E * cap * CLIP_WORDS * N * 4,
+                    C * cap * CLIP_WORDS * N * 4);
+    }
+    int rc = clip_clear(h, nullptr);
+    if (rc == COPO_OK && hipStreamSynchronize(nullptr) != hipSuccess) rc = fail(COPO_ERR_DEVICE, "copo_clip_create: clearing failed");
+    if (rc != COPO_OK) {
+        free_clip(h);
+        return rc;
+    }
+    *out = h;
+    return COPO_OK;
+}
+
+extern "C" int copo_clip_destroy(copo_clip* h) {
+    if (!h) return fail(COPO_ERR_NULL, "copo_clip_destroy: NULL handle");
+    (void)hipSetDevice(h->sim->device);
+    free_clip(h);
+    return COPO_OK;
+}
+
+extern "C" int copo_clip_record(copo_clip* h, const uint8_t* flags, const float* ttc, const float* gap, void* stream) {
+    if (!h) return fail(COPO_ERR_NULL, "copo_clip_record: NULL handle");
+    HIP_TRY(launch_clip_record(clip_args(h), flags, ttc, gap, static_cast<hipStream_t>(stream)));
+    return COPO_OK;
+}
+
+extern "C" int copo_clip_flush(copo_clip* h, void* stream) {
+    if (!h) return fail(COPO_ERR_NULL, "copo_clip_flush: NULL handle");
+    HIP_TRY(launch_clip_flush(clip_args(h), static_cast<hipStream_t>(stream)));
+    return COPO_OK;
+}
+
+extern "C" int copo_clip_count(copo_clip* h, int32_t* n_clips, int32_t* dropped, void* stream) {
+    if (!h || !n_clips || !dropped) return fail(COPO_ERR_NULL, "copo_clip_count: NULL argument");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    int32_t c[CLIP_COUNTERS];
+    HIP_TRY(hipMemcpyAsync(c, h->counters, sizeof(c), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    *n_clips = c[CC_CLIPS];
+    *dropped = c[CC_DROPPED];
+    return COPO_OK;
+}
+
+extern "C" int copo_clip_read(copo_clip* h, int32_t first, int32_t n, int32_t* header_out, uint32_t* snaps_out, int32_t* env_out, void* stream) {
+    if (!h) return fail(COPO_ERR_NULL, "copo_clip_read: NULL handle");
+    if (first < 0 || n < 0 || (int64_t)first + n > h->cfg.max_clips)
+        return fail(COPO_ERR_DIM, "copo_clip_read: clips [%d, %d + %d) of a pool of %d", first, first, n, h->cfg.max_clips);
+    if (n == 0) return COPO_OK;
+    if (!header_out || !snaps_out || !env_out) return fail(COPO_ERR_NULL, "copo_clip_read: NULL output");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const size_t per = (size_t)h->cap * CLIP_WORDS * h->sim->p.N, per_env = (size_t)h->cap * CLIP_ENV_WORDS;
+    HIP_TRY(hipMemcpyAsync(header_out, h->header + (size_t)first * CLIP_HEADER, (size_t)n * CLIP_HEADER * 4, hipMemcpyDeviceToDevice, st));
+    HIP_TRY(hipMemcpyAsync(snaps_out, h->pool + (size_t)first * per, (size_t)n * per * 4, hipMemcpyDeviceToDevice, st));
+    HIP_TRY(hipMemcpyAsync(env_out, h->pool_env + (size_t)first * per_env, (size_t)n * per_env * 4, hipMemcpyDeviceToDevice, st));
+    return COPO_OK;
+}
+
+extern "C" int copo_clip_reset(copo_clip* h, void* stream) {
+    if (!h) return fail(COPO_ERR_NULL, "copo_clip_reset: NULL handle");
+    return clip_clear(h, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int copo_clip_scatter(copo_sim* target, const uint32_t* snaps, const int32_t* envw, int32_t cap, int32_t N, const int32_t* clip_idx,
+                                 const int32_t* frame_idx, int32_t S, void* stream) {
+    if (!target || !snaps || !envw || !clip_idx || !frame_idx) return fail(COPO_ERR_NULL, "copo_clip_scatter: NULL argument");
+    if (cap < 1 || cap > COPO_CLIP_MAX_CAP) return fail(COPO_ERR_DIM, "copo_clip_scatter: cap=%d (1..%d)", cap, COPO_CLIP_MAX_CAP);
+    if (N != target->p.N) return fail(COPO_ERR_DIM, "copo_clip_scatter: clips of %d slots, a simulator of %d", N, target->p.N);
+    if (S < 1 || S > target->p.E) return fail(COPO_ERR_DIM, "copo_clip_scatter: S=%d scenes into a simulator of %d", S, target->p.E);
+    HIP_TRY(launch_clip_scatter(target->p.state, target->p.env, target->p.E, N, snaps, envw, cap, clip_idx, frame_idx, S,
+                                static_cast<hipStream_t>(stream)));
+    target->started = true;
+    return COPO_OK;
 }

@@ -62,7 +62,7 @@ class MultiAgentMetaDrive:
     @classmethod
     def default_config(cls):
         return dict(map=cls.MAP, num_envs=1, num_agents=None, start_seed=5000, horizon=1000, num_lasers=72,
-                    device=0, crash_done=True, out_of_road_done=True, allow_respawn=True, delay_done=25, interaction_metrics=False)
+                    device=0, crash_done=True, out_of_road_done=True, allow_respawn=True, delay_done=25, interaction_metrics=False, event_clips=None)
 
     def __init__(self, config=None):
         cfg = type(self).default_config()
@@ -74,6 +74,10 @@ class MultiAgentMetaDrive:
             kw.setdefault("seed", int(cfg.get("start_seed", 0)))
             cfg["map"], cfg["map_kwargs"] = "pgmap", kw
         self.config = cfg
+        clip_kwargs = None if cfg.get("event_clips") is None else dict(cfg["event_clips"])
+        if clip_kwargs and (clip_kwargs.get("ttc_below", 0.0) > 0.0 or clip_kwargs.get("gap_below", 0.0) > 0.0) \
+                and not cfg.get("interaction_metrics", False):
+            raise ValueError("event_clips with ttc_below / gap_below reads the interaction meter: set interaction_metrics=True")
         sim_kwargs = {k: v for k, v in cfg.items() if k in SIM_KEYS and k not in ("enable_lcf",)}
         sim_kwargs["enable_lcf"] = bool(self.ENABLE_LCF and cfg.get("enable_copo", True))
         sim_kwargs.update(type(self)._extension_kwargs(cfg))
@@ -89,6 +93,11 @@ class MultiAgentMetaDrive:
         if cfg.get("interaction_metrics", False):
             from copo_amd.interact import InteractionMeter
             self._meter = InteractionMeter(self.sim)
+        self._clips = None         # `event_clips`: flight recorder, clips of the records around a crash / near miss (copo_amd/clips.py)
+        if clip_kwargs is not None:
+            from copo_amd.clips import ClipRecorder
+            self._clips = ClipRecorder(self.sim, **clip_kwargs)
+            self._clips_records = 0
         self._slot_ids = None      # dict API state (num_envs == 1)
         self._next_obs = None
         self.current_lcf_mean, self.current_lcf_std = self.sim_config.lcf_mean, self.sim_config.lcf_std
@@ -144,12 +153,14 @@ class MultiAgentMetaDrive:
         out = self.sim.reset(seeds)
         self._restart_trail()
         self._restart_interaction()
+        self._record_clips(None)
         return out
 
     def vec_step(self, actions):
         out = self.sim.step(actions)
         self._record_trail()
         self._record_interaction()
+        self._record_clips(out["flags"])
         return out
 
     # ---- top-down rendering (copo/vis.py: env.render(mode="top_down", num_stack=25)) ------------------------------------------
@@ -200,6 +211,25 @@ class MultiAgentMetaDrive:
         assert self._meter is not None, "set interaction_metrics=True in the env config"
         return self._meter.summary(flush_open)
 
+    # ---- event clips (config key `event_clips`: None, or the arguments of `ClipRecorder`): one record of the state after reset and after
+    #      every step, fed with the step's flags and, for the ttc / gap triggers, the meter's arrays of that state.  Clips are kept over
+    #      resets; a clip still waiting for its `post` records when the scenes are reset by hand is committed with what it has ----
+    def _record_clips(self, flags):
+        c = self._clips
+        if c is None:
+            return
+        if flags is None and self._clips_records:
+            c.flush()
+        c.record(flags=flags, ttc=self._meter.ttc if c.ttc_below > 0.0 else None, gap=self._meter.gap if c.gap_below > 0.0 else None)
+        self._clips_records += 1
+
+    def event_clips(self, flush=False):
+        """The clips recorded so far as a `copo_amd.clips.ClipSet` (`flush`: the waiting ones too, shorter, as if they ended now)."""
+        assert self._clips is not None, "set event_clips={...} in the env config"
+        if flush:
+            self._clips.flush()
+        return self._clips.clips()
+
     def set_lcf_dist(self, mean, std):
         assert self.ENABLE_LCF, "set_lcf_dist needs an LCF env (get_lcf_env)"
         assert std > 0.0 and -1.0 <= mean <= 1.0
@@ -244,6 +274,7 @@ class MultiAgentMetaDrive:
         out = self.sim.reset(np.array([seed], np.uint64))
         self._restart_trail()
         self._restart_interaction()
+        self._record_clips(None)
         ids = self._ids(out)
         self._slot_ids = ["agent%d" % a for a in ids]
         self._just_terminated = {}
@@ -264,6 +295,7 @@ class MultiAgentMetaDrive:
         out = self.sim.step(torch.from_numpy(act).to(self.sim.device))
         self._record_trail()
         self._record_interaction()
+        self._record_clips(out["flags"])
         h = {k: v[0].cpu().numpy() for k, v in out.items() if v is not None}
         if self._meter is not None:      # of the state after the step: +inf for an agent that ended in it
             h["min_gap"], h["ttc"] = self._meter.gap[0].cpu().numpy(), self._meter.ttc[0].cpu().numpy()
@@ -349,6 +381,9 @@ class MultiAgentMetaDrive:
         if getattr(self, "_meter", None) is not None:
             self._meter.close()
             self._meter = None
+        if getattr(self, "_clips", None) is not None:
+            self._clips.close()
+            self._clips = None
         self.sim.close()
 
 

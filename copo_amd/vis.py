@@ -2,13 +2,19 @@
 top-down frames written to disk.
 
     python -m copo_amd.vis --env inter --algo copo --weights FILE.npz [--key copo_inter] --steps 300 --out DIR [--gif] [--follow SLOT]
-                           [--interaction]
+                           [--interaction] [--clips [--clip-pre N] [--clip-post N] [--clip-on crash,out,ttc<1.0,gap<0.5]]
+    python -m copo_amd.vis --replay FILE.npz --out DIR [--size W H] [--follow SLOT]
 
 `--weights` is a population file (`{ALGO}_{ENV}.npz` with the reference's key layout); `--key NAME` takes the arrays stored under
 `NAME/w/` of a bundle instead.  One PPM per step (`DIR/frame_00000.ppm`, ...), plus `DIR/vis.gif` with `--gif` (needs Pillow).
 At the end of every scene episode the reference's summary dict is printed; with `--interaction` the interaction metrics of that
 episode's agents (gaps, time to collision, near misses, harsh braking: copo_amd/interact.py) are printed next to it, and those of all
 agents of the run, finished or not, at the end.
+
+`--clips` runs the flight recorder (copo_amd/clips.py) next to the rollout: the `--clip-pre` steps before and `--clip-post` after every
+event of `--clip-on` -- step flags by name, `ttc<SECONDS`, `gap<METRES` -- are kept as clips, written at the end to `DIR/clips.npz` and,
+played back, to `DIR/clip_000/frame_00000.ppm`, ...  `--replay FILE.npz` renders the clips of such a file again: no policy, no
+simulator run, no `--weights`.
 """
 import argparse
 import os
@@ -38,18 +44,60 @@ def load_policy(algo, env, weights_path, key=None):
     return pf
 
 
-def make_env(env, interaction=False):
+def make_env(env, interaction=False, clips=None):
     from copo_amd.torch_copo.utils import env_wrappers as W
     cls_name, n = _SCENES[env]
-    return getattr(W, cls_name)(dict(num_agents=n, interaction_metrics=bool(interaction)))
+    return getattr(W, cls_name)(dict(num_agents=n, interaction_metrics=bool(interaction), event_clips=clips))
 
 
-def run(env_name, algo, weights, steps, out, key=None, gif=False, follow=None, film_size=(512, 512), seed=0, fps=10, interaction=False):
-    """Roll `steps` env steps, writing one frame per step; returns the list of frame paths."""
+def parse_clip_on(spec):
+    """`crash,out,ttc<1.0,gap<0.5` -> dict(flags, ttc_below, gap_below) of `ClipRecorder`."""
+    from copo_amd.clips import FLAG_BITS
+    flags, kw = [], dict(ttc_below=0.0, gap_below=0.0)
+    for item in (x.strip() for x in spec.split(",") if x.strip()):
+        name, lt, value = item.partition("<")
+        if lt and name in ("ttc", "gap") and float(value) > 0.0:
+            kw[name + "_below"] = float(value)
+        elif not lt and name in FLAG_BITS:
+            flags.append(name)
+        else:
+            raise ValueError("--clip-on item %r: a flag of %s, ttc<SECONDS or gap<METRES" % (item, "/".join(FLAG_BITS)))
+    return dict(flags=tuple(flags), **kw)
+
+
+def write_clips(clipset, out, film_size=(512, 512), follow=None, device=0):
+    """Play every clip of `clipset` back and write `out/clip_000/frame_00000.ppm`, ...; returns the paths."""
+    from copo_amd.clips import ClipPlayer
+    from copo_amd.render import write_ppm
+    paths = []
+    if not len(clipset):
+        return paths
+    player = ClipPlayer(clipset, device=device)
+    try:
+        for c in range(len(clipset)):
+            frames = player.render(c, film_size=film_size, view="map" if follow is None else "follow", follow_slot=follow)
+            paths += write_ppm(frames, os.path.join(out, "clip_%03d" % c))
+            print("clip %d:" % c, clipset.info(c))
+    finally:
+        player.close()
+    return paths
+
+
+def replay(path, out, film_size=(512, 512), follow=None):
+    """Render the clips of a saved clip set; returns the list of frame paths."""
+    from copo_amd.clips import ClipSet
+    return write_clips(ClipSet.load(path), out, film_size, follow)
+
+
+def run(env_name, algo, weights, steps, out, key=None, gif=False, follow=None, film_size=(512, 512), seed=0, fps=10, interaction=False,
+        clips=None):
+    """Roll `steps` env steps, writing one frame per step; returns the list of frame paths.  `clips`: the arguments of a `ClipRecorder`
+    (then `out/clips.npz` and the played-back clips are written too)."""
     from copo_amd.render import write_gif, write_ppm
     np.random.seed(seed)
     policy = load_policy(algo, env_name, weights, key)
-    env = make_env(env_name, interaction)
+    env = make_env(env_name, interaction or bool(clips and (clips.get("ttc_below") or clips.get("gap_below"))), clips)
+    clipset = None
     paths, kept = [], []
     try:
         o, d = env.reset(), {"__all__": False}
@@ -76,10 +124,17 @@ def run(env_name, algo, weights, steps, out, key=None, gif=False, follow=None, f
                 kept.append(frame)
         if interaction:
             print({"interaction, agents still driving included": env.interaction_summary(flush_open=True)})
+        if clips is not None:
+            clipset = env.event_clips(flush=True)
     finally:
         env.close()
     if gif and kept:
         write_gif(np.stack(kept), os.path.join(out, "vis.gif"), fps=fps)
+    if clipset is not None:
+        os.makedirs(out, exist_ok=True)
+        clipset.save(os.path.join(out, "clips.npz"))
+        clip_paths = write_clips(clipset, out, film_size, follow)
+        print("wrote %d clips (%d frames) to %s" % (len(clipset), len(clip_paths), out))
     return paths
 
 
@@ -87,7 +142,7 @@ def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--env", default="inter", choices=sorted(_SCENES))
     ap.add_argument("--algo", default="copo", choices=["cl", "copo", "ippo", "ccppo"])
-    ap.add_argument("--weights", required=True, help="population .npz")
+    ap.add_argument("--weights", default=None, help="population .npz (not needed with --replay)")
     ap.add_argument("--key", default=None, help="take the arrays under KEY/w/ of a bundle")
     ap.add_argument("--steps", type=int, default=300)
     ap.add_argument("--out", required=True, help="output directory")
@@ -96,9 +151,21 @@ def main(argv=None):
     ap.add_argument("--size", type=int, nargs=2, default=(512, 512), metavar=("W", "H"))
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--interaction", action="store_true", help="measure and print the interaction metrics")
+    ap.add_argument("--clips", action="store_true", help="record event clips: DIR/clips.npz and DIR/clip_NNN/frame_*.ppm")
+    ap.add_argument("--clip-pre", type=int, default=24, help="steps kept before an event")
+    ap.add_argument("--clip-post", type=int, default=8, help="steps kept after an event")
+    ap.add_argument("--clip-on", default="crash", help="events: step flags by name, ttc<SECONDS, gap<METRES, comma separated")
+    ap.add_argument("--replay", default=None, metavar="FILE.npz", help="render the clips of a saved clip set instead of running a policy")
     a = ap.parse_args(argv)
+    if a.replay:
+        paths = replay(a.replay, a.out, film_size=tuple(a.size), follow=a.follow)
+        print("wrote %d frames to %s" % (len(paths), a.out))
+        return
+    if not a.weights:
+        ap.error("--weights is required (unless --replay)")
+    clips = dict(pre=a.clip_pre, post=a.clip_post, **parse_clip_on(a.clip_on)) if a.clips else None
     paths = run(a.env, a.algo, a.weights, a.steps, a.out, key=a.key, gif=a.gif, follow=a.follow, film_size=tuple(a.size), seed=a.seed,
-                interaction=a.interaction)
+                interaction=a.interaction, clips=clips)
     print("wrote %d frames to %s" % (len(paths), a.out))
 
 

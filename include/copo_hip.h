@@ -318,6 +318,52 @@ int copo_interact_totals(copo_interact* h, int64_t* counts_i64, double* sums_f64
 int copo_interact_reset(copo_interact* h, void* stream);
 int copo_interact_destroy(copo_interact* h);
 
+/* ---- event clips: a flight recorder on the device.  A handle reads its simulator's state and must be destroyed
+ *      before it.  A snapshot of a scene holds, per slot, COPO_CLIP_WORDS 32-bit words -- the raw bits of state fields 0..3 (x, y,
+ *      heading, speed), the low byte of field 13 (status) and field 14 (agent id): what the renderer and the interaction meter read --
+ *      and the scene's env words 0 and 1 (t_env, episode).  Every scene keeps its last cap = pre + post + 1 snapshots in a ring.
+ * Trigger of a record: a slot fires when (flags & flag_mask) != 0, ttc < ttc_below or gap < gap_below (plain fp32 <: NaN and +inf never
+ * fire; a threshold or mask of 0 is off).  An idle scene that fires at record r is armed: trig_rec = r, trig_slot = its lowest firing
+ * slot, trig_aid = that slot's agent id, kind = OR over the scene of {1 flag, 2 ttc, 4 gap}, n_events = 1; an armed scene that fires
+ * counts it in n_events.  `post` records later (in the same record with post = 0) the scene commits the records
+ * [max(trig_rec - pre, lo), trig_rec + post] in chronological order as one clip and is idle again, with lo = trig_rec + post + 1 (two
+ * clips of a scene share no record; a scene reset does not end a clip: the snapshots carry the episode word).  The scenes that commit in one
+ * record take the clip ids n_clips, n_clips + 1, ... in ascending scene order; an id >= max_clips is not stored and counts as dropped.
+ * Header of a clip: COPO_CLIP_HEADER int32 = {scene, first_rec, length, trig_rec, trig_slot, kind, trig_aid, n_events}; records count
+ * from 0 since create / reset.  Frames of a clip beyond its length are 0. ---- */
+#define COPO_CLIP_MAX_CAP 256
+#define COPO_CLIP_WORDS 6
+#define COPO_CLIP_HEADER 8
+typedef struct copo_clip_cfg {
+    int32_t pre, post;         /* records kept before / after the trigger record: >= 0, pre + post + 1 <= COPO_CLIP_MAX_CAP (COPO_ERR_DIM) */
+    int32_t max_clips;         /* pool size, >= 1 (COPO_ERR_DIM) */
+    uint32_t flag_mask;        /* COPO_F_* bits */
+    float ttc_below, gap_below;   /* >= 0 and finite (COPO_ERR_CONFIG) */
+} copo_clip_cfg;
+typedef struct copo_clip copo_clip;
+/* allocates the rings (24 E N cap bytes) and the pool (24 max_clips N cap bytes): COPO_ERR_DEVICE when the device refuses */
+int copo_clip_create(copo_sim* sim, const copo_clip_cfg* cfg, copo_clip** out);
+/* snapshot of the current state of every scene, triggers from this record's arrays -- flags device [E][N] uint8 (the step's output), ttc /
+ * gap device [E][N] fp32 (the meter's outputs); NULL: that trigger is off for the call -- and the commit of the scenes that are due.
+ * Three launches on `stream`, no allocation, no host synchronisation; simulator memory is only read. */
+int copo_clip_record(copo_clip* h, const uint8_t* flags, const float* ttc, const float* gap, void* stream);
+/* commit every armed scene with the records it has so far (a shorter length; lo = the next record), same order and overflow rule */
+int copo_clip_flush(copo_clip* h, void* stream);
+/* HOST outputs: clips stored so far (<= max_clips) and clips dropped; waits for `stream` */
+int copo_clip_count(copo_clip* h, int32_t* n_clips, int32_t* dropped, void* stream);
+/* clips [first, first + n) of the pool, device to device: header_out [n][COPO_CLIP_HEADER], snaps_out [n][cap][COPO_CLIP_WORDS][N],
+ * env_out [n][cap][2]; first + n <= max_clips (COPO_ERR_DIM) */
+int copo_clip_read(copo_clip* h, int32_t first, int32_t n, int32_t* header_out, uint32_t* snaps_out, int32_t* env_out, void* stream);
+/* forget every clip, counter and armed scene; records count from 0 again */
+int copo_clip_reset(copo_clip* h, void* stream);
+int copo_clip_destroy(copo_clip* h);
+/* playback, no handle: for j < S, frame frame_idx[j] of clip clip_idx[j] of device pool arrays snaps [C][cap][COPO_CLIP_WORDS][N] / envw
+ * [C][cap][2] becomes scene j of `target`: fields 0..3 the raw bits, field 13 the status byte, field 14 the agent id, every other field 0,
+ * env words {t_env, episode, 0, 1}; frame_idx[j] == -1: an all-EMPTY scene.  N must be the target's, 1 <= S <= its E (COPO_ERR_DIM);
+ * scenes >= S are left alone; clip_idx is not checked against C.  The target is for the renderer and the meter, not for stepping. */
+int copo_clip_scatter(copo_sim* target, const uint32_t* snaps, const int32_t* envw, int32_t cap, int32_t N, const int32_t* clip_idx,
+                      const int32_t* frame_idx, int32_t S, void* stream);
+
 /* ---- stateless ops ---- */
 
 /* CCEnv._update_distance_map + _find_in_range (env_wrappers.py:125-158) + LCFEnv reward block (:313-326).
