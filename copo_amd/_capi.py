@@ -71,6 +71,14 @@ class ClipCfg(C.Structure):
 
 CLIP_MAX_CAP, CLIP_WORDS, CLIP_HEADER = 256, 6, 8
 
+
+class RewindCfg(C.Structure):
+    """Mirror of `copo_rewind_cfg`."""
+    _fields_ = [("depth", C.c_int32), ("stride", C.c_int32)]
+
+
+REWIND_MAX_DEPTH, REWIND_TALLY = 64, 8
+
 HEAD_PPO, HEAD_META_NEW, HEAD_META_OLD = 0, 1, 2
 OPERAND_F32, OPERAND_BF16 = 0, 1
 PPO_STATS = 8
@@ -148,6 +156,13 @@ _SIGS = {
     "copo_clip_reset": (C.c_int, [C.c_void_p, C.c_void_p]),
     "copo_clip_destroy": (C.c_int, [C.c_void_p]),
     "copo_clip_scatter": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
+    "copo_rewind_create": (C.c_int, [C.c_void_p, C.POINTER(RewindCfg), C.POINTER(C.c_void_p)]),
+    "copo_rewind_record": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "copo_rewind_reset": (C.c_int, [C.c_void_p]),
+    "copo_rewind_count": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
+    "copo_rewind_fork": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 8),
+    "copo_rewind_tally": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
+    "copo_rewind_destroy": (C.c_int, [C.c_void_p]),
     "copo_neighbours_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_float,
                                       C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                       C.c_void_p, C.c_void_p]),

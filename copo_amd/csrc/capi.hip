@@ -15,6 +15,7 @@
 #include "render_common.h"
 #include "interact_common.h"
 #include "clip_common.h"
+#include "rewind_common.h"
 
 using namespace copo;
 
@@ -947,5 +948,111 @@ extern "C" int copo_clip_scatter(copo_sim* target, const uint32_t* snaps, const 
     HIP_TRY(launch_clip_scatter(target->p.state, target->p.env, target->p.E, N, snaps, envw, cap, clip_idx, frame_idx, S,
                                 static_cast<hipStream_t>(stream)));
     target->started = true;
+    return COPO_OK;
+}
+
+// ---- scene rewind (rewind_kernels.hip) -------------------------------------------------------------------------
+
+struct copo_rewind {
+    copo_sim* sim;
+    int32_t depth, stride;
+    int64_t n_records;             // records made since create / reset (host side: the feature is eager only)
+    uint32_t* ring;
+    int32_t* ring_env;
+};
+
+static void free_rewind(copo_rewind* h) {
+    for (void* a : {(void*)h->ring, (void*)h->ring_env})
+        if (a) (void)hipFree(a);
+    delete h;
+}
+
+extern "C" int copo_rewind_create(copo_sim* sim, const copo_rewind_cfg* cfg, copo_rewind** out) {
+    if (!sim || !cfg || !out) return fail(COPO_ERR_NULL, "copo_rewind_create: NULL argument");
+    *out = nullptr;
+    if (cfg->depth < 1 || cfg->depth > COPO_REWIND_MAX_DEPTH || cfg->stride < 1)
+        return fail(COPO_ERR_DIM, "copo_rewind_create: depth=%d (1..%d) stride=%d (>= 1)", cfg->depth, COPO_REWIND_MAX_DEPTH, cfg->stride);
+    static_assert(COPO_REWIND_MAX_DEPTH == REWIND_MAX_DEPTH && COPO_REWIND_TALLY == REWIND_TALLY, "copo_hip.h / rewind_common.h");
+    HIP_TRY(hipSetDevice(sim->device));
+    copo_rewind* h = new (std::nothrow) copo_rewind();
+    if (!h) return fail(COPO_ERR_DEVICE, "out of host memory");
+    h->sim = sim; h->depth = cfg->depth; h->stride = cfg->stride; h->n_records = 0;
+    const size_t E = (size_t)sim->p.E, N = (size_t)sim->p.N, D = (size_t)cfg->depth;
+    const size_t ring_bytes = E * D * COPO_STATE_FIELDS * N * 4, env_bytes = E * D * REWIND_ENV_WORDS * 4;
+    hipError_t err = hipMalloc((void**)&h->ring, ring_bytes);
+    if (err == hipSuccess) err = hipMalloc((void**)&h->ring_env, env_bytes);
+    if (err == hipSuccess) err = hipMemset(h->ring, 0, ring_bytes);
+    if (err == hipSuccess) err = hipMemset(h->ring_env, 0, env_bytes);
+    if (err != hipSuccess) {
+        (void)hipGetLastError();               // (a refused request must not show up as the next launch's error)
+        free_rewind(h);
+        return fail(COPO_ERR_DEVICE, "copo_rewind_create: %s (ring %zu bytes)", hipGetErrorString(err), ring_bytes + env_bytes);
+    }
+    *out = h;
+    return COPO_OK;
+}
+
+extern "C" int copo_rewind_destroy(copo_rewind* h) {
+    if (!h) return fail(COPO_ERR_NULL, "copo_rewind_destroy: NULL handle");
+    (void)hipSetDevice(h->sim->device);
+    free_rewind(h);
+    return COPO_OK;
+}
+
+extern "C" int copo_rewind_record(copo_rewind* h, void* stream) {
+    if (!h) return fail(COPO_ERR_NULL, "copo_rewind_record: NULL handle");
+    const int64_t r = h->n_records;
+    if (r >= INT32_MAX) return fail(COPO_ERR_STATE, "copo_rewind_record: 2^31 - 1 records since the last reset");
+    if (r % h->stride == 0) {
+        const SimParams& p = h->sim->p;
+        RewindArgs a;
+        a.state = p.state; a.env = p.env; a.E = p.E; a.N = p.N; a.depth = h->depth; a.ring = h->ring; a.ring_env = h->ring_env;
+        HIP_TRY(launch_rewind_record(a, (int)((r / h->stride) % h->depth), static_cast<hipStream_t>(stream)));
+    }
+    h->n_records = r + 1;
+    return COPO_OK;
+}
+
+// (the ring needs no clearing: a fork never reaches back beyond the records made since)
+extern "C" int copo_rewind_reset(copo_rewind* h) {
+    if (!h) return fail(COPO_ERR_NULL, "copo_rewind_reset: NULL handle");
+    h->n_records = 0;
+    return COPO_OK;
+}
+
+extern "C" int copo_rewind_count(copo_rewind* h, int32_t* n_records) {
+    if (!h || !n_records) return fail(COPO_ERR_NULL, "copo_rewind_count: NULL argument");
+    *n_records = (int32_t)h->n_records;
+    return COPO_OK;
+}
+
+extern "C" int copo_rewind_fork(copo_rewind* h, copo_sim* target, int32_t first, int32_t S, const int32_t* scene, const int32_t* rec,
+                                const float* lcf, const uint64_t* seeds, const int32_t* watch_slot, int32_t* status, int32_t* watch_aid,
+                                void* stream) {
+    if (!h || !target || !scene || !rec || !status) return fail(COPO_ERR_NULL, "copo_rewind_fork: NULL argument");
+    const SimParams &sp = h->sim->p, &tp = target->p;
+    if (target == h->sim) return fail(COPO_ERR_CONFIG, "copo_rewind_fork: the target is the source simulator");
+    if (target->device != h->sim->device)
+        return fail(COPO_ERR_CONFIG, "copo_rewind_fork: the target lives on GPU %d, the source on GPU %d", target->device, h->sim->device);
+    if (tp.N != sp.N || tp.n_routes != sp.n_routes || tp.n_spawns != sp.n_spawns || tp.O != sp.O)
+        return fail(COPO_ERR_DIM, "copo_rewind_fork: target slots / routes / spawns / obs %d / %d / %d / %d, source %d / %d / %d / %d", tp.N,
+                    tp.n_routes, tp.n_spawns, tp.O, sp.N, sp.n_routes, sp.n_spawns, sp.O);
+    if (S < 1 || first < 0 || (int64_t)first + S > tp.E)
+        return fail(COPO_ERR_DIM, "copo_rewind_fork: scenes [%d, %d + %d) of a target of %d", first, first, S, tp.E);
+    RewindForkArgs a;
+    a.ring = h->ring; a.ring_env = h->ring_env; a.src_seeds = sp.seeds;
+    a.E = sp.E; a.N = sp.N; a.depth = h->depth; a.stride = h->stride; a.n_records = (int32_t)h->n_records;
+    a.state = tp.state; a.env = tp.env; a.seeds = const_cast<uint64_t*>(tp.seeds); a.TE = tp.E; a.first = first; a.S = S;
+    a.scene = scene; a.rec = rec; a.lcf = lcf; a.new_seeds = seeds; a.watch_slot = watch_slot; a.status = status; a.watch_aid = watch_aid;
+    HIP_TRY(launch_rewind_fork(a, static_cast<hipStream_t>(stream)));
+    target->started = true;
+    return COPO_OK;
+}
+
+extern "C" int copo_rewind_tally(const uint8_t* flags, const int32_t* watch_slot, int32_t* tally, int32_t B, int32_t N, void* stream) {
+    if (!flags || !tally) return fail(COPO_ERR_NULL, "copo_rewind_tally: NULL argument");
+    if (B < 0 || N < 1 || N > COPO_MAX_AGENTS) return fail(COPO_ERR_DIM, "copo_rewind_tally: B=%d N=%d (N in 1..%d)", B, N, COPO_MAX_AGENTS);
+    if (B == 0) return COPO_OK;
+    HIP_TRY(launch_rewind_tally(flags, watch_slot, tally, B, N, static_cast<hipStream_t>(stream)));
     return COPO_OK;
 }

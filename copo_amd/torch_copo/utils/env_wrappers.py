@@ -62,7 +62,7 @@ class MultiAgentMetaDrive:
     @classmethod
     def default_config(cls):
         return dict(map=cls.MAP, num_envs=1, num_agents=None, start_seed=5000, horizon=1000, num_lasers=72,
-                    device=0, crash_done=True, out_of_road_done=True, allow_respawn=True, delay_done=25, interaction_metrics=False, event_clips=None)
+                    device=0, crash_done=True, out_of_road_done=True, allow_respawn=True, delay_done=25, interaction_metrics=False, event_clips=None, rewind=None)
 
     def __init__(self, config=None):
         cfg = type(self).default_config()
@@ -98,6 +98,10 @@ class MultiAgentMetaDrive:
             from copo_amd.clips import ClipRecorder
             self._clips = ClipRecorder(self.sim, **clip_kwargs)
             self._clips_records = 0
+        self._rewind = None        # `rewind`: ring of full snapshots per scene to fork past records from (copo_amd/rewind.py)
+        if cfg.get("rewind") is not None:
+            from copo_amd.rewind import RewindBuffer
+            self._rewind = RewindBuffer(self.sim, **dict(cfg["rewind"]))
         self._slot_ids = None      # dict API state (num_envs == 1)
         self._next_obs = None
         self.current_lcf_mean, self.current_lcf_std = self.sim_config.lcf_mean, self.sim_config.lcf_std
@@ -154,6 +158,7 @@ class MultiAgentMetaDrive:
         self._restart_trail()
         self._restart_interaction()
         self._record_clips(None)
+        self._record_rewind(True)
         return out
 
     def vec_step(self, actions):
@@ -161,6 +166,7 @@ class MultiAgentMetaDrive:
         self._record_trail()
         self._record_interaction()
         self._record_clips(out["flags"])
+        self._record_rewind(False)
         return out
 
     # ---- top-down rendering (copo/vis.py: env.render(mode="top_down", num_stack=25)) ------------------------------------------
@@ -230,6 +236,24 @@ class MultiAgentMetaDrive:
             self._clips.flush()
         return self._clips.clips()
 
+    # ---- rewind (config key `rewind`: None, or the arguments of `RewindBuffer`): one record of the state after reset and after every
+    #      step, next to the clip recorder's, so that a clip header's first_rec / trig_rec name rewind records.  The clip recorder counts
+    #      on over a reset by hand, so the buffer does too; the records from before that reset can no longer be forked (`invalidate`) ----
+    def _record_rewind(self, after_reset):
+        b = self._rewind
+        if b is None:
+            return
+        if after_reset and b.n_records:
+            b.invalidate()
+        b.record()
+        if self._clips is not None:
+            assert b.n_records == self._clips_records, (b.n_records, self._clips_records)
+
+    def rewind_buffer(self):
+        """The env's `copo_amd.rewind.RewindBuffer`."""
+        assert self._rewind is not None, "set rewind={...} in the env config"
+        return self._rewind
+
     def set_lcf_dist(self, mean, std):
         assert self.ENABLE_LCF, "set_lcf_dist needs an LCF env (get_lcf_env)"
         assert std > 0.0 and -1.0 <= mean <= 1.0
@@ -275,6 +299,7 @@ class MultiAgentMetaDrive:
         self._restart_trail()
         self._restart_interaction()
         self._record_clips(None)
+        self._record_rewind(True)
         ids = self._ids(out)
         self._slot_ids = ["agent%d" % a for a in ids]
         self._just_terminated = {}
@@ -296,6 +321,7 @@ class MultiAgentMetaDrive:
         self._record_trail()
         self._record_interaction()
         self._record_clips(out["flags"])
+        self._record_rewind(False)
         h = {k: v[0].cpu().numpy() for k, v in out.items() if v is not None}
         if self._meter is not None:      # of the state after the step: +inf for an agent that ended in it
             h["min_gap"], h["ttc"] = self._meter.gap[0].cpu().numpy(), self._meter.ttc[0].cpu().numpy()
@@ -384,6 +410,9 @@ class MultiAgentMetaDrive:
         if getattr(self, "_clips", None) is not None:
             self._clips.close()
             self._clips = None
+        if getattr(self, "_rewind", None) is not None:
+            self._rewind.close()
+            self._rewind = None
         self.sim.close()
 
 

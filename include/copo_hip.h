@@ -364,6 +364,57 @@ int copo_clip_destroy(copo_clip* h);
 int copo_clip_scatter(copo_sim* target, const uint32_t* snaps, const int32_t* envw, int32_t cap, int32_t N, const int32_t* clip_idx,
                       const int32_t* frame_idx, int32_t S, void* stream);
 
+/* ---- scene rewind: a ring of FULL snapshots per scene on the device, forks of one scene at one past record into scenes of another
+ *      simulator, and a tally of how the forked branches end.  A handle reads its (source) simulator's state and
+ *      must be destroyed before it.  Eager only: the record count lives on the host, nothing here belongs inside a captured graph.
+ * A snapshot of a scene is everything the scene resumes from except its seed: all COPO_STATE_FIELDS 32-bit words of every slot, as raw
+ * bits, and the scene's four env words.  Every scene keeps its last `depth` snapshots: [E][depth][COPO_STATE_FIELDS][N] words plus
+ * [E][depth][4] env words, 64 N E depth + 16 E depth bytes.
+ * Records count from 0 since create / reset -- the counting of the clip recorder's records, so a clip header's first_rec / trig_rec name
+ * rewind records when the caller makes both records every time.  Record r is STORED iff r % stride == 0, in ring place
+ * (r / stride) % depth; the other records launch nothing.
+ * Fork, request j < S: scene first + j of `target` becomes scene scene[j] of the source at the newest stored record <= rec[j], that is
+ * record q * stride with q = min(rec[j], last record) / stride, and status[j] = q * stride.  All COPO_STATE_FIELDS fields are written as
+ * raw bits and the four env words are copied; the target's device seed of that scene becomes the source scene's CURRENT seed, or
+ * seeds[j] when `seeds` is given.  A request is invalid when nothing has been recorded, rec[j] < 0, the snapshot has left the ring (q <=
+ * last stored q - depth) or scene[j] is outside 0..E-1 (checked on the device): status[j] = -1 and the target scene is written all-EMPTY
+ * with env words {0, 0, 0, 1} (its seed is left alone unless `seeds` is given).
+ *   lcf[j]         NaN keeps the snapshot's LCF; any other value v sets field 10 of every slot of that scene whose status byte is ALIVE
+ *                  to min(max(v, -1), 1).  Slots that are not ALIVE keep their bits, and agents spawned after the fork draw their LCF
+ *                  from the TARGET's own distribution (the set_lcf_dist / set_force_lcf values of the target handle).
+ *   watch_slot[j]  watch_aid[j] = field 14 (agent id) of slot watch_slot[j] in the snapshot when that slot is ALIVE there, else -1 (also
+ *                  for a slot outside 0..N-1, an invalid request, or watch_slot == NULL).
+ * Tally, stateless: one step's flags [B][N] are added to the rows tally[B][COPO_REWIND_TALLY], which the caller initialises to
+ * {0, 0, 0, 0, 0, 0, 0, -1}: [0] += 1; [1] += slots with ACTED; [2] / [3] / [4] / [5] += slots with DONE and ARRIVE / CRASH / OUT /
+ * MAXSTEP; and when [6] == 0, watch_slot[b] is in 0..N-1 and that slot has DONE: [6] = its flags byte, [7] = [0] before the increment
+ * (the watched slot's first end only: a later occupant of the slot does not overwrite it). ---- */
+#define COPO_REWIND_MAX_DEPTH 64
+#define COPO_REWIND_TALLY 8
+typedef struct copo_rewind_cfg {
+    int32_t depth;             /* snapshots per scene, 1..COPO_REWIND_MAX_DEPTH (COPO_ERR_DIM) */
+    int32_t stride;            /* every stride-th record is stored, >= 1 (COPO_ERR_DIM) */
+} copo_rewind_cfg;
+typedef struct copo_rewind copo_rewind;
+/* allocates the rings (64 N E depth + 16 E depth bytes): COPO_ERR_DEVICE when the device refuses */
+int copo_rewind_create(copo_sim* sim, const copo_rewind_cfg* cfg, copo_rewind** out);
+/* one record of the current state of every scene.  A stored record is ONE launch on `stream`, no allocation, no host synchronisation;
+ * simulator memory is only read */
+int copo_rewind_record(copo_rewind* h, void* stream);
+/* forget everything; records count from 0 again (host side only: the ring needs no clearing) */
+int copo_rewind_reset(copo_rewind* h);
+/* HOST output: records made since create / reset */
+int copo_rewind_count(copo_rewind* h, int32_t* n_records);
+/* scene, rec, status: device [S] int32; lcf device [S] fp32 or NULL; seeds device [S] uint64 or NULL; watch_slot, watch_aid device [S]
+ * int32 or NULL.  `target` must not be the source and must live on its GPU (COPO_ERR_CONFIG); its slots, n_routes, n_spawns and
+ * observation width must equal the source's, 1 <= S, 0 <= first and first + S <= its E (COPO_ERR_DIM); a refused call launches nothing.
+ * One launch; scenes of the target outside [first, first + S) are untouched; afterwards the target counts as started and may be stepped */
+int copo_rewind_fork(copo_rewind* h, copo_sim* target, int32_t first, int32_t S, const int32_t* scene, const int32_t* rec, const float* lcf,
+                     const uint64_t* seeds, const int32_t* watch_slot, int32_t* status, int32_t* watch_aid, void* stream);
+/* flags device [B][N] uint8 (a step's output), watch_slot device [B] int32 or NULL, tally device [B][COPO_REWIND_TALLY] int32; B >= 0,
+ * N in 1..COPO_MAX_AGENTS (COPO_ERR_DIM).  One launch, no atomics */
+int copo_rewind_tally(const uint8_t* flags, const int32_t* watch_slot, int32_t* tally, int32_t B, int32_t N, void* stream);
+int copo_rewind_destroy(copo_rewind* h);
+
 /* ---- stateless ops ---- */
 
 /* CCEnv._update_distance_map + _find_in_range (env_wrappers.py:125-158) + LCFEnv reward block (:313-326).
