@@ -79,6 +79,15 @@ class RewindCfg(C.Structure):
 
 REWIND_MAX_DEPTH, REWIND_TALLY = 64, 8
 
+
+class FieldCfg(C.Structure):
+    """Mirror of `copo_field_cfg`."""
+    _fields_ = [("x0", C.c_float), ("y0", C.c_float), ("cell", C.c_float), ("W", C.c_int32), ("H", C.c_int32), ("G", C.c_int32),
+                ("ttc_below", C.c_float)]
+
+
+FIELD_LAYERS, FIELD_MAX_SIDE, FIELD_MAX_GROUPS = 10, 1024, 64
+
 HEAD_PPO, HEAD_META_NEW, HEAD_META_OLD = 0, 1, 2
 OPERAND_F32, OPERAND_BF16 = 0, 1
 PPO_STATS = 8
@@ -163,6 +172,13 @@ _SIGS = {
     "copo_rewind_fork": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 8),
     "copo_rewind_tally": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
     "copo_rewind_destroy": (C.c_int, [C.c_void_p]),
+    "copo_field_create": (C.c_int, [C.c_void_p, C.POINTER(FieldCfg), C.POINTER(C.c_void_p)]),
+    "copo_field_set_groups": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "copo_field_record": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
+    "copo_field_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "copo_field_forget": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "copo_field_reset": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "copo_field_destroy": (C.c_int, [C.c_void_p]),
     "copo_neighbours_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_float,
                                       C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                       C.c_void_p, C.c_void_p]),

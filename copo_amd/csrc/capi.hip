@@ -16,6 +16,7 @@
 #include "interact_common.h"
 #include "clip_common.h"
 #include "rewind_common.h"
+#include "field_common.h"
 
 using namespace copo;
 
@@ -1054,5 +1055,128 @@ extern "C" int copo_rewind_tally(const uint8_t* flags, const int32_t* watch_slot
     if (B < 0 || N < 1 || N > COPO_MAX_AGENTS) return fail(COPO_ERR_DIM, "copo_rewind_tally: B=%d N=%d (N in 1..%d)", B, N, COPO_MAX_AGENTS);
     if (B == 0) return COPO_OK;
     HIP_TRY(launch_rewind_tally(flags, watch_slot, tally, B, N, static_cast<hipStream_t>(stream)));
+    return COPO_OK;
+}
+
+// ---- traffic field maps (field_kernels.hip) --------------------------------------------------------------------
+
+struct copo_field {
+    copo_sim* sim;
+    copo_field_cfg cfg;
+    float inv_cell;
+    int32_t block, n_blocks;       // scenes per workgroup of the tile pass, and how many such blocks
+    int32_t* group;                // [E]
+    int32_t* last;                 // [E][N]
+    uint32_t* mask;                // [n_blocks][FIELD_MASK_WORDS]
+    long long* maps;               // [G][FIELD_LAYERS][H][W]
+    long long* scene_records;      // [G]
+    size_t last_bytes, mask_bytes, maps_bytes, rec_bytes;
+};
+
+static void free_field(copo_field* h) {
+    for (void* a : {(void*)h->group, (void*)h->last, (void*)h->mask, (void*)h->maps, (void*)h->scene_records})
+        if (a) (void)hipFree(a);
+    delete h;
+}
+
+static FieldArgs field_args(const copo_field* h, const uint8_t* flags, const float* ttc) {
+    const SimParams& p = h->sim->p;
+    FieldArgs a;
+    a.state = p.state; a.E = p.E; a.N = p.N; a.hl = p.hl; a.hw = p.hw;
+    a.x0 = h->cfg.x0; a.y0 = h->cfg.y0; a.cell = h->cfg.cell; a.inv_cell = h->inv_cell;
+    a.W = h->cfg.W; a.H = h->cfg.H; a.G = h->cfg.G; a.block = h->block; a.ttc_below = h->cfg.ttc_below;
+    a.group = h->group; a.flags = flags; a.ttc = ttc; a.last = h->last; a.mask = h->mask; a.maps = h->maps; a.scene_records = h->scene_records;
+    return a;
+}
+
+extern "C" int copo_field_create(copo_sim* sim, const copo_field_cfg* cfg, copo_field** out) {
+    if (!sim || !cfg || !out) return fail(COPO_ERR_NULL, "copo_field_create: NULL argument");
+    *out = nullptr;
+    static_assert(COPO_FIELD_LAYERS == FIELD_LAYERS && COPO_FIELD_MAX_SIDE == FIELD_MAX_SIDE && COPO_FIELD_MAX_GROUPS == FIELD_MAX_GROUPS,
+                  "copo_hip.h / field_common.h");
+    if (cfg->W < 1 || cfg->W > FIELD_MAX_SIDE || cfg->H < 1 || cfg->H > FIELD_MAX_SIDE || cfg->G < 1 || cfg->G > FIELD_MAX_GROUPS ||
+        !(cfg->cell > 0.0f) || !std::isfinite(cfg->cell))
+        return fail(COPO_ERR_DIM, "copo_field_create: W=%d H=%d (1..%d) G=%d (1..%d) cell=%g (> 0, finite)", cfg->W, cfg->H, FIELD_MAX_SIDE,
+                    cfg->G, FIELD_MAX_GROUPS, (double)cfg->cell);
+    const float inv_cell = (float)(1.0 / (double)cfg->cell);
+    if (!std::isfinite(cfg->x0) || !std::isfinite(cfg->y0) || !(cfg->ttc_below >= 0.0f) || !std::isfinite(cfg->ttc_below) ||
+        !std::isfinite(inv_cell))
+        return fail(COPO_ERR_CONFIG, "copo_field_create: x0=%g y0=%g 1/cell=%g (finite), ttc_below=%g (>= 0, finite)", (double)cfg->x0,
+                    (double)cfg->y0, (double)inv_cell, (double)cfg->ttc_below);
+    const size_t E = (size_t)sim->p.E, N = (size_t)sim->p.N;
+    // scenes per workgroup of the tile pass: 4 (one per wave) while the scenes are few, up to 64 -- every workgroup ends with one
+    // pass over its tile, which more scenes share
+    const int32_t block = 4 * (int32_t)std::min<size_t>(std::max<size_t>(E / 1024, 1), 16);
+    const size_t n_blocks = (E + block - 1) / block;
+    if (n_blocks > 65535) return fail(COPO_ERR_DIM, "copo_field_create: %zu scenes (at most %d)", E, 65535 * 64);
+    HIP_TRY(hipSetDevice(sim->device));
+    copo_field* h = new (std::nothrow) copo_field();
+    if (!h) return fail(COPO_ERR_DEVICE, "out of host memory");
+    h->sim = sim; h->cfg = *cfg; h->inv_cell = inv_cell; h->block = block; h->n_blocks = (int32_t)n_blocks;
+    h->last_bytes = E * N * sizeof(int32_t); h->mask_bytes = n_blocks * FIELD_MASK_WORDS * sizeof(uint32_t);
+    h->maps_bytes = (size_t)cfg->G * FIELD_LAYERS * cfg->H * cfg->W * sizeof(long long); h->rec_bytes = (size_t)cfg->G * sizeof(long long);
+    hipError_t err = hipMalloc((void**)&h->group, E * sizeof(int32_t));
+    if (err == hipSuccess) err = hipMalloc((void**)&h->last, h->last_bytes);
+    if (err == hipSuccess) err = hipMalloc((void**)&h->mask, h->mask_bytes);
+    if (err == hipSuccess) err = hipMalloc((void**)&h->maps, h->maps_bytes);
+    if (err == hipSuccess) err = hipMalloc((void**)&h->scene_records, h->rec_bytes);
+    if (err == hipSuccess) err = hipMemset(h->group, 0, E * sizeof(int32_t));
+    if (err == hipSuccess) err = hipMemset(h->last, 0xff, h->last_bytes);
+    if (err == hipSuccess) err = hipMemset(h->mask, 0, h->mask_bytes);
+    if (err == hipSuccess) err = hipMemset(h->maps, 0, h->maps_bytes);
+    if (err == hipSuccess) err = hipMemset(h->scene_records, 0, h->rec_bytes);
+    if (err != hipSuccess) {
+        (void)hipGetLastError();               // (a refused request must not show up as the next launch's error)
+        free_field(h);
+        return fail(COPO_ERR_DEVICE, "copo_field_create: %s (maps %zu bytes)", hipGetErrorString(err), (size_t)cfg->G * FIELD_LAYERS * cfg->H * cfg->W * 8);
+    }
+    *out = h;
+    return COPO_OK;
+}
+
+extern "C" int copo_field_destroy(copo_field* h) {
+    if (!h) return fail(COPO_ERR_NULL, "copo_field_destroy: NULL handle");
+    (void)hipSetDevice(h->sim->device);
+    free_field(h);
+    return COPO_OK;
+}
+
+extern "C" int copo_field_set_groups(copo_field* h, const int32_t* group_dev, void* stream) {
+    if (!h || !group_dev) return fail(COPO_ERR_NULL, "copo_field_set_groups: NULL argument");
+    HIP_TRY(hipMemcpyAsync(h->group, group_dev, (size_t)h->sim->p.E * sizeof(int32_t), hipMemcpyDeviceToDevice, static_cast<hipStream_t>(stream)));
+    return COPO_OK;
+}
+
+extern "C" int copo_field_record(copo_field* h, const uint8_t* flags, const float* ttc, int32_t accumulate, void* stream) {
+    if (!h) return fail(COPO_ERR_NULL, "copo_field_record: NULL handle");
+    if (accumulate != 0 && accumulate != 1) return fail(COPO_ERR_DIM, "copo_field_record: accumulate=%d (0 or 1)", accumulate);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const FieldArgs a = field_args(h, flags, ttc);
+    if (accumulate) HIP_TRY(hipMemsetAsync(h->mask, 0, h->mask_bytes, st));
+    HIP_TRY(launch_field_events(a, accumulate, st));
+    if (accumulate) HIP_TRY(launch_field_tiles(a, st));
+    return COPO_OK;
+}
+
+extern "C" int copo_field_read(copo_field* h, int64_t* maps_dev, int64_t* scene_records_dev, void* stream) {
+    if (!h || (!maps_dev && !scene_records_dev)) return fail(COPO_ERR_NULL, "copo_field_read: NULL argument");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (maps_dev) HIP_TRY(hipMemcpyAsync(maps_dev, h->maps, h->maps_bytes, hipMemcpyDeviceToDevice, st));
+    if (scene_records_dev) HIP_TRY(hipMemcpyAsync(scene_records_dev, h->scene_records, h->rec_bytes, hipMemcpyDeviceToDevice, st));
+    return COPO_OK;
+}
+
+extern "C" int copo_field_forget(copo_field* h, void* stream) {
+    if (!h) return fail(COPO_ERR_NULL, "copo_field_forget: NULL handle");
+    HIP_TRY(hipMemsetAsync(h->last, 0xff, h->last_bytes, static_cast<hipStream_t>(stream)));
+    return COPO_OK;
+}
+
+extern "C" int copo_field_reset(copo_field* h, void* stream) {
+    if (!h) return fail(COPO_ERR_NULL, "copo_field_reset: NULL handle");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    HIP_TRY(hipMemsetAsync(h->maps, 0, h->maps_bytes, st));
+    HIP_TRY(hipMemsetAsync(h->scene_records, 0, h->rec_bytes, st));
+    HIP_TRY(hipMemsetAsync(h->last, 0xff, h->last_bytes, st));
     return COPO_OK;
 }

@@ -62,7 +62,7 @@ class MultiAgentMetaDrive:
     @classmethod
     def default_config(cls):
         return dict(map=cls.MAP, num_envs=1, num_agents=None, start_seed=5000, horizon=1000, num_lasers=72,
-                    device=0, crash_done=True, out_of_road_done=True, allow_respawn=True, delay_done=25, interaction_metrics=False, event_clips=None, rewind=None)
+                    device=0, crash_done=True, out_of_road_done=True, allow_respawn=True, delay_done=25, interaction_metrics=False, event_clips=None, rewind=None, field_maps=None)
 
     def __init__(self, config=None):
         cfg = type(self).default_config()
@@ -78,6 +78,9 @@ class MultiAgentMetaDrive:
         if clip_kwargs and (clip_kwargs.get("ttc_below", 0.0) > 0.0 or clip_kwargs.get("gap_below", 0.0) > 0.0) \
                 and not cfg.get("interaction_metrics", False):
             raise ValueError("event_clips with ttc_below / gap_below reads the interaction meter: set interaction_metrics=True")
+        field_kwargs = None if cfg.get("field_maps") is None else dict(cfg["field_maps"])
+        if field_kwargs and field_kwargs.get("ttc_below", 0.0) > 0.0 and not cfg.get("interaction_metrics", False):
+            raise ValueError("field_maps with ttc_below reads the interaction meter: set interaction_metrics=True")
         sim_kwargs = {k: v for k, v in cfg.items() if k in SIM_KEYS and k not in ("enable_lcf",)}
         sim_kwargs["enable_lcf"] = bool(self.ENABLE_LCF and cfg.get("enable_copo", True))
         sim_kwargs.update(type(self)._extension_kwargs(cfg))
@@ -102,6 +105,11 @@ class MultiAgentMetaDrive:
         if cfg.get("rewind") is not None:
             from copo_amd.rewind import RewindBuffer
             self._rewind = RewindBuffer(self.sim, **dict(cfg["rewind"]))
+        self._fields = None        # `field_maps`: occupancy, speed, flow and event grids over scenes and steps (copo_amd/fields.py)
+        if field_kwargs is not None:
+            from copo_amd.fields import FieldMaps
+            explicit = all(k in field_kwargs for k in ("x0", "y0", "W", "H"))
+            self._fields = FieldMaps(self.sim, **field_kwargs) if explicit else FieldMaps.for_map(self.sim, **field_kwargs)
         self._slot_ids = None      # dict API state (num_envs == 1)
         self._next_obs = None
         self.current_lcf_mean, self.current_lcf_std = self.sim_config.lcf_mean, self.sim_config.lcf_std
@@ -159,6 +167,7 @@ class MultiAgentMetaDrive:
         self._restart_interaction()
         self._record_clips(None)
         self._record_rewind(True)
+        self._record_fields(None)
         return out
 
     def vec_step(self, actions):
@@ -167,6 +176,7 @@ class MultiAgentMetaDrive:
         self._record_interaction()
         self._record_clips(out["flags"])
         self._record_rewind(False)
+        self._record_fields(out["flags"])
         return out
 
     # ---- top-down rendering (copo/vis.py: env.render(mode="top_down", num_stack=25)) ------------------------------------------
@@ -254,6 +264,19 @@ class MultiAgentMetaDrive:
         assert self._rewind is not None, "set rewind={...} in the env config"
         return self._rewind
 
+    # ---- field maps (config key `field_maps`: None, or the arguments of `FieldMaps` -- with x0, y0, W, H an explicit grid, else
+    #      `FieldMaps.for_map`): one record of the state after reset (no flags: no event) and after every step, fed with the step's flags
+    #      and, for the critical layer, the meter's ttc of that state.  The maps are kept over resets ----
+    def _record_fields(self, flags):
+        f = self._fields
+        if f is not None:
+            f.record(flags=flags, ttc=self._meter.ttc if f.ttc_below > 0.0 else None)
+
+    def field_maps(self):
+        """The env's `copo_amd.fields.FieldMaps`."""
+        assert self._fields is not None, "set field_maps={...} in the env config"
+        return self._fields
+
     def set_lcf_dist(self, mean, std):
         assert self.ENABLE_LCF, "set_lcf_dist needs an LCF env (get_lcf_env)"
         assert std > 0.0 and -1.0 <= mean <= 1.0
@@ -300,6 +323,7 @@ class MultiAgentMetaDrive:
         self._restart_interaction()
         self._record_clips(None)
         self._record_rewind(True)
+        self._record_fields(None)
         ids = self._ids(out)
         self._slot_ids = ["agent%d" % a for a in ids]
         self._just_terminated = {}
@@ -322,6 +346,7 @@ class MultiAgentMetaDrive:
         self._record_interaction()
         self._record_clips(out["flags"])
         self._record_rewind(False)
+        self._record_fields(out["flags"])
         h = {k: v[0].cpu().numpy() for k, v in out.items() if v is not None}
         if self._meter is not None:      # of the state after the step: +inf for an agent that ended in it
             h["min_gap"], h["ttc"] = self._meter.gap[0].cpu().numpy(), self._meter.ttc[0].cpu().numpy()
@@ -413,6 +438,9 @@ class MultiAgentMetaDrive:
         if getattr(self, "_rewind", None) is not None:
             self._rewind.close()
             self._rewind = None
+        if getattr(self, "_fields", None) is not None:
+            self._fields.close()
+            self._fields = None
         self.sim.close()
 
 

@@ -3,6 +3,7 @@ top-down frames written to disk.
 
     python -m copo_amd.vis --env inter --algo copo --weights FILE.npz [--key copo_inter] --steps 300 --out DIR [--gif] [--follow SLOT]
                            [--interaction] [--clips [--clip-pre N] [--clip-post N] [--clip-on crash,out,ttc<1.0,gap<0.5]]
+                           [--heatmap LAYER [--heatmap-out FILE.ppm]]
     python -m copo_amd.vis --replay FILE.npz --out DIR [--size W H] [--follow SLOT]
 
 `--weights` is a population file (`{ALGO}_{ENV}.npz` with the reference's key layout); `--key NAME` takes the arrays stored under
@@ -15,6 +16,10 @@ agents of the run, finished or not, at the end.
 event of `--clip-on` -- step flags by name, `ttc<SECONDS`, `gap<METRES` -- are kept as clips, written at the end to `DIR/clips.npz` and,
 played back, to `DIR/clip_000/frame_00000.ppm`, ...  `--replay FILE.npz` renders the clips of such a file again: no policy, no
 simulator run, no `--weights`.
+
+`--heatmap LAYER` runs the field maps (copo_amd/fields.py, 1 m cells over the map) next to the rollout and writes, after the run, the map
+view with that layer -- one of the ten integer layers, `mean_speed` or `occupancy_s` -- blended over it to `--heatmap-out` (default
+`DIR/heatmap_LAYER.ppm`); `critical` counts the steps below a time to collision of 1.5 s.
 """
 import argparse
 import os
@@ -44,10 +49,26 @@ def load_policy(algo, env, weights_path, key=None):
     return pf
 
 
-def make_env(env, interaction=False, clips=None):
+def make_env(env, interaction=False, clips=None, fields=None):
     from copo_amd.torch_copo.utils import env_wrappers as W
     cls_name, n = _SCENES[env]
-    return getattr(W, cls_name)(dict(num_agents=n, interaction_metrics=bool(interaction), event_clips=clips))
+    return getattr(W, cls_name)(dict(num_agents=n, interaction_metrics=bool(interaction), event_clips=clips, field_maps=fields))
+
+
+HEATMAP_LAYERS = ("occupancy", "wreck", "visits", "speed_q", "vx_q", "vy_q", "crash", "out", "arrive", "critical", "mean_speed", "occupancy_s")
+
+
+def write_heatmap(env, layer, path, film_size=(512, 512)):
+    """The map view of scene 0 without a trail, `layer` of the env's field maps (group 0) blended over it, as one PPM; returns the path."""
+    from copo_amd.render import map_view
+    fm = env.field_maps()
+    frame = env.render(mode="top_down", num_stack=1, film_size=film_size)
+    out = fm.heat_overlay(frame, fm.read()[layer][0], map_view(env.sim.tables, int(film_size[0]), int(film_size[1])))
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    with open(path, "wb") as fh:                 # (binary PPM, as `render.write_ppm` writes its numbered frames)
+        fh.write(b"P6\n%d %d\n255\n" % (out.shape[1], out.shape[0]))
+        fh.write(out.tobytes())
+    return path
 
 
 def parse_clip_on(spec):
@@ -90,13 +111,19 @@ def replay(path, out, film_size=(512, 512), follow=None):
 
 
 def run(env_name, algo, weights, steps, out, key=None, gif=False, follow=None, film_size=(512, 512), seed=0, fps=10, interaction=False,
-        clips=None):
+        clips=None, heatmap=None, heatmap_out=None):
     """Roll `steps` env steps, writing one frame per step; returns the list of frame paths.  `clips`: the arguments of a `ClipRecorder`
     (then `out/clips.npz` and the played-back clips are written too)."""
     from copo_amd.render import write_gif, write_ppm
     np.random.seed(seed)
     policy = load_policy(algo, env_name, weights, key)
-    env = make_env(env_name, interaction or bool(clips and (clips.get("ttc_below") or clips.get("gap_below"))), clips)
+    fields = None
+    if heatmap is not None:
+        if heatmap not in HEATMAP_LAYERS:
+            raise ValueError("--heatmap %r: one of %s" % (heatmap, ", ".join(HEATMAP_LAYERS)))
+        fields = dict(cell=1.0, ttc_below=1.5 if heatmap == "critical" else 0.0)
+    env = make_env(env_name, interaction or bool(clips and (clips.get("ttc_below") or clips.get("gap_below"))) or heatmap == "critical", clips,
+                   fields)
     clipset = None
     paths, kept = [], []
     try:
@@ -126,6 +153,9 @@ def run(env_name, algo, weights, steps, out, key=None, gif=False, follow=None, f
             print({"interaction, agents still driving included": env.interaction_summary(flush_open=True)})
         if clips is not None:
             clipset = env.event_clips(flush=True)
+        if heatmap is not None:
+            p = write_heatmap(env, heatmap, heatmap_out or os.path.join(out, "heatmap_%s.ppm" % heatmap), film_size)
+            print("wrote the %s map of %d records to %s" % (heatmap, env.field_maps().n_records, p))
     finally:
         env.close()
     if gif and kept:
@@ -155,6 +185,8 @@ def main(argv=None):
     ap.add_argument("--clip-pre", type=int, default=24, help="steps kept before an event")
     ap.add_argument("--clip-post", type=int, default=8, help="steps kept after an event")
     ap.add_argument("--clip-on", default="crash", help="events: step flags by name, ttc<SECONDS, gap<METRES, comma separated")
+    ap.add_argument("--heatmap", default=None, metavar="LAYER", help="field maps: write the map view with this layer over it (%s)" % ", ".join(HEATMAP_LAYERS))
+    ap.add_argument("--heatmap-out", default=None, metavar="FILE.ppm", help="where the overlay goes (default DIR/heatmap_LAYER.ppm)")
     ap.add_argument("--replay", default=None, metavar="FILE.npz", help="render the clips of a saved clip set instead of running a policy")
     a = ap.parse_args(argv)
     if a.replay:
@@ -165,7 +197,7 @@ def main(argv=None):
         ap.error("--weights is required (unless --replay)")
     clips = dict(pre=a.clip_pre, post=a.clip_post, **parse_clip_on(a.clip_on)) if a.clips else None
     paths = run(a.env, a.algo, a.weights, a.steps, a.out, key=a.key, gif=a.gif, follow=a.follow, film_size=tuple(a.size), seed=a.seed,
-                interaction=a.interaction, clips=clips)
+                interaction=a.interaction, clips=clips, heatmap=a.heatmap, heatmap_out=a.heatmap_out)
     print("wrote %d frames to %s" % (len(paths), a.out))
 
 

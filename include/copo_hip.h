@@ -415,6 +415,49 @@ int copo_rewind_fork(copo_rewind* h, copo_sim* target, int32_t first, int32_t S,
 int copo_rewind_tally(const uint8_t* flags, const int32_t* watch_slot, int32_t* tally, int32_t B, int32_t N, void* stream);
 int copo_rewind_destroy(copo_rewind* h);
 
+/* ---- traffic field maps: where the scenes of a simulator drive, queue, crash and come close, summed on the device over scenes and
+ *      records into integer grids.  A handle reads its simulator's state and must be destroyed before it.  Eager
+ *      only.  Every accumulator is an integer, so the maps do not depend on the order the device adds in.
+ * Grid: cell (ix, iy) of W x H has the centre (x0 + (ix + 0.5) cell, y0 + (iy + 0.5) cell).  Scene e adds to the maps of group
+ * group[e] (all 0 after create); a value outside 0..G-1 (checked on the device) contributes nothing.  Bodies are read as the interaction
+ * meter reads them: state fields 0..3 (x, y, heading, speed), the status byte of field 13, veh_half_len x veh_half_wid.  Centre cell of a
+ * body: (floor((x - x0) inv), floor((y - y0) inv)) in fp32, every operation rounded by itself, inv = 1 / cell rounded once to fp32; outside
+ * the grid: no centre-cell layer.  Footprint: the cells whose centre p has |u . (p - c)| <= half_len and |n . (p - c)| <= half_wid.
+ * Layers, int64 [G][COPO_FIELD_LAYERS][H][W], what one accumulating record adds:
+ *   0 occupancy  +1 in every footprint cell of every ALIVE body        1 wreck   the same for every WRECK body
+ *   2 visits     +1 in the centre cell of every ALIVE body             3 speed_q rint(min(max(v, 0), 255) * 256) there (half to even)
+ *   4 vx_q, 5 vy_q   rint(min(max(v, -255), 255) * cos(heading) * 256), the same with sin, signed, there
+ *   6 crash, 7 out, 8 arrive   +1 at the LAST-SEEN cell of every slot whose flags carry DONE and CRASH / OUT / ARRIVE (one per set bit)
+ *   9 critical   +1 in the centre cell of every ALIVE slot with ttc < ttc_below (plain fp32 <; NULL array or threshold 0: off)
+ * scene_records int64 [G]: the scenes of each group over the accumulating records.  Last seen: per slot, the centre cell of the previous
+ * record of this handle if the slot was ALIVE inside the grid then (else none: no event counts); events are counted first, then the
+ * memory is overwritten from the current state.  Events count in EVERY record, also with accumulate = 0. ---- */
+#define COPO_FIELD_LAYERS 10
+#define COPO_FIELD_MAX_SIDE 1024
+#define COPO_FIELD_MAX_GROUPS 64
+typedef struct copo_field_cfg {
+    float x0, y0, cell;        /* finite; cell > 0 (COPO_ERR_DIM) */
+    int32_t W, H;              /* 1..COPO_FIELD_MAX_SIDE (COPO_ERR_DIM) */
+    int32_t G;                 /* 1..COPO_FIELD_MAX_GROUPS (COPO_ERR_DIM) */
+    float ttc_below;           /* >= 0 and finite (COPO_ERR_CONFIG); 0: the critical layer is off */
+} copo_field_cfg;
+typedef struct copo_field copo_field;
+/* allocates the maps (80 G H W bytes) and 4 E N bytes of last-seen memory: COPO_ERR_DEVICE when the device refuses */
+int copo_field_create(copo_sim* sim, const copo_field_cfg* cfg, copo_field** out);
+/* group_dev: device [E] int32, copied on `stream` */
+int copo_field_set_groups(copo_field* h, const int32_t* group_dev, void* stream);
+/* one record of the current state.  flags: device [E][N] uint8 (the step's output) or NULL (after a reset: no event); ttc: device [E][N]
+ * fp32 (the meter's output) or NULL; accumulate: 1, or 0 = events and the last-seen memory only (COPO_ERR_DIM otherwise).  At most three
+ * stream operations, no allocation, no host synchronisation; simulator memory is only read. */
+int copo_field_record(copo_field* h, const uint8_t* flags, const float* ttc, int32_t accumulate, void* stream);
+/* device to device: maps_dev [G][COPO_FIELD_LAYERS][H][W] int64, scene_records_dev [G] int64; either may be NULL, not both */
+int copo_field_read(copo_field* h, int64_t* maps_dev, int64_t* scene_records_dev, void* stream);
+/* forget the last-seen memory only (after a manual reset or set_state: the next record fires no event) */
+int copo_field_forget(copo_field* h, void* stream);
+/* zero the maps and scene_records and forget the last-seen memory; the groups stay */
+int copo_field_reset(copo_field* h, void* stream);
+int copo_field_destroy(copo_field* h);
+
 /* ---- stateless ops ---- */
 
 /* CCEnv._update_distance_map + _find_in_range (env_wrappers.py:125-158) + LCFEnv reward block (:313-326).
