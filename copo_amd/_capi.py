@@ -88,6 +88,15 @@ class FieldCfg(C.Structure):
 
 FIELD_LAYERS, FIELD_MAX_SIDE, FIELD_MAX_GROUPS = 10, 1024, 64
 
+
+class GateCfg(C.Structure):
+    """Mirror of `copo_gate_cfg`."""
+    _fields_ = [("L", C.c_int32), ("S", C.c_int32), ("G", C.c_int32), ("T", C.c_int32), ("bin_records", C.c_int32), ("HB", C.c_int32),
+                ("TB", C.c_int32), ("tt_bin", C.c_int32)]
+
+
+GATE_MAX_GATES, GATE_MAX_SECTIONS, GATE_MAX_GROUPS, GATE_MAX_BINS, GATE_MAX_HIST = 32, 64, 64, 256, 64
+
 HEAD_PPO, HEAD_META_NEW, HEAD_META_OLD = 0, 1, 2
 OPERAND_F32, OPERAND_BF16 = 0, 1
 PPO_STATS = 8
@@ -179,6 +188,14 @@ _SIGS = {
     "copo_field_forget": (C.c_int, [C.c_void_p, C.c_void_p]),
     "copo_field_reset": (C.c_int, [C.c_void_p, C.c_void_p]),
     "copo_field_destroy": (C.c_int, [C.c_void_p]),
+    "copo_gate_create": (C.c_int, [C.c_void_p, C.POINTER(GateCfg), C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
+    "copo_gate_set_groups": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "copo_gate_record": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "copo_gate_words": (C.c_int64, [C.POINTER(GateCfg)]),
+    "copo_gate_read": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_void_p]),
+    "copo_gate_forget": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "copo_gate_reset": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "copo_gate_destroy": (C.c_int, [C.c_void_p]),
     "copo_neighbours_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_float,
                                       C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                       C.c_void_p, C.c_void_p]),

@@ -17,6 +17,7 @@
 #include "clip_common.h"
 #include "rewind_common.h"
 #include "field_common.h"
+#include "gate_common.h"
 
 using namespace copo;
 
@@ -1178,5 +1179,155 @@ extern "C" int copo_field_reset(copo_field* h, void* stream) {
     HIP_TRY(hipMemsetAsync(h->maps, 0, h->maps_bytes, st));
     HIP_TRY(hipMemsetAsync(h->scene_records, 0, h->rec_bytes, st));
     HIP_TRY(hipMemsetAsync(h->last, 0xff, h->last_bytes, st));
+    return COPO_OK;
+}
+
+// ---- traffic gates (gate_kernels.hip) --------------------------------------------------------------------------
+
+struct copo_gate {
+    copo_sim* sim;
+    copo_gate_cfg cfg;
+    GateLayout at;
+    int32_t n_records;             // records since create / reset (host side: eager only)
+    float4* gates;                 // [L]
+    int2* sections;                // [max(S, 1)]
+    int32_t* group;                // [E]
+    uint32_t *mem_x, *mem_y;       // [E][N]
+    int32_t* mem_aid;              // [E][N]
+    int32_t* mem_episode;          // [E]
+    unsigned long long* mem_valid; // [E]
+    int32_t* last_fwd;             // [E][L]
+    int32_t* entry;                // [E][max(S, 1)][N]
+    long long* acc;                // [at.words]
+    size_t slot_bytes, valid_bytes, fwd_bytes, entry_bytes, acc_bytes;
+};
+
+static void free_gate(copo_gate* h) {
+    for (void* a : {(void*)h->gates, (void*)h->sections, (void*)h->group, (void*)h->mem_x, (void*)h->mem_y, (void*)h->mem_aid,
+                    (void*)h->mem_episode, (void*)h->mem_valid, (void*)h->last_fwd, (void*)h->entry, (void*)h->acc})
+        if (a) (void)hipFree(a);
+    delete h;
+}
+
+// the slot memory, last_fwd and entry: nothing is followed, nothing crossed
+static hipError_t gate_forget(copo_gate* h, hipStream_t st) {
+    hipError_t err = hipMemsetAsync(h->mem_valid, 0, h->valid_bytes, st);
+    if (err == hipSuccess) err = hipMemsetAsync(h->last_fwd, 0xff, h->fwd_bytes, st);
+    if (err == hipSuccess) err = hipMemsetAsync(h->entry, 0xff, h->entry_bytes, st);
+    return err;
+}
+
+extern "C" int copo_gate_create(copo_sim* sim, const copo_gate_cfg* cfg, const float* gates, const int32_t* sections, copo_gate** out) {
+    if (!sim || !cfg || !gates || !out || (cfg && cfg->S > 0 && !sections)) return fail(COPO_ERR_NULL, "copo_gate_create: NULL argument");
+    *out = nullptr;
+    static_assert(COPO_GATE_MAX_GATES == GATE_MAX_GATES && COPO_GATE_MAX_SECTIONS == GATE_MAX_SECTIONS && COPO_GATE_MAX_GROUPS == GATE_MAX_GROUPS &&
+                  COPO_GATE_MAX_BINS == GATE_MAX_BINS && COPO_GATE_MAX_HIST == GATE_MAX_HIST, "copo_hip.h / gate_common.h");
+    if (cfg->L < 1 || cfg->L > GATE_MAX_GATES || cfg->S < 0 || cfg->S > GATE_MAX_SECTIONS || cfg->G < 1 || cfg->G > GATE_MAX_GROUPS ||
+        cfg->T < 1 || cfg->T > GATE_MAX_BINS || cfg->bin_records < 1 || cfg->HB < 1 || cfg->HB > GATE_MAX_HIST || cfg->TB < 1 ||
+        cfg->TB > GATE_MAX_HIST || cfg->tt_bin < 1)
+        return fail(COPO_ERR_DIM, "copo_gate_create: L=%d (1..%d) S=%d (0..%d) G=%d (1..%d) T=%d (1..%d) bin_records=%d (>= 1) HB=%d TB=%d (1..%d) tt_bin=%d (>= 1)",
+                    cfg->L, GATE_MAX_GATES, cfg->S, GATE_MAX_SECTIONS, cfg->G, GATE_MAX_GROUPS, cfg->T, GATE_MAX_BINS, cfg->bin_records, cfg->HB,
+                    cfg->TB, GATE_MAX_HIST, cfg->tt_bin);
+    for (int s = 0; s < cfg->S; ++s)
+        if (sections[2 * s] < 0 || sections[2 * s] >= cfg->L || sections[2 * s + 1] < 0 || sections[2 * s + 1] >= cfg->L)
+            return fail(COPO_ERR_DIM, "copo_gate_create: section %d = (%d, %d): gate indices are 0..%d", s, sections[2 * s], sections[2 * s + 1], cfg->L - 1);
+    for (int l = 0; l < cfg->L; ++l) {
+        const float* q = gates + 4 * l;
+        if (!std::isfinite(q[0]) || !std::isfinite(q[1]) || !std::isfinite(q[2]) || !std::isfinite(q[3]) || (q[0] == q[2] && q[1] == q[3]))
+            return fail(COPO_ERR_CONFIG, "copo_gate_create: gate %d = (%g, %g) -> (%g, %g): finite, A != B", l, (double)q[0], (double)q[1], (double)q[2],
+                        (double)q[3]);
+    }
+    const size_t E = (size_t)sim->p.E, N = (size_t)sim->p.N, L = (size_t)cfg->L, S1 = (size_t)std::max(cfg->S, 1);
+    HIP_TRY(hipSetDevice(sim->device));
+    copo_gate* h = new (std::nothrow) copo_gate();
+    if (!h) return fail(COPO_ERR_DEVICE, "out of host memory");
+    h->sim = sim; h->cfg = *cfg; h->n_records = 0;
+    h->at = gate_layout(cfg->G, cfg->L, cfg->S, cfg->T, cfg->HB, cfg->TB);
+    h->slot_bytes = E * N * 4; h->valid_bytes = E * sizeof(unsigned long long); h->fwd_bytes = E * L * sizeof(int32_t);
+    h->entry_bytes = E * S1 * N * sizeof(int32_t); h->acc_bytes = (size_t)h->at.words * sizeof(long long);
+    hipError_t err = hipMalloc((void**)&h->gates, L * sizeof(float4));
+    if (err == hipSuccess) err = hipMalloc((void**)&h->sections, S1 * sizeof(int2));
+    if (err == hipSuccess) err = hipMalloc((void**)&h->group, E * sizeof(int32_t));
+    if (err == hipSuccess) err = hipMalloc((void**)&h->mem_x, h->slot_bytes);
+    if (err == hipSuccess) err = hipMalloc((void**)&h->mem_y, h->slot_bytes);
+    if (err == hipSuccess) err = hipMalloc((void**)&h->mem_aid, h->slot_bytes);
+    if (err == hipSuccess) err = hipMalloc((void**)&h->mem_episode, E * sizeof(int32_t));
+    if (err == hipSuccess) err = hipMalloc((void**)&h->mem_valid, h->valid_bytes);
+    if (err == hipSuccess) err = hipMalloc((void**)&h->last_fwd, h->fwd_bytes);
+    if (err == hipSuccess) err = hipMalloc((void**)&h->entry, h->entry_bytes);
+    if (err == hipSuccess) err = hipMalloc((void**)&h->acc, h->acc_bytes);
+    if (err == hipSuccess) err = hipMemcpy(h->gates, gates, L * sizeof(float4), hipMemcpyHostToDevice);
+    if (err == hipSuccess) err = hipMemset(h->sections, 0, S1 * sizeof(int2));
+    if (err == hipSuccess && cfg->S > 0) err = hipMemcpy(h->sections, sections, (size_t)cfg->S * sizeof(int2), hipMemcpyHostToDevice);
+    if (err == hipSuccess) err = hipMemset(h->group, 0, E * sizeof(int32_t));
+    if (err == hipSuccess) err = hipMemset(h->mem_x, 0, h->slot_bytes);
+    if (err == hipSuccess) err = hipMemset(h->mem_y, 0, h->slot_bytes);
+    if (err == hipSuccess) err = hipMemset(h->mem_aid, 0, h->slot_bytes);
+    if (err == hipSuccess) err = hipMemset(h->mem_episode, 0, E * sizeof(int32_t));
+    if (err == hipSuccess) err = hipMemset(h->acc, 0, h->acc_bytes);
+    if (err == hipSuccess) err = gate_forget(h, nullptr);
+    if (err == hipSuccess) err = hipDeviceSynchronize();
+    if (err != hipSuccess) {
+        (void)hipGetLastError();               // (a refused request must not show up as the next launch's error)
+        free_gate(h);
+        return fail(COPO_ERR_DEVICE, "copo_gate_create: %s (slot memory %zu bytes)", hipGetErrorString(err), E * N * 12 + E * S1 * N * 4);
+    }
+    *out = h;
+    return COPO_OK;
+}
+
+extern "C" int copo_gate_destroy(copo_gate* h) {
+    if (!h) return fail(COPO_ERR_NULL, "copo_gate_destroy: NULL handle");
+    (void)hipSetDevice(h->sim->device);
+    free_gate(h);
+    return COPO_OK;
+}
+
+extern "C" int copo_gate_set_groups(copo_gate* h, const int32_t* group_dev, void* stream) {
+    if (!h || !group_dev) return fail(COPO_ERR_NULL, "copo_gate_set_groups: NULL argument");
+    HIP_TRY(hipMemcpyAsync(h->group, group_dev, (size_t)h->sim->p.E * sizeof(int32_t), hipMemcpyDeviceToDevice, static_cast<hipStream_t>(stream)));
+    return COPO_OK;
+}
+
+extern "C" int copo_gate_record(copo_gate* h, void* stream) {
+    if (!h) return fail(COPO_ERR_NULL, "copo_gate_record: NULL handle");
+    if (h->n_records == INT32_MAX) return fail(COPO_ERR_STATE, "copo_gate_record: %d records made; reset the handle", h->n_records);
+    const SimParams& p = h->sim->p;
+    GateArgs a;
+    a.state = p.state; a.env = p.env; a.E = p.E; a.N = p.N;
+    a.L = h->cfg.L; a.S = h->cfg.S; a.G = h->cfg.G; a.T = h->cfg.T; a.HB = h->cfg.HB; a.TB = h->cfg.TB; a.tt_bin = h->cfg.tt_bin;
+    a.r = h->n_records; a.tbin = std::min(h->n_records / h->cfg.bin_records, h->cfg.T - 1);
+    a.gates = h->gates; a.sections = h->sections; a.group = h->group;
+    a.mem_x = h->mem_x; a.mem_y = h->mem_y; a.mem_aid = h->mem_aid; a.mem_episode = h->mem_episode; a.mem_valid = h->mem_valid;
+    a.last_fwd = h->last_fwd; a.entry = h->entry; a.acc = h->acc; a.at = h->at;
+    HIP_TRY(launch_gate_record(a, static_cast<hipStream_t>(stream)));
+    h->n_records += 1;
+    return COPO_OK;
+}
+
+extern "C" int64_t copo_gate_words(const copo_gate_cfg* cfg) {
+    if (!cfg) return 0;
+    return gate_layout(cfg->G, cfg->L, cfg->S, cfg->T, cfg->HB, cfg->TB).words;
+}
+
+extern "C" int copo_gate_read(copo_gate* h, int64_t* acc_dev, int32_t* n_records, void* stream) {
+    if (!h || (!acc_dev && !n_records)) return fail(COPO_ERR_NULL, "copo_gate_read: NULL argument");
+    if (acc_dev) HIP_TRY(hipMemcpyAsync(acc_dev, h->acc, h->acc_bytes, hipMemcpyDeviceToDevice, static_cast<hipStream_t>(stream)));
+    if (n_records) *n_records = h->n_records;
+    return COPO_OK;
+}
+
+extern "C" int copo_gate_forget(copo_gate* h, void* stream) {
+    if (!h) return fail(COPO_ERR_NULL, "copo_gate_forget: NULL handle");
+    HIP_TRY(gate_forget(h, static_cast<hipStream_t>(stream)));
+    return COPO_OK;
+}
+
+extern "C" int copo_gate_reset(copo_gate* h, void* stream) {
+    if (!h) return fail(COPO_ERR_NULL, "copo_gate_reset: NULL handle");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    HIP_TRY(gate_forget(h, st));
+    HIP_TRY(hipMemsetAsync(h->acc, 0, h->acc_bytes, st));
+    h->n_records = 0;
     return COPO_OK;
 }

@@ -62,7 +62,7 @@ class MultiAgentMetaDrive:
     @classmethod
     def default_config(cls):
         return dict(map=cls.MAP, num_envs=1, num_agents=None, start_seed=5000, horizon=1000, num_lasers=72,
-                    device=0, crash_done=True, out_of_road_done=True, allow_respawn=True, delay_done=25, interaction_metrics=False, event_clips=None, rewind=None, field_maps=None)
+                    device=0, crash_done=True, out_of_road_done=True, allow_respawn=True, delay_done=25, interaction_metrics=False, event_clips=None, rewind=None, field_maps=None, traffic_gates=None)
 
     def __init__(self, config=None):
         cfg = type(self).default_config()
@@ -110,6 +110,11 @@ class MultiAgentMetaDrive:
             from copo_amd.fields import FieldMaps
             explicit = all(k in field_kwargs for k in ("x0", "y0", "W", "H"))
             self._fields = FieldMaps(self.sim, **field_kwargs) if explicit else FieldMaps.for_map(self.sim, **field_kwargs)
+        self._gates = None         # `traffic_gates`: line-crossing counts, headways and travel times per gate (copo_amd/gates.py)
+        if cfg.get("traffic_gates") is not None:
+            from copo_amd.gates import TrafficGates
+            gate_kwargs = dict(cfg["traffic_gates"])
+            self._gates = TrafficGates(self.sim, **gate_kwargs) if "gates" in gate_kwargs else TrafficGates.for_map(self.sim, **gate_kwargs)
         self._slot_ids = None      # dict API state (num_envs == 1)
         self._next_obs = None
         self.current_lcf_mean, self.current_lcf_std = self.sim_config.lcf_mean, self.sim_config.lcf_std
@@ -168,6 +173,7 @@ class MultiAgentMetaDrive:
         self._record_clips(None)
         self._record_rewind(True)
         self._record_fields(None)
+        self._record_gates(True)
         return out
 
     def vec_step(self, actions):
@@ -177,6 +183,7 @@ class MultiAgentMetaDrive:
         self._record_clips(out["flags"])
         self._record_rewind(False)
         self._record_fields(out["flags"])
+        self._record_gates(False)
         return out
 
     # ---- top-down rendering (copo/vis.py: env.render(mode="top_down", num_stack=25)) ------------------------------------------
@@ -277,6 +284,21 @@ class MultiAgentMetaDrive:
         assert self._fields is not None, "set field_maps={...} in the env config"
         return self._fields
 
+    # ---- traffic gates (config key `traffic_gates`: None, or the arguments of `TrafficGates` -- with `gates` explicit gates, else
+    #      `TrafficGates.for_map`): one record after every step; after a reset by hand the memory is forgotten first, so that the reset
+    #      fires nothing.  The accumulators are kept over resets ----
+    def _record_gates(self, after_reset):
+        g = self._gates
+        if g is not None:
+            if after_reset:
+                g.forget()
+            g.record()
+
+    def traffic_gates(self):
+        """The env's `copo_amd.gates.TrafficGates`."""
+        assert self._gates is not None, "set traffic_gates={...} in the env config"
+        return self._gates
+
     def set_lcf_dist(self, mean, std):
         assert self.ENABLE_LCF, "set_lcf_dist needs an LCF env (get_lcf_env)"
         assert std > 0.0 and -1.0 <= mean <= 1.0
@@ -324,6 +346,7 @@ class MultiAgentMetaDrive:
         self._record_clips(None)
         self._record_rewind(True)
         self._record_fields(None)
+        self._record_gates(True)
         ids = self._ids(out)
         self._slot_ids = ["agent%d" % a for a in ids]
         self._just_terminated = {}
@@ -347,6 +370,7 @@ class MultiAgentMetaDrive:
         self._record_clips(out["flags"])
         self._record_rewind(False)
         self._record_fields(out["flags"])
+        self._record_gates(False)
         h = {k: v[0].cpu().numpy() for k, v in out.items() if v is not None}
         if self._meter is not None:      # of the state after the step: +inf for an agent that ended in it
             h["min_gap"], h["ttc"] = self._meter.gap[0].cpu().numpy(), self._meter.ttc[0].cpu().numpy()
@@ -441,6 +465,9 @@ class MultiAgentMetaDrive:
         if getattr(self, "_fields", None) is not None:
             self._fields.close()
             self._fields = None
+        if getattr(self, "_gates", None) is not None:
+            self._gates.close()
+            self._gates = None
         self.sim.close()
 
 

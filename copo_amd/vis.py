@@ -3,7 +3,7 @@ top-down frames written to disk.
 
     python -m copo_amd.vis --env inter --algo copo --weights FILE.npz [--key copo_inter] --steps 300 --out DIR [--gif] [--follow SLOT]
                            [--interaction] [--clips [--clip-pre N] [--clip-post N] [--clip-on crash,out,ttc<1.0,gap<0.5]]
-                           [--heatmap LAYER [--heatmap-out FILE.ppm]]
+                           [--heatmap LAYER [--heatmap-out FILE.ppm]] [--gates [--gate-inset METRES]]
     python -m copo_amd.vis --replay FILE.npz --out DIR [--size W H] [--follow SLOT]
 
 `--weights` is a population file (`{ALGO}_{ENV}.npz` with the reference's key layout); `--key NAME` takes the arrays stored under
@@ -20,6 +20,10 @@ simulator run, no `--weights`.
 `--heatmap LAYER` runs the field maps (copo_amd/fields.py, 1 m cells over the map) next to the rollout and writes, after the run, the map
 view with that layer -- one of the ten integer layers, `mean_speed` or `occupancy_s` -- blended over it to `--heatmap-out` (default
 `DIR/heatmap_LAYER.ppm`); `critical` counts the steps below a time to collision of 1.5 s.
+
+`--gates` runs the traffic gates (copo_amd/gates.py: an entry and an exit gate per route, `--gate-inset` metres from its ends) next to
+the rollout, draws them into every frame and prints the per-gate and per-section table -- crossings, vehicles per hour, mean speed,
+completed trips and mean travel time -- at the end.
 """
 import argparse
 import os
@@ -49,10 +53,10 @@ def load_policy(algo, env, weights_path, key=None):
     return pf
 
 
-def make_env(env, interaction=False, clips=None, fields=None):
+def make_env(env, interaction=False, clips=None, fields=None, gates=None):
     from copo_amd.torch_copo.utils import env_wrappers as W
     cls_name, n = _SCENES[env]
-    return getattr(W, cls_name)(dict(num_agents=n, interaction_metrics=bool(interaction), event_clips=clips, field_maps=fields))
+    return getattr(W, cls_name)(dict(num_agents=n, interaction_metrics=bool(interaction), event_clips=clips, field_maps=fields, traffic_gates=gates))
 
 
 HEATMAP_LAYERS = ("occupancy", "wreck", "visits", "speed_q", "vx_q", "vy_q", "crash", "out", "arrive", "critical", "mean_speed", "occupancy_s")
@@ -111,7 +115,7 @@ def replay(path, out, film_size=(512, 512), follow=None):
 
 
 def run(env_name, algo, weights, steps, out, key=None, gif=False, follow=None, film_size=(512, 512), seed=0, fps=10, interaction=False,
-        clips=None, heatmap=None, heatmap_out=None):
+        clips=None, heatmap=None, heatmap_out=None, gates=None):
     """Roll `steps` env steps, writing one frame per step; returns the list of frame paths.  `clips`: the arguments of a `ClipRecorder`
     (then `out/clips.npz` and the played-back clips are written too)."""
     from copo_amd.render import write_gif, write_ppm
@@ -123,7 +127,7 @@ def run(env_name, algo, weights, steps, out, key=None, gif=False, follow=None, f
             raise ValueError("--heatmap %r: one of %s" % (heatmap, ", ".join(HEATMAP_LAYERS)))
         fields = dict(cell=1.0, ttc_below=1.5 if heatmap == "critical" else 0.0)
     env = make_env(env_name, interaction or bool(clips and (clips.get("ttc_below") or clips.get("gap_below"))) or heatmap == "critical", clips,
-                   fields)
+                   fields, gates)
     clipset = None
     paths, kept = [], []
     try:
@@ -146,6 +150,9 @@ def run(env_name, algo, weights, steps, out, key=None, gif=False, follow=None, f
             ids = env._slot_ids or []
             track = ids[follow] if follow is not None and follow < len(ids) else None
             frame = env.render(mode="top_down", num_stack=25, film_size=film_size, track_agent=track)
+            if gates is not None and track is None:      # (the map view; a followed agent's view moves with it)
+                from copo_amd.render import map_view
+                frame = env.traffic_gates().gate_overlay(np.asarray(frame), map_view(env.sim.tables, int(film_size[0]), int(film_size[1])))
             paths += write_ppm(frame, out, start=t)
             if gif:
                 kept.append(frame)
@@ -153,6 +160,8 @@ def run(env_name, algo, weights, steps, out, key=None, gif=False, follow=None, f
             print({"interaction, agents still driving included": env.interaction_summary(flush_open=True)})
         if clips is not None:
             clipset = env.event_clips(flush=True)
+        if gates is not None:
+            print(env.traffic_gates().table())
         if heatmap is not None:
             p = write_heatmap(env, heatmap, heatmap_out or os.path.join(out, "heatmap_%s.ppm" % heatmap), film_size)
             print("wrote the %s map of %d records to %s" % (heatmap, env.field_maps().n_records, p))
@@ -187,6 +196,8 @@ def main(argv=None):
     ap.add_argument("--clip-on", default="crash", help="events: step flags by name, ttc<SECONDS, gap<METRES, comma separated")
     ap.add_argument("--heatmap", default=None, metavar="LAYER", help="field maps: write the map view with this layer over it (%s)" % ", ".join(HEATMAP_LAYERS))
     ap.add_argument("--heatmap-out", default=None, metavar="FILE.ppm", help="where the overlay goes (default DIR/heatmap_LAYER.ppm)")
+    ap.add_argument("--gates", action="store_true", help="traffic gates: draw them into the frames, print the flow table at the end")
+    ap.add_argument("--gate-inset", type=float, default=10.0, metavar="METRES", help="distance of the gates from the ends of every route")
     ap.add_argument("--replay", default=None, metavar="FILE.npz", help="render the clips of a saved clip set instead of running a policy")
     a = ap.parse_args(argv)
     if a.replay:
@@ -197,7 +208,8 @@ def main(argv=None):
         ap.error("--weights is required (unless --replay)")
     clips = dict(pre=a.clip_pre, post=a.clip_post, **parse_clip_on(a.clip_on)) if a.clips else None
     paths = run(a.env, a.algo, a.weights, a.steps, a.out, key=a.key, gif=a.gif, follow=a.follow, film_size=tuple(a.size), seed=a.seed,
-                interaction=a.interaction, clips=clips, heatmap=a.heatmap, heatmap_out=a.heatmap_out)
+                interaction=a.interaction, clips=clips, heatmap=a.heatmap, heatmap_out=a.heatmap_out,
+                gates=dict(inset=a.gate_inset) if a.gates else None)
     print("wrote %d frames to %s" % (len(paths), a.out))
 
 

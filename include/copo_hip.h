@@ -458,6 +458,69 @@ int copo_field_forget(copo_field* h, void* stream);
 int copo_field_reset(copo_field* h, void* stream);
 int copo_field_destroy(copo_field* h);
 
+/* ---- traffic gates: line-crossing counts, speeds, headways and travel times between gates, summed on the device over scenes and records
+ *      into int64 accumulators per scene group.  A handle reads its simulator's state and must be destroyed before
+ *      it.  Eager only: the record count lives on the host.  Every accumulator is an integer, so nothing depends on the order the device
+ *      adds in.
+ * Limits and inputs.  Gates: L in 1..COPO_GATE_MAX_GATES (COPO_ERR_DIM), each {ax, ay, bx, by} fp32, a directed segment A -> B in world
+ * coordinates, finite with A != B (COPO_ERR_CONFIG).  Sections: S in 0..COPO_GATE_MAX_SECTIONS pairs {gate_in, gate_out} of gate indices
+ * (they may be equal; an index outside 0..L-1: COPO_ERR_DIM).  Groups: G in 1..COPO_GATE_MAX_GROUPS; scene e adds to group[e] (all 0 after
+ * create); a value outside 0..G-1 (checked on the device) contributes nothing, but the scene's slot memory, last_fwd and entry records
+ * are still kept.  Bodies are read as the field maps read them: state fields 0, 1 (x, y) and 3 (speed), the status byte of field 13, field
+ * 14 (agent id), and env word 1 (episode).
+ * Continuity.  The handle keeps per slot, from its previous record: x and y as raw bits, the agent id, the scene's episode word and a
+ * valid bit.  A slot is FOLLOWED in this record iff it is ALIVE now, the memory is valid (the slot was ALIVE in the previous record of this
+ * handle), the agent id is equal and the episode is equal.  Otherwise the slot has no crossing in this record and its section entries
+ * are cleared.  Crossings are evaluated first, then the memory is overwritten from the current state: a respawn, a scene reset or a
+ * set_state never counts as a movement.  An agent's final step, after which its slot is no longer ALIVE, is not seen: a crossing made in
+ * that step is missed, at most one step per agent.
+ * Side of a gate.  All arithmetic is fp32, every operation rounded by itself (no contraction).  d = B - A;
+ * side(P) = d.x * (P.y - A.y) - d.y * (P.x - A.x).  FORWARD: side(prev) < 0 and side(cur) >= 0.  BACKWARD: side(prev) >= 0 and
+ * side(cur) < 0.  The crossing must also lie within the gate's extent: with m = cur - prev, a = m.x * (A.y - prev.y) - m.y * (A.x - prev.x)
+ * and b the same with B, (a <= 0 and b >= 0) or (a >= 0 and b <= 0).  Comparisons are plain fp32, so a NaN never crosses.
+ * Accumulators, int64, record r counting from 0 since create / reset:
+ *   count[G][L][2]       forward / backward crossings
+ *   speed_q[G][L][2]     sum of rint(min(max(v, 0), 255) * 256) over the crossings (half to even: the field maps' quantisation)
+ *   series[G][L][2][T]   the crossings again, in time bin min(r / bin_records, T - 1)
+ *   headway[G][L][HB]    forward crossings only.  The handle keeps last_fwd[E][L] (int32, -1 = none).  The forward crossings of one
+ *                        scene at one gate in one record are ordered by slot: the first has h = r - last_fwd and is counted only if
+ *                        last_fwd >= 0, every further one has h = 0; the bin is min(h, HB - 1); then last_fwd = r
+ *   sec_count[G][S], sec_sum[G][S], sec_hist[G][S][TB]
+ *                        the handle keeps entry[E][N][S] (int32, -1 = none).  A forward crossing of gate_in sets entry = r; after all
+ *                        entries of this record are written, a forward crossing of gate_out with entry >= 0 gives tt = r - entry:
+ *                        sec_count += 1, sec_sum += tt, sec_hist += 1 in bin min(tt / tt_bin, TB - 1); then entry = -1
+ *   scene_records[G]     += 1 per scene of the group and record
+ *   alive[G]             += the number of ALIVE slots (the density)
+ * They lie in ONE block of copo_gate_words() int64 words in this order, which copo_gate_read copies. ---- */
+#define COPO_GATE_MAX_GATES 32
+#define COPO_GATE_MAX_SECTIONS 64
+#define COPO_GATE_MAX_GROUPS 64
+#define COPO_GATE_MAX_BINS 256
+#define COPO_GATE_MAX_HIST 64
+typedef struct copo_gate_cfg {
+    int32_t L, S, G;           /* gates, sections, groups */
+    int32_t T, bin_records;    /* time bins of the series 1..COPO_GATE_MAX_BINS, records per bin >= 1 (COPO_ERR_DIM) */
+    int32_t HB;                /* headway bins (records), 1..COPO_GATE_MAX_HIST (COPO_ERR_DIM) */
+    int32_t TB, tt_bin;        /* travel-time bins 1..COPO_GATE_MAX_HIST of tt_bin >= 1 records each (COPO_ERR_DIM) */
+} copo_gate_cfg;
+typedef struct copo_gate copo_gate;
+/* gates: HOST [L][4] fp32; sections: HOST [S][2] int32 (NULL when S == 0).  Allocates 12 E N + 4 E N max(S, 1) + 4 E L + 12 E bytes of
+ * memory and the accumulators: COPO_ERR_DEVICE when the device refuses */
+int copo_gate_create(copo_sim* sim, const copo_gate_cfg* cfg, const float* gates, const int32_t* sections, copo_gate** out);
+/* group_dev: device [E] int32, copied on `stream` */
+int copo_gate_set_groups(copo_gate* h, const int32_t* group_dev, void* stream);
+/* one record of the current state: ONE launch on `stream`, no allocation, no host synchronisation; simulator memory is only read */
+int copo_gate_record(copo_gate* h, void* stream);
+/* int64 words of the accumulator block of a configuration (0 for NULL) */
+int64_t copo_gate_words(const copo_gate_cfg* cfg);
+/* device to device: acc_dev [copo_gate_words()] int64; n_records: HOST output, records since create / reset; either may be NULL, not both */
+int copo_gate_read(copo_gate* h, int64_t* acc_dev, int32_t* n_records, void* stream);
+/* forget the slot memory, last_fwd and entry only (after a manual reset or set_state: the next record fires nothing) */
+int copo_gate_forget(copo_gate* h, void* stream);
+/* the same, and zero the accumulators and the record count; the groups stay */
+int copo_gate_reset(copo_gate* h, void* stream);
+int copo_gate_destroy(copo_gate* h);
+
 /* ---- stateless ops ---- */
 
 /* CCEnv._update_distance_map + _find_in_range (env_wrappers.py:125-158) + LCFEnv reward block (:313-326).

@@ -42,7 +42,9 @@ def worker():
     torch.cuda.synchronize()
     dt = (time.perf_counter() - t0) / reps
     pa.status()
-    print("rank %d: %d mismatching calls of 200, %.1f us per call (n = %d floats, world %d, one shared GPU)" % (rank, bad, dt * 1e6, n, world), flush=True)
+    # one write for the line and its newline: the ranks share the pipe, and on an unbuffered stdout print() writes the two separately
+    sys.stdout.write("rank %d: %d mismatching calls of 200, %.1f us per call (n = %d floats, world %d, one shared GPU)\n" % (rank, bad, dt * 1e6, n, world))
+    sys.stdout.flush()
     pa.close()
     td.destroy_process_group()
     sys.exit(1 if bad else 0)
