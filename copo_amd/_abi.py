@@ -53,3 +53,43 @@ class SimCfg(C.Structure):
 class StepOut(C.Structure):
     """Mirror of `copo_step_out` (pointers, 0 = skip)."""
     _fields_ = [(n, C.c_void_p) for n in STEP_OUT_FIELDS]
+
+
+class InteractCfg(C.Structure):
+    """Mirror of `copo_interact_cfg`."""
+    _fields_ = [("horizon_s", C.c_float), ("ttc_crit_s", C.c_float), ("gap_near_m", C.c_float), ("brake_mps2", C.c_float)]
+
+
+class ClipCfg(C.Structure):
+    """Mirror of `copo_clip_cfg`."""
+    _fields_ = [("pre", C.c_int32), ("post", C.c_int32), ("max_clips", C.c_int32), ("flag_mask", C.c_uint32), ("ttc_below", C.c_float),
+                ("gap_below", C.c_float)]
+
+
+CLIP_MAX_CAP, CLIP_WORDS, CLIP_HEADER = 256, 6, 8
+
+
+class RewindCfg(C.Structure):
+    """Mirror of `copo_rewind_cfg`."""
+    _fields_ = [("depth", C.c_int32), ("stride", C.c_int32)]
+
+
+REWIND_MAX_DEPTH, REWIND_TALLY = 64, 8
+
+
+class FieldCfg(C.Structure):
+    """Mirror of `copo_field_cfg`."""
+    _fields_ = [("x0", C.c_float), ("y0", C.c_float), ("cell", C.c_float), ("W", C.c_int32), ("H", C.c_int32), ("G", C.c_int32),
+                ("ttc_below", C.c_float)]
+
+
+FIELD_LAYERS, FIELD_MAX_SIDE, FIELD_MAX_GROUPS = 10, 1024, 64
+
+
+class GateCfg(C.Structure):
+    """Mirror of `copo_gate_cfg`."""
+    _fields_ = [("L", C.c_int32), ("S", C.c_int32), ("G", C.c_int32), ("T", C.c_int32), ("bin_records", C.c_int32), ("HB", C.c_int32),
+                ("TB", C.c_int32), ("tt_bin", C.c_int32)]
+
+
+GATE_MAX_GATES, GATE_MAX_SECTIONS, GATE_MAX_GROUPS, GATE_MAX_BINS, GATE_MAX_HIST = 32, 64, 64, 256, 64

@@ -20,8 +20,7 @@ try:
 except ImportError:
     pass
 
-from ._abi import (ABI_VERSION, INFO_DIM, LINE_STRIDE, MAX_AGENTS, MAX_LASERS, MAX_LINES, MAX_ROUTES, MAX_SAFE,  # noqa: F401
-                   MAX_SEGS, MAX_SPAWNS, NAVI_DIM, SEG_STRIDE, STATE_DIM, STATE_FIELDS, SimCfg, StepOut)
+from ._abi import *  # noqa: F401,F403  (re-exported: the struct mirrors and limits live where no native code is loaded)
 
 LCF_STATS_DOUBLES = 8 + 6 * 2048
 
@@ -57,45 +56,6 @@ class PpoCfg(C.Structure):
         ("pol", NetLayout), ("val", NetLayout * 3), ("n_params", C.c_int64),
     ]
 
-
-class InteractCfg(C.Structure):
-    """Mirror of `copo_interact_cfg`."""
-    _fields_ = [("horizon_s", C.c_float), ("ttc_crit_s", C.c_float), ("gap_near_m", C.c_float), ("brake_mps2", C.c_float)]
-
-
-class ClipCfg(C.Structure):
-    """Mirror of `copo_clip_cfg`."""
-    _fields_ = [("pre", C.c_int32), ("post", C.c_int32), ("max_clips", C.c_int32), ("flag_mask", C.c_uint32), ("ttc_below", C.c_float),
-                ("gap_below", C.c_float)]
-
-
-CLIP_MAX_CAP, CLIP_WORDS, CLIP_HEADER = 256, 6, 8
-
-
-class RewindCfg(C.Structure):
-    """Mirror of `copo_rewind_cfg`."""
-    _fields_ = [("depth", C.c_int32), ("stride", C.c_int32)]
-
-
-REWIND_MAX_DEPTH, REWIND_TALLY = 64, 8
-
-
-class FieldCfg(C.Structure):
-    """Mirror of `copo_field_cfg`."""
-    _fields_ = [("x0", C.c_float), ("y0", C.c_float), ("cell", C.c_float), ("W", C.c_int32), ("H", C.c_int32), ("G", C.c_int32),
-                ("ttc_below", C.c_float)]
-
-
-FIELD_LAYERS, FIELD_MAX_SIDE, FIELD_MAX_GROUPS = 10, 1024, 64
-
-
-class GateCfg(C.Structure):
-    """Mirror of `copo_gate_cfg`."""
-    _fields_ = [("L", C.c_int32), ("S", C.c_int32), ("G", C.c_int32), ("T", C.c_int32), ("bin_records", C.c_int32), ("HB", C.c_int32),
-                ("TB", C.c_int32), ("tt_bin", C.c_int32)]
-
-
-GATE_MAX_GATES, GATE_MAX_SECTIONS, GATE_MAX_GROUPS, GATE_MAX_BINS, GATE_MAX_HIST = 32, 64, 64, 256, 64
 
 HEAD_PPO, HEAD_META_NEW, HEAD_META_OLD = 0, 1, 2
 OPERAND_F32, OPERAND_BF16 = 0, 1

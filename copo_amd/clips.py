@@ -14,7 +14,9 @@ import json
 
 import numpy as np
 
-WORDS, HEADER, MAX_CAP = 6, 8, 256
+from ._abi import CLIP_HEADER as HEADER, CLIP_MAX_CAP as MAX_CAP, CLIP_WORDS as WORDS
+from ._handle import Handle
+
 HEADER_KEYS = ("scene", "first_rec", "length", "trig_rec", "trig_slot", "kind", "trig_aid", "n_events")
 KIND_FLAG, KIND_TTC, KIND_GAP = 1, 2, 4
 KINDS = dict(flag=KIND_FLAG, ttc=KIND_TTC, gap=KIND_GAP)
@@ -111,39 +113,29 @@ def clip_meta(cfg, N, pre, post):
                 sim_config=dataclasses.asdict(cfg))
 
 
-class ClipRecorder:
+class ClipRecorder(Handle):
     """Flight recorder of a `VecSim`: clips of `pre` records before and `post` after the record in which a scene fires -- a slot whose
     step flags contain one of `flags` (names of `FLAG_BITS`, or the bits), whose TTC is below `ttc_below` seconds or whose gap is
-    below `gap_below` metres (0: off) --, at most `max_clips` of them (later ones are counted as dropped).  Destroy it (`close()`)
-    before its simulator; every call is asynchronous on torch's current stream except `count()` / `clips()`."""
+    below `gap_below` metres (0: off) --, at most `max_clips` of them (later ones are counted as dropped).  `close()` it when done
+    (before or after its simulator; no other call once the simulator is closed); every call is asynchronous on torch's current stream
+    except `count()` / `clips()`."""
+
+    _destroy = "copo_clip_destroy"
 
     def __init__(self, sim, pre=24, post=8, max_clips=256, flags=("crash",), ttc_below=0.0, gap_below=0.0):
-        from . import _capi
-        self._capi, self.sim = _capi, sim
+        self._attach(sim)
         self.pre, self.post, self.max_clips = int(pre), int(post), int(max_clips)
         self.flag_mask, self.ttc_below, self.gap_below = flag_mask(flags), float(ttc_below), float(gap_below)
-        cfg = _capi.ClipCfg(self.pre, self.post, self.max_clips, self.flag_mask, self.ttc_below, self.gap_below)
-        h = C.c_void_p()
-        _capi.check(_capi.lib.copo_clip_create(sim._h, C.byref(cfg), C.byref(h)))
-        self._h = h
+        cfg = self._capi.ClipCfg(self.pre, self.post, self.max_clips, self.flag_mask, self.ttc_below, self.gap_below)
+        self._create(self._capi.lib.copo_clip_create, sim._h, C.byref(cfg))
         self.cap = self.pre + self.post + 1
-
-    def _stream(self):
-        return self.sim._torch.cuda.current_stream(self.sim.device).cuda_stream
-
-    def _arg(self, t, dtype, name):
-        if t is None:
-            return None
-        if not (t.is_cuda and t.dtype == dtype and t.is_contiguous() and t.numel() == self.sim.E * self.sim.N):
-            raise ValueError("%s must be a contiguous %s cuda tensor [E, N]" % (name, dtype))
-        return t.data_ptr()
 
     def record(self, flags=None, ttc=None, gap=None):
         """Snapshot the current state of every scene; `flags` (uint8 [E, N], the step's output) and `ttc` / `gap` (float32 [E, N],
         `InteractionMeter.record()`'s) feed the triggers of this record, None switches one off for the call."""
         torch = self.sim._torch
-        self._capi.check(self._capi.lib.copo_clip_record(self._h, self._arg(flags, torch.uint8, "flags"), self._arg(ttc, torch.float32, "ttc"),
-                                                         self._arg(gap, torch.float32, "gap"), self._stream()))
+        self._capi.check(self._capi.lib.copo_clip_record(self._h, self._en_arg(flags, torch.uint8, "flags"), self._en_arg(ttc, torch.float32, "ttc"),
+                                                         self._en_arg(gap, torch.float32, "gap"), self._stream()))
 
     def flush(self):
         """Commit the clips of the scenes that are still waiting for their `post` records, with what they have."""
@@ -171,17 +163,6 @@ class ClipRecorder:
     def reset(self):
         """Forget every clip, counter and waiting scene; records count from 0 again."""
         self._capi.check(self._capi.lib.copo_clip_reset(self._h, self._stream()))
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            self._capi.lib.copo_clip_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 class ClipPlayer:

@@ -1,4 +1,5 @@
-// C ABI of libcopo_hip.so (include/copo_hip.h): argument validation, handle lifetime, error strings.
+// C ABI of libcopo_hip.so (include/copo_hip.h): version and error string, the simulator handle, the stateless ops.  The handles that
+// observe a simulator are in capi_observers.hip; what both share is capi_common.h.
 // No torch types; all launches are asynchronous on the caller's stream.
 #include <cstdarg>
 #include <cstdio>
@@ -6,53 +7,21 @@
 #include <new>
 #include <algorithm>
 #include <vector>
-
-#include <array>
 #include <cmath>
-#include <set>
 
-#include "sim_common.h"
-#include "render_common.h"
-#include "interact_common.h"
-#include "clip_common.h"
-#include "rewind_common.h"
-#include "field_common.h"
-#include "gate_common.h"
+#include "capi_common.h"
 
 using namespace copo;
 
 static thread_local char g_err[512] = "";
 
-static int fail(int code, const char* fmt, ...) {
+int copo::fail(int code, const char* fmt, ...) {
     va_list ap;
     va_start(ap, fmt);
     vsnprintf(g_err, sizeof(g_err), fmt, ap);
     va_end(ap);
     return code;
 }
-
-#define HIP_TRY(expr)                                                                              \
-    do {                                                                                           \
-        hipError_t _e = (expr);                                                                    \
-        if (_e != hipSuccess) return fail(COPO_ERR_DEVICE, "%s: %s", #expr, hipGetErrorString(_e)); \
-    } while (0)
-
-struct copo_sim {
-    SimParams p;
-    SimParams* p_dev;          // device copy of p (the kernels' parameter block)
-    int device;
-    int block;
-    bool started;
-    double lcf_mean, lcf_std, force_lcf;
-    int capacity;              // active agent slots (curriculum), num_agents by default
-    float lcf_host[4];         // {mean, std, capacity, 0}: what the kernels read from p.lcf_dist
-    bool lcf_dirty;
-    std::vector<void*> allocs;
-    // host copies of the map tables for copo_render_create: road records [n_routes][seg_rows][COPO_SEG_STRIDE], route_meta,
-    // lane lines (on the device only when a detector reads them) and static boxes
-    std::vector<float> h_segs, h_meta, h_lines, h_boxes;
-    bool boxes_hidden;
-};
 
 extern "C" int copo_version(void) { return COPO_ABI_VERSION; }
 #define COPO_STR2(x) #x
@@ -66,16 +35,6 @@ extern "C" const char* copo_build_info(void) {
 #endif
 }
 extern "C" const char* copo_last_error(void) { return g_err; }
-
-template <typename T>
-static int upload(copo_sim* s, const T* host, size_t count, const T** dev) {
-    void* d = nullptr;
-    HIP_TRY(hipMalloc(&d, count * sizeof(T) ? count * sizeof(T) : sizeof(T)));
-    s->allocs.push_back(d);
-    if (count) HIP_TRY(hipMemcpy(d, host, count * sizeof(T), hipMemcpyHostToDevice));
-    *dev = static_cast<const T*>(d);
-    return COPO_OK;
-}
 
 // measured (scripts/bench_sim.py, 40 slots, populated scenes): up to one scene per CU -> 16 waves per scene; two per CU -> 8;
 // then 4; from ~12 scenes per CU on, ONE wave per scene with the small LDS footprint (sim_shape_params, ~20 scenes resident
@@ -255,22 +214,14 @@ extern "C" int copo_sim_create(const copo_sim_cfg* cfg, int device, copo_sim** o
         p.n_spaces = std::max(p.n_spaces, (int32_t)d);
     }
     p.n_lines = (cfg->side_lasers || cfg->lane_line_lasers) ? cfg->n_lines : 0;
-    int rc = COPO_OK;
+    DevPool& mem = s->mem;
+    mem.device = device;
     const size_t EN = (size_t)p.E * p.N;
-    void* d = nullptr;
-    auto dev_alloc = [&](size_t bytes, void** ptr) -> int {
-        hipError_t e = hipMalloc(ptr, bytes);
-        if (e != hipSuccess) return fail(COPO_ERR_DEVICE, "hipMalloc(%zu): %s", bytes, hipGetErrorString(e));
-        s->allocs.push_back(*ptr);
-        e = hipMemset(*ptr, 0, bytes);
-        if (e != hipSuccess) return fail(COPO_ERR_DEVICE, "hipMemset: %s", hipGetErrorString(e));
-        return COPO_OK;
-    };
-    if (rc == COPO_OK && (rc = dev_alloc(COPO_STATE_FIELDS * EN * 4, &d)) == COPO_OK) p.state = (float*)d;
-    if (rc == COPO_OK && (rc = dev_alloc((size_t)p.E * 16, &d)) == COPO_OK) p.env = (int32_t*)d;
-    if (rc == COPO_OK && (rc = dev_alloc((size_t)p.E * 8, &d)) == COPO_OK) p.seeds = (const uint64_t*)d;
-    if (rc == COPO_OK && (rc = dev_alloc(16, &d)) == COPO_OK) p.lcf_dist = (const float*)d;
-    if (rc == COPO_OK) {      // device table: only as many road records per route as the longest route needs (+ its terminal record)
+    p.state = mem.alloc<float>(COPO_STATE_FIELDS * EN);
+    p.env = mem.alloc<int32_t>((size_t)p.E * 4);
+    p.seeds = mem.alloc<uint64_t>((size_t)p.E);
+    p.lcf_dist = mem.alloc<float>(4);
+    {   // device table: only as many road records per route as the longest route needs (+ its terminal record)
         int rows = 2;
         for (int r = 0; r < cfg->n_routes; ++r) rows = std::max(rows, (int)cfg->route_meta[r * 4 + 1] + 1);
         p.seg_rows = rows;
@@ -278,20 +229,20 @@ extern "C" int copo_sim_create(const copo_sim_cfg* cfg, int device, copo_sim** o
         for (int r = 0; r < cfg->n_routes; ++r)
             memcpy(compact.data() + (size_t)r * rows * COPO_SEG_STRIDE,
                    cfg->route_segs + (size_t)r * (COPO_MAX_SEGS + 1) * COPO_SEG_STRIDE, sizeof(float) * rows * COPO_SEG_STRIDE);
-        rc = upload(s, compact.data(), compact.size(), &p.route_segs);
+        p.route_segs = mem.upload(compact.data(), compact.size());
         s->h_segs = std::move(compact);
         s->h_meta.assign(cfg->route_meta, cfg->route_meta + (size_t)cfg->n_routes * 4);
         if (cfg->n_lines > 0 && cfg->lines) s->h_lines.assign(cfg->lines, cfg->lines + (size_t)cfg->n_lines * COPO_LINE_STRIDE);
         if (cfg->n_boxes > 0) s->h_boxes.assign(cfg->boxes, cfg->boxes + (size_t)cfg->n_boxes * COPO_BOX_STRIDE);
         s->boxes_hidden = cfg->boxes_hidden != 0;
     }
-    if (rc == COPO_OK) rc = upload(s, cfg->route_meta, (size_t)cfg->n_routes * 4, &p.route_meta);
-    if (rc == COPO_OK) rc = upload(s, cfg->spawn_tab, (size_t)cfg->n_spawns * 4, &p.spawn_tab);
-    if (rc == COPO_OK) rc = upload(s, cfg->spawn_s, (size_t)cfg->n_spawns, &p.spawn_s);
-    if (rc == COPO_OK) rc = upload(s, cfg->ray_cs, (size_t)cfg->num_lasers * 2, &p.ray_cs);
-    if (rc == COPO_OK) rc = upload(s, safe.data(), safe.size(), &p.safe_ids);
-    if (rc == COPO_OK) {      // pose of every respawn place (sim_kernels.hip spawn_pose, the same float operations in the same order)
-        std::vector<float> sp4(4 * std::max<size_t>(safe.size(), 1), 0.0f);
+    p.route_meta = mem.upload(cfg->route_meta, (size_t)cfg->n_routes * 4);
+    p.spawn_tab = mem.upload(cfg->spawn_tab, (size_t)cfg->n_spawns * 4);
+    p.spawn_s = mem.upload(cfg->spawn_s, (size_t)cfg->n_spawns);
+    p.ray_cs = mem.upload(cfg->ray_cs, (size_t)cfg->num_lasers * 2);
+    p.safe_ids = mem.upload(safe.data(), safe.size());
+    {   // pose of every respawn place (sim_kernels.hip spawn_pose, the same float operations in the same order)
+        std::vector<float> sp4(4 * safe.size(), 0.0f);
         for (size_t q = 0; q < safe.size(); ++q) {
             const int sp = safe[q];
             const float* g = cfg->route_segs + (size_t)cfg->spawn_tab[sp * 4 + 0] * (COPO_MAX_SEGS + 1) * COPO_SEG_STRIDE;
@@ -302,37 +253,21 @@ extern "C" int copo_sim_create(const copo_sim_cfg* cfg, int device, copo_sim** o
             sp4[4 * q + 2] = g[2];
             sp4[4 * q + 3] = g[3];
         }
-        rc = upload(s, sp4.data(), sp4.size(), &p.safe_pose);
+        p.safe_pose = mem.upload(sp4.data(), sp4.size());
     }
-    if (rc == COPO_OK && p.n_lines) rc = upload(s, cfg->lines, (size_t)cfg->n_lines * COPO_LINE_STRIDE, &p.lines);
+    if (p.n_lines) p.lines = mem.upload(cfg->lines, (size_t)cfg->n_lines * COPO_LINE_STRIDE);
     p.n_boxes = cfg->n_boxes;
     p.n_boxes_lidar = cfg->boxes_hidden ? 0 : cfg->n_boxes;
-    if (rc == COPO_OK && p.n_boxes) rc = upload(s, cfg->boxes, (size_t)cfg->n_boxes * COPO_BOX_STRIDE, &p.boxes);
-    if (rc == COPO_OK && cfg->side_lasers) rc = upload(s, cfg->side_cs, (size_t)cfg->side_lasers * 2, &p.side_cs);
-    if (rc == COPO_OK && cfg->lane_line_lasers) rc = upload(s, cfg->lane_line_cs, (size_t)cfg->lane_line_lasers * 2, &p.lane_cs);
+    if (p.n_boxes) p.boxes = mem.upload(cfg->boxes, (size_t)cfg->n_boxes * COPO_BOX_STRIDE);
+    if (cfg->side_lasers) p.side_cs = mem.upload(cfg->side_cs, (size_t)cfg->side_lasers * 2);
+    if (cfg->lane_line_lasers) p.lane_cs = mem.upload(cfg->lane_line_cs, (size_t)cfg->lane_line_lasers * 2);
     s->block = pick_block(cfg->num_envs, p.nbr_fast != 0, packed_scenes(p));      // (after the observation layout: the packed shape depends on it)
     sim_shape_params(p, s->block);
-    if (rc == COPO_OK) {
-        const SimParams* pd = nullptr;
-        rc = upload(s, &s->p, 1, &pd);
-        s->p_dev = const_cast<SimParams*>(pd);
-    }
-    if (rc != COPO_OK) {
-        for (void* a : s->allocs) (void)hipFree(a);
-        delete s;
-        return rc;
-    }
-    *out = s;
-    return COPO_OK;
+    s->p_dev = mem.upload(&s->p, 1);
+    return finish_create(s, out, "copo_sim_create");
 }
 
-extern "C" int copo_sim_destroy(copo_sim* s) {
-    if (!s) return fail(COPO_ERR_NULL, "copo_sim_destroy: NULL handle");
-    (void)hipSetDevice(s->device);
-    for (void* a : s->allocs) (void)hipFree(a);
-    delete s;
-    return COPO_OK;
-}
+extern "C" int copo_sim_destroy(copo_sim* s) { return destroy_handle(s, "copo_sim_destroy"); }
 
 // Push the LCF distribution to device memory on `st` (kernels read it from there, so launches captured
 // in a hipGraph keep seeing later updates).  Skipped while the stream is capturing.
@@ -547,787 +482,5 @@ extern "C" int copo_lcf_mix_apply_f32(const float* mixed, const float* glob_adv,
     if (B < 0) return fail(COPO_ERR_DIM, "copo_lcf_mix_apply_f32: B=%lld", (long long)B);
     if (B == 0) return COPO_OK;
     HIP_TRY(launch_lcf_mix_apply(mixed, glob_adv, valid, B, stats, norm_adv, glob_adv_std, static_cast<hipStream_t>(stream)));
-    return COPO_OK;
-}
-
-// ---- top-down renderer (render_kernels.hip) ----------------------------------------------------------------
-
-struct copo_render {
-    copo_sim* sim;
-    int W, H, cap, head, count;
-    int n_roads, n_lines;
-    uint32_t box_rgba;
-    const float* roads;        // [n_roads][RENDER_ROAD_STRIDE] deduplicated road records + world boxes
-    const float* lines;        // [n_lines][RENDER_LINE_STRIDE]
-    const uint32_t* palette;   // [12]
-    int32_t* ring;             // [cap][RENDER_RING_FIELDS][E][N]
-    int32_t* ring_ep;          // [cap][E]
-    std::vector<void*> allocs;
-};
-
-static void free_render(copo_render* r) {
-    for (void* a : r->allocs) (void)hipFree(a);
-    delete r;
-}
-
-template <typename T>
-static int render_upload(copo_render* r, const T* host, size_t count, const T** dev) {
-    void* d = nullptr;
-    HIP_TRY(hipMalloc(&d, count ? count * sizeof(T) : sizeof(T)));
-    r->allocs.push_back(d);
-    if (count && host) HIP_TRY(hipMemcpy(d, host, count * sizeof(T), hipMemcpyHostToDevice));
-    else HIP_TRY(hipMemset(d, 0, count ? count * sizeof(T) : sizeof(T)));      // (no host table: zeros)
-    *dev = static_cast<const T*>(d);
-    return COPO_OK;
-}
-
-// world box {x0, x1, y0, y1} of the points at lateral offsets lat0 and lat1 (left +) of a straight or arc of `len` metres starting at
-// (x0, y0) with heading (c, s) and curvature kap; sampled finely enough that 0.5 m of padding covers the chords
-static void prim_box(double x0, double y0, double c, double s, double len, double kap, double lat0, double lat1, float* bb) {
-    double lo_x = 1e30, hi_x = -1e30, lo_y = 1e30, hi_y = -1e30;
-    const int n = 129;
-    for (int k = 0; k < n; ++k) {
-        const double sl = len * k / (n - 1), a = kap * sl;
-        double px, py, hc, hs;
-        if (kap == 0.0) {
-            px = x0 + c * sl; py = y0 + s * sl; hc = c; hs = s;
-        } else {
-            const double r = 1.0 / kap;       // signed
-            hc = c * std::cos(a) - s * std::sin(a);
-            hs = s * std::cos(a) + c * std::sin(a);
-            px = x0 + r * (hs - s); py = y0 - r * (hc - c);
-        }
-        for (double lat : {lat0, lat1}) {
-            const double qx = px - hs * lat, qy = py + hc * lat;
-            lo_x = std::min(lo_x, qx); hi_x = std::max(hi_x, qx); lo_y = std::min(lo_y, qy); hi_y = std::max(hi_y, qy);
-        }
-    }
-    bb[0] = (float)(lo_x - 0.5); bb[1] = (float)(hi_x + 0.5); bb[2] = (float)(lo_y - 0.5); bb[3] = (float)(hi_y + 0.5);
-}
-
-extern "C" int copo_render_create(copo_sim* sim, int32_t width, int32_t height, int32_t trail, const uint8_t* palette_rgb,
-                                  copo_render** out) {
-    if (!sim || !palette_rgb || !out) return fail(COPO_ERR_NULL, "copo_render_create: NULL argument");
-    *out = nullptr;
-    if (width < 1 || width > RENDER_MAX_SIZE || height < 1 || height > RENDER_MAX_SIZE || trail < 0 || trail > RENDER_MAX_TRAIL)
-        return fail(COPO_ERR_DIM, "copo_render_create: %d x %d pixels (1..%d each), trail %d (0..%d)", width, height, RENDER_MAX_SIZE,
-                    trail, RENDER_MAX_TRAIL);
-    HIP_TRY(hipSetDevice(sim->device));
-    copo_render* r = new (std::nothrow) copo_render();
-    if (!r) return fail(COPO_ERR_DEVICE, "out of host memory");
-    r->sim = sim; r->W = width; r->H = height; r->cap = trail; r->head = 0; r->count = 0;
-    const SimParams& p = sim->p;
-    const double w = p.lane_width;
-    // road records of every route, deduplicated on the fields the road rule reads (routes share their roads)
-    std::vector<float> roads;
-    std::set<std::array<float, 10>> seen;
-    for (int q = 0; q < p.n_routes; ++q) {
-        const int nseg = (int)sim->h_meta[(size_t)q * 4 + 1];
-        for (int k = 0; k < nseg; ++k) {
-            const float* g = sim->h_segs.data() + ((size_t)q * p.seg_rows + k) * COPO_SEG_STRIDE;
-            const std::array<float, 10> key = {g[0], g[1], g[2], g[3], g[4], g[5], floorf(g[COPO_SEG_LANES]), g[12], g[14], g[15]};
-            if (!seen.insert(key).second) continue;
-            const size_t o = roads.size();
-            roads.resize(o + RENDER_ROAD_STRIDE);
-            std::copy(g, g + COPO_SEG_STRIDE, roads.begin() + o);
-            const double lanes = std::floor((double)g[COPO_SEG_LANES]);
-            const double funnel = (g[5] == 0.0f && g[12] != 0.0f) ? std::fabs((double)g[14]) : 0.0;
-            prim_box(g[0], g[1], g[2], g[3], g[4], g[5], 0.5 * w, -((lanes - 0.5) * w + funnel), roads.data() + o + 16);
-        }
-    }
-    std::vector<float> lines;
-    const int nl = (int)(sim->h_lines.size() / COPO_LINE_STRIDE);
-    for (int k = 0; k < nl; ++k) {
-        const float* L = sim->h_lines.data() + (size_t)k * COPO_LINE_STRIDE;
-        const size_t o = lines.size();
-        lines.resize(o + RENDER_LINE_STRIDE);
-        std::copy(L, L + COPO_LINE_STRIDE, lines.begin() + o);
-        prim_box(L[1], L[2], L[3], L[4], L[5], L[6], 0.0, 0.0, lines.data() + o + 12);
-    }
-    uint32_t pal[12];
-    for (int k = 0; k < 12; ++k)
-        pal[k] = (uint32_t)palette_rgb[3 * k] | ((uint32_t)palette_rgb[3 * k + 1] << 8) | ((uint32_t)palette_rgb[3 * k + 2] << 16) | 0xff000000u;
-    r->n_roads = (int)(roads.size() / RENDER_ROAD_STRIDE);
-    r->n_lines = nl;
-    r->box_rgba = sim->boxes_hidden ? (190u | (150u << 8) | (110u << 16) | 0xff000000u) : (120u | (80u << 8) | (50u << 16) | 0xff000000u);
-    const size_t EN = (size_t)p.E * p.N;
-    const int32_t* ring = nullptr;
-    const int32_t* ring_ep = nullptr;
-    int rc = render_upload(r, roads.data(), roads.size(), &r->roads);
-    if (rc == COPO_OK) rc = render_upload(r, lines.data(), lines.size(), &r->lines);
-    if (rc == COPO_OK) rc = render_upload(r, pal, 12, &r->palette);
-    if (rc == COPO_OK) rc = render_upload<int32_t>(r, nullptr, (size_t)std::max(trail, 1) * RENDER_RING_FIELDS * EN, &ring);
-    if (rc == COPO_OK) rc = render_upload<int32_t>(r, nullptr, (size_t)std::max(trail, 1) * p.E, &ring_ep);
-    if (rc != COPO_OK) {
-        free_render(r);
-        return rc;
-    }
-    r->ring = const_cast<int32_t*>(ring);
-    r->ring_ep = const_cast<int32_t*>(ring_ep);
-    *out = r;
-    return COPO_OK;
-}
-
-extern "C" int copo_render_destroy(copo_render* r) {
-    if (!r) return fail(COPO_ERR_NULL, "copo_render_destroy: NULL handle");
-    (void)hipSetDevice(r->sim->device);
-    free_render(r);
-    return COPO_OK;
-}
-
-extern "C" int copo_render_record(copo_render* r, void* stream) {
-    if (!r) return fail(COPO_ERR_NULL, "copo_render_record: NULL handle");
-    if (r->cap == 0) return COPO_OK;
-    const SimParams& p = r->sim->p;
-    HIP_TRY(launch_render_record(p.state, p.env, p.E, p.N, r->ring, r->ring_ep, r->head, static_cast<hipStream_t>(stream)));
-    r->head = (r->head + 1) % r->cap;
-    r->count = std::min(r->count + 1, r->cap);
-    return COPO_OK;
-}
-
-extern "C" int copo_render_clear(copo_render* r, void* stream) {
-    (void)stream;
-    if (!r) return fail(COPO_ERR_NULL, "copo_render_clear: NULL handle");
-    r->head = 0;
-    r->count = 0;
-    return COPO_OK;
-}
-
-extern "C" int copo_render_frames(copo_render* r, const int32_t* scenes, int32_t S, const float* views, int32_t trail, uint32_t* rgba,
-                                  void* stream) {
-    if (!r || !scenes || !views || !rgba) return fail(COPO_ERR_NULL, "copo_render_frames: NULL argument");
-    const SimParams& p = r->sim->p;
-    if (S < 1 || S > p.E) return fail(COPO_ERR_DIM, "copo_render_frames: S=%d scenes (1..%d)", S, p.E);
-    if (trail < 0 || trail > r->cap) return fail(COPO_ERR_DIM, "copo_render_frames: trail=%d (0..%d, the capacity at create)", trail, r->cap);
-    RenderArgs a;
-    a.state = p.state; a.env = p.env; a.E = p.E; a.N = p.N;
-    a.roads = r->roads; a.lines = r->lines; a.boxes = p.boxes;
-    a.n_roads = r->n_roads; a.n_lines = r->n_lines; a.n_boxes = p.n_boxes;
-    a.box_rgba = r->box_rgba; a.palette = r->palette;
-    a.ring = r->ring; a.ring_ep = r->ring_ep; a.cap = r->cap; a.head = r->head;
-    a.K = trail; a.Kd = std::min(trail, r->count);
-    a.hl = p.hl; a.hw = p.hw; a.lane_w = p.lane_width;
-    a.scenes = scenes; a.views = views; a.S = S; a.W = r->W; a.H = r->H; a.out = rgba;
-    HIP_TRY(launch_render_frames(a, static_cast<hipStream_t>(stream)));
-    return COPO_OK;
-}
-
-// ---- interaction meter (interact_kernels.hip) ----------------------------------------------------------------
-
-struct copo_interact {
-    copo_sim* sim;
-    copo_interact_cfg cfg;
-    int32_t* acc;              // [INTERACT_ACC_WORDS][E][N]
-    double* tit;               // [E][N]
-    long long* counts;         // [E][INTERACT_COUNTS]
-    double* sums;              // [E][INTERACT_SUMS]
-    size_t acc_bytes, tit_bytes, counts_bytes, sums_bytes;
-};
-
-static void free_interact(copo_interact* h) {
-    for (void* a : {(void*)h->acc, (void*)h->tit, (void*)h->counts, (void*)h->sums})
-        if (a) (void)hipFree(a);
-    delete h;
-}
-
-static InteractArgs interact_args(const copo_interact* h) {
-    const SimParams& p = h->sim->p;
-    InteractArgs a;
-    a.state = p.state; a.env = p.env; a.E = p.E; a.N = p.N;
-    a.hl = p.hl; a.hw = p.hw; a.dt = p.dt;
-    a.horizon_s = h->cfg.horizon_s; a.ttc_crit_s = h->cfg.ttc_crit_s; a.gap_near_m = h->cfg.gap_near_m; a.brake_mps2 = h->cfg.brake_mps2;
-    a.acc = h->acc; a.tit = h->tit; a.counts = h->counts; a.sums = h->sums;
-    return a;
-}
-
-static int interact_clear(copo_interact* h, hipStream_t stream) {
-    HIP_TRY(hipMemsetAsync(h->acc, 0, h->acc_bytes, stream));
-    HIP_TRY(hipMemsetAsync(h->tit, 0, h->tit_bytes, stream));
-    HIP_TRY(hipMemsetAsync(h->counts, 0, h->counts_bytes, stream));
-    HIP_TRY(hipMemsetAsync(h->sums, 0, h->sums_bytes, stream));
-    return COPO_OK;
-}
-
-extern "C" int copo_interact_create(copo_sim* sim, const copo_interact_cfg* cfg, copo_interact** out) {
-    if (!sim || !cfg || !out) return fail(COPO_ERR_NULL, "copo_interact_create: NULL argument");
-    *out = nullptr;
-    if (!(cfg->horizon_s > 0.0f) || !(cfg->brake_mps2 > 0.0f) || !(cfg->ttc_crit_s >= 0.0f) || !(cfg->gap_near_m >= 0.0f) ||
-        !std::isfinite(cfg->horizon_s) || !std::isfinite(cfg->brake_mps2) || !std::isfinite(cfg->ttc_crit_s) || !std::isfinite(cfg->gap_near_m))
-        return fail(COPO_ERR_CONFIG, "copo_interact_create: horizon_s=%g brake_mps2=%g (> 0), ttc_crit_s=%g gap_near_m=%g (>= 0), all finite",
-                    (double)cfg->horizon_s, (double)cfg->brake_mps2, (double)cfg->ttc_crit_s, (double)cfg->gap_near_m);
-    HIP_TRY(hipSetDevice(sim->device));
-    copo_interact* h = new (std::nothrow) copo_interact();
-    if (!h) return fail(COPO_ERR_DEVICE, "out of host memory");
-    h->sim = sim; h->cfg = *cfg;
-    const size_t E = (size_t)sim->p.E, EN = E * sim->p.N;
-    h->acc_bytes = (size_t)INTERACT_ACC_WORDS * EN * sizeof(int32_t); h->tit_bytes = EN * sizeof(double);
-    h->counts_bytes = E * INTERACT_COUNTS * sizeof(long long); h->sums_bytes = E * INTERACT_SUMS * sizeof(double);
-    hipError_t err = hipMalloc((void**)&h->acc, h->acc_bytes);
-    if (err == hipSuccess) err = hipMalloc((void**)&h->tit, h->tit_bytes);
-    if (err == hipSuccess) err = hipMalloc((void**)&h->counts, h->counts_bytes);
-    if (err == hipSuccess) err = hipMalloc((void**)&h->sums, h->sums_bytes);
-    if (err == hipSuccess) err = hipMemset(h->acc, 0, h->acc_bytes);
-    if (err == hipSuccess) err = hipMemset(h->tit, 0, h->tit_bytes);
-    if (err == hipSuccess) err = hipMemset(h->counts, 0, h->counts_bytes);
-    if (err == hipSuccess) err = hipMemset(h->sums, 0, h->sums_bytes);
-    if (err != hipSuccess) {
-        free_interact(h);
-        return fail(COPO_ERR_DEVICE, "copo_interact_create: %s", hipGetErrorString(err));
-    }
-    *out = h;
-    return COPO_OK;
-}
-
-extern "C" int copo_interact_destroy(copo_interact* h) {
-    if (!h) return fail(COPO_ERR_NULL, "copo_interact_destroy: NULL handle");
-    (void)hipSetDevice(h->sim->device);
-    free_interact(h);
-    return COPO_OK;
-}
-
-extern "C" int copo_interact_record(copo_interact* h, float* gap, float* ttc, void* stream) {
-    if (!h) return fail(COPO_ERR_NULL, "copo_interact_record: NULL handle");
-    HIP_TRY(launch_interact_record(interact_args(h), gap, ttc, static_cast<hipStream_t>(stream)));
-    return COPO_OK;
-}
-
-extern "C" int copo_interact_totals(copo_interact* h, int64_t* counts_i64, double* sums_f64, int32_t flush_open, void* stream) {
-    if (!h || !counts_i64 || !sums_f64) return fail(COPO_ERR_NULL, "copo_interact_totals: NULL argument");
-    if (flush_open != 0 && flush_open != 1) return fail(COPO_ERR_DIM, "copo_interact_totals: flush_open=%d (0 or 1)", flush_open);
-    HIP_TRY(launch_interact_totals(interact_args(h), reinterpret_cast<long long*>(counts_i64), sums_f64, flush_open,
-                                   static_cast<hipStream_t>(stream)));
-    return COPO_OK;
-}
-
-extern "C" int copo_interact_reset(copo_interact* h, void* stream) {
-    if (!h) return fail(COPO_ERR_NULL, "copo_interact_reset: NULL handle");
-    return interact_clear(h, static_cast<hipStream_t>(stream));
-}
-
-// ---- event clips (clip_kernels.hip) ----------------------------------------------------------------------------
-
-struct copo_clip {
-    copo_sim* sim;
-    copo_clip_cfg cfg;
-    int32_t cap;
-    uint32_t *ring, *pool;
-    int32_t *ring_env, *scene, *ready, *cid, *counters, *pool_env, *header;
-    size_t ring_bytes, ring_env_bytes, scene_bytes, ready_bytes, pool_bytes, pool_env_bytes, header_bytes;
-};
-
-static void free_clip(copo_clip* h) {
-    for (void* a : {(void*)h->ring, (void*)h->pool, (void*)h->ring_env, (void*)h->scene, (void*)h->ready, (void*)h->cid, (void*)h->counters,
-                    (void*)h->pool_env, (void*)h->header})
-        if (a) (void)hipFree(a);
-    delete h;
-}
-
-static ClipArgs clip_args(const copo_clip* h) {
-    const SimParams& p = h->sim->p;
-    ClipArgs a;
-    a.state = p.state; a.env = p.env; a.E = p.E; a.N = p.N;
-    a.pre = h->cfg.pre; a.post = h->cfg.post; a.cap = h->cap; a.max_clips = h->cfg.max_clips;
-    a.flag_mask = h->cfg.flag_mask; a.ttc_below = h->cfg.ttc_below; a.gap_below = h->cfg.gap_below;
-    a.ring = h->ring; a.ring_env = h->ring_env; a.scene = h->scene; a.ready = h->ready; a.cid = h->cid; a.counters = h->counters;
-    a.pool = h->pool; a.pool_env = h->pool_env; a.header = h->header;
-    return a;
-}
-
-// idle state machines, no clip, record 0; the pool is zeroed so that frames beyond a clip's length read 0 (the ring needs no clearing:
-// a clip never reaches back beyond the records made since)
-static int clip_clear(copo_clip* h, hipStream_t stream) {
-    HIP_TRY(hipMemsetAsync(h->scene, 0, h->scene_bytes, stream));
-    HIP_TRY(hipMemsetAsync(h->ready, 0, h->ready_bytes, stream));
-    HIP_TRY(hipMemsetAsync(h->cid, 0, h->ready_bytes, stream));
-    HIP_TRY(hipMemsetAsync(h->counters, 0, CLIP_COUNTERS * sizeof(int32_t), stream));
-    HIP_TRY(hipMemsetAsync(h->pool, 0, h->pool_bytes, stream));
-    HIP_TRY(hipMemsetAsync(h->pool_env, 0, h->pool_env_bytes, stream));
-    HIP_TRY(hipMemsetAsync(h->header, 0, h->header_bytes, stream));
-    return COPO_OK;
-}
-
-extern "C" int copo_clip_create(copo_sim* sim, const copo_clip_cfg* cfg, copo_clip** out) {
-    if (!sim || !cfg || !out) return fail(COPO_ERR_NULL, "copo_clip_create: NULL argument");
-    *out = nullptr;
-    if (cfg->pre < 0 || cfg->post < 0 || cfg->pre > COPO_CLIP_MAX_CAP || cfg->post > COPO_CLIP_MAX_CAP || cfg->pre + cfg->post + 1 > COPO_CLIP_MAX_CAP)
-        return fail(COPO_ERR_DIM, "copo_clip_create: pre=%d post=%d (>= 0, pre + post + 1 <= %d)", cfg->pre, cfg->post, COPO_CLIP_MAX_CAP);
-    if (cfg->max_clips < 1) return fail(COPO_ERR_DIM, "copo_clip_create: max_clips=%d (>= 1)", cfg->max_clips);
-    if (!(cfg->ttc_below >= 0.0f) || !(cfg->gap_below >= 0.0f) || !std::isfinite(cfg->ttc_below) || !std::isfinite(cfg->gap_below) ||
-        cfg->flag_mask > 0xffu)
-        return fail(COPO_ERR_CONFIG, "copo_clip_create: ttc_below=%g gap_below=%g (>= 0, finite; 0 = off), flag_mask=0x%x (COPO_F_* bits)",
-                    (double)cfg->ttc_below, (double)cfg->gap_below, cfg->flag_mask);
-    static_assert(COPO_CLIP_MAX_CAP == CLIP_MAX_CAP && COPO_CLIP_WORDS == CLIP_WORDS && COPO_CLIP_HEADER == CLIP_HEADER, "copo_hip.h / clip_common.h");
-    HIP_TRY(hipSetDevice(sim->device));
-    copo_clip* h = new (std::nothrow) copo_clip();
-    if (!h) return fail(COPO_ERR_DEVICE, "out of host memory");
-    h->sim = sim; h->cfg = *cfg; h->cap = cfg->pre + cfg->post + 1;
-    const size_t E = (size_t)sim->p.E, N = (size_t)sim->p.N, cap = (size_t)h->cap, C = (size_t)cfg->max_clips;
-    h->ring_bytes = E * cap * CLIP_WORDS * N * 4; h->ring_env_bytes = E * cap * CLIP_ENV_WORDS * 4;
-    h->scene_bytes = E * CLIP_SCENE_WORDS * 4; h->ready_bytes = E * 4;
-    h->pool_bytes = C * cap * CLIP_WORDS * N * 4; h->pool_env_bytes = C * cap * CLIP_ENV_WORDS * 4; h->header_bytes = C * CLIP_HEADER * 4;
-    hipError_t err = hipMalloc((void**)&h->ring, h->ring_bytes);
-    if (err == hipSuccess) err = hipMalloc((void**)&h->ring_env, h->ring_env_bytes);
-    if (err == hipSuccess) err = hipMalloc((void**)&h->scene, h->scene_bytes);
-    if (err == hipSuccess) err = hipMalloc((void**)&h->ready, h->ready_bytes);
-    if (err == hipSuccess) err = hipMalloc((void**)&h->cid, h->ready_bytes);
-    if (err == hipSuccess) err = hipMalloc((void**)&h->counters, CLIP_COUNTERS * sizeof(int32_t));
-    if (err == hipSuccess) err = hipMalloc((void**)&h->pool, h->pool_bytes);
-    if (err == hipSuccess) err = hipMalloc((void**)&h->pool_env, h->pool_env_bytes);
-    if (err == hipSuccess) err = hipMalloc((void**)&h->header, h->header_bytes);
-    if (err == hipSuccess) err = hipMemset(h->ring, 0, h->ring_bytes);
-    if (err == hipSuccess) err = hipMemset(h->ring_env, 0, h->ring_env_bytes);
-    if (err != hipSuccess) {
-        (void)hipGetLastError();               // (a refused request must not show up as the next launch's error)
-        free_clip(h);
-        return fail(COPO_ERR_DEVICE, "copo_clip_create: %s (ring %zu bytes, pool %zu bytes)", hipGetErrorString(err), E * cap * CLIP_WORDS * N * 4,
-                    C * cap * CLIP_WORDS * N * 4);
-    }
-    int rc = clip_clear(h, nullptr);
-    if (rc == COPO_OK && hipStreamSynchronize(nullptr) != hipSuccess) rc = fail(COPO_ERR_DEVICE, "copo_clip_create: clearing failed");
-    if (rc != COPO_OK) {
-        free_clip(h);
-        return rc;
-    }
-    *out = h;
-    return COPO_OK;
-}
-
-extern "C" int copo_clip_destroy(copo_clip* h) {
-    if (!h) return fail(COPO_ERR_NULL, "copo_clip_destroy: NULL handle");
-    (void)hipSetDevice(h->sim->device);
-    free_clip(h);
-    return COPO_OK;
-}
-
-extern "C" int copo_clip_record(copo_clip* h, const uint8_t* flags, const float* ttc, const float* gap, void* stream) {
-    if (!h) return fail(COPO_ERR_NULL, "copo_clip_record: NULL handle");
-    HIP_TRY(launch_clip_record(clip_args(h), flags, ttc, gap, static_cast<hipStream_t>(stream)));
-    return COPO_OK;
-}
-
-extern "C" int copo_clip_flush(copo_clip* h, void* stream) {
-    if (!h) return fail(COPO_ERR_NULL, "copo_clip_flush: NULL handle");
-    HIP_TRY(launch_clip_flush(clip_args(h), static_cast<hipStream_t>(stream)));
-    return COPO_OK;
-}
-
-extern "C" int copo_clip_count(copo_clip* h, int32_t* n_clips, int32_t* dropped, void* stream) {
-    if (!h || !n_clips || !dropped) return fail(COPO_ERR_NULL, "copo_clip_count: NULL argument");
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    int32_t c[CLIP_COUNTERS];
-    HIP_TRY(hipMemcpyAsync(c, h->counters, sizeof(c), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    *n_clips = c[CC_CLIPS];
-    *dropped = c[CC_DROPPED];
-    return COPO_OK;
-}
-
-extern "C" int copo_clip_read(copo_clip* h, int32_t first, int32_t n, int32_t* header_out, uint32_t* snaps_out, int32_t* env_out, void* stream) {
-    if (!h) return fail(COPO_ERR_NULL, "copo_clip_read: NULL handle");
-    if (first < 0 || n < 0 || (int64_t)first + n > h->cfg.max_clips)
-        return fail(COPO_ERR_DIM, "copo_clip_read: clips [%d, %d + %d) of a pool of %d", first, first, n, h->cfg.max_clips);
-    if (n == 0) return COPO_OK;
-    if (!header_out || !snaps_out || !env_out) return fail(COPO_ERR_NULL, "copo_clip_read: NULL output");
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const size_t per = (size_t)h->cap * CLIP_WORDS * h->sim->p.N, per_env = (size_t)h->cap * CLIP_ENV_WORDS;
-    HIP_TRY(hipMemcpyAsync(header_out, h->header + (size_t)first * CLIP_HEADER, (size_t)n * CLIP_HEADER * 4, hipMemcpyDeviceToDevice, st));
-    HIP_TRY(hipMemcpyAsync(snaps_out, h->pool + (size_t)first * per, (size_t)n * per * 4, hipMemcpyDeviceToDevice, st));
-    HIP_TRY(hipMemcpyAsync(env_out, h->pool_env + (size_t)first * per_env, (size_t)n * per_env * 4, hipMemcpyDeviceToDevice, st));
-    return COPO_OK;
-}
-
-extern "C" int copo_clip_reset(copo_clip* h, void* stream) {
-    if (!h) return fail(COPO_ERR_NULL, "copo_clip_reset: NULL handle");
-    return clip_clear(h, static_cast<hipStream_t>(stream));
-}
-
-extern "C" int copo_clip_scatter(copo_sim* target, const uint32_t* snaps, const int32_t* envw, int32_t cap, int32_t N, const int32_t* clip_idx,
-                                 const int32_t* frame_idx, int32_t S, void* stream) {
-    if (!target || !snaps || !envw || !clip_idx || !frame_idx) return fail(COPO_ERR_NULL, "copo_clip_scatter: NULL argument");
-    if (cap < 1 || cap > COPO_CLIP_MAX_CAP) return fail(COPO_ERR_DIM, "copo_clip_scatter: cap=%d (1..%d)", cap, COPO_CLIP_MAX_CAP);
-    if (N != target->p.N) return fail(COPO_ERR_DIM, "copo_clip_scatter: clips of %d slots, a simulator of %d", N, target->p.N);
-    if (S < 1 || S > target->p.E) return fail(COPO_ERR_DIM, "copo_clip_scatter: S=%d scenes into a simulator of %d", S, target->p.E);
-    HIP_TRY(launch_clip_scatter(target->p.state, target->p.env, target->p.E, N, snaps, envw, cap, clip_idx, frame_idx, S,
-                                static_cast<hipStream_t>(stream)));
-    target->started = true;
-    return COPO_OK;
-}
-
-// ---- scene rewind (rewind_kernels.hip) -------------------------------------------------------------------------
-
-struct copo_rewind {
-    copo_sim* sim;
-    int32_t depth, stride;
-    int64_t n_records;             // records made since create / reset (host side: the feature is eager only)
-    uint32_t* ring;
-    int32_t* ring_env;
-};
-
-static void free_rewind(copo_rewind* h) {
-    for (void* a : {(void*)h->ring, (void*)h->ring_env})
-        if (a) (void)hipFree(a);
-    delete h;
-}
-
-extern "C" int copo_rewind_create(copo_sim* sim, const copo_rewind_cfg* cfg, copo_rewind** out) {
-    if (!sim || !cfg || !out) return fail(COPO_ERR_NULL, "copo_rewind_create: NULL argument");
-    *out = nullptr;
-    if (cfg->depth < 1 || cfg->depth > COPO_REWIND_MAX_DEPTH || cfg->stride < 1)
-        return fail(COPO_ERR_DIM, "copo_rewind_create: depth=%d (1..%d) stride=%d (>= 1)", cfg->depth, COPO_REWIND_MAX_DEPTH, cfg->stride);
-    static_assert(COPO_REWIND_MAX_DEPTH == REWIND_MAX_DEPTH && COPO_REWIND_TALLY == REWIND_TALLY, "copo_hip.h / rewind_common.h");
-    HIP_TRY(hipSetDevice(sim->device));
-    copo_rewind* h = new (std::nothrow) copo_rewind();
-    if (!h) return fail(COPO_ERR_DEVICE, "out of host memory");
-    h->sim = sim; h->depth = cfg->depth; h->stride = cfg->stride; h->n_records = 0;
-    const size_t E = (size_t)sim->p.E, N = (size_t)sim->p.N, D = (size_t)cfg->depth;
-    const size_t ring_bytes = E * D * COPO_STATE_FIELDS * N * 4, env_bytes = E * D * REWIND_ENV_WORDS * 4;
-    hipError_t err = hipMalloc((void**)&h->ring, ring_bytes);
-    if (err == hipSuccess) err = hipMalloc((void**)&h->ring_env, env_bytes);
-    if (err == hipSuccess) err = hipMemset(h->ring, 0, ring_bytes);
-    if (err == hipSuccess) err = hipMemset(h->ring_env, 0, env_bytes);
-    if (err != hipSuccess) {
-        (void)hipGetLastError();               // (a refused request must not show up as the next launch's error)
-        free_rewind(h);
-        return fail(COPO_ERR_DEVICE, "copo_rewind_create: %s (ring %zu bytes)", hipGetErrorString(err), ring_bytes + env_bytes);
-    }
-    *out = h;
-    return COPO_OK;
-}
-
-extern "C" int copo_rewind_destroy(copo_rewind* h) {
-    if (!h) return fail(COPO_ERR_NULL, "copo_rewind_destroy: NULL handle");
-    (void)hipSetDevice(h->sim->device);
-    free_rewind(h);
-    return COPO_OK;
-}
-
-extern "C" int copo_rewind_record(copo_rewind* h, void* stream) {
-    if (!h) return fail(COPO_ERR_NULL, "copo_rewind_record: NULL handle");
-    const int64_t r = h->n_records;
-    if (r >= INT32_MAX) return fail(COPO_ERR_STATE, "copo_rewind_record: 2^31 - 1 records since the last reset");
-    if (r % h->stride == 0) {
-        const SimParams& p = h->sim->p;
-        RewindArgs a;
-        a.state = p.state; a.env = p.env; a.E = p.E; a.N = p.N; a.depth = h->depth; a.ring = h->ring; a.ring_env = h->ring_env;
-        HIP_TRY(launch_rewind_record(a, (int)((r / h->stride) % h->depth), static_cast<hipStream_t>(stream)));
-    }
-    h->n_records = r + 1;
-    return COPO_OK;
-}
-
-// (the ring needs no clearing: a fork never reaches back beyond the records made since)
-extern "C" int copo_rewind_reset(copo_rewind* h) {
-    if (!h) return fail(COPO_ERR_NULL, "copo_rewind_reset: NULL handle");
-    h->n_records = 0;
-    return COPO_OK;
-}
-
-extern "C" int copo_rewind_count(copo_rewind* h, int32_t* n_records) {
-    if (!h || !n_records) return fail(COPO_ERR_NULL, "copo_rewind_count: NULL argument");
-    *n_records = (int32_t)h->n_records;
-    return COPO_OK;
-}
-
-extern "C" int copo_rewind_fork(copo_rewind* h, copo_sim* target, int32_t first, int32_t S, const int32_t* scene, const int32_t* rec,
-                                const float* lcf, const uint64_t* seeds, const int32_t* watch_slot, int32_t* status, int32_t* watch_aid,
-                                void* stream) {
-    if (!h || !target || !scene || !rec || !status) return fail(COPO_ERR_NULL, "copo_rewind_fork: NULL argument");
-    const SimParams &sp = h->sim->p, &tp = target->p;
-    if (target == h->sim) return fail(COPO_ERR_CONFIG, "copo_rewind_fork: the target is the source simulator");
-    if (target->device != h->sim->device)
-        return fail(COPO_ERR_CONFIG, "copo_rewind_fork: the target lives on GPU %d, the source on GPU %d", target->device, h->sim->device);
-    if (tp.N != sp.N || tp.n_routes != sp.n_routes || tp.n_spawns != sp.n_spawns || tp.O != sp.O)
-        return fail(COPO_ERR_DIM, "copo_rewind_fork: target slots / routes / spawns / obs %d / %d / %d / %d, source %d / %d / %d / %d", tp.N,
-                    tp.n_routes, tp.n_spawns, tp.O, sp.N, sp.n_routes, sp.n_spawns, sp.O);
-    if (S < 1 || first < 0 || (int64_t)first + S > tp.E)
-        return fail(COPO_ERR_DIM, "copo_rewind_fork: scenes [%d, %d + %d) of a target of %d", first, first, S, tp.E);
-    RewindForkArgs a;
-    a.ring = h->ring; a.ring_env = h->ring_env; a.src_seeds = sp.seeds;
-    a.E = sp.E; a.N = sp.N; a.depth = h->depth; a.stride = h->stride; a.n_records = (int32_t)h->n_records;
-    a.state = tp.state; a.env = tp.env; a.seeds = const_cast<uint64_t*>(tp.seeds); a.TE = tp.E; a.first = first; a.S = S;
-    a.scene = scene; a.rec = rec; a.lcf = lcf; a.new_seeds = seeds; a.watch_slot = watch_slot; a.status = status; a.watch_aid = watch_aid;
-    HIP_TRY(launch_rewind_fork(a, static_cast<hipStream_t>(stream)));
-    target->started = true;
-    return COPO_OK;
-}
-
-extern "C" int copo_rewind_tally(const uint8_t* flags, const int32_t* watch_slot, int32_t* tally, int32_t B, int32_t N, void* stream) {
-    if (!flags || !tally) return fail(COPO_ERR_NULL, "copo_rewind_tally: NULL argument");
-    if (B < 0 || N < 1 || N > COPO_MAX_AGENTS) return fail(COPO_ERR_DIM, "copo_rewind_tally: B=%d N=%d (N in 1..%d)", B, N, COPO_MAX_AGENTS);
-    if (B == 0) return COPO_OK;
-    HIP_TRY(launch_rewind_tally(flags, watch_slot, tally, B, N, static_cast<hipStream_t>(stream)));
-    return COPO_OK;
-}
-
-// ---- traffic field maps (field_kernels.hip) --------------------------------------------------------------------
-
-struct copo_field {
-    copo_sim* sim;
-    copo_field_cfg cfg;
-    float inv_cell;
-    int32_t block, n_blocks;       // scenes per workgroup of the tile pass, and how many such blocks
-    int32_t* group;                // [E]
-    int32_t* last;                 // [E][N]
-    uint32_t* mask;                // [n_blocks][FIELD_MASK_WORDS]
-    long long* maps;               // [G][FIELD_LAYERS][H][W]
-    long long* scene_records;      // [G]
-    size_t last_bytes, mask_bytes, maps_bytes, rec_bytes;
-};
-
-static void free_field(copo_field* h) {
-    for (void* a : {(void*)h->group, (void*)h->last, (void*)h->mask, (void*)h->maps, (void*)h->scene_records})
-        if (a) (void)hipFree(a);
-    delete h;
-}
-
-static FieldArgs field_args(const copo_field* h, const uint8_t* flags, const float* ttc) {
-    const SimParams& p = h->sim->p;
-    FieldArgs a;
-    a.state = p.state; a.E = p.E; a.N = p.N; a.hl = p.hl; a.hw = p.hw;
-    a.x0 = h->cfg.x0; a.y0 = h->cfg.y0; a.cell = h->cfg.cell; a.inv_cell = h->inv_cell;
-    a.W = h->cfg.W; a.H = h->cfg.H; a.G = h->cfg.G; a.block = h->block; a.ttc_below = h->cfg.ttc_below;
-    a.group = h->group; a.flags = flags; a.ttc = ttc; a.last = h->last; a.mask = h->mask; a.maps = h->maps; a.scene_records = h->scene_records;
-    return a;
-}
-
-extern "C" int copo_field_create(copo_sim* sim, const copo_field_cfg* cfg, copo_field** out) {
-    if (!sim || !cfg || !out) return fail(COPO_ERR_NULL, "copo_field_create: NULL argument");
-    *out = nullptr;
-    static_assert(COPO_FIELD_LAYERS == FIELD_LAYERS && COPO_FIELD_MAX_SIDE == FIELD_MAX_SIDE && COPO_FIELD_MAX_GROUPS == FIELD_MAX_GROUPS,
-                  "copo_hip.h / field_common.h");
-    if (cfg->W < 1 || cfg->W > FIELD_MAX_SIDE || cfg->H < 1 || cfg->H > FIELD_MAX_SIDE || cfg->G < 1 || cfg->G > FIELD_MAX_GROUPS ||
-        !(cfg->cell > 0.0f) || !std::isfinite(cfg->cell))
-        return fail(COPO_ERR_DIM, "copo_field_create: W=%d H=%d (1..%d) G=%d (1..%d) cell=%g (> 0, finite)", cfg->W, cfg->H, FIELD_MAX_SIDE,
-                    cfg->G, FIELD_MAX_GROUPS, (double)cfg->cell);
-    const float inv_cell = (float)(1.0 / (double)cfg->cell);
-    if (!std::isfinite(cfg->x0) || !std::isfinite(cfg->y0) || !(cfg->ttc_below >= 0.0f) || !std::isfinite(cfg->ttc_below) ||
-        !std::isfinite(inv_cell))
-        return fail(COPO_ERR_CONFIG, "copo_field_create: x0=%g y0=%g 1/cell=%g (finite), ttc_below=%g (>= 0, finite)", (double)cfg->x0,
-                    (double)cfg->y0, (double)inv_cell, (double)cfg->ttc_below);
-    const size_t E = (size_t)sim->p.E, N = (size_t)sim->p.N;
-    // scenes per workgroup of the tile pass: 4 (one per wave) while the scenes are few, up to 64 -- every workgroup ends with one
-    // pass over its tile, which more scenes share
-    const int32_t block = 4 * (int32_t)std::min<size_t>(std::max<size_t>(E / 1024, 1), 16);
-    const size_t n_blocks = (E + block - 1) / block;
-    if (n_blocks > 65535) return fail(COPO_ERR_DIM, "copo_field_create: %zu scenes (at most %d)", E, 65535 * 64);
-    HIP_TRY(hipSetDevice(sim->device));
-    copo_field* h = new (std::nothrow) copo_field();
-    if (!h) return fail(COPO_ERR_DEVICE, "out of host memory");
-    h->sim = sim; h->cfg = *cfg; h->inv_cell = inv_cell; h->block = block; h->n_blocks = (int32_t)n_blocks;
-    h->last_bytes = E * N * sizeof(int32_t); h->mask_bytes = n_blocks * FIELD_MASK_WORDS * sizeof(uint32_t);
-    h->maps_bytes = (size_t)cfg->G * FIELD_LAYERS * cfg->H * cfg->W * sizeof(long long); h->rec_bytes = (size_t)cfg->G * sizeof(long long);
-    hipError_t err = hipMalloc((void**)&h->group, E * sizeof(int32_t));
-    if (err == hipSuccess) err = hipMalloc((void**)&h->last, h->last_bytes);
-    if (err == hipSuccess) err = hipMalloc((void**)&h->mask, h->mask_bytes);
-    if (err == hipSuccess) err = hipMalloc((void**)&h->maps, h->maps_bytes);
-    if (err == hipSuccess) err = hipMalloc((void**)&h->scene_records, h->rec_bytes);
-    if (err == hipSuccess) err = hipMemset(h->group, 0, E * sizeof(int32_t));
-    if (err == hipSuccess) err = hipMemset(h->last, 0xff, h->last_bytes);
-    if (err == hipSuccess) err = hipMemset(h->mask, 0, h->mask_bytes);
-    if (err == hipSuccess) err = hipMemset(h->maps, 0, h->maps_bytes);
-    if (err == hipSuccess) err = hipMemset(h->scene_records, 0, h->rec_bytes);
-    if (err != hipSuccess) {
-        (void)hipGetLastError();               // (a refused request must not show up as the next launch's error)
-        free_field(h);
-        return fail(COPO_ERR_DEVICE, "copo_field_create: %s (maps %zu bytes)", hipGetErrorString(err), (size_t)cfg->G * FIELD_LAYERS * cfg->H * cfg->W * 8);
-    }
-    *out = h;
-    return COPO_OK;
-}
-
-extern "C" int copo_field_destroy(copo_field* h) {
-    if (!h) return fail(COPO_ERR_NULL, "copo_field_destroy: NULL handle");
-    (void)hipSetDevice(h->sim->device);
-    free_field(h);
-    return COPO_OK;
-}
-
-extern "C" int copo_field_set_groups(copo_field* h, const int32_t* group_dev, void* stream) {
-    if (!h || !group_dev) return fail(COPO_ERR_NULL, "copo_field_set_groups: NULL argument");
-    HIP_TRY(hipMemcpyAsync(h->group, group_dev, (size_t)h->sim->p.E * sizeof(int32_t), hipMemcpyDeviceToDevice, static_cast<hipStream_t>(stream)));
-    return COPO_OK;
-}
-
-extern "C" int copo_field_record(copo_field* h, const uint8_t* flags, const float* ttc, int32_t accumulate, void* stream) {
-    if (!h) return fail(COPO_ERR_NULL, "copo_field_record: NULL handle");
-    if (accumulate != 0 && accumulate != 1) return fail(COPO_ERR_DIM, "copo_field_record: accumulate=%d (0 or 1)", accumulate);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const FieldArgs a = field_args(h, flags, ttc);
-    if (accumulate) HIP_TRY(hipMemsetAsync(h->mask, 0, h->mask_bytes, st));
-    HIP_TRY(launch_field_events(a, accumulate, st));
-    if (accumulate) HIP_TRY(launch_field_tiles(a, st));
-    return COPO_OK;
-}
-
-extern "C" int copo_field_read(copo_field* h, int64_t* maps_dev, int64_t* scene_records_dev, void* stream) {
-    if (!h || (!maps_dev && !scene_records_dev)) return fail(COPO_ERR_NULL, "copo_field_read: NULL argument");
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (maps_dev) HIP_TRY(hipMemcpyAsync(maps_dev, h->maps, h->maps_bytes, hipMemcpyDeviceToDevice, st));
-    if (scene_records_dev) HIP_TRY(hipMemcpyAsync(scene_records_dev, h->scene_records, h->rec_bytes, hipMemcpyDeviceToDevice, st));
-    return COPO_OK;
-}
-
-extern "C" int copo_field_forget(copo_field* h, void* stream) {
-    if (!h) return fail(COPO_ERR_NULL, "copo_field_forget: NULL handle");
-    HIP_TRY(hipMemsetAsync(h->last, 0xff, h->last_bytes, static_cast<hipStream_t>(stream)));
-    return COPO_OK;
-}
-
-extern "C" int copo_field_reset(copo_field* h, void* stream) {
-    if (!h) return fail(COPO_ERR_NULL, "copo_field_reset: NULL handle");
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    HIP_TRY(hipMemsetAsync(h->maps, 0, h->maps_bytes, st));
-    HIP_TRY(hipMemsetAsync(h->scene_records, 0, h->rec_bytes, st));
-    HIP_TRY(hipMemsetAsync(h->last, 0xff, h->last_bytes, st));
-    return COPO_OK;
-}
-
-// ---- traffic gates (gate_kernels.hip) --------------------------------------------------------------------------
-
-struct copo_gate {
-    copo_sim* sim;
-    copo_gate_cfg cfg;
-    GateLayout at;
-    int32_t n_records;             // records since create / reset (host side: eager only)
-    float4* gates;                 // [L]
-    int2* sections;                // [max(S, 1)]
-    int32_t* group;                // [E]
-    uint32_t *mem_x, *mem_y;       // [E][N]
-    int32_t* mem_aid;              // [E][N]
-    int32_t* mem_episode;          // [E]
-    unsigned long long* mem_valid; // [E]
-    int32_t* last_fwd;             // [E][L]
-    int32_t* entry;                // [E][max(S, 1)][N]
-    long long* acc;                // [at.words]
-    size_t slot_bytes, valid_bytes, fwd_bytes, entry_bytes, acc_bytes;
-};
-
-static void free_gate(copo_gate* h) {
-    for (void* a : {(void*)h->gates, (void*)h->sections, (void*)h->group, (void*)h->mem_x, (void*)h->mem_y, (void*)h->mem_aid,
-                    (void*)h->mem_episode, (void*)h->mem_valid, (void*)h->last_fwd, (void*)h->entry, (void*)h->acc})
-        if (a) (void)hipFree(a);
-    delete h;
-}
-
-// the slot memory, last_fwd and entry: nothing is followed, nothing crossed
-static hipError_t gate_forget(copo_gate* h, hipStream_t st) {
-    hipError_t err = hipMemsetAsync(h->mem_valid, 0, h->valid_bytes, st);
-    if (err == hipSuccess) err = hipMemsetAsync(h->last_fwd, 0xff, h->fwd_bytes, st);
-    if (err == hipSuccess) err = hipMemsetAsync(h->entry, 0xff, h->entry_bytes, st);
-    return err;
-}
-
-extern "C" int copo_gate_create(copo_sim* sim, const copo_gate_cfg* cfg, const float* gates, const int32_t* sections, copo_gate** out) {
-    if (!sim || !cfg || !gates || !out || (cfg && cfg->S > 0 && !sections)) return fail(COPO_ERR_NULL, "copo_gate_create: NULL argument");
-    *out = nullptr;
-    static_assert(COPO_GATE_MAX_GATES == GATE_MAX_GATES && COPO_GATE_MAX_SECTIONS == GATE_MAX_SECTIONS && COPO_GATE_MAX_GROUPS == GATE_MAX_GROUPS &&
-                  COPO_GATE_MAX_BINS == GATE_MAX_BINS && COPO_GATE_MAX_HIST == GATE_MAX_HIST, "copo_hip.h / gate_common.h");
-    if (cfg->L < 1 || cfg->L > GATE_MAX_GATES || cfg->S < 0 || cfg->S > GATE_MAX_SECTIONS || cfg->G < 1 || cfg->G > GATE_MAX_GROUPS ||
-        cfg->T < 1 || cfg->T > GATE_MAX_BINS || cfg->bin_records < 1 || cfg->HB < 1 || cfg->HB > GATE_MAX_HIST || cfg->TB < 1 ||
-        cfg->TB > GATE_MAX_HIST || cfg->tt_bin < 1)
-        return fail(COPO_ERR_DIM, "copo_gate_create: L=%d (1..%d) S=%d (0..%d) G=%d (1..%d) T=%d (1..%d) bin_records=%d (>= 1) HB=%d TB=%d (1..%d) tt_bin=%d (>= 1)",
-                    cfg->L, GATE_MAX_GATES, cfg->S, GATE_MAX_SECTIONS, cfg->G, GATE_MAX_GROUPS, cfg->T, GATE_MAX_BINS, cfg->bin_records, cfg->HB,
-                    cfg->TB, GATE_MAX_HIST, cfg->tt_bin);
-    for (int s = 0; s < cfg->S; ++s)
-        if (sections[2 * s] < 0 || sections[2 * s] >= cfg->L || sections[2 * s + 1] < 0 || sections[2 * s + 1] >= cfg->L)
-            return fail(COPO_ERR_DIM, "copo_gate_create: section %d = (%d, %d): gate indices are 0..%d", s, sections[2 * s], sections[2 * s + 1], cfg->L - 1);
-    for (int l = 0; l < cfg->L; ++l) {
-        const float* q = gates + 4 * l;
-        if (!std::isfinite(q[0]) || !std::isfinite(q[1]) || !std::isfinite(q[2]) || !std::isfinite(q[3]) || (q[0] == q[2] && q[1] == q[3]))
-            return fail(COPO_ERR_CONFIG, "copo_gate_create: gate %d = (%g, %g) -> (%g, %g): finite, A != B", l, (double)q[0], (double)q[1], (double)q[2],
-                        (double)q[3]);
-    }
-    const size_t E = (size_t)sim->p.E, N = (size_t)sim->p.N, L = (size_t)cfg->L, S1 = (size_t)std::max(cfg->S, 1);
-    HIP_TRY(hipSetDevice(sim->device));
-    copo_gate* h = new (std::nothrow) copo_gate();
-    if (!h) return fail(COPO_ERR_DEVICE, "out of host memory");
-    h->sim = sim; h->cfg = *cfg; h->n_records = 0;
-    h->at = gate_layout(cfg->G, cfg->L, cfg->S, cfg->T, cfg->HB, cfg->TB);
-    h->slot_bytes = E * N * 4; h->valid_bytes = E * sizeof(unsigned long long); h->fwd_bytes = E * L * sizeof(int32_t);
-    h->entry_bytes = E * S1 * N * sizeof(int32_t); h->acc_bytes = (size_t)h->at.words * sizeof(long long);
-    hipError_t err = hipMalloc((void**)&h->gates, L * sizeof(float4));
-    if (err == hipSuccess) err = hipMalloc((void**)&h->sections, S1 * sizeof(int2));
-    if (err == hipSuccess) err = hipMalloc((void**)&h->group, E * sizeof(int32_t));
-    if (err == hipSuccess) err = hipMalloc((void**)&h->mem_x, h->slot_bytes);
-    if (err == hipSuccess) err = hipMalloc((void**)&h->mem_y, h->slot_bytes);
-    if (err == hipSuccess) err = hipMalloc((void**)&h->mem_aid, h->slot_bytes);
-    if (err == hipSuccess) err = hipMalloc((void**)&h->mem_episode, E * sizeof(int32_t));
-    if (err == hipSuccess) err = hipMalloc((void**)&h->mem_valid, h->valid_bytes);
-    if (err == hipSuccess) err = hipMalloc((void**)&h->last_fwd, h->fwd_bytes);
-    if (err == hipSuccess) err = hipMalloc((void**)&h->entry, h->entry_bytes);
-    if (err == hipSuccess) err = hipMalloc((void**)&h->acc, h->acc_bytes);
-    if (err == hipSuccess) err = hipMemcpy(h->gates, gates, L * sizeof(float4), hipMemcpyHostToDevice);
-    if (err == hipSuccess) err = hipMemset(h->sections, 0, S1 * sizeof(int2));
-    if (err == hipSuccess && cfg->S > 0) err = hipMemcpy(h->sections, sections, (size_t)cfg->S * sizeof(int2), hipMemcpyHostToDevice);
-    if (err == hipSuccess) err = hipMemset(h->group, 0, E * sizeof(int32_t));
-    if (err == hipSuccess) err = hipMemset(h->mem_x, 0, h->slot_bytes);
-    if (err == hipSuccess) err = hipMemset(h->mem_y, 0, h->slot_bytes);
-    if (err == hipSuccess) err = hipMemset(h->mem_aid, 0, h->slot_bytes);
-    if (err == hipSuccess) err = hipMemset(h->mem_episode, 0, E * sizeof(int32_t));
-    if (err == hipSuccess) err = hipMemset(h->acc, 0, h->acc_bytes);
-    if (err == hipSuccess) err = gate_forget(h, nullptr);
-    if (err == hipSuccess) err = hipDeviceSynchronize();
-    if (err != hipSuccess) {
-        (void)hipGetLastError();               // (a refused request must not show up as the next launch's error)
-        free_gate(h);
-        return fail(COPO_ERR_DEVICE, "copo_gate_create: %s (slot memory %zu bytes)", hipGetErrorString(err), E * N * 12 + E * S1 * N * 4);
-    }
-    *out = h;
-    return COPO_OK;
-}
-
-extern "C" int copo_gate_destroy(copo_gate* h) {
-    if (!h) return fail(COPO_ERR_NULL, "copo_gate_destroy: NULL handle");
-    (void)hipSetDevice(h->sim->device);
-    free_gate(h);
-    return COPO_OK;
-}
-
-extern "C" int copo_gate_set_groups(copo_gate* h, const int32_t* group_dev, void* stream) {
-    if (!h || !group_dev) return fail(COPO_ERR_NULL, "copo_gate_set_groups: NULL argument");
-    HIP_TRY(hipMemcpyAsync(h->group, group_dev, (size_t)h->sim->p.E * sizeof(int32_t), hipMemcpyDeviceToDevice, static_cast<hipStream_t>(stream)));
-    return COPO_OK;
-}
-
-extern "C" int copo_gate_record(copo_gate* h, void* stream) {
-    if (!h) return fail(COPO_ERR_NULL, "copo_gate_record: NULL handle");
-    if (h->n_records == INT32_MAX) return fail(COPO_ERR_STATE, "copo_gate_record: %d records made; reset the handle", h->n_records);
-    const SimParams& p = h->sim->p;
-    GateArgs a;
-    a.state = p.state; a.env = p.env; a.E = p.E; a.N = p.N;
-    a.L = h->cfg.L; a.S = h->cfg.S; a.G = h->cfg.G; a.T = h->cfg.T; a.HB = h->cfg.HB; a.TB = h->cfg.TB; a.tt_bin = h->cfg.tt_bin;
-    a.r = h->n_records; a.tbin = std::min(h->n_records / h->cfg.bin_records, h->cfg.T - 1);
-    a.gates = h->gates; a.sections = h->sections; a.group = h->group;
-    a.mem_x = h->mem_x; a.mem_y = h->mem_y; a.mem_aid = h->mem_aid; a.mem_episode = h->mem_episode; a.mem_valid = h->mem_valid;
-    a.last_fwd = h->last_fwd; a.entry = h->entry; a.acc = h->acc; a.at = h->at;
-    HIP_TRY(launch_gate_record(a, static_cast<hipStream_t>(stream)));
-    h->n_records += 1;
-    return COPO_OK;
-}
-
-extern "C" int64_t copo_gate_words(const copo_gate_cfg* cfg) {
-    if (!cfg) return 0;
-    return gate_layout(cfg->G, cfg->L, cfg->S, cfg->T, cfg->HB, cfg->TB).words;
-}
-
-extern "C" int copo_gate_read(copo_gate* h, int64_t* acc_dev, int32_t* n_records, void* stream) {
-    if (!h || (!acc_dev && !n_records)) return fail(COPO_ERR_NULL, "copo_gate_read: NULL argument");
-    if (acc_dev) HIP_TRY(hipMemcpyAsync(acc_dev, h->acc, h->acc_bytes, hipMemcpyDeviceToDevice, static_cast<hipStream_t>(stream)));
-    if (n_records) *n_records = h->n_records;
-    return COPO_OK;
-}
-
-extern "C" int copo_gate_forget(copo_gate* h, void* stream) {
-    if (!h) return fail(COPO_ERR_NULL, "copo_gate_forget: NULL handle");
-    HIP_TRY(gate_forget(h, static_cast<hipStream_t>(stream)));
-    return COPO_OK;
-}
-
-extern "C" int copo_gate_reset(copo_gate* h, void* stream) {
-    if (!h) return fail(COPO_ERR_NULL, "copo_gate_reset: NULL handle");
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    HIP_TRY(gate_forget(h, st));
-    HIP_TRY(hipMemsetAsync(h->acc, 0, h->acc_bytes, st));
-    h->n_records = 0;
     return COPO_OK;
 }

@@ -14,9 +14,12 @@ import math
 
 import numpy as np
 
+from ._abi import FIELD_MAX_GROUPS as MAX_GROUPS, FIELD_MAX_SIDE as MAX_SIDE
+from ._handle import Handle
+
 LAYERS = ("occupancy", "wreck", "visits", "speed_q", "vx_q", "vy_q", "crash", "out", "arrive", "critical")
 DERIVED = ("mean_speed", "flow", "occupancy_s", "occupancy_frac")
-MAX_SIDE, MAX_GROUPS, QUANT = 1024, 64, 256
+QUANT = 256
 # colour ramp of `heat_overlay`: stops at t = 0, 1/3, 2/3, 1, linear in between
 RAMP = np.array([(40, 60, 200), (40, 200, 200), (240, 220, 40), (220, 40, 40)], np.float64)
 
@@ -105,25 +108,24 @@ def heat_overlay(frame_rgb, layer2d, view, lo=None, hi=None, alpha=160, grid=Non
     return out
 
 
-class FieldMaps:
+class FieldMaps(Handle):
     """Field maps of a `VecSim` on a grid of `W` x `H` cells of `cell` metres with the origin (`x0`, `y0`), for `groups` scene groups
     (`set_groups`: scene e adds to group[e], a value outside 0..groups-1 to nothing; all 0 at first).  `ttc_below` > 0 switches the
     `critical` layer on (it reads the `ttc` handed to `record`).  Record r adds to the state layers iff `r % stride == 0` (records
-    count from 0 since creation / `reset()`); events count in every record.  Destroy it (`close()`) before its simulator; every call
-    is asynchronous on torch's current stream except `read()` / `save()`."""
+    count from 0 since creation / `reset()`); events count in every record.  `close()` it when done (before or after its simulator;
+    no other call once the simulator is closed); every call is asynchronous on torch's current stream except `read()` / `save()`."""
+
+    _destroy = "copo_field_destroy"
 
     def __init__(self, sim, x0, y0, W, H, cell=1.0, groups=1, ttc_below=0.0, stride=1):
-        from . import _capi
-        self._capi, self.sim = _capi, sim
+        self._attach(sim)
         self.x0, self.y0, self.cell = float(np.float32(x0)), float(np.float32(y0)), float(np.float32(cell))
         self.W, self.H, self.groups = int(W), int(H), int(groups)
         self.ttc_below, self.stride = float(ttc_below), int(stride)
         if self.stride < 1:
             raise ValueError("stride=%d (>= 1)" % self.stride)
-        cfg = _capi.FieldCfg(self.x0, self.y0, self.cell, self.W, self.H, self.groups, self.ttc_below)
-        h = C.c_void_p()
-        _capi.check(_capi.lib.copo_field_create(sim._h, C.byref(cfg), C.byref(h)))
-        self._h = h
+        cfg = self._capi.FieldCfg(self.x0, self.y0, self.cell, self.W, self.H, self.groups, self.ttc_below)
+        self._create(self._capi.lib.copo_field_create, sim._h, C.byref(cfg))
         self.n_records = 0
 
     @classmethod
@@ -134,25 +136,9 @@ class FieldMaps:
 
     grid = property(lambda self: (self.x0, self.y0, self.cell))
 
-    def _stream(self):
-        return self.sim._torch.cuda.current_stream(self.sim.device).cuda_stream
-
-    def _arg(self, t, dtype, name):
-        if t is None:
-            return None
-        if not (t.is_cuda and t.dtype == dtype and t.is_contiguous() and t.numel() == self.sim.E * self.sim.N):
-            raise ValueError("%s must be a contiguous %s cuda tensor [E, N]" % (name, dtype))
-        return t.data_ptr()
-
     def set_groups(self, group):
         """Scene groups: int32 [E] (torch tensor on the simulator's device, or anything numpy reads)."""
-        torch = self.sim._torch
-        if not hasattr(group, "is_cuda"):
-            group = torch.from_numpy(np.ascontiguousarray(np.asarray(group, np.int32).reshape(-1)))
-        group = group.to(device=self.sim.device, dtype=torch.int32).contiguous()
-        if group.numel() != self.sim.E:
-            raise ValueError("one group per scene: %d values for %d scenes" % (group.numel(), self.sim.E))
-        self._capi.check(self._capi.lib.copo_field_set_groups(self._h, group.data_ptr(), self._stream()))
+        self._capi.check(self._capi.lib.copo_field_set_groups(self._h, self._groups(group).data_ptr(), self._stream()))
 
     def record(self, flags=None, ttc=None):
         """One record of the current state.  `flags`: uint8 [E, N], the output of the step that led to this state (None after a reset:
@@ -160,7 +146,7 @@ class FieldMaps:
         torch = self.sim._torch
         if self.ttc_below > 0.0 and ttc is None and self.n_records % self.stride == 0:
             raise ValueError("ttc_below=%g needs the meter's ttc in every record that accumulates" % self.ttc_below)
-        self._capi.check(self._capi.lib.copo_field_record(self._h, self._arg(flags, torch.uint8, "flags"), self._arg(ttc, torch.float32, "ttc"),
+        self._capi.check(self._capi.lib.copo_field_record(self._h, self._en_arg(flags, torch.uint8, "flags"), self._en_arg(ttc, torch.float32, "ttc"),
                                                           1 if self.n_records % self.stride == 0 else 0, self._stream()))
         self.n_records += 1
 
@@ -201,14 +187,3 @@ class FieldMaps:
 
     def heat_overlay(self, frame_rgb, layer2d, view, lo=None, hi=None, alpha=160):
         return heat_overlay(frame_rgb, layer2d, view, lo, hi, alpha, grid=self.grid)
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            self._capi.lib.copo_field_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

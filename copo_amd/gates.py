@@ -16,7 +16,11 @@ import math
 
 import numpy as np
 
-MAX_GATES, MAX_SECTIONS, MAX_GROUPS, MAX_BINS, MAX_HIST, QUANT = 32, 64, 64, 256, 64, 256
+from ._abi import (GATE_MAX_BINS as MAX_BINS, GATE_MAX_GATES as MAX_GATES, GATE_MAX_GROUPS as MAX_GROUPS, GATE_MAX_HIST as MAX_HIST,
+                   GATE_MAX_SECTIONS as MAX_SECTIONS)
+from ._handle import Handle
+
+QUANT = 256
 RAW = ("count", "speed_q", "series", "headway", "sec_count", "sec_sum", "sec_hist", "scene_records", "alive")
 DERIVED = ("flow_per_hour", "mean_speed", "headway_s", "mean_travel_s", "density")
 GATE_COLOUR, TICK_COLOUR = (255, 0, 255), (255, 255, 0)
@@ -162,27 +166,27 @@ def gate_overlay(frame_rgb, view, gates, colour=GATE_COLOUR, tick=TICK_COLOUR, t
     return out
 
 
-class TrafficGates:
+class TrafficGates(Handle):
     """Gates of a `VecSim`: `gates` [L, 4] = {ax, ay, bx, by} (1..32), `sections` = pairs (gate_in, gate_out) (0..64), `groups` scene
     groups (`set_groups`: scene e adds to group[e], a value outside 0..groups-1 to nothing; all 0 at first), `bins` = (T, records per
     bin) of the time series, `headway_bins` bins of one record each, `tt_bins` = (TB, records per bin) of the travel times; the last bin
-    of each holds everything beyond.  Records count from 0 since creation / `reset()`.  Destroy it (`close()`) before its simulator;
-    every call is asynchronous on torch's current stream except `read()` / `save()`."""
+    of each holds everything beyond.  Records count from 0 since creation / `reset()`.  `close()` it when done (before or after its
+    simulator; no other call once the simulator is closed); every call is asynchronous on torch's current stream except `read()` /
+    `save()`."""
+
+    _destroy = "copo_gate_destroy"
 
     def __init__(self, sim, gates, sections=(), groups=1, bins=(1, 1), headway_bins=32, tt_bins=(32, 10)):
-        from . import _capi
-        self._capi, self.sim = _capi, sim
+        self._attach(sim)
         self.gates = np.ascontiguousarray(np.asarray(gates, np.float32).reshape(-1, 4))
         self.sections = [(int(a), int(b)) for a, b in sections]
         self.groups = int(groups)
         (self.T, self.bin_records), self.HB, (self.TB, self.tt_bin) = (int(v) for v in bins), int(headway_bins), (int(v) for v in tt_bins)
         self.L, self.S = int(self.gates.shape[0]), len(self.sections)
-        cfg = _capi.GateCfg(self.L, self.S, self.groups, self.T, self.bin_records, self.HB, self.TB, self.tt_bin)
+        cfg = self._capi.GateCfg(self.L, self.S, self.groups, self.T, self.bin_records, self.HB, self.TB, self.tt_bin)
         sec = np.ascontiguousarray(np.asarray(self.sections, np.int32).reshape(-1, 2))
-        h = C.c_void_p()
-        _capi.check(_capi.lib.copo_gate_create(sim._h, C.byref(cfg), self.gates.ctypes.data, sec.ctypes.data if self.S else None, C.byref(h)))
-        self._h = h
-        self._words = int(_capi.lib.copo_gate_words(C.byref(cfg)))
+        self._create(self._capi.lib.copo_gate_create, sim._h, C.byref(cfg), self.gates.ctypes.data, sec.ctypes.data if self.S else None)
+        self._words = int(self._capi.lib.copo_gate_words(C.byref(cfg)))
         self.n_records = 0
         self.route_section = None
 
@@ -197,18 +201,9 @@ class TrafficGates:
 
     dims = property(lambda self: (self.groups, self.L, self.S, self.T, self.HB, self.TB))
 
-    def _stream(self):
-        return self.sim._torch.cuda.current_stream(self.sim.device).cuda_stream
-
     def set_groups(self, group):
         """Scene groups: int32 [E] (torch tensor on the simulator's device, or anything numpy reads)."""
-        torch = self.sim._torch
-        if not hasattr(group, "is_cuda"):
-            group = torch.from_numpy(np.ascontiguousarray(np.asarray(group, np.int32).reshape(-1)))
-        group = group.to(device=self.sim.device, dtype=torch.int32).contiguous()
-        if group.numel() != self.sim.E:
-            raise ValueError("one group per scene: %d values for %d scenes" % (group.numel(), self.sim.E))
-        self._capi.check(self._capi.lib.copo_gate_set_groups(self._h, group.data_ptr(), self._stream()))
+        self._capi.check(self._capi.lib.copo_gate_set_groups(self._h, self._groups(group).data_ptr(), self._stream()))
 
     def record(self):
         """One record of the current state (it reads simulator state only)."""
@@ -265,14 +260,3 @@ class TrafficGates:
             rows.append("%7d  %2d -> %2d  %9d  %8.2f" % (s, a, b, d["sec_count"][group, s], d["mean_travel_s"][group, s]))
         rows.append("density %.2f vehicles per scene over %d scene-records" % (d["density"][group], d["scene_records"][group]))
         return "\n".join(rows)
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            self._capi.lib.copo_gate_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

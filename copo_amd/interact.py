@@ -9,6 +9,8 @@ them in float64.
 """
 import ctypes as C
 
+from ._handle import Handle
+
 COUNT_KEYS = ("agents", "steps", "tet_steps", "near_events", "brake_events", "agents_with_finite_ttc")
 SUM_KEYS = ("min_gap", "min_ttc", "tit")
 
@@ -31,25 +33,22 @@ def summarise(counts, sums):
         brake_events_per_agent=brake / agents if agents else nan)
 
 
-class InteractionMeter:
+class InteractionMeter(Handle):
     """Surrogate safety measures of a `VecSim`'s agents: TTC beyond `horizon` seconds counts as none, a step is critical below
-    `ttc_crit` seconds, near below that or below `gap_near` metres, harsh braking above `brake` m/s^2.  Destroy it (`close()`)
-    before its simulator; every call is asynchronous on torch's current stream."""
+    `ttc_crit` seconds, near below that or below `gap_near` metres, harsh braking above `brake` m/s^2.  `close()` it when done
+    (before or after its simulator; no other call once the simulator is closed); every call is asynchronous on torch's current
+    stream."""
+
+    _destroy = "copo_interact_destroy"
 
     def __init__(self, sim, horizon=6.0, ttc_crit=1.5, gap_near=0.5, brake=4.0):
-        from . import _capi
-        self._capi, self.sim = _capi, sim
+        self._attach(sim)
         self.horizon, self.ttc_crit, self.gap_near, self.brake = float(horizon), float(ttc_crit), float(gap_near), float(brake)
-        cfg = _capi.InteractCfg(self.horizon, self.ttc_crit, self.gap_near, self.brake)
-        h = C.c_void_p()
-        _capi.check(_capi.lib.copo_interact_create(sim._h, C.byref(cfg), C.byref(h)))
-        self._h = h
+        cfg = self._capi.InteractCfg(self.horizon, self.ttc_crit, self.gap_near, self.brake)
+        self._create(self._capi.lib.copo_interact_create, sim._h, C.byref(cfg))
         torch = sim._torch
         self.gap = torch.empty(sim.E, sim.N, dtype=torch.float32, device=sim.device)
         self.ttc = torch.empty(sim.E, sim.N, dtype=torch.float32, device=sim.device)
-
-    def _stream(self):
-        return self.sim._torch.cuda.current_stream(self.sim.device).cuda_stream
 
     def record(self):
         """Measure the current state: (gap, ttc), float32 [E, N] device tensors owned by the meter (overwritten by the next call);
@@ -77,14 +76,3 @@ class InteractionMeter:
     def reset(self):
         """Empty every accumulator and the totals (after a manual reset or set_state)."""
         self._capi.check(self._capi.lib.copo_interact_reset(self._h, self._stream()))
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            self._capi.lib.copo_interact_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

@@ -5,12 +5,12 @@
 (paint order, colours, trail weights) are DESIGN.md section 8; `tests/render_numpy.py` restates them.  This is the reference's
 `env.render(mode="top_down", num_stack=25)` (copo/vis.py); MetaDrive's own renderer is not copied pixel for pixel.
 """
-import ctypes as C
 import os
 
 import numpy as np
 
 from . import maps as _maps
+from ._handle import Handle
 
 # vehicle colours by agent id % 12 (the only copy: handed to the library at create)
 PALETTE = np.array([
@@ -29,22 +29,19 @@ def map_view(tables, width, height, margin=1.05):
     return 0.5 * (x0 + x1), 0.5 * (y0 + y1), m
 
 
-class TopDownRenderer:
-    """Frames of a `VecSim`'s scenes, `width` x `height` pixels, with a trail ring of `trail` snapshots (0..32).  Destroy it
-    (`close()`) before its simulator; every call is asynchronous on torch's current stream."""
+class TopDownRenderer(Handle):
+    """Frames of a `VecSim`'s scenes, `width` x `height` pixels, with a trail ring of `trail` snapshots (0..32).  `close()` it
+    when done (before or after its simulator; no other call once the simulator is closed); every call is asynchronous on torch's
+    current stream."""
+
+    _destroy = "copo_render_destroy"
 
     def __init__(self, sim, width=512, height=512, trail=0):
-        from . import _capi
-        self._capi, self.sim = _capi, sim
+        self._attach(sim)
         self.W, self.H, self.trail = int(width), int(height), int(trail)
         self._pal = np.ascontiguousarray(PALETTE)
-        h = C.c_void_p()
-        _capi.check(_capi.lib.copo_render_create(sim._h, self.W, self.H, self.trail, self._pal.ctypes.data, C.byref(h)))
-        self._h = h
+        self._create(self._capi.lib.copo_render_create, sim._h, self.W, self.H, self.trail, self._pal.ctypes.data)
         self.recorded = 0
-
-    def _stream(self):
-        return self.sim._torch.cuda.current_stream(self.sim.device).cuda_stream
 
     def record(self):
         """Push every slot's current pose / status / agent id and each scene's episode counter into the trail ring."""
@@ -92,17 +89,6 @@ class TopDownRenderer:
         self._capi.check(self._capi.lib.copo_render_frames(self._h, sc.data_ptr(), int(scenes.size), vt.data_ptr(), trail,
                                                            out.data_ptr(), self._stream()))
         return out.view(torch.uint8).view(scenes.size, self.H, self.W, 4)
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            self._capi.lib.copo_render_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def to_numpy_rgb(frames):

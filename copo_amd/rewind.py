@@ -14,7 +14,9 @@ import dataclasses
 
 import numpy as np
 
-MAX_DEPTH, TALLY = 64, 8
+from ._abi import REWIND_MAX_DEPTH as MAX_DEPTH, REWIND_TALLY as TALLY
+from ._handle import Handle
+
 TALLY_KEYS = ("steps", "acted", "arrive", "crash", "out", "maxstep", "watch_flags", "watch_step")
 TALLY_INIT = (0, 0, 0, 0, 0, 0, 0, -1)
 
@@ -33,28 +35,25 @@ def _per_target(x, S, copies, dtype, name):
     return np.ascontiguousarray(a)
 
 
-class RewindBuffer:
+class RewindBuffer(Handle):
     """Ring of the last `depth` (1..64) stored records of every scene of `sim`; record r is stored iff `r % stride == 0`.  Memory:
     `64 N E depth + 16 E depth` bytes.  `keep_obs`: the observation of every stored record is kept next to it (`368 N E depth` bytes more
-    at 92 columns), so that `Branches.rollout` has the policy's first input -- a snapshot holds state, not observations.  Destroy it
-    (`close()`) before its simulator; `record` and `fork` are asynchronous on torch's current stream."""
+    at 92 columns), so that `Branches.rollout` has the policy's first input -- a snapshot holds state, not observations.  `close()` it
+    when done (before or after its simulator; no other call once the simulator is closed); `record` and `fork` are asynchronous on
+    torch's current stream."""
+
+    _destroy = "copo_rewind_destroy"
 
     def __init__(self, sim, depth=8, stride=4, keep_obs=False):
-        from . import _capi
-        self._capi, self.sim = _capi, sim
+        self._attach(sim)
         self.depth, self.stride, self.keep_obs = int(depth), int(stride), bool(keep_obs)
-        cfg = _capi.RewindCfg(self.depth, self.stride)
-        h = C.c_void_p()
-        _capi.check(_capi.lib.copo_rewind_create(sim._h, C.byref(cfg), C.byref(h)))
-        self._h = h
+        cfg = self._capi.RewindCfg(self.depth, self.stride)
+        self._create(self._capi.lib.copo_rewind_create, sim._h, C.byref(cfg))
         self._floor = 0            # first record a fork may take (`invalidate`)
         self._obs = None
         if self.keep_obs:
             torch = sim._torch
             self._obs = torch.zeros(self.depth, sim.E, sim.N, sim.O, dtype=torch.float32, device=sim.device)
-
-    def _stream(self):
-        return self.sim._torch.cuda.current_stream(self.sim.device).cuda_stream
 
     @property
     def n_records(self):
@@ -146,17 +145,6 @@ class RewindBuffer:
             over = (ok & ~torch.isnan(lv)).view(-1, 1)
             rows[:, :, lcf_col] = torch.where(over, col.view(-1, 1), rows[:, :, lcf_col])
         out.copy_(rows)
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            self._capi.lib.copo_rewind_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def tally(flags, watch_slots, rows):

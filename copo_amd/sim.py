@@ -11,6 +11,7 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from . import maps as _maps
+from ._handle import Handle
 
 STATE_DIM, NAVI_DIM = 6, 10
 
@@ -205,11 +206,12 @@ def fill_cfg_struct(cfg: SimConfig, struct_cls):
     return c, keep
 
 
-class VecSim:
+class VecSim(Handle):
     """E independent scenes x N agent slots on one GPU; every call is asynchronous on torch's current stream."""
 
     OUT_FIELDS = ("obs", "rew", "nei_rew", "glob_rew", "flags", "nbr_idx", "nbr_cnt", "mf_cnt", "nbr_dist", "lcf",
                   "info", "agent_id")
+    _destroy = "copo_sim_destroy"
 
     def __init__(self, cfg: SimConfig, device=0, with_info=True):
         import torch
@@ -221,9 +223,7 @@ class VecSim:
         self.A = cfg.act_dim
         self.device = torch.device("cuda", device)
         struct, self._keep = fill_cfg_struct(cfg, _capi.SimCfg)
-        h = C.c_void_p()
-        _capi.check(_capi.lib.copo_sim_create(C.byref(struct), device, C.byref(h)))
-        self._h = h
+        self._create(_capi.lib.copo_sim_create, C.byref(struct), device)
         self.on_shape_change = []        # weak references to callables (VecSampler registers the reset of its captured rollout)
         E, N, O, K, dev = self.E, self.N, self.O, self.K, self.device
         f32, i32, u8 = torch.float32, torch.int32, torch.uint8
@@ -244,9 +244,6 @@ class VecSim:
             t = tensors.get(k)
             setattr(so, k, t.data_ptr() if t is not None else None)
         return so
-
-    def _stream(self):
-        return self._torch.cuda.current_stream(self.device).cuda_stream
 
     def reset(self, seeds=None, out=None):
         if seeds is None:
@@ -310,14 +307,3 @@ class VecSim:
     def set_state(self, st, env):
         assert st.is_cuda and env.is_cuda and st.is_contiguous() and env.is_contiguous()
         self._capi.check(self._capi.lib.copo_sim_set_state(self._h, st.data_ptr(), env.data_ptr(), self._stream()))
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            self._capi.lib.copo_sim_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
