@@ -93,3 +93,11 @@ class GateCfg(C.Structure):
 
 
 GATE_MAX_GATES, GATE_MAX_SECTIONS, GATE_MAX_GROUPS, GATE_MAX_BINS, GATE_MAX_HIST = 32, 64, 64, 256, 64
+
+
+class TripCfg(C.Structure):
+    """Mirror of `copo_trip_cfg`."""
+    _fields_ = [("max_rows", C.c_int32), ("stop_speed", C.c_float)]
+
+
+TRIP_WORDS, TRIP_DONE, TRIP_VANISHED, TRIP_FLUSHED = 16, 1, 2, 3

@@ -156,6 +156,14 @@ _SIGS = {
     "copo_gate_forget": (C.c_int, [C.c_void_p, C.c_void_p]),
     "copo_gate_reset": (C.c_int, [C.c_void_p, C.c_void_p]),
     "copo_gate_destroy": (C.c_int, [C.c_void_p]),
+    "copo_trip_create": (C.c_int, [C.c_void_p, C.POINTER(TripCfg), C.POINTER(C.c_void_p)]),
+    "copo_trip_record": (C.c_int, [C.c_void_p] * 6),
+    "copo_trip_flush": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "copo_trip_count": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.c_void_p]),
+    "copo_trip_read": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "copo_trip_clear": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "copo_trip_reset": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "copo_trip_destroy": (C.c_int, [C.c_void_p]),
     "copo_neighbours_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_float,
                                       C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                       C.c_void_p, C.c_void_p]),

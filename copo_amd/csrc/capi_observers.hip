@@ -1,5 +1,5 @@
 // C ABI of the handles that observe a simulator (include/copo_hip.h): renderer, interaction meter, event clips, scene rewind, field
-// maps, traffic gates.  Each owns its device buffers through a DevPool (capi_common.h) on the simulator's device; every call but
+// maps, traffic gates, trip log.  Each owns its device buffers through a DevPool (capi_common.h) on the simulator's device; every call but
 // *_destroy reads the simulator, which therefore has to be alive.  All launches are asynchronous on the caller's stream.
 #include <algorithm>
 #include <array>
@@ -15,6 +15,7 @@
 #include "rewind_common.h"
 #include "field_common.h"
 #include "gate_common.h"
+#include "trip_common.h"
 
 using namespace copo;
 
@@ -634,6 +635,116 @@ extern "C" int copo_gate_reset(copo_gate* h, void* stream) {
     hipStream_t st = static_cast<hipStream_t>(stream);
     HIP_TRY(gate_forget(h, st));
     HIP_TRY(h->acc.fill(0, st));
+    h->n_records = 0;
+    return COPO_OK;
+}
+
+// ---- trip log (trip_kernels.hip) -------------------------------------------------------------------------------
+
+struct copo_trip {
+    copo_sim* sim;
+    DevPool mem;
+    copo_trip_cfg cfg;
+    int32_t n_records;                     // records since create / reset (host side: eager only)
+    DevBuf<unsigned long long> open;       // [E]
+    DevBuf<int32_t> episode;               // [E]
+    DevBuf<uint32_t> slots;                // [TRIP_MEM_WORDS][E][N]
+    DevBuf<unsigned long long> closing;    // [E]
+    DevBuf<uint32_t> endw;                 // [E][N]
+    DevBuf<int32_t> base;                  // [E]
+    DevBuf<long long> counters;            // [TRIP_COUNTERS]
+    DevBuf<uint32_t> pool;                 // [max_rows][TRIP_WORDS]
+};
+
+static TripArgs trip_args(const copo_trip* h) {
+    const SimParams& p = h->sim->p;
+    TripArgs a;
+    a.state = p.state; a.env = p.env; a.E = p.E; a.N = p.N;
+    a.max_rows = h->cfg.max_rows; a.r = h->n_records; a.stop_speed = h->cfg.stop_speed;
+    a.flags = nullptr; a.rew = nullptr; a.gap = nullptr; a.ttc = nullptr;
+    a.open = h->open; a.episode = h->episode; a.mem = h->slots; a.closing = h->closing; a.endw = h->endw; a.base = h->base;
+    a.counters = h->counters; a.pool = h->pool;
+    return a;
+}
+
+extern "C" int copo_trip_create(copo_sim* sim, const copo_trip_cfg* cfg, copo_trip** out) {
+    if (!sim || !cfg || !out) return fail(COPO_ERR_NULL, "copo_trip_create: NULL argument");
+    *out = nullptr;
+    static_assert(COPO_TRIP_WORDS == TRIP_WORDS && COPO_TRIP_DONE == TRIP_KIND_DONE && COPO_TRIP_VANISHED == TRIP_KIND_VANISHED &&
+                  COPO_TRIP_FLUSHED == TRIP_KIND_FLUSH, "copo_hip.h / trip_common.h");
+    if (cfg->max_rows < 1) return fail(COPO_ERR_DIM, "copo_trip_create: max_rows=%d (>= 1)", cfg->max_rows);
+    if (!(cfg->stop_speed >= 0.0f) || !std::isfinite(cfg->stop_speed))
+        return fail(COPO_ERR_CONFIG, "copo_trip_create: stop_speed=%g (>= 0, finite)", (double)cfg->stop_speed);
+    const size_t E = (size_t)sim->p.E, N = (size_t)sim->p.N;
+    HIP_TRY(hipSetDevice(sim->device));
+    copo_trip* h = new (std::nothrow) copo_trip();
+    if (!h) return fail(COPO_ERR_DEVICE, "out of host memory");
+    h->sim = sim; h->mem.device = sim->device; h->cfg = *cfg; h->n_records = 0;
+    h->open = h->mem.alloc<unsigned long long>(E);
+    h->episode = h->mem.alloc<int32_t>(E);
+    h->slots = h->mem.alloc<uint32_t>((size_t)TRIP_MEM_WORDS * E * N);
+    h->closing = h->mem.alloc<unsigned long long>(E);
+    h->endw = h->mem.alloc<uint32_t>(E * N);
+    h->base = h->mem.alloc<int32_t>(E);
+    h->counters = h->mem.alloc<long long>(TRIP_COUNTERS);
+    h->pool = h->mem.alloc<uint32_t>((size_t)cfg->max_rows * TRIP_WORDS);
+    return finish_create(h, out, "copo_trip_create");
+}
+
+extern "C" int copo_trip_destroy(copo_trip* h) { return destroy_handle(h, "copo_trip_destroy"); }
+
+extern "C" int copo_trip_record(copo_trip* h, const uint8_t* flags, const float* rew, const float* gap, const float* ttc, void* stream) {
+    if (!h) return fail(COPO_ERR_NULL, "copo_trip_record: NULL handle");
+    if (h->n_records == INT32_MAX) return fail(COPO_ERR_STATE, "copo_trip_record: %d records made; reset the handle", h->n_records);
+    TripArgs a = trip_args(h);
+    a.flags = flags; a.rew = rew; a.gap = gap; a.ttc = ttc;
+    HIP_TRY(launch_trip_record(a, static_cast<hipStream_t>(stream)));
+    h->n_records += 1;
+    return COPO_OK;
+}
+
+extern "C" int copo_trip_flush(copo_trip* h, void* stream) {
+    if (!h) return fail(COPO_ERR_NULL, "copo_trip_flush: NULL handle");
+    HIP_TRY(launch_trip_flush(trip_args(h), static_cast<hipStream_t>(stream)));
+    return COPO_OK;
+}
+
+extern "C" int copo_trip_count(copo_trip* h, int64_t* out, void* stream) {
+    if (!h || !out) return fail(COPO_ERR_NULL, "copo_trip_count: NULL argument");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    long long c[TRIP_COUNTERS];
+    HIP_TRY(hipMemcpyAsync(c, h->counters, sizeof(c), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    out[0] = c[TC_ROWS];
+    out[1] = c[TC_DROPPED];
+    return COPO_OK;
+}
+
+extern "C" int copo_trip_read(copo_trip* h, int32_t first, int32_t n, int32_t* rows_out, void* stream) {
+    if (!h) return fail(COPO_ERR_NULL, "copo_trip_read: NULL handle");
+    if (first < 0 || n < 0 || (int64_t)first + n > h->cfg.max_rows)
+        return fail(COPO_ERR_DIM, "copo_trip_read: rows [%d, %d + %d) of a pool of %d", first, first, n, h->cfg.max_rows);
+    if (n == 0) return COPO_OK;
+    if (!rows_out) return fail(COPO_ERR_NULL, "copo_trip_read: NULL output");
+    HIP_TRY(hipMemcpyAsync(rows_out, h->pool.p + (size_t)first * TRIP_WORDS, (size_t)n * TRIP_WORDS * 4, hipMemcpyDeviceToDevice,
+                           static_cast<hipStream_t>(stream)));
+    return COPO_OK;
+}
+
+// (the rows need no clearing: nothing reads beyond n_rows)
+extern "C" int copo_trip_clear(copo_trip* h, void* stream) {
+    if (!h) return fail(COPO_ERR_NULL, "copo_trip_clear: NULL handle");
+    HIP_TRY(h->counters.fill(0, static_cast<hipStream_t>(stream)));
+    return COPO_OK;
+}
+
+// (the slot memory needs no clearing: a slot is written when its trip opens)
+extern "C" int copo_trip_reset(copo_trip* h, void* stream) {
+    if (!h) return fail(COPO_ERR_NULL, "copo_trip_reset: NULL handle");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    HIP_TRY(h->counters.fill(0, st));
+    HIP_TRY(h->open.fill(0, st));
+    HIP_TRY(h->pool.fill(0, st));
     h->n_records = 0;
     return COPO_OK;
 }

@@ -62,7 +62,7 @@ class MultiAgentMetaDrive:
     @classmethod
     def default_config(cls):
         return dict(map=cls.MAP, num_envs=1, num_agents=None, start_seed=5000, horizon=1000, num_lasers=72,
-                    device=0, crash_done=True, out_of_road_done=True, allow_respawn=True, delay_done=25, interaction_metrics=False, event_clips=None, rewind=None, field_maps=None, traffic_gates=None)
+                    device=0, crash_done=True, out_of_road_done=True, allow_respawn=True, delay_done=25, interaction_metrics=False, event_clips=None, rewind=None, field_maps=None, traffic_gates=None, trip_log=None)
 
     def __init__(self, config=None):
         cfg = type(self).default_config()
@@ -115,6 +115,10 @@ class MultiAgentMetaDrive:
             from copo_amd.gates import TrafficGates
             gate_kwargs = dict(cfg["traffic_gates"])
             self._gates = TrafficGates(self.sim, **gate_kwargs) if "gates" in gate_kwargs else TrafficGates.for_map(self.sim, **gate_kwargs)
+        self._trips = None         # `trip_log`: one device-written row per finished agent (copo_amd/trips.py)
+        if cfg.get("trip_log") is not None:
+            from copo_amd.trips import TripLog
+            self._trips = TripLog(self.sim, **dict(cfg["trip_log"]))
         self._slot_ids = None      # dict API state (num_envs == 1)
         self._next_obs = None
         self.current_lcf_mean, self.current_lcf_std = self.sim_config.lcf_mean, self.sim_config.lcf_std
@@ -174,6 +178,7 @@ class MultiAgentMetaDrive:
         self._record_rewind(True)
         self._record_fields(None)
         self._record_gates(True)
+        self._record_trips(None)
         return out
 
     def vec_step(self, actions):
@@ -184,6 +189,7 @@ class MultiAgentMetaDrive:
         self._record_rewind(False)
         self._record_fields(out["flags"])
         self._record_gates(False)
+        self._record_trips(out)
         return out
 
     # ---- top-down rendering (copo/vis.py: env.render(mode="top_down", num_stack=25)) ------------------------------------------
@@ -299,6 +305,22 @@ class MultiAgentMetaDrive:
         assert self._gates is not None, "set traffic_gates={...} in the env config"
         return self._gates
 
+    # ---- trip log (config key `trip_log`: None, or the arguments of `TripLog`): one record of the state after reset (no arrays: a trip that
+    #      was open ends only because its agent is gone) and after every step, fed with the step's flags and rew and, with
+    #      `interaction_metrics`, the meter's gap / ttc of that state.  The rows are kept over resets; a reset that
+    #      restores a slot's agent id and episode word continues its trip (`trip_log().flush()` before the reset cuts every trip there) ----
+    def _record_trips(self, out):
+        t = self._trips
+        if t is not None:
+            m = self._meter
+            t.record(flags=None if out is None else out["flags"], rew=None if out is None else out["rew"],
+                     gap=None if m is None else m.gap, ttc=None if m is None else m.ttc)
+
+    def trip_log(self):
+        """The env's `copo_amd.trips.TripLog`."""
+        assert self._trips is not None, "set trip_log={...} in the env config"
+        return self._trips
+
     def set_lcf_dist(self, mean, std):
         assert self.ENABLE_LCF, "set_lcf_dist needs an LCF env (get_lcf_env)"
         assert std > 0.0 and -1.0 <= mean <= 1.0
@@ -347,6 +369,7 @@ class MultiAgentMetaDrive:
         self._record_rewind(True)
         self._record_fields(None)
         self._record_gates(True)
+        self._record_trips(None)
         ids = self._ids(out)
         self._slot_ids = ["agent%d" % a for a in ids]
         self._just_terminated = {}
@@ -371,6 +394,7 @@ class MultiAgentMetaDrive:
         self._record_rewind(False)
         self._record_fields(out["flags"])
         self._record_gates(False)
+        self._record_trips(out)
         h = {k: v[0].cpu().numpy() for k, v in out.items() if v is not None}
         if self._meter is not None:      # of the state after the step: +inf for an agent that ended in it
             h["min_gap"], h["ttc"] = self._meter.gap[0].cpu().numpy(), self._meter.ttc[0].cpu().numpy()
@@ -468,6 +492,9 @@ class MultiAgentMetaDrive:
         if getattr(self, "_gates", None) is not None:
             self._gates.close()
             self._gates = None
+        if getattr(self, "_trips", None) is not None:
+            self._trips.close()
+            self._trips = None
         self.sim.close()
 
 

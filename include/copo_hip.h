@@ -521,6 +521,55 @@ int copo_gate_forget(copo_gate* h, void* stream);
 int copo_gate_reset(copo_gate* h, void* stream);
 int copo_gate_destroy(copo_gate* h);
 
+/* ---- trip log: ONE row per finished agent, written on the device into a bounded pool.  A handle reads its
+ *      simulator's state and must be destroyed before it.  Eager only: the record count lives on the host.  Everything the device computes
+ *      is integer logic, one fp32 add per record (the reward), the field maps' speed quantisation and plain fp32 `<`, so the rows are
+ *      reproducible bit for bit.
+ * Records count from 0 since create / reset.  State fields by number: 3 speed, 9 route progress, 10 LCF, 12 route | road << 16, 13
+ * status | timer << 8 | age << 16, 14 agent id; env word 1 is the scene's episode.  A slot's IDENTITY is (agent id, episode word).  The
+ * handle keeps per scene an open mask of 64 bits and the episode word, per slot the agent id and the accumulators below.
+ * Record r, with the optional device arrays flags u8 [E][N] (the step's output), rew, gap, ttc fp32 [E][N] (NULL = absent), for every slot:
+ *   1 CLOSE, when a trip is open in the slot.  With flags & COPO_F_ACTED and rew given: reward = reward + rew (a plain fp32 add).  With
+ *     flags & COPO_F_DONE: the trip closes with kind COPO_TRIP_DONE and end = the flags byte.  Otherwise, if the slot is not ALIVE now
+ *     with the same identity: it closes with kind COPO_TRIP_VANISHED (a scene reset, a set_state, or records that were skipped) and
+ *     end = 0.  flags = NULL (the record after a reset) can close only that way.
+ *   2 OPEN, when the slot is ALIVE and no trip is open in it, also after a close in this same record: first_rec = r, route = the low 16
+ *     bits of field 12, lcf = the raw bits of field 10, prog0 = the raw bits of field 9, steps = speed_sum = speed_max = stops = 0,
+ *     reward = +0.0f, min_gap = min_ttc = +inf.
+ *   3 ACCUMULATE, when a trip is open after 1 and 2: steps += 1; prog1 = the raw bits of field 9; q = rint(min(max(v, 0), 255) * 256)
+ *     (fp32, half to even: the field maps' quantisation; a NaN gives 0); speed_sum += q (uint32); speed_max = max(speed_max, q);
+ *     stops += (v < stop_speed); min_gap = gap if gap < min_gap, min_ttc likewise (plain `<`: a NaN never enters).
+ * Row, COPO_TRIP_WORDS 32-bit words: {scene, slot | route << 16, agent id, episode, first_rec, steps, end flags | kind << 8, lcf bits,
+ * prog0 bits, prog1 bits, speed_sum, speed_max, stops, reward bits, min_gap bits, min_ttc bits}.
+ * Order.  The rows closed in one record take the ids n_rows, n_rows + 1, ... in ascending (scene, slot) order; an id >= max_rows is not
+ * stored and counts as dropped, the trip is closed all the same.  No atomic decides an id: which rows exist and their order do not
+ * depend on scheduling. ---- */
+#define COPO_TRIP_WORDS 16
+#define COPO_TRIP_DONE 1
+#define COPO_TRIP_VANISHED 2
+#define COPO_TRIP_FLUSHED 3
+typedef struct copo_trip_cfg {
+    int32_t max_rows;          /* pool size, >= 1 (COPO_ERR_DIM) */
+    float stop_speed;          /* m/s, finite and >= 0 (COPO_ERR_CONFIG): a record with v < stop_speed counts as a stop */
+} copo_trip_cfg;
+typedef struct copo_trip copo_trip;
+/* allocates the pool (64 max_rows bytes) and 56 E N + 24 E bytes of memory: COPO_ERR_DEVICE when the device refuses */
+int copo_trip_create(copo_sim* sim, const copo_trip_cfg* cfg, copo_trip** out);
+/* one record of the current state.  Three launches on `stream`, no allocation, no host synchronisation; simulator memory is only read */
+int copo_trip_record(copo_trip* h, const uint8_t* flags, const float* rew, const float* gap, const float* ttc, void* stream);
+/* every open trip closes with kind COPO_TRIP_FLUSHED and end = 0 under the same order and overflow rule; nothing stays open (a slot that
+ * is still ALIVE opens a new trip in the next record).  Not a record: the count does not move */
+int copo_trip_flush(copo_trip* h, void* stream);
+/* HOST output: out[0] = rows stored so far (<= max_rows), out[1] = rows dropped; the one call that waits for `stream` */
+int copo_trip_count(copo_trip* h, int64_t* out, void* stream);
+/* rows [first, first + n) of the pool, device to device: rows_out [n][COPO_TRIP_WORDS] int32; first + n <= max_rows (COPO_ERR_DIM) */
+int copo_trip_read(copo_trip* h, int32_t first, int32_t n, int32_t* rows_out, void* stream);
+/* n_rows = dropped = 0; the open trips and the record count stay (drains a bounded pool during a long run) */
+int copo_trip_clear(copo_trip* h, void* stream);
+/* forget everything: rows, counters, open trips; records count from 0 again */
+int copo_trip_reset(copo_trip* h, void* stream);
+int copo_trip_destroy(copo_trip* h);
+
 /* ---- stateless ops ---- */
 
 /* CCEnv._update_distance_map + _find_in_range (env_wrappers.py:125-158) + LCFEnv reward block (:313-326).
