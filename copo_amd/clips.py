@@ -130,6 +130,19 @@ class ClipRecorder(Handle):
         self._create(self._capi.lib.copo_clip_create, sim._h, C.byref(cfg))
         self.cap = self.pre + self.post + 1
 
+    @classmethod
+    def from_env(cls, sim, value):
+        """The env's recorder (config key `event_clips`: None, or the arguments of `ClipRecorder`)."""
+        return cls(sim, **dict(value))
+
+    def env_record(self, feed):
+        """One record of the state after reset and after every step, fed with the step's flags and, for the ttc / gap triggers, the
+        meter's arrays of that state.  Clips are kept over resets; a clip still waiting for its `post` records when the scenes are
+        reset by hand is committed with what it has."""
+        if feed.after_reset and feed.records > 0:
+            self.flush()
+        self.record(flags=feed.flags, ttc=feed.ttc if self.ttc_below > 0.0 else None, gap=feed.gap if self.gap_below > 0.0 else None)
+
     def record(self, flags=None, ttc=None, gap=None):
         """Snapshot the current state of every scene; `flags` (uint8 [E, N], the step's output) and `ttc` / `gap` (float32 [E, N],
         `InteractionMeter.record()`'s) feed the triggers of this record, None switches one off for the call."""

@@ -228,7 +228,8 @@ class RecorderEnv:
         ret["svo_estimate_deg_mean"], ret["svo_estimate_deg_min"] = np.mean(svos), np.min(svos)
         ret["svo_estimate_deg_max"] = np.max(svos)
         ret["svo_reward"] = np.sum(svo_rewards) / n
-        if getattr(self.unwrapped, "_meter", None) is not None:      # env config `interaction_metrics`: the agents that ended since reset()
+        observer = getattr(self.unwrapped, "observer", lambda key: None)      # (any dict-API env may be wrapped)
+        if observer("interaction_metrics") is not None:      # env config `interaction_metrics`: the agents that ended since reset()
             for k, v in self.unwrapped.interaction_summary().items():
                 ret["interaction_" + k] = v
         return ret

@@ -134,7 +134,20 @@ class FieldMaps(Handle):
         x0, y0, W, H = grid_for_map(sim.tables, cell, margin)
         return cls(sim, x0, y0, W, H, cell=cell, **kwargs)
 
-    grid = property(lambda self: (self.x0, self.y0, self.cell))
+    @classmethod
+    def from_env(cls, sim, value):
+        """The env's maps (config key `field_maps`: None, or the arguments of `FieldMaps` -- with x0, y0, W, H an explicit grid, else
+        `for_map`)."""
+        kwargs = dict(value)
+        explicit = all(k in kwargs for k in ("x0", "y0", "W", "H"))
+        return cls(sim, **kwargs) if explicit else cls.for_map(sim, **kwargs)
+
+    def env_record(self, feed):
+        """One record of the state after reset (no flags: no event) and after every step, fed with the step's flags and, for the
+        critical layer, the meter's ttc of that state.  The maps are kept over resets."""
+        self.record(flags=feed.flags, ttc=feed.ttc if self.ttc_below > 0.0 else None)
+
+    grid =property(lambda self: (self.x0, self.y0, self.cell))
 
     def set_groups(self, group):
         """Scene groups: int32 [E] (torch tensor on the simulator's device, or anything numpy reads)."""

@@ -199,7 +199,21 @@ class TrafficGates(Handle):
         self.route_section = route_section
         return self
 
-    dims = property(lambda self: (self.groups, self.L, self.S, self.T, self.HB, self.TB))
+    @classmethod
+    def from_env(cls, sim, value):
+        """The env's gates (config key `traffic_gates`: None, or the arguments of `TrafficGates` -- with `gates` explicit gates, else
+        `for_map`)."""
+        kwargs = dict(value)
+        return cls(sim, **kwargs) if "gates" in kwargs else cls.for_map(sim, **kwargs)
+
+    def env_record(self, feed):
+        """One record after every step; after a reset by hand the memory is forgotten first, so that the reset fires nothing.  The
+        accumulators are kept over resets."""
+        if feed.after_reset:
+            self.forget()
+        self.record()
+
+    dims =property(lambda self: (self.groups, self.L, self.S, self.T, self.HB, self.TB))
 
     def set_groups(self, group):
         """Scene groups: int32 [E] (torch tensor on the simulator's device, or anything numpy reads)."""

@@ -50,6 +50,17 @@ class InteractionMeter(Handle):
         self.gap = torch.empty(sim.E, sim.N, dtype=torch.float32, device=sim.device)
         self.ttc = torch.empty(sim.E, sim.N, dtype=torch.float32, device=sim.device)
 
+    @classmethod
+    def from_env(cls, sim, value):
+        """The env's meter (config key `interaction_metrics`: on or off, no arguments)."""
+        return cls(sim)
+
+    def env_record(self, feed):
+        """One measurement of the state after reset and after every step; a reset empties the accumulators first."""
+        if feed.after_reset:
+            self.reset()
+        self.record()
+
     def record(self):
         """Measure the current state: (gap, ttc), float32 [E, N] device tensors owned by the meter (overwritten by the next call);
         +inf for a slot that does not drive or has no partner."""

@@ -43,6 +43,12 @@ class TopDownRenderer(Handle):
         self._create(self._capi.lib.copo_render_create, sim._h, self.W, self.H, self.trail, self._pal.ctypes.data)
         self.recorded = 0
 
+    def env_record(self, feed):
+        """One snapshot after reset and after every step; a reset empties the trail first."""
+        if feed.after_reset:
+            self.clear()
+        self.record()
+
     def record(self):
         """Push every slot's current pose / status / agent id and each scene's episode counter into the trail ring."""
         self._capi.check(self._capi.lib.copo_render_record(self._h, self._stream()))

@@ -55,6 +55,19 @@ class RewindBuffer(Handle):
             torch = sim._torch
             self._obs = torch.zeros(self.depth, sim.E, sim.N, sim.O, dtype=torch.float32, device=sim.device)
 
+    @classmethod
+    def from_env(cls, sim, value):
+        """The env's buffer (config key `rewind`: None, or the arguments of `RewindBuffer`)."""
+        return cls(sim, **dict(value))
+
+    def env_record(self, feed):
+        """One record of the state after reset and after every step, next to the clip recorder's, so that a clip header's first_rec /
+        trig_rec name rewind records.  The clip recorder counts on over a reset by hand, so the buffer does too; the records from
+        before that reset can no longer be forked (`invalidate`)."""
+        if feed.after_reset and self.n_records:
+            self.invalidate()
+        self.record()
+
     @property
     def n_records(self):
         """Records made since creation / `reset()`."""

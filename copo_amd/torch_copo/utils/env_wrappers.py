@@ -21,6 +21,7 @@ import numpy as np
 from copo_amd import _capi
 from copo_amd.engine import Box, DictSpace
 from copo_amd.maps import MAP_BUILDERS
+from copo_amd.observers import ENV_OBSERVERS, ObserverList
 from copo_amd.sim import MAP_OBS_DEFAULTS, SimConfig, VecSim
 
 _ENV_REGISTRY = {}
@@ -62,7 +63,8 @@ class MultiAgentMetaDrive:
     @classmethod
     def default_config(cls):
         return dict(map=cls.MAP, num_envs=1, num_agents=None, start_seed=5000, horizon=1000, num_lasers=72,
-                    device=0, crash_done=True, out_of_road_done=True, allow_respawn=True, delay_done=25, interaction_metrics=False, event_clips=None, rewind=None, field_maps=None, traffic_gates=None, trip_log=None)
+                    device=0, crash_done=True, out_of_road_done=True, allow_respawn=True, delay_done=25,
+                    **{row.key: row.default for row in ENV_OBSERVERS})
 
     def __init__(self, config=None):
         cfg = type(self).default_config()
@@ -74,13 +76,7 @@ class MultiAgentMetaDrive:
             kw.setdefault("seed", int(cfg.get("start_seed", 0)))
             cfg["map"], cfg["map_kwargs"] = "pgmap", kw
         self.config = cfg
-        clip_kwargs = None if cfg.get("event_clips") is None else dict(cfg["event_clips"])
-        if clip_kwargs and (clip_kwargs.get("ttc_below", 0.0) > 0.0 or clip_kwargs.get("gap_below", 0.0) > 0.0) \
-                and not cfg.get("interaction_metrics", False):
-            raise ValueError("event_clips with ttc_below / gap_below reads the interaction meter: set interaction_metrics=True")
-        field_kwargs = None if cfg.get("field_maps") is None else dict(cfg["field_maps"])
-        if field_kwargs and field_kwargs.get("ttc_below", 0.0) > 0.0 and not cfg.get("interaction_metrics", False):
-            raise ValueError("field_maps with ttc_below reads the interaction meter: set interaction_metrics=True")
+        ObserverList.validate(cfg)
         sim_kwargs = {k: v for k, v in cfg.items() if k in SIM_KEYS and k not in ("enable_lcf",)}
         sim_kwargs["enable_lcf"] = bool(self.ENABLE_LCF and cfg.get("enable_copo", True))
         sim_kwargs.update(type(self)._extension_kwargs(cfg))
@@ -92,33 +88,7 @@ class MultiAgentMetaDrive:
             self.sim_config.nbr_k = max(1, self.sim_config.resolved()[1] - 1)
         self.sim = VecSim(self.sim_config, device=int(cfg.get("device", 0) or 0))
         self.num_envs, self.num_agents = self.sim.E, self.sim.N
-        self._meter = None         # `interaction_metrics`: gaps, time to collision, near misses of every step (copo_amd/interact.py)
-        if cfg.get("interaction_metrics", False):
-            from copo_amd.interact import InteractionMeter
-            self._meter = InteractionMeter(self.sim)
-        self._clips = None         # `event_clips`: flight recorder, clips of the records around a crash / near miss (copo_amd/clips.py)
-        if clip_kwargs is not None:
-            from copo_amd.clips import ClipRecorder
-            self._clips = ClipRecorder(self.sim, **clip_kwargs)
-            self._clips_records = 0
-        self._rewind = None        # `rewind`: ring of full snapshots per scene to fork past records from (copo_amd/rewind.py)
-        if cfg.get("rewind") is not None:
-            from copo_amd.rewind import RewindBuffer
-            self._rewind = RewindBuffer(self.sim, **dict(cfg["rewind"]))
-        self._fields = None        # `field_maps`: occupancy, speed, flow and event grids over scenes and steps (copo_amd/fields.py)
-        if field_kwargs is not None:
-            from copo_amd.fields import FieldMaps
-            explicit = all(k in field_kwargs for k in ("x0", "y0", "W", "H"))
-            self._fields = FieldMaps(self.sim, **field_kwargs) if explicit else FieldMaps.for_map(self.sim, **field_kwargs)
-        self._gates = None         # `traffic_gates`: line-crossing counts, headways and travel times per gate (copo_amd/gates.py)
-        if cfg.get("traffic_gates") is not None:
-            from copo_amd.gates import TrafficGates
-            gate_kwargs = dict(cfg["traffic_gates"])
-            self._gates = TrafficGates(self.sim, **gate_kwargs) if "gates" in gate_kwargs else TrafficGates.for_map(self.sim, **gate_kwargs)
-        self._trips = None         # `trip_log`: one device-written row per finished agent (copo_amd/trips.py)
-        if cfg.get("trip_log") is not None:
-            from copo_amd.trips import TripLog
-            self._trips = TripLog(self.sim, **dict(cfg["trip_log"]))
+        self.observers = ObserverList(self.sim, cfg)      # the config keys of `copo_amd.observers.ENV_OBSERVERS`
         self._slot_ids = None      # dict API state (num_envs == 1)
         self._next_obs = None
         self.current_lcf_mean, self.current_lcf_std = self.sim_config.lcf_mean, self.sim_config.lcf_std
@@ -172,24 +142,12 @@ class MultiAgentMetaDrive:
     # ---- vector API ----------------------------------------------------------------------------------------
     def vec_reset(self, seeds=None):
         out = self.sim.reset(seeds)
-        self._restart_trail()
-        self._restart_interaction()
-        self._record_clips(None)
-        self._record_rewind(True)
-        self._record_fields(None)
-        self._record_gates(True)
-        self._record_trips(None)
+        self.observers.after_reset()
         return out
 
     def vec_step(self, actions):
         out = self.sim.step(actions)
-        self._record_trail()
-        self._record_interaction()
-        self._record_clips(out["flags"])
-        self._record_rewind(False)
-        self._record_fields(out["flags"])
-        self._record_gates(False)
-        self._record_trips(out)
+        self.observers.after_step(out)
         return out
 
     # ---- top-down rendering (copo/vis.py: env.render(mode="top_down", num_stack=25)) ------------------------------------------
@@ -202,11 +160,10 @@ class MultiAgentMetaDrive:
             raise NotImplementedError("only mode='top_down' is built (no 3D renderer)")
         from copo_amd.render import MAX_TRAIL, TopDownRenderer, to_numpy_rgb
         W, H = int(film_size[0]), int(film_size[1])
-        r = getattr(self, "_renderer", None)
+        r = self.observers.get("renderer")
         if r is None or (r.W, r.H) != (W, H):
-            if r is not None:
-                r.close()
-            self._renderer = r = TopDownRenderer(self.sim, W, H, trail=MAX_TRAIL)
+            r = TopDownRenderer(self.sim, W, H, trail=MAX_TRAIL)
+            self.observers.add_first("renderer", r)      # (one of another size is closed and replaced)
             r.record()
         trail = max(0, min(int(num_stack) - 1, MAX_TRAIL))
         ids = self._slot_ids or []
@@ -216,110 +173,42 @@ class MultiAgentMetaDrive:
             f = r.frames(scenes=[0], view="map", trail=trail)
         return to_numpy_rgb(f)[0]
 
-    def _record_trail(self):
-        if getattr(self, "_renderer", None) is not None:
-            self._renderer.record()
+    # ---- the observers of `copo_amd.observers.ENV_OBSERVERS`, by config key ----------------------------------------------
+    def observer(self, key):
+        """The observer that config key `key` switched on, None when it is off (or the env is closed)."""
+        return self.observers.get(key)
 
-    def _restart_trail(self):
-        if getattr(self, "_renderer", None) is not None:
-            self._renderer.clear()
-            self._renderer.record()
-
-    # ---- interaction metrics (config key `interaction_metrics`): one measurement of the state after reset and after every step ----
-    def _record_interaction(self):
-        if self._meter is not None:
-            self._meter.record()
-
-    def _restart_interaction(self):
-        if self._meter is not None:
-            self._meter.reset()
-            self._meter.record()
+    def _observer(self, key, hint):
+        o = self.observers.get(key)
+        assert o is not None, "set %s in the env config" % hint
+        return o
 
     def interaction_summary(self, flush_open=False):
         """`InteractionMeter.summary` over the agents that ended since the last reset (`flush_open`: and those still driving)."""
-        assert self._meter is not None, "set interaction_metrics=True in the env config"
-        return self._meter.summary(flush_open)
-
-    # ---- event clips (config key `event_clips`: None, or the arguments of `ClipRecorder`): one record of the state after reset and after
-    #      every step, fed with the step's flags and, for the ttc / gap triggers, the meter's arrays of that state.  Clips are kept over
-    #      resets; a clip still waiting for its `post` records when the scenes are reset by hand is committed with what it has ----
-    def _record_clips(self, flags):
-        c = self._clips
-        if c is None:
-            return
-        if flags is None and self._clips_records:
-            c.flush()
-        c.record(flags=flags, ttc=self._meter.ttc if c.ttc_below > 0.0 else None, gap=self._meter.gap if c.gap_below > 0.0 else None)
-        self._clips_records += 1
+        return self._observer("interaction_metrics", "interaction_metrics=True").summary(flush_open)
 
     def event_clips(self, flush=False):
         """The clips recorded so far as a `copo_amd.clips.ClipSet` (`flush`: the waiting ones too, shorter, as if they ended now)."""
-        assert self._clips is not None, "set event_clips={...} in the env config"
+        c = self._observer("event_clips", "event_clips={...}")
         if flush:
-            self._clips.flush()
-        return self._clips.clips()
-
-    # ---- rewind (config key `rewind`: None, or the arguments of `RewindBuffer`): one record of the state after reset and after every
-    #      step, next to the clip recorder's, so that a clip header's first_rec / trig_rec name rewind records.  The clip recorder counts
-    #      on over a reset by hand, so the buffer does too; the records from before that reset can no longer be forked (`invalidate`) ----
-    def _record_rewind(self, after_reset):
-        b = self._rewind
-        if b is None:
-            return
-        if after_reset and b.n_records:
-            b.invalidate()
-        b.record()
-        if self._clips is not None:
-            assert b.n_records == self._clips_records, (b.n_records, self._clips_records)
+            c.flush()
+        return c.clips()
 
     def rewind_buffer(self):
         """The env's `copo_amd.rewind.RewindBuffer`."""
-        assert self._rewind is not None, "set rewind={...} in the env config"
-        return self._rewind
-
-    # ---- field maps (config key `field_maps`: None, or the arguments of `FieldMaps` -- with x0, y0, W, H an explicit grid, else
-    #      `FieldMaps.for_map`): one record of the state after reset (no flags: no event) and after every step, fed with the step's flags
-    #      and, for the critical layer, the meter's ttc of that state.  The maps are kept over resets ----
-    def _record_fields(self, flags):
-        f = self._fields
-        if f is not None:
-            f.record(flags=flags, ttc=self._meter.ttc if f.ttc_below > 0.0 else None)
+        return self._observer("rewind", "rewind={...}")
 
     def field_maps(self):
         """The env's `copo_amd.fields.FieldMaps`."""
-        assert self._fields is not None, "set field_maps={...} in the env config"
-        return self._fields
-
-    # ---- traffic gates (config key `traffic_gates`: None, or the arguments of `TrafficGates` -- with `gates` explicit gates, else
-    #      `TrafficGates.for_map`): one record after every step; after a reset by hand the memory is forgotten first, so that the reset
-    #      fires nothing.  The accumulators are kept over resets ----
-    def _record_gates(self, after_reset):
-        g = self._gates
-        if g is not None:
-            if after_reset:
-                g.forget()
-            g.record()
+        return self._observer("field_maps", "field_maps={...}")
 
     def traffic_gates(self):
         """The env's `copo_amd.gates.TrafficGates`."""
-        assert self._gates is not None, "set traffic_gates={...} in the env config"
-        return self._gates
-
-    # ---- trip log (config key `trip_log`: None, or the arguments of `TripLog`): one record of the state after reset (no arrays: a trip that
-    #      was open ends only because its agent is gone) and after every step, fed with the step's flags and rew and, with
-    #      `interaction_metrics`, the meter's gap / ttc of that state.  The rows are kept over resets; a reset that
-    #      restores a slot's agent id and episode word continues its trip (`trip_log().flush()` before the reset cuts every trip there) ----
-    def _record_trips(self, out):
-        t = self._trips
-        if t is not None:
-            m = self._meter
-            t.record(flags=None if out is None else out["flags"], rew=None if out is None else out["rew"],
-                     gap=None if m is None else m.gap, ttc=None if m is None else m.ttc)
+        return self._observer("traffic_gates", "traffic_gates={...}")
 
     def trip_log(self):
         """The env's `copo_amd.trips.TripLog`."""
-        assert self._trips is not None, "set trip_log={...} in the env config"
-        return self._trips
+        return self._observer("trip_log", "trip_log={...}")
 
     def set_lcf_dist(self, mean, std):
         assert self.ENABLE_LCF, "set_lcf_dist needs an LCF env (get_lcf_env)"
@@ -363,13 +252,7 @@ class MultiAgentMetaDrive:
         assert self.num_envs == 1, "the dict API serves one scene; use vec_reset/vec_step for num_envs > 1"
         seed = self.config.get("start_seed", 5000) if force_seed is None else force_seed
         out = self.sim.reset(np.array([seed], np.uint64))
-        self._restart_trail()
-        self._restart_interaction()
-        self._record_clips(None)
-        self._record_rewind(True)
-        self._record_fields(None)
-        self._record_gates(True)
-        self._record_trips(None)
+        self.observers.after_reset()
         ids = self._ids(out)
         self._slot_ids = ["agent%d" % a for a in ids]
         self._just_terminated = {}
@@ -388,16 +271,11 @@ class MultiAgentMetaDrive:
             if a is not None:
                 act[0, s] = np.asarray(actions[a], np.float32)[:self.sim.A]
         out = self.sim.step(torch.from_numpy(act).to(self.sim.device))
-        self._record_trail()
-        self._record_interaction()
-        self._record_clips(out["flags"])
-        self._record_rewind(False)
-        self._record_fields(out["flags"])
-        self._record_gates(False)
-        self._record_trips(out)
+        self.observers.after_step(out)
         h = {k: v[0].cpu().numpy() for k, v in out.items() if v is not None}
-        if self._meter is not None:      # of the state after the step: +inf for an agent that ended in it
-            h["min_gap"], h["ttc"] = self._meter.gap[0].cpu().numpy(), self._meter.ttc[0].cpu().numpy()
+        meter = self.observer("interaction_metrics")
+        if meter is not None:            # of the state after the step: +inf for an agent that ended in it
+            h["min_gap"], h["ttc"] = meter.gap[0].cpu().numpy(), meter.ttc[0].cpu().numpy()
         flags = h["flags"]
         env_reset = bool((flags & F.F_ENV_RESET).any())
         self._episode_over = False
@@ -435,7 +313,7 @@ class MultiAgentMetaDrive:
             self._episode_energy[a] = self._episode_energy.get(a, 0.0) + e_step
             info.update(step_energy=e_step, episode_energy=self._episode_energy[a],
                         raw_action=np.asarray(actions.get(a, (0.0, 0.0)), np.float32)[:2].copy())
-            if self._meter is not None:      # (a slot whose agent ended may already hold the next one: that one's figures are not this agent's)
+            if meter is not None:            # (a slot whose agent ended may already hold the next one: that one's figures are not this agent's)
                 info.update(min_gap=math.inf if d[a] else float(h["min_gap"][s]), ttc=math.inf if d[a] else float(h["ttc"][s]))
             if self.ENABLE_LCF:
                 lcf, nei_r = float(h["lcf"][s]), float(h["nei_rew"][s])
@@ -474,27 +352,7 @@ class MultiAgentMetaDrive:
         return o, r, d, i
 
     def close(self):
-        if getattr(self, "_renderer", None) is not None:
-            self._renderer.close()
-            self._renderer = None
-        if getattr(self, "_meter", None) is not None:
-            self._meter.close()
-            self._meter = None
-        if getattr(self, "_clips", None) is not None:
-            self._clips.close()
-            self._clips = None
-        if getattr(self, "_rewind", None) is not None:
-            self._rewind.close()
-            self._rewind = None
-        if getattr(self, "_fields", None) is not None:
-            self._fields.close()
-            self._fields = None
-        if getattr(self, "_gates", None) is not None:
-            self._gates.close()
-            self._gates = None
-        if getattr(self, "_trips", None) is not None:
-            self._trips.close()
-            self._trips = None
+        self.observers.close()
         self.sim.close()
 
 

@@ -157,6 +157,18 @@ class TripLog(Handle):
         self._create(self._capi.lib.copo_trip_create, sim._h, C.byref(cfg))
         self.n_records = 0
 
+    @classmethod
+    def from_env(cls, sim, value):
+        """The env's log (config key `trip_log`: None, or the arguments of `TripLog`)."""
+        return cls(sim, **dict(value))
+
+    def env_record(self, feed):
+        """One record of the state after reset (no arrays: a trip that was open ends only because its agent is gone) and after every
+        step, fed with the step's flags and rew and, with `interaction_metrics`, the meter's gap / ttc of that state.  The rows are
+        kept over resets; a reset that restores a slot's agent id and episode word continues its trip (`flush()` before the reset
+        cuts every trip there)."""
+        self.record(flags=feed.flags, rew=feed.rew, gap=feed.gap, ttc=feed.ttc)
+
     def record(self, flags=None, rew=None, gap=None, ttc=None):
         """One record of the current state; `flags` (uint8 [E, N]) and `rew` (float32 [E, N]) are the step's outputs, `gap` / `ttc`
         (float32 [E, N]) `InteractionMeter.record()`'s of this state.  None: absent (no flags: the record after a reset, which ends a

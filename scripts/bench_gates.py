@@ -9,52 +9,17 @@ One line per shape and a JSON line at the end.
 
     python scripts/bench_gates.py [--scenes 256 16384] [--agents 40] [--inset 10.0] [--iters 20] [--batch 10]
 """
-import argparse
-import json
-import os
-import sys
-
-import numpy as np
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-
-
-def timed(torch, fn, iters, batch):
-    """median, min microseconds per call over `iters` batches of `batch` back-to-back calls"""
-    times = []
-    for _ in range(iters):
-        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        t0.record()
-        for _ in range(batch):
-            fn()
-        t1.record()
-        torch.cuda.synchronize()
-        times.append(t0.elapsed_time(t1) * 1e3 / batch)
-    return float(np.median(times)), float(min(times))
+from _bench_common import base_parser, driven_sim, emit, timed
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--scenes", type=int, nargs="+", default=[256, 16384])
-    ap.add_argument("--agents", type=int, default=40)
-    ap.add_argument("--inset", type=float, default=10.0)
-    ap.add_argument("--iters", type=int, default=20)
-    ap.add_argument("--batch", type=int, default=10)
-    a = ap.parse_args()
+    a = base_parser(inset=10.0).parse_args()
     import torch
     assert torch.cuda.is_available(), "bench_gates needs a GPU"
     from copo_amd.gates import TrafficGates
-    from copo_amd.sim import SimConfig, VecSim
     rows = []
     for E in a.scenes:
-        sim = VecSim(SimConfig(map="intersection", num_envs=E, num_agents=a.agents))
-        rng = np.random.RandomState(0)
-        act = np.zeros((E, sim.N, 2), np.float32)
-        act[..., 0] = rng.uniform(-0.3, 0.3, act.shape[:2])
-        act[..., 1] = rng.uniform(0.0, 1.0, act.shape[:2])
-        act = torch.from_numpy(act).cuda()
-        sim.reset()
+        sim, act = driven_sim(torch, E, a.agents)
         tg = TrafficGates.for_map(sim, inset=a.inset)
         tg.record()
         for _ in range(30):
@@ -78,7 +43,7 @@ def main():
                          scene_records=recs))
         tg.close()
         sim.close()
-    print(json.dumps(dict(metric="gate_record_us", rows=rows)))
+    emit("gate_record_us", rows)
 
 
 if __name__ == "__main__":

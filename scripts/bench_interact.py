@@ -5,52 +5,18 @@ One line per shape and a JSON line at the end.
 
     python scripts/bench_interact.py [--scenes 256 16384] [--agents 40] [--iters 20] [--batch 10]
 """
-import argparse
-import json
-import os
-import sys
-
-import numpy as np
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-
-
-def timed(torch, fn, iters, batch):
-    """median, min microseconds per call over `iters` batches of `batch` back-to-back calls"""
-    times = []
-    for _ in range(iters):
-        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        t0.record()
-        for _ in range(batch):
-            fn()
-        t1.record()
-        torch.cuda.synchronize()
-        times.append(t0.elapsed_time(t1) * 1e3 / batch)
-    return float(np.median(times)), float(min(times))
+from _bench_common import base_parser, driven_sim, emit, timed
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--scenes", type=int, nargs="+", default=[256, 16384])
-    ap.add_argument("--agents", type=int, default=40)
-    ap.add_argument("--iters", type=int, default=20)
-    ap.add_argument("--batch", type=int, default=10)
-    a = ap.parse_args()
+    a = base_parser().parse_args()
     import torch
     assert torch.cuda.is_available(), "bench_interact needs a GPU"
     from copo_amd.interact import InteractionMeter
-    from copo_amd.sim import SimConfig, VecSim
     rows = []
     for E in a.scenes:
-        sim = VecSim(SimConfig(map="intersection", num_envs=E, num_agents=a.agents))
+        sim, act = driven_sim(torch, E, a.agents)
         meter = InteractionMeter(sim)
-        rng = np.random.RandomState(0)
-        act = np.zeros((E, sim.N, 2), np.float32)
-        act[..., 0] = rng.uniform(-0.3, 0.3, act.shape[:2])
-        act[..., 1] = rng.uniform(0.0, 1.0, act.shape[:2])
-        act = torch.from_numpy(act).cuda()
-        sim.reset()
         for _ in range(30):
             sim.step(act)
             meter.record()
@@ -70,7 +36,7 @@ def main():
                          tet_frac=summary["tet_frac"], min_gap_mean=summary["min_gap_mean"]))
         meter.close()
         sim.close()
-    print(json.dumps(dict(metric="interact_record_us", rows=rows)))
+    emit("interact_record_us", rows)
 
 
 if __name__ == "__main__":

@@ -6,54 +6,20 @@ of `--branches` target scenes from random scenes and stored records.  One line p
 
     python scripts/bench_rewind.py [--scenes 256 16384] [--agents 40] [--depth 8] [--branches 1024] [--iters 20] [--batch 10]
 """
-import argparse
-import json
-import os
-import sys
-
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-
-
-def timed(torch, fn, iters, batch):
-    """median, min microseconds per call over `iters` batches of `batch` back-to-back calls"""
-    times = []
-    for _ in range(iters):
-        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        t0.record()
-        for _ in range(batch):
-            fn()
-        t1.record()
-        torch.cuda.synchronize()
-        times.append(t0.elapsed_time(t1) * 1e3 / batch)
-    return float(np.median(times)), float(min(times))
+from _bench_common import base_parser, driven_sim, emit, timed
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--scenes", type=int, nargs="+", default=[256, 16384])
-    ap.add_argument("--agents", type=int, default=40)
-    ap.add_argument("--depth", type=int, default=8)
-    ap.add_argument("--branches", type=int, default=1024)
-    ap.add_argument("--iters", type=int, default=20)
-    ap.add_argument("--batch", type=int, default=10)
-    a = ap.parse_args()
+    a = base_parser(depth=8, branches=1024).parse_args()
     import torch
     assert torch.cuda.is_available(), "bench_rewind needs a GPU"
     from copo_amd import _capi
     from copo_amd.rewind import Branches, RewindBuffer
-    from copo_amd.sim import SimConfig, VecSim
     rows = []
     for E in a.scenes:
-        sim = VecSim(SimConfig(map="intersection", num_envs=E, num_agents=a.agents))
-        rng = np.random.RandomState(0)
-        act = np.zeros((E, sim.N, 2), np.float32)
-        act[..., 0] = rng.uniform(-0.3, 0.3, act.shape[:2])
-        act[..., 1] = rng.uniform(0.0, 1.0, act.shape[:2])
-        act = torch.from_numpy(act).cuda()
-        sim.reset()
+        sim, act = driven_sim(torch, E, a.agents)
         for _ in range(30):
             sim.step(act)
         b1, b4 = RewindBuffer(sim, depth=a.depth, stride=1), RewindBuffer(sim, depth=a.depth, stride=4)
@@ -71,6 +37,7 @@ def main():
         # ---- fork: the raw entry point on device arrays made once (RewindBuffer.fork uploads its requests on every call) ----
         br = Branches(b1, a.branches)
         lo, hi = b1.span()
+        rng = np.random.RandomState(0)
         scene = torch.from_numpy(rng.randint(0, E, a.branches).astype(np.int32)).cuda()
         recs = torch.from_numpy(rng.randint(lo, hi + 1, a.branches).astype(np.int32)).cuda()
         status = torch.empty(a.branches, dtype=torch.int32, device="cuda")
@@ -96,7 +63,7 @@ def main():
         b1.close()
         b4.close()
         sim.close()
-    print(json.dumps(dict(metric="rewind_record_us", rows=rows)))
+    emit("rewind_record_us", rows)
 
 
 if __name__ == "__main__":

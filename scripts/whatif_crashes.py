@@ -86,7 +86,7 @@ def main():
         n_seen = 0
         for t in range(a.steps):
             out = env.vec_step(policy(out["obs"]))
-            n_now, _ = env._clips.count()
+            n_now, _ = env.observer("event_clips").count()
             if n_now == n_seen:
                 continue
             cs = env.event_clips()

@@ -42,7 +42,12 @@ def _gates(sim):
     return TrafficGates(sim, [[0.0, -5.0, 0.0, 5.0]])
 
 
-OBSERVERS = [_renderer, _meter, _clips, _rewind, _fields, _gates]
+def _trips(sim):
+    from copo_amd.trips import TripLog
+    return TripLog(sim, max_rows=8)
+
+
+OBSERVERS = [_renderer, _meter, _clips, _rewind, _fields, _gates, _trips]
 
 
 def _sim():
@@ -87,6 +92,8 @@ def test_observer_closed_after_its_simulator(make):
         torch.cuda.synchronize()
         if make in (_fields, _gates):                  # the one record: every scene once, in group 0
             assert int(obs.read()["scene_records"][0]) == E
+        if make is _trips:                             # the one record: counted, and no trip has ended in it
+            assert obs.n_records == 1 and obs.count() == (0, 0)
         obs.close()
     finally:
         sim.close()

@@ -364,4 +364,4 @@ def test_dict_env_key_and_file(tmp_path):
         assert len(t) >= 8 and (t.first_rec + t.steps <= 6).all() and (t.kind == 1).sum() == ended and np.isinf(t.min_ttc).all()
     finally:
         one.close()
-    assert one._trips is None
+    assert one.observer("trip_log") is None
