@@ -101,3 +101,11 @@ class TripCfg(C.Structure):
 
 
 TRIP_WORDS, TRIP_DONE, TRIP_VANISHED, TRIP_FLUSHED = 16, 1, 2, 3
+
+
+class ConflictCfg(C.Structure):
+    """Mirror of `copo_conflict_cfg`."""
+    _fields_ = [("max_rows", C.c_int32), ("radius", C.c_float), ("leave_radius", C.c_float)]
+
+
+CONFLICT_WORDS, CONFLICT_DONE, CONFLICT_VANISHED, CONFLICT_PARTED, CONFLICT_FLUSHED = 16, 1, 2, 3, 4

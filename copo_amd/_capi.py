@@ -164,6 +164,14 @@ _SIGS = {
     "copo_trip_clear": (C.c_int, [C.c_void_p, C.c_void_p]),
     "copo_trip_reset": (C.c_int, [C.c_void_p, C.c_void_p]),
     "copo_trip_destroy": (C.c_int, [C.c_void_p]),
+    "copo_conflict_create": (C.c_int, [C.c_void_p, C.POINTER(ConflictCfg), C.POINTER(C.c_void_p)]),
+    "copo_conflict_record": (C.c_int, [C.c_void_p] * 3),
+    "copo_conflict_flush": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "copo_conflict_count": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.c_void_p]),
+    "copo_conflict_read": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "copo_conflict_clear": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "copo_conflict_reset": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "copo_conflict_destroy": (C.c_int, [C.c_void_p]),
     "copo_neighbours_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_float,
                                       C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                       C.c_void_p, C.c_void_p]),

@@ -1,5 +1,5 @@
 // C ABI of the handles that observe a simulator (include/copo_hip.h): renderer, interaction meter, event clips, scene rewind, field
-// maps, traffic gates, trip log.  Each owns its device buffers through a DevPool (capi_common.h) on the simulator's device; every call but
+// maps, traffic gates, trip log, conflict log.  Each owns its device buffers through a DevPool (capi_common.h) on the simulator's device; every call but
 // *_destroy reads the simulator, which therefore has to be alive.  All launches are asynchronous on the caller's stream.
 #include <algorithm>
 #include <array>
@@ -16,6 +16,7 @@
 #include "field_common.h"
 #include "gate_common.h"
 #include "trip_common.h"
+#include "conflict_common.h"
 
 using namespace copo;
 
@@ -741,6 +742,122 @@ extern "C" int copo_trip_clear(copo_trip* h, void* stream) {
 // (the slot memory needs no clearing: a slot is written when its trip opens)
 extern "C" int copo_trip_reset(copo_trip* h, void* stream) {
     if (!h) return fail(COPO_ERR_NULL, "copo_trip_reset: NULL handle");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    HIP_TRY(h->counters.fill(0, st));
+    HIP_TRY(h->open.fill(0, st));
+    HIP_TRY(h->pool.fill(0, st));
+    h->n_records = 0;
+    return COPO_OK;
+}
+
+// ---- conflict log (conflict_kernels.hip) -----------------------------------------------------------------------
+
+struct copo_conflict {
+    copo_sim* sim;
+    DevPool mem;
+    copo_conflict_cfg cfg;
+    float r2_in, r2_out;                   // radius^2, leave_radius^2, rounded once
+    int32_t n_records;                     // records since create / reset (host side: eager only)
+    DevBuf<unsigned long long> open;       // [E][N]
+    DevBuf<int32_t> aid;                   // [E][N]
+    DevBuf<int32_t> episode;               // [E]
+    DevBuf<uint32_t> pairs;                // [E][N (N - 1) / 2][CONFLICT_PAIR_WORDS]
+    DevBuf<unsigned long long> closing;    // [E][N]
+    DevBuf<int32_t> n_closing;             // [E]
+    DevBuf<int32_t> base;                  // [E]
+    DevBuf<long long> counters;            // [CONFLICT_COUNTERS]
+    DevBuf<uint32_t> pool;                 // [max_rows][CONFLICT_WORDS]
+};
+
+static ConflictArgs conflict_args(const copo_conflict* h) {
+    const SimParams& p = h->sim->p;
+    ConflictArgs a;
+    a.state = p.state; a.env = p.env; a.E = p.E; a.N = p.N;
+    a.max_rows = h->cfg.max_rows; a.r = h->n_records; a.r2_in = h->r2_in; a.r2_out = h->r2_out;
+    a.flags = nullptr;
+    a.open = h->open; a.aid = h->aid; a.episode = h->episode; a.pairs = h->pairs; a.closing = h->closing; a.n_closing = h->n_closing;
+    a.base = h->base; a.counters = h->counters; a.pool = h->pool;
+    return a;
+}
+
+extern "C" int copo_conflict_create(copo_sim* sim, const copo_conflict_cfg* cfg, copo_conflict** out) {
+    if (!sim || !cfg || !out) return fail(COPO_ERR_NULL, "copo_conflict_create: NULL argument");
+    *out = nullptr;
+    static_assert(COPO_CONFLICT_WORDS == CONFLICT_WORDS && COPO_CONFLICT_DONE == CONFLICT_KIND_DONE && COPO_CONFLICT_VANISHED == CONFLICT_KIND_VANISHED &&
+                  COPO_CONFLICT_PARTED == CONFLICT_KIND_PARTED && COPO_CONFLICT_FLUSHED == CONFLICT_KIND_FLUSH, "copo_hip.h / conflict_common.h");
+    if (cfg->max_rows < 1) return fail(COPO_ERR_DIM, "copo_conflict_create: max_rows=%d (>= 1)", cfg->max_rows);
+    const float r2_in = (float)((double)cfg->radius * (double)cfg->radius), r2_out = (float)((double)cfg->leave_radius * (double)cfg->leave_radius);
+    if (!std::isfinite(cfg->radius) || !std::isfinite(cfg->leave_radius) || !(cfg->radius > 0.0f) || !(cfg->leave_radius >= cfg->radius) ||
+        !std::isfinite(r2_out))
+        return fail(COPO_ERR_CONFIG, "copo_conflict_create: radius=%g (> 0) leave_radius=%g (>= radius), both and their squares finite",
+                    (double)cfg->radius, (double)cfg->leave_radius);
+    const size_t E = (size_t)sim->p.E, N = (size_t)sim->p.N;
+    HIP_TRY(hipSetDevice(sim->device));
+    copo_conflict* h = new (std::nothrow) copo_conflict();
+    if (!h) return fail(COPO_ERR_DEVICE, "out of host memory");
+    h->sim = sim; h->mem.device = sim->device; h->cfg = *cfg; h->r2_in = r2_in; h->r2_out = r2_out; h->n_records = 0;
+    h->open = h->mem.alloc<unsigned long long>(E * N);
+    h->aid = h->mem.alloc<int32_t>(E * N);
+    h->episode = h->mem.alloc<int32_t>(E);
+    h->pairs = h->mem.alloc<uint32_t>(E * (N * (N - 1) / 2) * CONFLICT_PAIR_WORDS);       // (one slot: never indexed)
+    h->closing = h->mem.alloc<unsigned long long>(E * N);
+    h->n_closing = h->mem.alloc<int32_t>(E);
+    h->base = h->mem.alloc<int32_t>(E);
+    h->counters = h->mem.alloc<long long>(CONFLICT_COUNTERS);
+    h->pool = h->mem.alloc<uint32_t>((size_t)cfg->max_rows * CONFLICT_WORDS);
+    return finish_create(h, out, "copo_conflict_create");
+}
+
+extern "C" int copo_conflict_destroy(copo_conflict* h) { return destroy_handle(h, "copo_conflict_destroy"); }
+
+extern "C" int copo_conflict_record(copo_conflict* h, const uint8_t* flags, void* stream) {
+    if (!h) return fail(COPO_ERR_NULL, "copo_conflict_record: NULL handle");
+    if (h->n_records == INT32_MAX) return fail(COPO_ERR_STATE, "copo_conflict_record: %d records made; reset the handle", h->n_records);
+    ConflictArgs a = conflict_args(h);
+    a.flags = flags;
+    HIP_TRY(launch_conflict_record(a, static_cast<hipStream_t>(stream)));
+    h->n_records += 1;
+    return COPO_OK;
+}
+
+extern "C" int copo_conflict_flush(copo_conflict* h, void* stream) {
+    if (!h) return fail(COPO_ERR_NULL, "copo_conflict_flush: NULL handle");
+    HIP_TRY(launch_conflict_flush(conflict_args(h), static_cast<hipStream_t>(stream)));
+    return COPO_OK;
+}
+
+extern "C" int copo_conflict_count(copo_conflict* h, int64_t* out, void* stream) {
+    if (!h || !out) return fail(COPO_ERR_NULL, "copo_conflict_count: NULL argument");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    long long c[CONFLICT_COUNTERS];
+    HIP_TRY(hipMemcpyAsync(c, h->counters, sizeof(c), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    out[0] = c[CC_ROWS];
+    out[1] = c[CC_DROPPED_ROWS];
+    return COPO_OK;
+}
+
+extern "C" int copo_conflict_read(copo_conflict* h, int32_t first, int32_t n, int32_t* rows_out, void* stream) {
+    if (!h) return fail(COPO_ERR_NULL, "copo_conflict_read: NULL handle");
+    if (first < 0 || n < 0 || (int64_t)first + n > h->cfg.max_rows)
+        return fail(COPO_ERR_DIM, "copo_conflict_read: rows [%d, %d + %d) of a pool of %d", first, first, n, h->cfg.max_rows);
+    if (n == 0) return COPO_OK;
+    if (!rows_out) return fail(COPO_ERR_NULL, "copo_conflict_read: NULL output");
+    HIP_TRY(hipMemcpyAsync(rows_out, h->pool.p + (size_t)first * CONFLICT_WORDS, (size_t)n * CONFLICT_WORDS * 4, hipMemcpyDeviceToDevice,
+                           static_cast<hipStream_t>(stream)));
+    return COPO_OK;
+}
+
+// (the rows need no clearing: nothing reads beyond n_rows)
+extern "C" int copo_conflict_clear(copo_conflict* h, void* stream) {
+    if (!h) return fail(COPO_ERR_NULL, "copo_conflict_clear: NULL handle");
+    HIP_TRY(h->counters.fill(0, static_cast<hipStream_t>(stream)));
+    return COPO_OK;
+}
+
+// (the pair and slot memory needs no clearing: it is read only where an encounter is open, and written when one opens)
+extern "C" int copo_conflict_reset(copo_conflict* h, void* stream) {
+    if (!h) return fail(COPO_ERR_NULL, "copo_conflict_reset: NULL handle");
     hipStream_t st = static_cast<hipStream_t>(stream);
     HIP_TRY(h->counters.fill(0, st));
     HIP_TRY(h->open.fill(0, st));

@@ -76,6 +76,13 @@ class ObserverList:
             old.close()
         self._members = [(name, observer)] + [m for m in self._members if m[0] != name]
 
+    def add(self, name, observer):
+        """`observer` records after the rest from now on; one of that name already in the list is closed and replaced."""
+        old = self.get(name)
+        if old is not None:
+            old.close()
+        self._members = [m for m in self._members if m[0] != name] + [(name, observer)]
+
     def after_reset(self):
         self._record(Feed(after_reset=True, records=self.records))
 

@@ -210,6 +210,18 @@ class MultiAgentMetaDrive:
         """The env's `copo_amd.trips.TripLog`."""
         return self._observer("trip_log", "trip_log={...}")
 
+    def conflict_log(self, **kwargs):
+        """The env's `copo_amd.conflicts.ConflictLog`, attached the way the renderer is: the first call (or one with arguments, those of
+        `ConflictLog`) creates it, makes one record of the current state at once and has it record after every reset and step from
+        then on; a call without arguments returns the same object again."""
+        log = self.observers.get("conflict_log")
+        if log is None or kwargs:
+            from copo_amd.conflicts import ConflictLog
+            log = ConflictLog.from_env(self.sim, kwargs)
+            self.observers.add("conflict_log", log)      # (an earlier one is closed and replaced)
+            log.record()
+        return log
+
     def set_lcf_dist(self, mean, std):
         assert self.ENABLE_LCF, "set_lcf_dist needs an LCF env (get_lcf_env)"
         assert std > 0.0 and -1.0 <= mean <= 1.0

@@ -570,6 +570,57 @@ int copo_trip_clear(copo_trip* h, void* stream);
 int copo_trip_reset(copo_trip* h, void* stream);
 int copo_trip_destroy(copo_trip* h);
 
+/* ---- conflict log: ONE row per pairwise encounter, written on the device into a bounded pool; no counterpart in
+ *      the reference.  A handle reads its simulator's state and must be destroyed before it.  Eager only: the record count lives on the
+ *      host.  Everything the device computes is integer logic and, per pair, two fp32 subtractions, two products and one add, each rounded by
+ *      itself, and plain fp32 `<`: no fused multiply-add, square root or division, so the rows are reproducible bit for bit.
+ * Records count from 0 since create / reset.  State fields 0..3 (x, y, heading, speed) are read as raw bits, the status byte of field 13,
+ * field 14 (agent id) and env word 1 (episode).  A party's IDENTITY is (agent id, episode word).  ALIVE-WRECK pairs are out of scope.
+ * Closeness of slots a < b, both ALIVE now: dx = x_b - x_a, dy = y_b - y_a, d2 = dx dx + dy dy; r2_in = radius^2 and r2_out =
+ * leave_radius^2 are rounded once to fp32 on the host; a NaN is never close.
+ * Memory of the handle: per slot the agent id of the previous record and a 64-bit open mask (bit b > a: pair (a, b) has an open
+ * encounter), per scene the episode word, per pair 12 words {first_rec, steps, d2min bits, min_off, pose of a, pose of b at the minimum},
+ * indexed densely: 48 B x N (N - 1) / 2 per scene (37 KB at 40 slots, 9.6 MB at 256 scenes, 0.6 GB at 16 384 scenes).
+ * Record r, with the optional device array flags u8 [E][N] (the step's output, NULL = absent), per scene in this order:
+ *   1 CLOSE, every open pair: with flags given and COPO_F_DONE on slot a or b: kind COPO_CONFLICT_DONE, end_a = the flags byte of a if it
+ *     carries DONE, else 0, end_b likewise; otherwise, if either slot is not ALIVE now with its remembered identity: kind
+ *     COPO_CONFLICT_VANISHED, ends 0; otherwise, if !(d2 < r2_out): kind COPO_CONFLICT_PARTED, ends 0.
+ *   2 OPEN, every pair a < b, both ALIVE now, without an open encounter after 1 (also one that closed in this record) and d2 < r2_in:
+ *     first_rec = r, steps = 0, d2min = +inf, min_off = 0.
+ *   3 ACCUMULATE, every pair open after 1 and 2: steps = min(steps + 1, 65535); if d2 < d2min: d2min = d2, min_off = min(r - first_rec,
+ *     65535) and the eight pose words {x, y, heading, speed} of a and of b are copied as raw bits.
+ *   4 the slot and scene memory is overwritten from the current state.
+ * Row, COPO_CONFLICT_WORDS 32-bit words: {scene, slot_a | slot_b << 6 | kind << 12 | end_a << 16 | end_b << 24, aid_a, aid_b, episode,
+ * first_rec, steps | min_off << 16, d2min bits, pose_a[4], pose_b[4]}.
+ * Order.  The rows closed in one record take the ids n_rows, n_rows + 1, ... in ascending (scene, slot_a, slot_b) order; an id >= max_rows
+ * is not stored and counts as dropped, the encounter is closed all the same.  No atomic decides an id. ---- */
+#define COPO_CONFLICT_WORDS 16
+#define COPO_CONFLICT_DONE 1
+#define COPO_CONFLICT_VANISHED 2
+#define COPO_CONFLICT_PARTED 3
+#define COPO_CONFLICT_FLUSHED 4
+typedef struct copo_conflict_cfg {
+    int32_t max_rows;          /* pool size, >= 1 (COPO_ERR_DIM) */
+    float radius;              /* m, finite and > 0 (COPO_ERR_CONFIG): an encounter opens below it */
+    float leave_radius;        /* m, finite and >= radius (COPO_ERR_CONFIG): an encounter parts at or beyond it */
+} copo_conflict_cfg;
+typedef struct copo_conflict copo_conflict;
+/* allocates the pool (64 max_rows bytes) and 24 E N (N - 1) + 20 E N + 12 E bytes of memory: COPO_ERR_DEVICE when the device refuses */
+int copo_conflict_create(copo_sim* sim, const copo_conflict_cfg* cfg, copo_conflict** out);
+/* one record of the current state.  Three launches on `stream`, no allocation, no host synchronisation; simulator memory is only read */
+int copo_conflict_record(copo_conflict* h, const uint8_t* flags, void* stream);
+/* every open encounter closes with kind COPO_CONFLICT_FLUSHED and ends 0 under the same order and overflow rule.  Not a record */
+int copo_conflict_flush(copo_conflict* h, void* stream);
+/* HOST output: out[0] = rows stored so far (<= max_rows), out[1] = rows dropped; the one call that waits for `stream` */
+int copo_conflict_count(copo_conflict* h, int64_t* out, void* stream);
+/* rows [first, first + n) of the pool, device to device: rows_out [n][COPO_CONFLICT_WORDS] int32; first + n <= max_rows (COPO_ERR_DIM) */
+int copo_conflict_read(copo_conflict* h, int32_t first, int32_t n, int32_t* rows_out, void* stream);
+/* n_rows = dropped = 0; the open encounters and the record count stay */
+int copo_conflict_clear(copo_conflict* h, void* stream);
+/* forget everything: rows, counters, open encounters; records count from 0 again */
+int copo_conflict_reset(copo_conflict* h, void* stream);
+int copo_conflict_destroy(copo_conflict* h);
+
 /* ---- stateless ops ---- */
 
 /* CCEnv._update_distance_map + _find_in_range (env_wrappers.py:125-158) + LCFEnv reward block (:313-326).

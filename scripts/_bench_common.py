@@ -1,5 +1,5 @@
-"""What the observer benchmarks (`bench_interact`, `bench_clips`, `bench_rewind`, `bench_fields`, `bench_gates`, `bench_trips`) share: the
-timing loop, the command line, the scene they measure on and the JSON line they end with."""
+"""What the observer benchmarks (`bench_interact`, `bench_clips`, `bench_rewind`, `bench_fields`, `bench_gates`, `bench_trips`, `bench_conflicts`) share:
+the timing loop, the command line, the scene they measure on and the JSON line they end with."""
 import argparse
 import json
 import os
