@@ -13,13 +13,12 @@ plus 20 B per slot, 12 B per scene and 64 B per pool row (`ConflictLog.state_byt
 """
 import ctypes as C
 import dataclasses
-import json
 
 import numpy as np
 
 from ._abi import (CONFLICT_DONE as KIND_DONE, CONFLICT_FLUSHED as KIND_FLUSHED, CONFLICT_PARTED as KIND_PARTED,
                    CONFLICT_VANISHED as KIND_VANISHED, CONFLICT_WORDS as WORDS)
-from ._handle import Handle
+from ._rowlog import RowLog, RowTable
 
 ROW_KEYS = ("scene", "pair", "aid_a", "aid_b", "episode", "first_rec", "steps_off", "d2min", "x_a", "y_a", "heading_a", "speed_a", "x_b", "y_b",
             "heading_b", "speed_b")
@@ -96,37 +95,14 @@ def decode(raw, dt, hl, hw):
     return out
 
 
-class ConflictTable:
+class ConflictTable(RowTable):
     """Encounters as numpy: `raw` uint32 [n, 16] (the rows as the device wrote them, columns `ROW_KEYS`), `meta` (dict: `dt`, `hl`, `hw`,
     `num_agents`, `max_rows`, `radius`, `leave_radius`, `dropped`, `n_records`, `sim_config`), and the columns of `decode` as attributes
     / items."""
 
-    def __init__(self, raw, meta):
-        self.raw = np.ascontiguousarray(np.asarray(raw).reshape(-1, WORDS)).view(np.uint32).copy()
-        self.meta = dict(meta)
-        self.columns = decode(self.raw, self.meta["dt"], self.meta["hl"], self.meta["hw"])
-
-    def __len__(self):
-        return len(self.raw)
-
-    def __getitem__(self, key):
-        return self.columns[key]
-
-    def __getattr__(self, key):
-        cols = self.__dict__.get("columns")
-        if cols is not None and key in cols:
-            return cols[key]
-        raise AttributeError(key)
-
-    def save(self, path):
-        """One `.npz` without pickled objects (`np.load(path, allow_pickle=False)` reads it): the raw rows and `meta` as JSON."""
-        np.savez_compressed(path, rows=self.raw, meta=np.array(json.dumps(self.meta, sort_keys=True)))
-        return path
-
-    @classmethod
-    def load(cls, path):
-        with np.load(path, allow_pickle=False) as f:
-            return cls(f["rows"], json.loads(str(f["meta"][()])))
+    @staticmethod
+    def _decode(raw, meta):
+        return decode(raw, meta["dt"], meta["hl"], meta["hw"])
 
     def frame(self):
         """pandas DataFrame of every scalar column."""
@@ -196,7 +172,7 @@ def state_bytes(E, N, max_rows):
     return 48 * E * (N * (N - 1) // 2) + 20 * E * N + 12 * E + 64 * int(max_rows) + 16
 
 
-class ConflictLog(Handle):
+class ConflictLog(RowLog):
     """Per-pair encounter rows of a `VecSim`: a pool of `max_rows` rows (later ones are counted as dropped); an encounter opens when two
     ALIVE agents of a scene are closer than `radius` metres (centre to centre) and parts at `leave_radius` or beyond.  Records count from
     0 since creation / `reset()`.  The pair memory is dense: 48 B x N (N - 1) / 2 per scene (37 KB at 40 slots, 9.6 MB at 256 scenes, 0.6
@@ -204,7 +180,7 @@ class ConflictLog(Handle):
     the simulator is closed); every call is asynchronous on torch's current stream except `count()` and what reads rows to the host
     (`table()`, `drain()`)."""
 
-    _destroy = "copo_conflict_destroy"
+    _destroy, _prefix, _table_cls = "copo_conflict_destroy", "copo_conflict_", ConflictTable
 
     def __init__(self, sim, max_rows=65536, radius=8.0, leave_radius=10.0):
         self._attach(sim)
@@ -229,42 +205,5 @@ class ConflictLog(Handle):
         self._capi.check(self._capi.lib.copo_conflict_record(self._h, self._en_arg(flags, self._torch.uint8, "flags"), self._stream()))
         self.n_records += 1
 
-    def flush(self):
-        """Close every open encounter as it stands (kind 4, outcome "open"); a pair that is still close opens a new one in the next record."""
-        self._capi.check(self._capi.lib.copo_conflict_flush(self._h, self._stream()))
-
-    def count(self):
-        """(rows stored, rows dropped); waits for the stream."""
-        out = (C.c_int64 * 2)()
-        self._capi.check(self._capi.lib.copo_conflict_count(self._h, out, self._stream()))
-        return int(out[0]), int(out[1])
-
-    def clear(self):
-        """Empty the pool and the dropped count; open encounters and the record count stay."""
-        self._capi.check(self._capi.lib.copo_conflict_clear(self._h, self._stream()))
-
-    def reset(self):
-        """Forget every row, counter and open encounter; records count from 0 again."""
-        self._capi.check(self._capi.lib.copo_conflict_reset(self._h, self._stream()))
-        self.n_records = 0
-
-    def rows(self):
-        """The stored rows, device int32 [n, 16] (a copy)."""
-        torch = self._torch
-        n, _ = self.count()
-        out = torch.empty(n, WORDS, dtype=torch.int32, device=self.device)
-        if n:
-            self._capi.check(self._capi.lib.copo_conflict_read(self._h, 0, n, out.data_ptr(), self._stream()))
-        return out
-
-    def table(self):
-        """The stored rows as a `ConflictTable`."""
-        _, dropped = self.count()
-        return ConflictTable(self.rows().cpu().numpy(), conflict_meta(self.sim.cfg, self.sim.N, self.max_rows, self.radius, self.leave_radius,
-                                                                      dropped, self.n_records))
-
-    def drain(self):
-        """`table()`, then `clear()`: what a long run calls now and then to keep a bounded pool from overflowing."""
-        t = self.table()
-        self.clear()
-        return t
+    def _meta(self, dropped):
+        return conflict_meta(self.sim.cfg, self.sim.N, self.max_rows, self.radius, self.leave_radius, dropped, self.n_records)

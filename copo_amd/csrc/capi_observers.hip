@@ -640,114 +640,150 @@ extern "C" int copo_gate_reset(copo_gate* h, void* stream) {
     return COPO_OK;
 }
 
+// ---- row pool of the trip log and the conflict log (rowlog_common.h) --------------------------------------------
+
+// Host side of a log's pool: the record count, the three buffers and the calls that are the same for every log.  `who` is the entry
+// point's name for the error string.
+struct RowPool {
+    int32_t max_rows = 0;
+    int32_t n_records = 0;                 // records since create / reset (host side: eager only)
+    DevBuf<int32_t> base;                  // [E]
+    DevBuf<long long> counters;            // [ROWLOG_COUNTERS]
+    DevBuf<uint32_t> pool;                 // [max_rows][ROWLOG_WORDS]
+
+    static int check(int32_t max_rows, const char* who) {
+        return max_rows < 1 ? fail(COPO_ERR_DIM, "%s: max_rows=%d (>= 1)", who, max_rows) : COPO_OK;
+    }
+
+    void create(DevPool& mem, size_t E, int32_t rows) {
+        max_rows = rows;
+        base = mem.alloc<int32_t>(E);
+        counters = mem.alloc<long long>(ROWLOG_COUNTERS);
+        pool = mem.alloc<uint32_t>((size_t)rows * ROWLOG_WORDS);
+    }
+
+    RowPoolArgs args() const { return RowPoolArgs{max_rows, base, counters, pool}; }
+
+    // COPO_OK while the next record still has a number
+    int can_record(const char* who) const {
+        return n_records == INT32_MAX ? fail(COPO_ERR_STATE, "%s: %d records made; reset the handle", who, n_records) : COPO_OK;
+    }
+
+    int count(int64_t* out, void* stream) const {
+        hipStream_t st = static_cast<hipStream_t>(stream);
+        long long c[ROWLOG_COUNTERS];
+        HIP_TRY(hipMemcpyAsync(c, counters, sizeof(c), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        out[0] = c[RL_ROWS];
+        out[1] = c[RL_DROPPED];
+        return COPO_OK;
+    }
+
+    int read(int32_t first, int32_t n, int32_t* rows_out, void* stream, const char* who) const {
+        if (first < 0 || n < 0 || (int64_t)first + n > max_rows)
+            return fail(COPO_ERR_DIM, "%s: rows [%d, %d + %d) of a pool of %d", who, first, first, n, max_rows);
+        if (n == 0) return COPO_OK;
+        if (!rows_out) return fail(COPO_ERR_NULL, "%s: NULL output", who);
+        HIP_TRY(hipMemcpyAsync(rows_out, pool.p + (size_t)first * ROWLOG_WORDS, (size_t)n * ROWLOG_WORDS * 4, hipMemcpyDeviceToDevice,
+                               static_cast<hipStream_t>(stream)));
+        return COPO_OK;
+    }
+
+    // (the rows need no clearing: nothing reads beyond n_rows)
+    int clear(void* stream) const {
+        HIP_TRY(counters.fill(0, static_cast<hipStream_t>(stream)));
+        return COPO_OK;
+    }
+
+    int reset(void* stream) {
+        HIP_TRY(counters.fill(0, static_cast<hipStream_t>(stream)));
+        HIP_TRY(pool.fill(0, static_cast<hipStream_t>(stream)));
+        n_records = 0;
+        return COPO_OK;
+    }
+};
+
+static int null_handle(const char* who) { return fail(COPO_ERR_NULL, "%s: NULL handle", who); }
+
 // ---- trip log (trip_kernels.hip) -------------------------------------------------------------------------------
 
 struct copo_trip {
     copo_sim* sim;
     DevPool mem;
     copo_trip_cfg cfg;
-    int32_t n_records;                     // records since create / reset (host side: eager only)
+    RowPool rows;
     DevBuf<unsigned long long> open;       // [E]
     DevBuf<int32_t> episode;               // [E]
     DevBuf<uint32_t> slots;                // [TRIP_MEM_WORDS][E][N]
     DevBuf<unsigned long long> closing;    // [E]
     DevBuf<uint32_t> endw;                 // [E][N]
-    DevBuf<int32_t> base;                  // [E]
-    DevBuf<long long> counters;            // [TRIP_COUNTERS]
-    DevBuf<uint32_t> pool;                 // [max_rows][TRIP_WORDS]
 };
 
 static TripArgs trip_args(const copo_trip* h) {
     const SimParams& p = h->sim->p;
     TripArgs a;
     a.state = p.state; a.env = p.env; a.E = p.E; a.N = p.N;
-    a.max_rows = h->cfg.max_rows; a.r = h->n_records; a.stop_speed = h->cfg.stop_speed;
+    a.r = h->rows.n_records; a.stop_speed = h->cfg.stop_speed;
     a.flags = nullptr; a.rew = nullptr; a.gap = nullptr; a.ttc = nullptr;
-    a.open = h->open; a.episode = h->episode; a.mem = h->slots; a.closing = h->closing; a.endw = h->endw; a.base = h->base;
-    a.counters = h->counters; a.pool = h->pool;
+    a.open = h->open; a.episode = h->episode; a.mem = h->slots; a.closing = h->closing; a.endw = h->endw; a.rows = h->rows.args();
     return a;
 }
 
 extern "C" int copo_trip_create(copo_sim* sim, const copo_trip_cfg* cfg, copo_trip** out) {
     if (!sim || !cfg || !out) return fail(COPO_ERR_NULL, "copo_trip_create: NULL argument");
     *out = nullptr;
-    static_assert(COPO_TRIP_WORDS == TRIP_WORDS && COPO_TRIP_DONE == TRIP_KIND_DONE && COPO_TRIP_VANISHED == TRIP_KIND_VANISHED &&
+    static_assert(COPO_TRIP_WORDS == ROWLOG_WORDS && COPO_TRIP_DONE == TRIP_KIND_DONE && COPO_TRIP_VANISHED == TRIP_KIND_VANISHED &&
                   COPO_TRIP_FLUSHED == TRIP_KIND_FLUSH, "copo_hip.h / trip_common.h");
-    if (cfg->max_rows < 1) return fail(COPO_ERR_DIM, "copo_trip_create: max_rows=%d (>= 1)", cfg->max_rows);
+    if (int rc = RowPool::check(cfg->max_rows, "copo_trip_create")) return rc;
     if (!(cfg->stop_speed >= 0.0f) || !std::isfinite(cfg->stop_speed))
         return fail(COPO_ERR_CONFIG, "copo_trip_create: stop_speed=%g (>= 0, finite)", (double)cfg->stop_speed);
     const size_t E = (size_t)sim->p.E, N = (size_t)sim->p.N;
     HIP_TRY(hipSetDevice(sim->device));
     copo_trip* h = new (std::nothrow) copo_trip();
     if (!h) return fail(COPO_ERR_DEVICE, "out of host memory");
-    h->sim = sim; h->mem.device = sim->device; h->cfg = *cfg; h->n_records = 0;
+    h->sim = sim; h->mem.device = sim->device; h->cfg = *cfg;
     h->open = h->mem.alloc<unsigned long long>(E);
     h->episode = h->mem.alloc<int32_t>(E);
     h->slots = h->mem.alloc<uint32_t>((size_t)TRIP_MEM_WORDS * E * N);
     h->closing = h->mem.alloc<unsigned long long>(E);
     h->endw = h->mem.alloc<uint32_t>(E * N);
-    h->base = h->mem.alloc<int32_t>(E);
-    h->counters = h->mem.alloc<long long>(TRIP_COUNTERS);
-    h->pool = h->mem.alloc<uint32_t>((size_t)cfg->max_rows * TRIP_WORDS);
+    h->rows.create(h->mem, E, cfg->max_rows);
     return finish_create(h, out, "copo_trip_create");
 }
 
 extern "C" int copo_trip_destroy(copo_trip* h) { return destroy_handle(h, "copo_trip_destroy"); }
 
 extern "C" int copo_trip_record(copo_trip* h, const uint8_t* flags, const float* rew, const float* gap, const float* ttc, void* stream) {
-    if (!h) return fail(COPO_ERR_NULL, "copo_trip_record: NULL handle");
-    if (h->n_records == INT32_MAX) return fail(COPO_ERR_STATE, "copo_trip_record: %d records made; reset the handle", h->n_records);
+    if (!h) return null_handle("copo_trip_record");
+    if (int rc = h->rows.can_record("copo_trip_record")) return rc;
     TripArgs a = trip_args(h);
     a.flags = flags; a.rew = rew; a.gap = gap; a.ttc = ttc;
     HIP_TRY(launch_trip_record(a, static_cast<hipStream_t>(stream)));
-    h->n_records += 1;
+    h->rows.n_records += 1;
     return COPO_OK;
 }
 
 extern "C" int copo_trip_flush(copo_trip* h, void* stream) {
-    if (!h) return fail(COPO_ERR_NULL, "copo_trip_flush: NULL handle");
+    if (!h) return null_handle("copo_trip_flush");
     HIP_TRY(launch_trip_flush(trip_args(h), static_cast<hipStream_t>(stream)));
     return COPO_OK;
 }
 
 extern "C" int copo_trip_count(copo_trip* h, int64_t* out, void* stream) {
-    if (!h || !out) return fail(COPO_ERR_NULL, "copo_trip_count: NULL argument");
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    long long c[TRIP_COUNTERS];
-    HIP_TRY(hipMemcpyAsync(c, h->counters, sizeof(c), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    out[0] = c[TC_ROWS];
-    out[1] = c[TC_DROPPED];
-    return COPO_OK;
+    return h && out ? h->rows.count(out, stream) : fail(COPO_ERR_NULL, "copo_trip_count: NULL argument");
 }
 
 extern "C" int copo_trip_read(copo_trip* h, int32_t first, int32_t n, int32_t* rows_out, void* stream) {
-    if (!h) return fail(COPO_ERR_NULL, "copo_trip_read: NULL handle");
-    if (first < 0 || n < 0 || (int64_t)first + n > h->cfg.max_rows)
-        return fail(COPO_ERR_DIM, "copo_trip_read: rows [%d, %d + %d) of a pool of %d", first, first, n, h->cfg.max_rows);
-    if (n == 0) return COPO_OK;
-    if (!rows_out) return fail(COPO_ERR_NULL, "copo_trip_read: NULL output");
-    HIP_TRY(hipMemcpyAsync(rows_out, h->pool.p + (size_t)first * TRIP_WORDS, (size_t)n * TRIP_WORDS * 4, hipMemcpyDeviceToDevice,
-                           static_cast<hipStream_t>(stream)));
-    return COPO_OK;
+    return h ? h->rows.read(first, n, rows_out, stream, "copo_trip_read") : null_handle("copo_trip_read");
 }
 
-// (the rows need no clearing: nothing reads beyond n_rows)
-extern "C" int copo_trip_clear(copo_trip* h, void* stream) {
-    if (!h) return fail(COPO_ERR_NULL, "copo_trip_clear: NULL handle");
-    HIP_TRY(h->counters.fill(0, static_cast<hipStream_t>(stream)));
-    return COPO_OK;
-}
+extern "C" int copo_trip_clear(copo_trip* h, void* stream) { return h ? h->rows.clear(stream) : null_handle("copo_trip_clear"); }
 
 // (the slot memory needs no clearing: a slot is written when its trip opens)
 extern "C" int copo_trip_reset(copo_trip* h, void* stream) {
-    if (!h) return fail(COPO_ERR_NULL, "copo_trip_reset: NULL handle");
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    HIP_TRY(h->counters.fill(0, st));
-    HIP_TRY(h->open.fill(0, st));
-    HIP_TRY(h->pool.fill(0, st));
-    h->n_records = 0;
-    return COPO_OK;
+    if (!h) return null_handle("copo_trip_reset");
+    HIP_TRY(h->open.fill(0, static_cast<hipStream_t>(stream)));
+    return h->rows.reset(stream);
 }
 
 // ---- conflict log (conflict_kernels.hip) -----------------------------------------------------------------------
@@ -757,35 +793,32 @@ struct copo_conflict {
     DevPool mem;
     copo_conflict_cfg cfg;
     float r2_in, r2_out;                   // radius^2, leave_radius^2, rounded once
-    int32_t n_records;                     // records since create / reset (host side: eager only)
+    RowPool rows;
     DevBuf<unsigned long long> open;       // [E][N]
     DevBuf<int32_t> aid;                   // [E][N]
     DevBuf<int32_t> episode;               // [E]
     DevBuf<uint32_t> pairs;                // [E][N (N - 1) / 2][CONFLICT_PAIR_WORDS]
     DevBuf<unsigned long long> closing;    // [E][N]
     DevBuf<int32_t> n_closing;             // [E]
-    DevBuf<int32_t> base;                  // [E]
-    DevBuf<long long> counters;            // [CONFLICT_COUNTERS]
-    DevBuf<uint32_t> pool;                 // [max_rows][CONFLICT_WORDS]
 };
 
 static ConflictArgs conflict_args(const copo_conflict* h) {
     const SimParams& p = h->sim->p;
     ConflictArgs a;
     a.state = p.state; a.env = p.env; a.E = p.E; a.N = p.N;
-    a.max_rows = h->cfg.max_rows; a.r = h->n_records; a.r2_in = h->r2_in; a.r2_out = h->r2_out;
+    a.r = h->rows.n_records; a.r2_in = h->r2_in; a.r2_out = h->r2_out;
     a.flags = nullptr;
     a.open = h->open; a.aid = h->aid; a.episode = h->episode; a.pairs = h->pairs; a.closing = h->closing; a.n_closing = h->n_closing;
-    a.base = h->base; a.counters = h->counters; a.pool = h->pool;
+    a.rows = h->rows.args();
     return a;
 }
 
 extern "C" int copo_conflict_create(copo_sim* sim, const copo_conflict_cfg* cfg, copo_conflict** out) {
     if (!sim || !cfg || !out) return fail(COPO_ERR_NULL, "copo_conflict_create: NULL argument");
     *out = nullptr;
-    static_assert(COPO_CONFLICT_WORDS == CONFLICT_WORDS && COPO_CONFLICT_DONE == CONFLICT_KIND_DONE && COPO_CONFLICT_VANISHED == CONFLICT_KIND_VANISHED &&
+    static_assert(COPO_CONFLICT_WORDS == ROWLOG_WORDS && COPO_CONFLICT_DONE == CONFLICT_KIND_DONE && COPO_CONFLICT_VANISHED == CONFLICT_KIND_VANISHED &&
                   COPO_CONFLICT_PARTED == CONFLICT_KIND_PARTED && COPO_CONFLICT_FLUSHED == CONFLICT_KIND_FLUSH, "copo_hip.h / conflict_common.h");
-    if (cfg->max_rows < 1) return fail(COPO_ERR_DIM, "copo_conflict_create: max_rows=%d (>= 1)", cfg->max_rows);
+    if (int rc = RowPool::check(cfg->max_rows, "copo_conflict_create")) return rc;
     const float r2_in = (float)((double)cfg->radius * (double)cfg->radius), r2_out = (float)((double)cfg->leave_radius * (double)cfg->leave_radius);
     if (!std::isfinite(cfg->radius) || !std::isfinite(cfg->leave_radius) || !(cfg->radius > 0.0f) || !(cfg->leave_radius >= cfg->radius) ||
         !std::isfinite(r2_out))
@@ -795,73 +828,48 @@ extern "C" int copo_conflict_create(copo_sim* sim, const copo_conflict_cfg* cfg,
     HIP_TRY(hipSetDevice(sim->device));
     copo_conflict* h = new (std::nothrow) copo_conflict();
     if (!h) return fail(COPO_ERR_DEVICE, "out of host memory");
-    h->sim = sim; h->mem.device = sim->device; h->cfg = *cfg; h->r2_in = r2_in; h->r2_out = r2_out; h->n_records = 0;
+    h->sim = sim; h->mem.device = sim->device; h->cfg = *cfg; h->r2_in = r2_in; h->r2_out = r2_out;
     h->open = h->mem.alloc<unsigned long long>(E * N);
     h->aid = h->mem.alloc<int32_t>(E * N);
     h->episode = h->mem.alloc<int32_t>(E);
     h->pairs = h->mem.alloc<uint32_t>(E * (N * (N - 1) / 2) * CONFLICT_PAIR_WORDS);       // (one slot: never indexed)
     h->closing = h->mem.alloc<unsigned long long>(E * N);
     h->n_closing = h->mem.alloc<int32_t>(E);
-    h->base = h->mem.alloc<int32_t>(E);
-    h->counters = h->mem.alloc<long long>(CONFLICT_COUNTERS);
-    h->pool = h->mem.alloc<uint32_t>((size_t)cfg->max_rows * CONFLICT_WORDS);
+    h->rows.create(h->mem, E, cfg->max_rows);
     return finish_create(h, out, "copo_conflict_create");
 }
 
 extern "C" int copo_conflict_destroy(copo_conflict* h) { return destroy_handle(h, "copo_conflict_destroy"); }
 
 extern "C" int copo_conflict_record(copo_conflict* h, const uint8_t* flags, void* stream) {
-    if (!h) return fail(COPO_ERR_NULL, "copo_conflict_record: NULL handle");
-    if (h->n_records == INT32_MAX) return fail(COPO_ERR_STATE, "copo_conflict_record: %d records made; reset the handle", h->n_records);
+    if (!h) return null_handle("copo_conflict_record");
+    if (int rc = h->rows.can_record("copo_conflict_record")) return rc;
     ConflictArgs a = conflict_args(h);
     a.flags = flags;
     HIP_TRY(launch_conflict_record(a, static_cast<hipStream_t>(stream)));
-    h->n_records += 1;
+    h->rows.n_records += 1;
     return COPO_OK;
 }
 
 extern "C" int copo_conflict_flush(copo_conflict* h, void* stream) {
-    if (!h) return fail(COPO_ERR_NULL, "copo_conflict_flush: NULL handle");
+    if (!h) return null_handle("copo_conflict_flush");
     HIP_TRY(launch_conflict_flush(conflict_args(h), static_cast<hipStream_t>(stream)));
     return COPO_OK;
 }
 
 extern "C" int copo_conflict_count(copo_conflict* h, int64_t* out, void* stream) {
-    if (!h || !out) return fail(COPO_ERR_NULL, "copo_conflict_count: NULL argument");
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    long long c[CONFLICT_COUNTERS];
-    HIP_TRY(hipMemcpyAsync(c, h->counters, sizeof(c), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    out[0] = c[CC_ROWS];
-    out[1] = c[CC_DROPPED_ROWS];
-    return COPO_OK;
+    return h && out ? h->rows.count(out, stream) : fail(COPO_ERR_NULL, "copo_conflict_count: NULL argument");
 }
 
 extern "C" int copo_conflict_read(copo_conflict* h, int32_t first, int32_t n, int32_t* rows_out, void* stream) {
-    if (!h) return fail(COPO_ERR_NULL, "copo_conflict_read: NULL handle");
-    if (first < 0 || n < 0 || (int64_t)first + n > h->cfg.max_rows)
-        return fail(COPO_ERR_DIM, "copo_conflict_read: rows [%d, %d + %d) of a pool of %d", first, first, n, h->cfg.max_rows);
-    if (n == 0) return COPO_OK;
-    if (!rows_out) return fail(COPO_ERR_NULL, "copo_conflict_read: NULL output");
-    HIP_TRY(hipMemcpyAsync(rows_out, h->pool.p + (size_t)first * CONFLICT_WORDS, (size_t)n * CONFLICT_WORDS * 4, hipMemcpyDeviceToDevice,
-                           static_cast<hipStream_t>(stream)));
-    return COPO_OK;
+    return h ? h->rows.read(first, n, rows_out, stream, "copo_conflict_read") : null_handle("copo_conflict_read");
 }
 
-// (the rows need no clearing: nothing reads beyond n_rows)
-extern "C" int copo_conflict_clear(copo_conflict* h, void* stream) {
-    if (!h) return fail(COPO_ERR_NULL, "copo_conflict_clear: NULL handle");
-    HIP_TRY(h->counters.fill(0, static_cast<hipStream_t>(stream)));
-    return COPO_OK;
-}
+extern "C" int copo_conflict_clear(copo_conflict* h, void* stream) { return h ? h->rows.clear(stream) : null_handle("copo_conflict_clear"); }
 
 // (the pair and slot memory needs no clearing: it is read only where an encounter is open, and written when one opens)
 extern "C" int copo_conflict_reset(copo_conflict* h, void* stream) {
-    if (!h) return fail(COPO_ERR_NULL, "copo_conflict_reset: NULL handle");
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    HIP_TRY(h->counters.fill(0, st));
-    HIP_TRY(h->open.fill(0, st));
-    HIP_TRY(h->pool.fill(0, st));
-    h->n_records = 0;
-    return COPO_OK;
+    if (!h) return null_handle("copo_conflict_reset");
+    HIP_TRY(h->open.fill(0, static_cast<hipStream_t>(stream)));
+    return h->rows.reset(stream);
 }

@@ -1,13 +1,13 @@
 // Conflict log over the simulator's scenes (copo_conflict_*, include/copo_hip.h): one row per pairwise encounter; no counterpart in the
 // reference.  An encounter of slots a < b opens in the record that sees both ALIVE closer than `radius`, is followed in the pair's 48
 // bytes of memory (steps, the smallest squared distance and both poses at it) and leaves as ONE 64-byte row into a bounded pool when a
-// party ends, vanishes or the two part beyond `leave_radius`.  Three launches per record, in the shape of trip_kernels.hip:
-//   close:   one wave per scene, four scenes per 256-thread workgroup, lane n = slot n; at most CONFLICT_MAX_WG workgroups, beyond that a
+// party ends, vanishes or the two part beyond `leave_radius`.  Three launches per record; the pool, the assign launch and the rule that
+// decides the row ids are rowlog_common.h:
+//   close:   one wave per scene, four scenes per 256-thread workgroup, lane n = slot n; at most MAX_WG workgroups, beyond that a
 //            workgroup walks its scenes in strides of the grid.  The positions and one word per slot (end flags, same identity, ALIVE) are
 //            staged into LDS; lane a walks the partners of its open mask, decides which encounters close and writes its 64-bit closing
 //            mask and the scene's close count
-//   assign:  ONE workgroup walks the scene counts in order, a prefix over lanes and waves: every scene gets the row id of its first
-//            closing pair.  No atomic decides an id, so which rows exist, their order and which are dropped do not depend on scheduling
+//   assign:  a scene's closes are its close count: every scene gets the row id of its first closing pair
 //   commit:  wave per scene again: a closing pair's id is the scene's base + the popcounts of the closing masks of the lanes below a (a
 //            prefix over lanes) + the popcount of a's mask below b; its row goes out as four 16-byte stores.  Then lane a walks the ALIVE
 //            partners above it: pairs closer than `radius` open, every open pair accumulates this record
@@ -20,15 +20,12 @@
 
 namespace copo {
 
+using namespace rowlog;
+
 namespace {
 
-constexpr int TB = 256, NW = TB / 64;
-constexpr int CONFLICT_MAX_WG = 1024;      // four workgroups per CU: beyond that a workgroup takes several batches of scenes
-constexpr int ASSIGN_THREADS = 1024, ASSIGN_WAVES = ASSIGN_THREADS / 64;
 constexpr uint32_t SW_SAME = 1u << 8, SW_ALIVE = 1u << 9;      // above the end byte of a slot word
 constexpr uint32_t INF_BITS = 0x7f800000u;
-
-typedef unsigned long long u64;
 
 // bits above lane a (a = 63: none)
 __device__ __forceinline__ u64 above(int a) { return (~1ull) << a; }
@@ -97,42 +94,8 @@ __global__ __launch_bounds__(TB) void conflict_close_kernel(ConflictArgs a, int 
     }
 }
 
-// ONE workgroup: the row ids of the closing pairs in ascending (scene, slot_a, slot_b) order, then the counters
 __global__ __launch_bounds__(ASSIGN_THREADS) void conflict_assign_kernel(ConflictArgs a) {
-    __shared__ int wsum[ASSIGN_WAVES];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const long long first = a.counters[CC_ROWS];      // (read by every thread before the first barrier, written after the last)
-    long long total = 0;
-    for (int e0 = 0; e0 < a.E; e0 += ASSIGN_THREADS) {
-        const int e = e0 + tid;
-        const int c = e < a.E ? a.n_closing[e] : 0;
-        int inc = c;                                   // inclusive prefix over the wave's lanes (at most 64 x 2 016)
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const int t = __shfl_up(inc, d);
-            if (lane >= d) inc += t;
-        }
-        if (lane == 63) wsum[wave] = inc;
-        __syncthreads();
-        int off = 0, sum = 0;
-#pragma unroll
-        for (int w = 0; w < ASSIGN_WAVES; ++w) {
-            const int s = wsum[w];
-            off += w < wave ? s : 0;
-            sum += s;
-        }
-        if (e < a.E) {
-            const long long id = first + total + off + (inc - c);
-            a.base[e] = (int32_t)(id < a.max_rows ? id : a.max_rows);       // (every id from max_rows on is dropped alike)
-        }
-        total += sum;
-        __syncthreads();
-    }
-    if (tid == 0) {
-        const long long stored = first + total < a.max_rows ? first + total : a.max_rows;
-        a.counters[CC_ROWS] = stored;
-        a.counters[CC_DROPPED_ROWS] += first + total - stored;
-    }
+    assign(a.rows, a.E, [&](int e) { return a.n_closing[e]; });
 }
 
 // flush != 0: rows only, nothing opens or accumulates and no encounter stays open
@@ -171,8 +134,9 @@ __global__ __launch_bounds__(TB) void conflict_commit_kernel(ConflictArgs a, int
         }
         if (cm) {
             const uint32_t wa = sw[wave][lane];
-            long long id = (long long)a.base[e] + (inc - c);
-            for (u64 m = cm; m && id < a.max_rows; m &= m - 1ull, ++id) {
+            long long id = (long long)a.rows.base[e] + (inc - c);
+            uint4* R;
+            for (u64 m = cm; m && row(a.rows, id, R); m &= m - 1ull, ++id) {
                 const int b = __ffsll((long long)m) - 1;
                 const uint32_t wb = sw[wave][b];
                 uint32_t kind = CONFLICT_KIND_FLUSH, end_a = 0u, end_b = 0u;
@@ -185,7 +149,6 @@ __global__ __launch_bounds__(TB) void conflict_commit_kernel(ConflictArgs a, int
                 }
                 const uint4* M = mem + (size_t)pair_index(lane, b, N) * (CONFLICT_PAIR_WORDS / 4);
                 const uint4 h = M[0];                  // {first_rec, steps, d2min bits, min_off}
-                uint4* R = reinterpret_cast<uint4*>(a.pool) + (size_t)id * (CONFLICT_WORDS / 4);
                 R[0] = make_uint4((uint32_t)e, (uint32_t)lane | ((uint32_t)b << 6) | (kind << 12) | (end_a << 16) | (end_b << 24), (uint32_t)aid_mem,
                                   (uint32_t)said[wave][b]);
                 R[1] = make_uint4((uint32_t)ep_mem, h.x, h.y | (h.w << 16), h.z);
@@ -235,16 +198,8 @@ __global__ __launch_bounds__(TB) void conflict_commit_kernel(ConflictArgs a, int
     }
 }
 
-static dim3 scene_grid(int E) {
-    const int batches = (E + NW - 1) / NW;
-    return dim3(batches < CONFLICT_MAX_WG ? batches : CONFLICT_MAX_WG);
-}
-
 static hipError_t launch_all(const ConflictArgs& a, int flush, hipStream_t stream) {
-    hipLaunchKernelGGL(conflict_close_kernel, scene_grid(a.E), dim3(TB), 0, stream, a, flush);
-    hipLaunchKernelGGL(conflict_assign_kernel, dim3(1), dim3(ASSIGN_THREADS), 0, stream, a);
-    hipLaunchKernelGGL(conflict_commit_kernel, scene_grid(a.E), dim3(TB), 0, stream, a, flush);
-    return hipGetLastError();
+    return launch(conflict_close_kernel, conflict_assign_kernel, conflict_commit_kernel, a, flush, stream);
 }
 
 hipError_t launch_conflict_record(const ConflictArgs& a, hipStream_t stream) { return launch_all(a, 0, stream); }

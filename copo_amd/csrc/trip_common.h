@@ -1,13 +1,10 @@
 // Shared declarations of the trip log (trip_kernels.hip) and its C entry points (capi_observers.hip).
 #pragma once
-#include <hip/hip_runtime.h>
-#include <stdint.h>
+#include "rowlog_common.h"
 
 namespace copo {
 
-constexpr int TRIP_WORDS = 16;             // 32-bit words of a row
 constexpr int TRIP_KIND_DONE = 1, TRIP_KIND_VANISHED = 2, TRIP_KIND_FLUSH = 3;
-enum { TC_ROWS = 0, TC_DROPPED, TRIP_COUNTERS };
 // per-slot memory: TRIP_MEM_WORDS planes of [E][N] 32-bit words, owned by the scene's wave
 enum { TM_AID = 0, TM_FIRST, TM_ROUTE, TM_LCF, TM_PROG0, TM_PROG1, TM_STEPS, TM_SPEED_SUM, TM_SPEED_MAX, TM_STOPS, TM_REWARD, TM_MIN_GAP,
        TM_MIN_TTC, TRIP_MEM_WORDS };
@@ -17,7 +14,7 @@ struct TripArgs {
     const float* state;            // [COPO_STATE_FIELDS][E][N]
     const int32_t* env;            // [E][4]
     int32_t E, N;
-    int32_t max_rows, r;           // pool size; this record's number
+    int32_t r;                     // this record's number
     float stop_speed;
     // this record's optional inputs, [E][N] each, NULL = absent
     const uint8_t* flags;
@@ -28,9 +25,7 @@ struct TripArgs {
     // between the launches of one call
     unsigned long long* closing;   // [E] bit n: slot n's trip closes in this call
     uint32_t* endw;                // [E][N] end flags | kind << 8 of the closing slots
-    int32_t* base;                 // [E] row id of the scene's first closing slot, min(id, max_rows)
-    long long* counters;           // [TRIP_COUNTERS]
-    uint32_t* pool;                // [max_rows][TRIP_WORDS]
+    RowPoolArgs rows;              // the pool; a scene's closes are its closing slots in ascending order
 };
 
 hipError_t launch_trip_record(const TripArgs& a, hipStream_t stream);

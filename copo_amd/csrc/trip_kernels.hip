@@ -1,12 +1,10 @@
 // Trip log over the simulator's scenes (copo_trip_*, include/copo_hip.h): one row per finished agent.  A trip is followed in its slot
 // from the first record that sees the agent ALIVE to the record that ends it, and then leaves as ONE 64-byte row into a bounded pool.
-// Three launches per record:
+// Three launches per record; the pool, the assign launch and the rule that decides the row ids are rowlog_common.h:
 //   close:   one wave per scene, four scenes per 256-thread workgroup, lane n = slot n (every load and store over the slots is coalesced);
-//            at most TRIP_MAX_WG workgroups, beyond that a workgroup walks its scenes in strides of the grid.  Adds the step's reward to
+//            at most MAX_WG workgroups, beyond that a workgroup walks its scenes in strides of the grid.  Adds the step's reward to
 //            the open trips, decides which of them end and writes the scene's 64-bit closing mask and the slots' end words
-//   assign:  ONE workgroup walks the scenes in order, popcounts of the masks, a prefix over lanes and waves: every scene gets the row id
-//            of its first closing slot.  No atomic decides an id, so which rows exist, their order and which are dropped do not depend
-//            on how workgroups are scheduled (the clip recorder's rule)
+//   assign:  a scene's closes are the popcount of its mask: every scene gets the row id of its first closing slot
 //   commit:  wave per scene again: a closing lane's id is the scene's base + the popcount of the mask below its lane, its row goes out as
 //            four 16-byte stores; then the slots that are ALIVE without a trip open one, and every open trip accumulates this record
 // No workgroup waits for another; the per-slot memory belongs to the scene's wave and no atomic touches it.  Integer logic, one fp32 add
@@ -17,13 +15,9 @@
 
 namespace copo {
 
+using namespace rowlog;
+
 namespace {
-
-constexpr int TB = 256, NW = TB / 64;
-constexpr int TRIP_MAX_WG = 1024;          // four workgroups per CU: beyond that a workgroup takes several batches of scenes
-constexpr int ASSIGN_THREADS = 1024, ASSIGN_WAVES = ASSIGN_THREADS / 64;
-
-typedef unsigned long long u64;
 
 __device__ __forceinline__ uint32_t* plane(const TripArgs& a, int k) { return a.mem + (size_t)k * a.E * a.N; }
 
@@ -66,42 +60,8 @@ __global__ __launch_bounds__(TB) void trip_close_kernel(TripArgs a, int flush) {
     }
 }
 
-// ONE workgroup: the row ids of the closing slots in ascending (scene, slot) order, then the counters
 __global__ __launch_bounds__(ASSIGN_THREADS) void trip_assign_kernel(TripArgs a) {
-    __shared__ int wsum[ASSIGN_WAVES];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const long long first = a.counters[TC_ROWS];      // (read by every thread before the first barrier, written after the last)
-    long long total = 0;
-    for (int e0 = 0; e0 < a.E; e0 += ASSIGN_THREADS) {
-        const int e = e0 + tid;
-        const int c = e < a.E ? __popcll(a.closing[e]) : 0;
-        int inc = c;                                   // inclusive prefix over the wave's lanes
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const int t = __shfl_up(inc, d);
-            if (lane >= d) inc += t;
-        }
-        if (lane == 63) wsum[wave] = inc;
-        __syncthreads();
-        int off = 0, sum = 0;
-#pragma unroll
-        for (int w = 0; w < ASSIGN_WAVES; ++w) {
-            const int s = wsum[w];
-            off += w < wave ? s : 0;
-            sum += s;
-        }
-        if (e < a.E) {
-            const long long id = first + total + off + (inc - c);
-            a.base[e] = (int32_t)(id < a.max_rows ? id : a.max_rows);       // (every id from max_rows on is dropped alike)
-        }
-        total += sum;
-        __syncthreads();
-    }
-    if (tid == 0) {
-        const long long stored = first + total < a.max_rows ? first + total : a.max_rows;
-        a.counters[TC_ROWS] = stored;
-        a.counters[TC_DROPPED] += first + total - stored;
-    }
+    assign(a.rows, a.E, [&](int e) { return __popcll(a.closing[e]); });
 }
 
 // flush != 0: rows only, nothing opens or accumulates and no trip stays open
@@ -117,9 +77,8 @@ __global__ __launch_bounds__(TB) void trip_commit_kernel(TripArgs a, int flush) 
         const int32_t ep_mem = a.episode[e];
         const bool closing = (m >> lane) & 1ull;       // (closing is a subset of open, open of the lanes below N)
         if (closing) {
-            const long long id = (long long)a.base[e] + __popcll(m & ((1ull << lane) - 1ull));
-            if (id < a.max_rows) {
-                uint4* R = reinterpret_cast<uint4*>(a.pool) + (size_t)id * (TRIP_WORDS / 4);
+            uint4* R;
+            if (row(a.rows, (long long)a.rows.base[e] + __popcll(m & ((1ull << lane) - 1ull)), R)) {
                 R[0] = make_uint4((uint32_t)e, (uint32_t)lane | (plane(a, TM_ROUTE)[o] << 16), plane(a, TM_AID)[o], (uint32_t)ep_mem);
                 R[1] = make_uint4(plane(a, TM_FIRST)[o], plane(a, TM_STEPS)[o], a.endw[o], plane(a, TM_LCF)[o]);
                 R[2] = make_uint4(plane(a, TM_PROG0)[o], plane(a, TM_PROG1)[o], plane(a, TM_SPEED_SUM)[o], plane(a, TM_SPEED_MAX)[o]);
@@ -174,16 +133,8 @@ __global__ __launch_bounds__(TB) void trip_commit_kernel(TripArgs a, int flush) 
     }
 }
 
-static dim3 scene_grid(int E) {
-    const int batches = (E + NW - 1) / NW;
-    return dim3(batches < TRIP_MAX_WG ? batches : TRIP_MAX_WG);
-}
-
 static hipError_t launch_all(const TripArgs& a, int flush, hipStream_t stream) {
-    hipLaunchKernelGGL(trip_close_kernel, scene_grid(a.E), dim3(TB), 0, stream, a, flush);
-    hipLaunchKernelGGL(trip_assign_kernel, dim3(1), dim3(ASSIGN_THREADS), 0, stream, a);
-    hipLaunchKernelGGL(trip_commit_kernel, scene_grid(a.E), dim3(TB), 0, stream, a, flush);
-    return hipGetLastError();
+    return launch(trip_close_kernel, trip_assign_kernel, trip_commit_kernel, a, flush, stream);
 }
 
 hipError_t launch_trip_record(const TripArgs& a, hipStream_t stream) { return launch_all(a, 0, stream); }

@@ -10,12 +10,11 @@ the minimum TTC, and `of(scene, aid, episode)` for "which agent was that" of a c
 """
 import ctypes as C
 import dataclasses
-import json
 
 import numpy as np
 
 from ._abi import TRIP_DONE as KIND_DONE, TRIP_FLUSHED as KIND_FLUSHED, TRIP_VANISHED as KIND_VANISHED, TRIP_WORDS as WORDS
-from ._handle import Handle
+from ._rowlog import RowLog, RowTable
 
 ROW_KEYS = ("scene", "slot_route", "aid", "episode", "first_rec", "steps", "end", "lcf", "prog0", "prog1", "speed_sum", "speed_max", "stops",
             "reward", "min_gap", "min_ttc")
@@ -52,36 +51,13 @@ def decode(raw, dt):
     return out
 
 
-class TripTable:
+class TripTable(RowTable):
     """Finished trips as numpy: `raw` uint32 [n, 16] (the rows as the device wrote them, columns `ROW_KEYS`), `meta` (dict: `dt`,
     `num_agents`, `max_rows`, `stop_speed`, `dropped`, `n_records`, `sim_config`), and the columns of `decode` as attributes / items."""
 
-    def __init__(self, raw, meta):
-        self.raw = np.ascontiguousarray(np.asarray(raw).reshape(-1, WORDS)).view(np.uint32).copy()
-        self.meta = dict(meta)
-        self.columns = decode(self.raw, self.meta["dt"])
-
-    def __len__(self):
-        return len(self.raw)
-
-    def __getitem__(self, key):
-        return self.columns[key]
-
-    def __getattr__(self, key):
-        cols = self.__dict__.get("columns")
-        if cols is not None and key in cols:
-            return cols[key]
-        raise AttributeError(key)
-
-    def save(self, path):
-        """One `.npz` without pickled objects (`np.load(path, allow_pickle=False)` reads it): the raw rows and `meta` as JSON."""
-        np.savez_compressed(path, rows=self.raw, meta=np.array(json.dumps(self.meta, sort_keys=True)))
-        return path
-
-    @classmethod
-    def load(cls, path):
-        with np.load(path, allow_pickle=False) as f:
-            return cls(f["rows"], json.loads(str(f["meta"][()])))
+    @staticmethod
+    def _decode(raw, meta):
+        return decode(raw, meta["dt"])
 
     def frame(self):
         """pandas DataFrame of every column."""
@@ -142,13 +118,13 @@ def trip_meta(cfg, N, max_rows, stop_speed, dropped=0, n_records=0):
                 n_records=int(n_records), sim_config=dataclasses.asdict(cfg))
 
 
-class TripLog(Handle):
+class TripLog(RowLog):
     """Per-agent trip rows of a `VecSim`: a pool of `max_rows` rows (later ones are counted as dropped), a record with speed below
     `stop_speed` m/s counts as a stop.  Records count from 0 since creation / `reset()`.  `close()` it when done (before or after its
     simulator; no other call once the simulator is closed); every call is asynchronous on torch's current stream except `count()` and
     what reads rows to the host (`table()`, `drain()`)."""
 
-    _destroy = "copo_trip_destroy"
+    _destroy, _prefix, _table_cls = "copo_trip_destroy", "copo_trip_", TripTable
 
     def __init__(self, sim, max_rows=65536, stop_speed=0.5):
         self._attach(sim)
@@ -179,41 +155,5 @@ class TripLog(Handle):
                                                          self._stream()))
         self.n_records += 1
 
-    def flush(self):
-        """Close every open trip as it stands (kind 3, outcome "open"); an agent that drives on opens a new trip in the next record."""
-        self._capi.check(self._capi.lib.copo_trip_flush(self._h, self._stream()))
-
-    def count(self):
-        """(rows stored, rows dropped); waits for the stream."""
-        out = (C.c_int64 * 2)()
-        self._capi.check(self._capi.lib.copo_trip_count(self._h, out, self._stream()))
-        return int(out[0]), int(out[1])
-
-    def clear(self):
-        """Empty the pool and the dropped count; open trips and the record count stay."""
-        self._capi.check(self._capi.lib.copo_trip_clear(self._h, self._stream()))
-
-    def reset(self):
-        """Forget every row, counter and open trip; records count from 0 again."""
-        self._capi.check(self._capi.lib.copo_trip_reset(self._h, self._stream()))
-        self.n_records = 0
-
-    def rows(self):
-        """The stored rows, device int32 [n, 16] (a copy)."""
-        torch = self._torch
-        n, _ = self.count()
-        out = torch.empty(n, WORDS, dtype=torch.int32, device=self.device)
-        if n:
-            self._capi.check(self._capi.lib.copo_trip_read(self._h, 0, n, out.data_ptr(), self._stream()))
-        return out
-
-    def table(self):
-        """The stored rows as a `TripTable`."""
-        _, dropped = self.count()
-        return TripTable(self.rows().cpu().numpy(), trip_meta(self.sim.cfg, self.sim.N, self.max_rows, self.stop_speed, dropped, self.n_records))
-
-    def drain(self):
-        """`table()`, then `clear()`: what a long run calls now and then to keep a bounded pool from overflowing."""
-        t = self.table()
-        self.clear()
-        return t
+    def _meta(self, dropped):
+        return trip_meta(self.sim.cfg, self.sim.N, self.max_rows, self.stop_speed, dropped, self.n_records)

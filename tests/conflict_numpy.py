@@ -25,12 +25,10 @@ import struct
 
 import numpy as np
 
-ST_EMPTY, ST_ALIVE, ST_WRECK = 0, 1, 2
-F_ACTED, F_DONE, F_ARRIVE, F_CRASH, F_OUT, F_MAXSTEP, F_SPAWNED, F_ENV_RESET = (1 << i for i in range(8))
+from rowlog_numpy import (F_ACTED, F_ARRIVE, F_CRASH, F_DONE, F_ENV_RESET, F_MAXSTEP, F_OUT, F_SPAWNED, M32, ST_ALIVE, ST_EMPTY, ST_WRECK,  # noqa: F401
+                          WORDS, RowPool, compare, f32)
+
 KIND_DONE, KIND_VANISHED, KIND_PARTED, KIND_FLUSHED = 1, 2, 3, 4
-WORDS = 16
-f32 = np.float32
-M32 = 0xFFFFFFFF
 CAP = 65535
 INF = float("inf")
 
@@ -55,7 +53,7 @@ def dist2(xa, ya, xb, yb):
 FIRST_REC, STEPS, D2MIN, MIN_OFF, POSE_A, POSE_B = range(6)      # the pair memory: a list per open pair
 
 
-class ConflictLog:
+class ConflictLog(RowPool):
     def __init__(self, E, N, max_rows=65536, radius=8.0, leave_radius=10.0):
         self.E, self.N, self.max_rows = E, N, int(max_rows)
         self.r2_in, self.r2_out = float(r2(radius)), float(r2(leave_radius))
@@ -74,25 +72,12 @@ class ConflictLog:
         self.close_and_open_in_one_record = 0
         self.max_encounters_of_one_slot = 0
 
-    def clear(self):
-        self._rows, self.close_rec, self.dropped = [], [], 0
-
-    n_rows = property(lambda self: len(self._rows))
-
-    def rows(self):
-        return np.array(self._rows, np.uint32).reshape(-1, WORDS)
-
     def n_open(self):
         return sum(len(d) for d in self.open)
 
     def _commit(self, e, a, b, p, kind, end_a, end_b):
-        self.total_closed += 1
-        if len(self._rows) >= self.max_rows:
-            self.dropped += 1
-            return
-        self._rows.append([e, a | (b << 6) | (kind << 12) | (end_a << 16) | (end_b << 24), int(self.aid[e, a]) & M32, int(self.aid[e, b]) & M32,
-                           int(self.episode[e]) & M32, p[FIRST_REC], p[STEPS] | (p[MIN_OFF] << 16), bits(p[D2MIN])] + p[POSE_A] + p[POSE_B])
-        self.close_rec.append(self.r)
+        self._store([e, a | (b << 6) | (kind << 12) | (end_a << 16) | (end_b << 24), int(self.aid[e, a]) & M32, int(self.aid[e, b]) & M32,
+                     int(self.episode[e]) & M32, p[FIRST_REC], p[STEPS] | (p[MIN_OFF] << 16), bits(p[D2MIN])] + p[POSE_A] + p[POSE_B], self.r)
 
     def record(self, state, env, flags=None):
         """state [16][E][N] float32 words, env [E][4] int32 of the simulator after a step / reset / set_state"""
@@ -158,10 +143,3 @@ class ConflictLog:
             for (a, b) in sorted(self.open[e]):
                 self._commit(e, a, b, self.open[e][(a, b)], KIND_FLUSHED, 0, 0)
             self.open[e] = dict()
-
-
-def compare(got_rows, got_count, ref):
-    """the device's rows (anything numpy reads as [n, 16] words) and (n_rows, dropped) equal the restatement's, word for word"""
-    a, b = np.ascontiguousarray(np.asarray(got_rows).reshape(-1, WORDS)).view(np.uint32), ref.rows()
-    assert tuple(int(v) for v in got_count) == (ref.n_rows, ref.dropped), (got_count, ref.n_rows, ref.dropped)
-    assert a.shape == b.shape and np.array_equal(a, b), (a.shape, b.shape, np.argwhere(a != b)[:8].tolist() if a.shape == b.shape else None)

@@ -10,34 +10,10 @@ import pytest
 import conflict_cases as cc
 import conflict_numpy as cn
 import interact_cases as ic
+from rowlog_gpu import Both, _dev, _np_state, _read, _set_state, _sim64
 from copo_amd.sim import SimConfig
 
 pytestmark = pytest.mark.gpu
-
-
-def _np_state(sim):
-    st, env = sim.get_state()
-    return st.cpu().numpy(), env.cpu().numpy()
-
-
-def _set_state(sim, st, env):
-    import torch
-    sim.set_state(torch.from_numpy(np.ascontiguousarray(st)).cuda(), torch.from_numpy(np.ascontiguousarray(env)).cuda())
-
-
-def _dev(a):
-    import torch
-    return None if a is None else torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def _read(log):
-    return log.rows().cpu().numpy().view(np.uint32), log.count()
-
-
-def _sim64(E, N):
-    from copo_amd.sim import VecSim
-    kw = dict(map="intersection", num_envs=E, num_agents=N)
-    return VecSim(SimConfig(map_kwargs=dict(exit_length=80.0), **kw) if N == 64 else SimConfig(**kw))
 
 
 @pytest.mark.parametrize("N", [7, 64])
@@ -57,16 +33,7 @@ def test_hand_sequence(N):
             log.record(_dev(flags))
             ref.record(st, env, flags)
             cn.compare(*_read(log), ref)
-
-        class Both:
-            def clear(self):
-                log.clear()
-                ref.clear()
-
-            def flush(self):
-                log.flush()
-                ref.flush()
-        mid, end = cc.run_hand(Both(), N, record, lambda: _read(log), st0, env0)
+        mid, end = cc.run_hand(Both(log, ref), N, record, lambda: _read(log), st0, env0)
         before, after = cc.hand_expected(N)
         for (got, count), want in ((mid, before), (end, after)):
             assert count == (len(want), 0) and got.shape == want.shape and np.array_equal(got, want), np.argwhere(got != want).tolist()

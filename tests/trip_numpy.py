@@ -17,13 +17,11 @@ is dropped.  `flush` closes every open trip with kind 3 and end = 0 under the sa
 count only."""
 import numpy as np
 
-ST_EMPTY, ST_ALIVE, ST_WRECK = 0, 1, 2
-F_ACTED, F_DONE, F_ARRIVE, F_CRASH, F_OUT, F_MAXSTEP, F_SPAWNED, F_ENV_RESET = (1 << i for i in range(8))
+from rowlog_numpy import (F_ACTED, F_ARRIVE, F_CRASH, F_DONE, F_ENV_RESET, F_MAXSTEP, F_OUT, F_SPAWNED, M32, ST_ALIVE, ST_EMPTY, ST_WRECK,  # noqa: F401
+                          WORDS, RowPool, compare, f32)
+
 KIND_DONE, KIND_VANISHED, KIND_FLUSHED = 1, 2, 3
-WORDS = 16
-f32 = np.float32
 INF_BITS = 0x7F800000
-M32 = 0xFFFFFFFF
 
 
 def bits(x):
@@ -43,7 +41,7 @@ class _Trip:
                  "min_ttc")
 
 
-class TripLog:
+class TripLog(RowPool):
     def __init__(self, E, N, max_rows=65536, stop_speed=0.5):
         self.E, self.N, self.max_rows, self.stop_speed = E, N, int(max_rows), f32(stop_speed)
         self.reset()
@@ -58,22 +56,9 @@ class TripLog:
         self.records_with_closes_in_two_scenes = 0
         self.close_and_open_in_one_record = 0
 
-    def clear(self):
-        self._rows, self.close_rec, self.dropped = [], [], 0
-
-    n_rows = property(lambda self: len(self._rows))
-
-    def rows(self):
-        return np.array(self._rows, np.uint32).reshape(-1, WORDS)
-
     def _commit(self, e, n, t, end, kind, close_rec):
-        self.total_closed += 1
-        if len(self._rows) >= self.max_rows:
-            self.dropped += 1
-            return
-        self._rows.append([e, n | (t.route << 16), t.aid & M32, t.episode & M32, t.first_rec, t.steps & M32, end | (kind << 8), t.lcf, t.prog0, t.prog1,
-                           t.speed_sum & M32, t.speed_max, t.stops & M32, bits(t.reward), bits(t.min_gap), bits(t.min_ttc)])
-        self.close_rec.append(close_rec)
+        self._store([e, n | (t.route << 16), t.aid & M32, t.episode & M32, t.first_rec, t.steps & M32, end | (kind << 8), t.lcf, t.prog0, t.prog1,
+                     t.speed_sum & M32, t.speed_max, t.stops & M32, bits(t.reward), bits(t.min_gap), bits(t.min_ttc)], close_rec)
 
     def record(self, state, env, flags=None, rew=None, gap=None, ttc=None):
         """state [16][E][N] float32 words, env [E][4] int32 of the simulator after a step / reset / set_state"""
@@ -137,10 +122,3 @@ class TripLog:
 
     def n_open(self):
         return sum(t is not None for row in self.open for t in row)
-
-
-def compare(got_rows, got_count, ref):
-    """the device's rows (anything numpy reads as [n, 16] words) and (n_rows, dropped) equal the restatement's, word for word"""
-    a, b = np.ascontiguousarray(np.asarray(got_rows).reshape(-1, WORDS)).view(np.uint32), ref.rows()
-    assert tuple(int(v) for v in got_count) == (ref.n_rows, ref.dropped), (got_count, ref.n_rows, ref.dropped)
-    assert a.shape == b.shape and np.array_equal(a, b), (a.shape, b.shape, np.argwhere(a != b)[:8].tolist() if a.shape == b.shape else None)
