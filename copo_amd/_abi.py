@@ -109,3 +109,12 @@ class ConflictCfg(C.Structure):
 
 
 CONFLICT_WORDS, CONFLICT_DONE, CONFLICT_VANISHED, CONFLICT_PARTED, CONFLICT_FLUSHED = 16, 1, 2, 3, 4
+
+
+class PetCfg(C.Structure):
+    """Mirror of `copo_pet_cfg`."""
+    _fields_ = [("x0", C.c_float), ("y0", C.c_float), ("cell", C.c_float), ("W", C.c_int32), ("H", C.c_int32), ("G", C.c_int32),
+                ("window", C.c_int32), ("critical_records", C.c_int32), ("max_rows", C.c_int32)]
+
+
+PET_WORDS, PET_MAX_WINDOW, PET_TYPES = 16, 4096, 3

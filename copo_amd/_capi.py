@@ -172,6 +172,17 @@ _SIGS = {
     "copo_conflict_clear": (C.c_int, [C.c_void_p, C.c_void_p]),
     "copo_conflict_reset": (C.c_int, [C.c_void_p, C.c_void_p]),
     "copo_conflict_destroy": (C.c_int, [C.c_void_p]),
+    "copo_pet_create": (C.c_int, [C.c_void_p, C.POINTER(PetCfg), C.POINTER(C.c_void_p)]),
+    "copo_pet_set_groups": (C.c_int, [C.c_void_p] * 3),
+    "copo_pet_record": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "copo_pet_forget": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "copo_pet_count": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.c_void_p]),
+    "copo_pet_read": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "copo_pet_aggregates": (C.c_int, [C.c_void_p] * 4),
+    "copo_pet_memory": (C.c_int, [C.c_void_p] * 4),
+    "copo_pet_clear": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "copo_pet_reset": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "copo_pet_destroy": (C.c_int, [C.c_void_p]),
     "copo_neighbours_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_float,
                                       C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                       C.c_void_p, C.c_void_p]),

@@ -1,4 +1,4 @@
-"""What the trip log and the conflict log share on the host (`trips.py`, `conflicts.py`; the device side is `csrc/rowlog_common.h`): a
+"""What the trip log, the conflict log and the encroachment log share on the host (`trips.py`, `conflicts.py`, `encroach.py`; the device side is `csrc/rowlog_common.h`): a
 table of raw 16-word rows with its `.npz` file, and the handle calls over a bounded pool of such rows.  DESIGN.md section 8g."""
 import ctypes as C
 import json

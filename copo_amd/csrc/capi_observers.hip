@@ -1,5 +1,5 @@
 // C ABI of the handles that observe a simulator (include/copo_hip.h): renderer, interaction meter, event clips, scene rewind, field
-// maps, traffic gates, trip log, conflict log.  Each owns its device buffers through a DevPool (capi_common.h) on the simulator's device; every call but
+// maps, traffic gates, trip log, conflict log, encroachment log.  Each owns its device buffers through a DevPool (capi_common.h) on the simulator's device; every call but
 // *_destroy reads the simulator, which therefore has to be alive.  All launches are asynchronous on the caller's stream.
 #include <algorithm>
 #include <array>
@@ -17,6 +17,7 @@
 #include "gate_common.h"
 #include "trip_common.h"
 #include "conflict_common.h"
+#include "encroach_common.h"
 
 using namespace copo;
 
@@ -640,7 +641,7 @@ extern "C" int copo_gate_reset(copo_gate* h, void* stream) {
     return COPO_OK;
 }
 
-// ---- row pool of the trip log and the conflict log (rowlog_common.h) --------------------------------------------
+// ---- row pool of the trip log, the conflict log and the encroachment log (rowlog_common.h) --------------------------------------------
 
 // Host side of a log's pool: the record count, the three buffers and the calls that are the same for every log.  `who` is the entry
 // point's name for the error string.
@@ -871,5 +872,130 @@ extern "C" int copo_conflict_clear(copo_conflict* h, void* stream) { return h ? 
 extern "C" int copo_conflict_reset(copo_conflict* h, void* stream) {
     if (!h) return null_handle("copo_conflict_reset");
     HIP_TRY(h->open.fill(0, static_cast<hipStream_t>(stream)));
+    return h->rows.reset(stream);
+}
+
+// ---- encroachment log (encroach_kernels.hip) -------------------------------------------------------------------
+
+struct copo_pet {
+    copo_sim* sim;
+    DevPool mem;
+    copo_pet_cfg cfg;
+    float inv_cell;
+    RowPool rows;
+    DevBuf<int32_t> group;                 // [E]
+    DevBuf<unsigned long long> grid;       // [E][H][W]
+    DevBuf<int32_t> aid;                   // [E][N]
+    DevBuf<unsigned long long> met;        // [E][N]
+    DevBuf<int32_t> episode, epoch;        // [E]
+    DevBuf<long long> hist;                // [G][PET_TYPES][window]
+    DevBuf<long long> critical;            // [G][H][W]
+    DevBuf<unsigned long long> fresh;      // [E][N]
+    DevBuf<int32_t> n_fresh;               // [E]
+};
+
+extern "C" int copo_pet_create(copo_sim* sim, const copo_pet_cfg* cfg, copo_pet** out) {
+    if (!sim || !cfg || !out) return fail(COPO_ERR_NULL, "copo_pet_create: NULL argument");
+    *out = nullptr;
+    static_assert(COPO_PET_WORDS == ROWLOG_WORDS && COPO_PET_MAX_WINDOW == PET_MAX_WINDOW && COPO_PET_TYPES == PET_TYPES, "copo_hip.h / encroach_common.h");
+    if (int rc = RowPool::check(cfg->max_rows, "copo_pet_create")) return rc;
+    if (cfg->W < 1 || cfg->W > FIELD_MAX_SIDE || cfg->H < 1 || cfg->H > FIELD_MAX_SIDE || cfg->G < 1 || cfg->G > FIELD_MAX_GROUPS ||
+        cfg->window < 1 || cfg->window > PET_MAX_WINDOW || cfg->critical_records < 0 || !(cfg->cell > 0.0f) || !std::isfinite(cfg->cell))
+        return fail(COPO_ERR_DIM, "copo_pet_create: W=%d H=%d (1..%d) G=%d (1..%d) window=%d (1..%d) critical_records=%d (>= 0) cell=%g (> 0, finite)", cfg->W,
+                    cfg->H, FIELD_MAX_SIDE, cfg->G, FIELD_MAX_GROUPS, cfg->window, PET_MAX_WINDOW, cfg->critical_records, (double)cfg->cell);
+    const float inv_cell = (float)(1.0 / (double)cfg->cell);
+    if (!std::isfinite(cfg->x0) || !std::isfinite(cfg->y0) || !std::isfinite(inv_cell))
+        return fail(COPO_ERR_CONFIG, "copo_pet_create: x0=%g y0=%g 1/cell=%g (finite)", (double)cfg->x0, (double)cfg->y0, (double)inv_cell);
+    // a wider cell lets a body pass between cell centres
+    const double widest = 2.0 * (double)sim->p.hw / std::sqrt(2.0);
+    if (!((double)cfg->cell <= widest))
+        return fail(COPO_ERR_CONFIG, "copo_pet_create: cell=%g m is wider than 2 hw / sqrt(2) = %g m: a body could pass between cell centres",
+                    (double)cfg->cell, widest);
+    const size_t E = (size_t)sim->p.E, N = (size_t)sim->p.N, HW = (size_t)cfg->H * cfg->W;
+    HIP_TRY(hipSetDevice(sim->device));
+    copo_pet* h = new (std::nothrow) copo_pet();
+    if (!h) return fail(COPO_ERR_DEVICE, "out of host memory");
+    h->sim = sim; h->mem.device = sim->device; h->cfg = *cfg; h->inv_cell = inv_cell;
+    h->group = h->mem.alloc<int32_t>(E);
+    h->grid = h->mem.alloc<unsigned long long>(E * HW);
+    h->aid = h->mem.alloc<int32_t>(E * N);
+    h->met = h->mem.alloc<unsigned long long>(E * N);
+    h->episode = h->mem.alloc<int32_t>(E);
+    h->epoch = h->mem.alloc<int32_t>(E);
+    h->hist = h->mem.alloc<long long>((size_t)cfg->G * PET_TYPES * cfg->window);
+    h->critical = h->mem.alloc<long long>((size_t)cfg->G * HW);
+    h->fresh = h->mem.alloc<unsigned long long>(E * N);
+    h->n_fresh = h->mem.alloc<int32_t>(E);
+    h->rows.create(h->mem, E, cfg->max_rows);
+    return finish_create(h, out, "copo_pet_create");
+}
+
+extern "C" int copo_pet_destroy(copo_pet* h) { return destroy_handle(h, "copo_pet_destroy"); }
+
+extern "C" int copo_pet_set_groups(copo_pet* h, const int32_t* group_dev, void* stream) {
+    if (!h || !group_dev) return fail(COPO_ERR_NULL, "copo_pet_set_groups: NULL argument");
+    HIP_TRY(h->group.copy_from(group_dev, static_cast<hipStream_t>(stream)));
+    return COPO_OK;
+}
+
+extern "C" int copo_pet_record(copo_pet* h, void* stream) {
+    if (!h) return null_handle("copo_pet_record");
+    if (int rc = h->rows.can_record("copo_pet_record")) return rc;
+    const SimParams& p = h->sim->p;
+    PetArgs a;
+    a.state = p.state; a.env = p.env; a.E = p.E; a.N = p.N; a.r = h->rows.n_records; a.hl = p.hl; a.hw = p.hw;
+    a.x0 = h->cfg.x0; a.y0 = h->cfg.y0; a.cell = h->cfg.cell; a.inv_cell = h->inv_cell;
+    a.W = h->cfg.W; a.H = h->cfg.H; a.G = h->cfg.G; a.window = h->cfg.window; a.critical_records = h->cfg.critical_records;
+    a.group = h->group; a.grid = h->grid; a.aid = h->aid; a.met = h->met; a.episode = h->episode; a.epoch = h->epoch;
+    a.hist = h->hist; a.critical = h->critical; a.fresh = h->fresh; a.n_fresh = h->n_fresh; a.rows = h->rows.args();
+    HIP_TRY(launch_pet_record(a, static_cast<hipStream_t>(stream)));
+    h->rows.n_records += 1;
+    return COPO_OK;
+}
+
+extern "C" int copo_pet_forget(copo_pet* h, void* stream) {
+    if (!h) return null_handle("copo_pet_forget");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    HIP_TRY(h->met.fill(0, st));
+    HIP_TRY(launch_pet_forget(h->epoch, h->sim->p.E, h->rows.n_records, st));
+    return COPO_OK;
+}
+
+extern "C" int copo_pet_count(copo_pet* h, int64_t* out, void* stream) {
+    return h && out ? h->rows.count(out, stream) : fail(COPO_ERR_NULL, "copo_pet_count: NULL argument");
+}
+
+extern "C" int copo_pet_read(copo_pet* h, int32_t first, int32_t n, int32_t* rows_out, void* stream) {
+    return h ? h->rows.read(first, n, rows_out, stream, "copo_pet_read") : null_handle("copo_pet_read");
+}
+
+extern "C" int copo_pet_aggregates(copo_pet* h, int64_t* hist_dev, int64_t* critical_dev, void* stream) {
+    if (!h || (!hist_dev && !critical_dev)) return fail(COPO_ERR_NULL, "copo_pet_aggregates: NULL argument");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (hist_dev) HIP_TRY(h->hist.copy_to(hist_dev, st));
+    if (critical_dev) HIP_TRY(h->critical.copy_to(critical_dev, st));
+    return COPO_OK;
+}
+
+extern "C" int copo_pet_memory(copo_pet* h, uint64_t* grid_dev, uint64_t* met_dev, void* stream) {
+    if (!h || (!grid_dev && !met_dev)) return fail(COPO_ERR_NULL, "copo_pet_memory: NULL argument");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (grid_dev) HIP_TRY(h->grid.copy_to(grid_dev, st));
+    if (met_dev) HIP_TRY(h->met.copy_to(met_dev, st));
+    return COPO_OK;
+}
+
+extern "C" int copo_pet_clear(copo_pet* h, void* stream) { return h ? h->rows.clear(stream) : null_handle("copo_pet_clear"); }
+
+extern "C" int copo_pet_reset(copo_pet* h, void* stream) {
+    if (!h) return null_handle("copo_pet_reset");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    HIP_TRY(h->grid.fill(0, st));
+    HIP_TRY(h->aid.fill(0, st));
+    HIP_TRY(h->met.fill(0, st));
+    HIP_TRY(h->episode.fill(0, st));
+    HIP_TRY(h->epoch.fill(0, st));
+    HIP_TRY(h->hist.fill(0, st));
+    HIP_TRY(h->critical.fill(0, st));
     return h->rows.reset(stream);
 }

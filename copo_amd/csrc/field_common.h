@@ -36,4 +36,19 @@ hipError_t launch_field_events(const FieldArgs& a, int accumulate, hipStream_t s
 // occupancy, wreck, visits, speed, flow and critical layers of the current state (one launch; reads the tile bits of launch_field_events)
 hipError_t launch_field_tiles(const FieldArgs& a, hipStream_t stream);
 
+#ifdef __HIPCC__
+// What the kernels over a grid of cells share (field_kernels.hip, encroach_kernels.hip).
+// cells [lo, hi] of an axis of n cells that a footprint around coordinate f (in cells) can reach, r cells to either side
+__device__ __forceinline__ bool reach(float f, float r, int n, int& lo, int& hi) {
+    const float a = floorf(f - r), b = floorf(f + r);
+    if (!(b >= 0.0f) || !(a < (float)n)) return false;      // (NaN reaches nothing)
+    lo = (int)fmaxf(a, 0.0f);
+    hi = (int)fminf(b, (float)(n - 1));
+    return true;
+}
+
+// half a body's diagonal stays below hl + hw; one cell on top for the rounding of the cell coordinates
+__device__ __forceinline__ float reach_radius(float hl, float hw, float inv_cell) { return (hl + hw) * inv_cell + 1.0f; }
+#endif
+
 }  // namespace copo

@@ -25,15 +25,6 @@ static_assert(FIELD_MASK_WORDS <= FB, "one lane per word of the tile bits");
 
 typedef unsigned long long u64;
 
-// cells [lo, hi] of an axis of n cells that a footprint around coordinate f (in cells) can reach, r cells to either side
-__device__ __forceinline__ bool reach(float f, float r, int n, int& lo, int& hi) {
-    const float a = floorf(f - r), b = floorf(f + r);
-    if (!(b >= 0.0f) || !(a < (float)n)) return false;      // (NaN reaches nothing)
-    lo = (int)fmaxf(a, 0.0f);
-    hi = (int)fminf(b, (float)(n - 1));
-    return true;
-}
-
 // iy * W + ix of the cell that holds (x, y), -1 outside the grid: subtraction, product and floor rounded one by one
 __device__ __forceinline__ int centre_cell(const FieldArgs& a, float x, float y) {
     const float fx = floorf((x - a.x0) * a.inv_cell), fy = floorf((y - a.y0) * a.inv_cell);
@@ -41,8 +32,7 @@ __device__ __forceinline__ int centre_cell(const FieldArgs& a, float x, float y)
     return (int)fy * a.W + (int)fx;
 }
 
-// half a body's diagonal stays below hl + hw; one cell on top for the rounding of the cell coordinates
-__device__ __forceinline__ float reach_cells(const FieldArgs& a) { return (a.hl + a.hw) * a.inv_cell + 1.0f; }
+__device__ __forceinline__ float reach_cells(const FieldArgs& a) { return reach_radius(a.hl, a.hw, a.inv_cell); }
 
 }  // namespace
 

@@ -222,6 +222,18 @@ class MultiAgentMetaDrive:
             log.record()
         return log
 
+    def encroachment_log(self, **kwargs):
+        """The env's `copo_amd.encroach.EncroachmentLog`, attached the way the conflict log is: the first call (or one with arguments,
+        those of `EncroachmentLog`; without x0, y0, W, H the grid covers the map) creates it, makes one record of the current state at
+        once and has it record after every reset and step from then on; a call without arguments returns the same object again."""
+        log = self.observers.get("encroachment_log")
+        if log is None or kwargs:
+            from copo_amd.encroach import EncroachmentLog
+            log = EncroachmentLog.from_env(self.sim, kwargs)
+            self.observers.add("encroachment_log", log)      # (an earlier one is closed and replaced)
+            log.record()
+        return log
+
     def set_lcf_dist(self, mean, std):
         assert self.ENABLE_LCF, "set_lcf_dist needs an LCF env (get_lcf_env)"
         assert std > 0.0 and -1.0 <= mean <= 1.0

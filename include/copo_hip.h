@@ -621,6 +621,69 @@ int copo_conflict_clear(copo_conflict* h, void* stream);
 int copo_conflict_reset(copo_conflict* h, void* stream);
 int copo_conflict_destroy(copo_conflict* h);
 
+/* ---- encroachment log: post-encroachment times (PET) from a grid of stamps per scene, ONE row per encounter written on the device into a
+ *      bounded pool, and integer aggregates per scene group; no counterpart in the reference.  A handle reads its
+ *      simulator's state and must be destroyed before it.  Eager only: the record count lives on the host.  The footprint is the field
+ *      maps' rule operation for operation; everything else is integer logic and one fp32 product, so rows, grid and aggregates are
+ *      reproducible bit for bit and do not depend on how workgroups are scheduled.
+ * Grid: W x H cells of `cell` metres from (x0, y0) per scene, 8 bytes each.  C(n), the footprint of slot n: the cells whose centre
+ *   (x0 + (ix + 0.5) cell, y0 + (iy + 0.5) cell) lies in the body: sincos_det of the heading, u = fm(dx, c, dy s), w = fm(dy, c, -(dx s)),
+ *   |u| <= hl && |w| <= hw.  Cells outside the grid do not exist.
+ * Stamp: (q + 1) << 32 | (aid & 0xffff) << 16 | hq << 8 | slot for a stamp written in record q, hq = __float2int_rn(heading * (float)(128 /
+ *   pi)) & 255; 0 = empty.
+ * Record r, per scene, in this order:
+ *   1 TURNOVER: slot n turns over when it is not ALIVE, when its agent id (state field 14) differs from the remembered one, or when the
+ *     episode word (env word 1) differs from the remembered one.  It clears its `met` mask and every slot of the scene clears bit n of
+ *     its own.  An episode change sets the scene's epoch = r.  Ids and the episode word are remembered.
+ *   2 VALID: a stamp {q + 1, a16, hq, s} under C(n) is valid for ALIVE slot n iff s != n, slot s is ALIVE now with (aid & 0xffff) == a16,
+ *     q + 1 > epoch, and 1 <= r - q <= window.  P(n): the slots with a valid stamp under C(n).
+ *   3 ENCOUNTER: for every s of P(n) & ~met[n], ascending, one row: pet = the smallest r - q over the valid stamps of s under C(n), cell =
+ *     the lowest iy * W + ix that attains it, hq_a = that stamp's hq, n_cells = the cells under C(n) with valid stamps of s.  Then
+ *     met[n] |= P(n).  With g = group[e] in 0..G-1: hist[g][type][pet - 1] += 1, type from d = min(rel, 256 - rel), rel = (hq_b - hq_a) &
+ *     255: 0 following d <= 21, 2 opposing d >= 107, else 1 crossing; critical[g][cell] += 1 when pet <= critical_records.  A dropped row
+ *     counts in both all the same.
+ *   4 STAMP, after every read of the record: every ALIVE slot n writes max(old, stamp) into each cell of C(n), a 64-bit atomic max.
+ * Row, COPO_PET_WORDS 32-bit words: {scene, slot_b | slot_a << 6, aid_b, aid_a, episode, r, pet, cell, n_cells, speed_a bits, x_b, y_b,
+ * heading_b, speed_b bits, hq_a, hq_b}: b = n entered, a = s had left; poses and speeds of record r.
+ * Order.  The rows of one record take the ids n_rows, n_rows + 1, ... in ascending (scene, slot_b, slot_a) order; an id >= max_rows is not
+ * stored and counts as dropped.  No atomic decides an id. ---- */
+#define COPO_PET_WORDS 16
+#define COPO_PET_MAX_WINDOW 4096
+#define COPO_PET_TYPES 3
+typedef struct copo_pet_cfg {
+    float x0, y0;              /* m, finite (COPO_ERR_CONFIG) */
+    float cell;                /* m, > 0 and finite (COPO_ERR_DIM), 1 / cell finite and cell <= 2 hw / sqrt(2) (COPO_ERR_CONFIG) */
+    int32_t W, H;              /* cells, 1..COPO_FIELD_MAX_SIDE each (COPO_ERR_DIM) */
+    int32_t G;                 /* scene groups, 1..COPO_FIELD_MAX_GROUPS (COPO_ERR_DIM) */
+    int32_t window;            /* records a stamp stays valid for = bins of the histogram, 1..COPO_PET_MAX_WINDOW (COPO_ERR_DIM) */
+    int32_t critical_records;  /* >= 0 (COPO_ERR_DIM): encounters with pet <= this count in the critical map */
+    int32_t max_rows;          /* pool size, >= 1 (COPO_ERR_DIM) */
+} copo_pet_cfg;
+typedef struct copo_pet copo_pet;
+/* allocates 8 E H W bytes of grid, 20 E N + 16 E bytes of memory, the aggregates (8 G (3 window + H W)) and the pool (64 max_rows):
+ * COPO_ERR_DEVICE when the device refuses.  Every scene is in group 0 */
+int copo_pet_create(copo_sim* sim, const copo_pet_cfg* cfg, copo_pet** out);
+/* group_dev: device int32 [E]; scene e adds to the aggregates of group_dev[e], a value outside 0..G-1 to none (its rows are written) */
+int copo_pet_set_groups(copo_pet* h, const int32_t* group_dev, void* stream);
+/* one record of the current state.  Four launches on `stream`, no allocation, no host synchronisation; simulator memory is only read */
+int copo_pet_record(copo_pet* h, void* stream);
+/* epoch = the next record's number in every scene and every `met` mask cleared: no stamp written so far is valid any more (after a
+ * reset or set_state by hand) */
+int copo_pet_forget(copo_pet* h, void* stream);
+/* HOST output: out[0] = rows stored so far (<= max_rows), out[1] = rows dropped; the one call that waits for `stream` */
+int copo_pet_count(copo_pet* h, int64_t* out, void* stream);
+/* rows [first, first + n) of the pool, device to device: rows_out [n][COPO_PET_WORDS] int32; first + n <= max_rows (COPO_ERR_DIM) */
+int copo_pet_read(copo_pet* h, int32_t first, int32_t n, int32_t* rows_out, void* stream);
+/* copies of hist int64 [G][COPO_PET_TYPES][window] and critical int64 [G][H][W], device to device; either may be NULL, not both */
+int copo_pet_aggregates(copo_pet* h, int64_t* hist_dev, int64_t* critical_dev, void* stream);
+/* copies of the stamps uint64 [E][H][W] and the met masks uint64 [E][N], device to device; either may be NULL, not both */
+int copo_pet_memory(copo_pet* h, uint64_t* grid_dev, uint64_t* met_dev, void* stream);
+/* n_rows = dropped = 0; stamps, masks, aggregates and the record count stay */
+int copo_pet_clear(copo_pet* h, void* stream);
+/* forget everything but the groups: rows, counters, stamps, masks, aggregates; records count from 0 again */
+int copo_pet_reset(copo_pet* h, void* stream);
+int copo_pet_destroy(copo_pet* h);
+
 /* ---- stateless ops ---- */
 
 /* CCEnv._update_distance_map + _find_in_range (env_wrappers.py:125-158) + LCFEnv reward block (:313-326).

@@ -1,4 +1,4 @@
-"""What the observer benchmarks (`bench_interact`, `bench_clips`, `bench_rewind`, `bench_fields`, `bench_gates`, `bench_trips`, `bench_conflicts`) share:
+"""What the observer benchmarks (`bench_interact`, `bench_clips`, `bench_rewind`, `bench_fields`, `bench_gates`, `bench_trips`, `bench_conflicts`, `bench_pet`) share:
 the timing loop, the command line, the scene they measure on and the JSON line they end with."""
 import argparse
 import json
