@@ -3,11 +3,11 @@ import ctypes as C
 
 
 class Handle:
-    """`_h` is the library's handle, made by `_create` and given to the library's function `_destroy` by `close()`; `device` and
+    """`_h` is the library's handle, made by `_create` and given to the library's `<_prefix>destroy` by `close()`; `device` and
     `_torch` name where its calls run.  An observer calls `_attach(sim)` first.  `close()` is idempotent, and an observer's may come
     after its simulator's; every other call on an observer whose simulator is closed is undefined."""
 
-    _destroy = None                # name of the library's destroy function
+    _prefix = None                 # "copo_<handle>_": the library's entry points for this handle are `<_prefix>record` ...
 
     def _attach(self, sim):
         from . import _capi
@@ -21,6 +21,10 @@ class Handle:
     def _stream(self):
         return self._torch.cuda.current_stream(self.device).cuda_stream
 
+    def _call(self, name, *args):
+        """`<_prefix><name>(handle, *args, torch's current stream)`, checked.  Not for `record()`: a call per step spells itself out."""
+        self._capi.check(getattr(self._capi.lib, self._prefix + name)(self._h, *args, self._stream()))
+
     def _en_arg(self, t, dtype, name):
         if t is None:
             return None
@@ -28,20 +32,9 @@ class Handle:
             raise ValueError("%s must be a contiguous %s cuda tensor [E, N]" % (name, dtype))
         return t.data_ptr()
 
-    def _groups(self, group):
-        """int32 [E] on the simulator's device, of a torch tensor or anything numpy reads"""
-        import numpy as np
-        torch = self._torch
-        if not hasattr(group, "is_cuda"):
-            group = torch.from_numpy(np.ascontiguousarray(np.asarray(group, np.int32).reshape(-1)))
-        group = group.to(device=self.device, dtype=torch.int32).contiguous()
-        if group.numel() != self.sim.E:
-            raise ValueError("one group per scene: %d values for %d scenes" % (group.numel(), self.sim.E))
-        return group
-
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
-            getattr(self._capi.lib, self._destroy)(self._h)
+            getattr(self._capi.lib, self._prefix + "destroy")(self._h)
             self._h = C.c_void_p()
 
     def __del__(self):
@@ -49,3 +42,18 @@ class Handle:
             self.close()
         except Exception:
             pass
+
+
+class Grouped:
+    """Mixin of an observer with scene groups: scene e adds to group[e], a value outside 0..groups-1 to nothing; all 0 at first."""
+
+    def set_groups(self, group):
+        """Scene groups: int32 [E] (torch tensor on the simulator's device, or anything numpy reads)."""
+        import numpy as np
+        torch = self._torch
+        if not hasattr(group, "is_cuda"):
+            group = torch.from_numpy(np.ascontiguousarray(np.asarray(group, np.int32).reshape(-1)))
+        group = group.to(device=self.device, dtype=torch.int32).contiguous()
+        if group.numel() != self.sim.E:
+            raise ValueError("one group per scene: %d values for %d scenes" % (group.numel(), self.sim.E))
+        self._call("set_groups", group.data_ptr())

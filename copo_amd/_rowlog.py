@@ -1,10 +1,10 @@
 """What the trip log, the conflict log and the encroachment log share on the host (`trips.py`, `conflicts.py`, `encroach.py`; the device side is `csrc/rowlog_common.h`): a
 table of raw 16-word rows with its `.npz` file, and the handle calls over a bounded pool of such rows.  DESIGN.md section 8g."""
 import ctypes as C
-import json
 
 import numpy as np
 
+from . import _npz
 from ._handle import Handle
 
 WORDS = 16
@@ -33,21 +33,16 @@ class RowTable:
 
     def save(self, path):
         """One `.npz` without pickled objects (`np.load(path, allow_pickle=False)` reads it): the raw rows and `meta` as JSON."""
-        np.savez_compressed(path, rows=self.raw, meta=np.array(json.dumps(self.meta, sort_keys=True)))
-        return path
+        return _npz.save(path, self.meta, rows=self.raw)
 
     @classmethod
     def load(cls, path):
-        with np.load(path, allow_pickle=False) as f:
-            return cls(f["rows"], json.loads(str(f["meta"][()])))
+        return cls(*_npz.load(path, "rows"))
 
 
 class RowLog(Handle):
     """A handle whose `record()` commits rows into a pool of `max_rows` (later ones are counted as dropped).  The subclass supplies
-    `_prefix` (its entry points are `<_prefix>flush` ...), `_table_cls`, `_meta(dropped)` and `record`, and counts `n_records`."""
-
-    def _call(self, name, *args):
-        self._capi.check(getattr(self._capi.lib, self._prefix + name)(self._h, *args, self._stream()))
+    `_prefix`, `_table_cls`, `_meta(dropped)` and `record`, and counts `n_records`."""
 
     def flush(self):
         """Close everything that is open as it stands (the last kind, outcome "open"); what goes on opens anew in the next record."""

@@ -10,11 +10,11 @@ restates them.
 """
 import ctypes as C
 import dataclasses
-import json
 
 import numpy as np
 
 from ._abi import CLIP_HEADER as HEADER, CLIP_MAX_CAP as MAX_CAP, CLIP_WORDS as WORDS
+from . import _npz
 from ._handle import Handle
 
 HEADER_KEYS = ("scene", "first_rec", "length", "trig_rec", "trig_slot", "kind", "trig_aid", "n_events")
@@ -91,13 +91,11 @@ class ClipSet:
 
     def save(self, path):
         """One `.npz` without pickled objects (`np.load(path, allow_pickle=False)` reads it)."""
-        np.savez_compressed(path, header=self.header, snaps=self.snaps, envw=self.envw, meta=np.array(json.dumps(self.meta, sort_keys=True)))
-        return path
+        return _npz.save(path, self.meta, header=self.header, snaps=self.snaps, envw=self.envw)
 
     @classmethod
     def load(cls, path):
-        with np.load(path, allow_pickle=False) as f:
-            return cls(f["header"], f["snaps"], f["envw"], json.loads(str(f["meta"][()])))
+        return cls(*_npz.load(path, "header", "snaps", "envw"))
 
     def sim_config(self, num_envs=1):
         """`SimConfig` of the recorded map with `num_envs` scenes."""
@@ -120,7 +118,7 @@ class ClipRecorder(Handle):
     (before or after its simulator; no other call once the simulator is closed); every call is asynchronous on torch's current stream
     except `count()` / `clips()`."""
 
-    _destroy = "copo_clip_destroy"
+    _prefix = "copo_clip_"
 
     def __init__(self, sim, pre=24, post=8, max_clips=256, flags=("crash",), ttc_below=0.0, gap_below=0.0):
         self._attach(sim)
@@ -152,12 +150,12 @@ class ClipRecorder(Handle):
 
     def flush(self):
         """Commit the clips of the scenes that are still waiting for their `post` records, with what they have."""
-        self._capi.check(self._capi.lib.copo_clip_flush(self._h, self._stream()))
+        self._call("flush")
 
     def count(self):
         """(clips stored, clips dropped); waits for the stream."""
         n, d = C.c_int32(), C.c_int32()
-        self._capi.check(self._capi.lib.copo_clip_count(self._h, C.byref(n), C.byref(d), self._stream()))
+        self._call("count", C.byref(n), C.byref(d))
         return n.value, d.value
 
     def clips(self):
@@ -169,13 +167,13 @@ class ClipRecorder(Handle):
         snaps = torch.empty(n, self.cap, WORDS, N, dtype=torch.int32, device=dev)
         envw = torch.empty(n, self.cap, 2, dtype=torch.int32, device=dev)
         if n:
-            self._capi.check(self._capi.lib.copo_clip_read(self._h, 0, n, header.data_ptr(), snaps.data_ptr(), envw.data_ptr(), self._stream()))
+            self._call("read", 0, n, header.data_ptr(), snaps.data_ptr(), envw.data_ptr())
         return ClipSet(header.cpu().numpy(), snaps.cpu().numpy().view(np.uint32), envw.cpu().numpy(),
                        clip_meta(self.sim.cfg, N, self.pre, self.post))
 
     def reset(self):
         """Forget every clip, counter and waiting scene; records count from 0 again."""
-        self._capi.check(self._capi.lib.copo_clip_reset(self._h, self._stream()))
+        self._call("reset")
 
 
 class ClipPlayer:

@@ -180,7 +180,7 @@ class ConflictLog(RowLog):
     the simulator is closed); every call is asynchronous on torch's current stream except `count()` and what reads rows to the host
     (`table()`, `drain()`)."""
 
-    _destroy, _prefix, _table_cls = "copo_conflict_destroy", "copo_conflict_", ConflictTable
+    _prefix, _table_cls = "copo_conflict_", ConflictTable
 
     def __init__(self, sim, max_rows=65536, radius=8.0, leave_radius=10.0):
         self._attach(sim)

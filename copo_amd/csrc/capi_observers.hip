@@ -423,15 +423,38 @@ extern "C" int copo_rewind_tally(const uint8_t* flags, const int32_t* watch_slot
     return COPO_OK;
 }
 
+// ---- scene grid and scene groups of the field maps, the traffic gates and the encroachment log (grid_common.h) --------------------------
+// The checks of a grid that are the same for every handle over one, and its GridSpec.  `who`: the entry point, for the error string.
+static int make_grid(float x0, float y0, float cell, int32_t W, int32_t H, const char* who, GridSpec* out) {
+    if (W < 1 || W > GRID_MAX_SIDE || H < 1 || H > GRID_MAX_SIDE || !(cell > 0.0f) || !std::isfinite(cell))
+        return fail(COPO_ERR_DIM, "%s: W=%d H=%d (1..%d) cell=%g (> 0, finite)", who, W, H, GRID_MAX_SIDE, (double)cell);
+    const float inv_cell = (float)(1.0 / (double)cell);
+    if (!std::isfinite(x0) || !std::isfinite(y0) || !std::isfinite(inv_cell))
+        return fail(COPO_ERR_CONFIG, "%s: x0=%g y0=%g 1/cell=%g (finite)", who, (double)x0, (double)y0, (double)inv_cell);
+    *out = GridSpec{x0, y0, cell, inv_cell, W, H};
+    return COPO_OK;
+}
+
+// Host side of the routing of scenes into scene groups: all scenes in group 0 at first
+struct GroupTable {
+    DevBuf<int32_t> group;                 // [E]
+    SceneGroups args(int32_t G) const { return SceneGroups{group, G}; }
+    template <typename H> static int set(H* h, const int32_t* group_dev, void* stream, const char* who) {      // (h owns a `groups`)
+        if (!h || !group_dev) return fail(COPO_ERR_NULL, "%s: NULL argument", who);
+        HIP_TRY(h->groups.group.copy_from(group_dev, static_cast<hipStream_t>(stream)));
+        return COPO_OK;
+    }
+};
+
 // ---- traffic field maps (field_kernels.hip) --------------------------------------------------------------------
 
 struct copo_field {
     copo_sim* sim;
     DevPool mem;
     copo_field_cfg cfg;
-    float inv_cell;
+    GridSpec grid;
     int32_t block, n_blocks;           // scenes per workgroup of the tile pass, and how many such blocks
-    DevBuf<int32_t> group;             // [E]
+    GroupTable groups;
     DevBuf<int32_t> last;              // [E][N]
     DevBuf<uint32_t> mask;             // [n_blocks][FIELD_MASK_WORDS]
     DevBuf<long long> maps;            // [G][FIELD_LAYERS][H][W]
@@ -442,9 +465,8 @@ static FieldArgs field_args(const copo_field* h, const uint8_t* flags, const flo
     const SimParams& p = h->sim->p;
     FieldArgs a;
     a.state = p.state; a.E = p.E; a.N = p.N; a.hl = p.hl; a.hw = p.hw;
-    a.x0 = h->cfg.x0; a.y0 = h->cfg.y0; a.cell = h->cfg.cell; a.inv_cell = h->inv_cell;
-    a.W = h->cfg.W; a.H = h->cfg.H; a.G = h->cfg.G; a.block = h->block; a.ttc_below = h->cfg.ttc_below;
-    a.group = h->group; a.flags = flags; a.ttc = ttc; a.last = h->last; a.mask = h->mask; a.maps = h->maps; a.scene_records = h->scene_records;
+    a.grid = h->grid; a.block = h->block; a.ttc_below = h->cfg.ttc_below;
+    a.groups = h->groups.args(h->cfg.G); a.flags = flags; a.ttc = ttc; a.last = h->last; a.mask = h->mask; a.maps = h->maps; a.scene_records = h->scene_records;
     return a;
 }
 
@@ -453,15 +475,11 @@ extern "C" int copo_field_create(copo_sim* sim, const copo_field_cfg* cfg, copo_
     *out = nullptr;
     static_assert(COPO_FIELD_LAYERS == FIELD_LAYERS && COPO_FIELD_MAX_SIDE == FIELD_MAX_SIDE && COPO_FIELD_MAX_GROUPS == FIELD_MAX_GROUPS,
                   "copo_hip.h / field_common.h");
-    if (cfg->W < 1 || cfg->W > FIELD_MAX_SIDE || cfg->H < 1 || cfg->H > FIELD_MAX_SIDE || cfg->G < 1 || cfg->G > FIELD_MAX_GROUPS ||
-        !(cfg->cell > 0.0f) || !std::isfinite(cfg->cell))
-        return fail(COPO_ERR_DIM, "copo_field_create: W=%d H=%d (1..%d) G=%d (1..%d) cell=%g (> 0, finite)", cfg->W, cfg->H, FIELD_MAX_SIDE,
-                    cfg->G, FIELD_MAX_GROUPS, (double)cfg->cell);
-    const float inv_cell = (float)(1.0 / (double)cfg->cell);
-    if (!std::isfinite(cfg->x0) || !std::isfinite(cfg->y0) || !(cfg->ttc_below >= 0.0f) || !std::isfinite(cfg->ttc_below) ||
-        !std::isfinite(inv_cell))
-        return fail(COPO_ERR_CONFIG, "copo_field_create: x0=%g y0=%g 1/cell=%g (finite), ttc_below=%g (>= 0, finite)", (double)cfg->x0,
-                    (double)cfg->y0, (double)inv_cell, (double)cfg->ttc_below);
+    if (cfg->G < 1 || cfg->G > FIELD_MAX_GROUPS) return fail(COPO_ERR_DIM, "copo_field_create: G=%d (1..%d)", cfg->G, FIELD_MAX_GROUPS);
+    GridSpec grid;
+    if (int rc = make_grid(cfg->x0, cfg->y0, cfg->cell, cfg->W, cfg->H, "copo_field_create", &grid)) return rc;
+    if (!(cfg->ttc_below >= 0.0f) || !std::isfinite(cfg->ttc_below))
+        return fail(COPO_ERR_CONFIG, "copo_field_create: ttc_below=%g (>= 0, finite)", (double)cfg->ttc_below);
     const size_t E = (size_t)sim->p.E, N = (size_t)sim->p.N;
     // scenes per workgroup of the tile pass: 4 (one per wave) while the scenes are few, up to 64 -- every workgroup ends with one
     // pass over its tile, which more scenes share
@@ -471,8 +489,8 @@ extern "C" int copo_field_create(copo_sim* sim, const copo_field_cfg* cfg, copo_
     HIP_TRY(hipSetDevice(sim->device));
     copo_field* h = new (std::nothrow) copo_field();
     if (!h) return fail(COPO_ERR_DEVICE, "out of host memory");
-    h->sim = sim; h->mem.device = sim->device; h->cfg = *cfg; h->inv_cell = inv_cell; h->block = block; h->n_blocks = (int32_t)n_blocks;
-    h->group = h->mem.alloc<int32_t>(E);
+    h->sim = sim; h->mem.device = sim->device; h->cfg = *cfg; h->grid = grid; h->block = block; h->n_blocks = (int32_t)n_blocks;
+    h->groups.group = h->mem.alloc<int32_t>(E);
     h->last = h->mem.alloc<int32_t>(E * N, 0xff);
     h->mask = h->mem.alloc<uint32_t>(n_blocks * FIELD_MASK_WORDS);
     h->maps = h->mem.alloc<long long>((size_t)cfg->G * FIELD_LAYERS * cfg->H * cfg->W);
@@ -482,11 +500,7 @@ extern "C" int copo_field_create(copo_sim* sim, const copo_field_cfg* cfg, copo_
 
 extern "C" int copo_field_destroy(copo_field* h) { return destroy_handle(h, "copo_field_destroy"); }
 
-extern "C" int copo_field_set_groups(copo_field* h, const int32_t* group_dev, void* stream) {
-    if (!h || !group_dev) return fail(COPO_ERR_NULL, "copo_field_set_groups: NULL argument");
-    HIP_TRY(h->group.copy_from(group_dev, static_cast<hipStream_t>(stream)));
-    return COPO_OK;
-}
+extern "C" int copo_field_set_groups(copo_field* h, const int32_t* group_dev, void* stream) { return GroupTable::set(h, group_dev, stream, "copo_field_set_groups"); }
 
 extern "C" int copo_field_record(copo_field* h, const uint8_t* flags, const float* ttc, int32_t accumulate, void* stream) {
     if (!h) return fail(COPO_ERR_NULL, "copo_field_record: NULL handle");
@@ -532,7 +546,7 @@ struct copo_gate {
     int32_t n_records;                     // records since create / reset (host side: eager only)
     DevBuf<float4> gates;                  // [L]
     DevBuf<int2> sections;                 // [S]
-    DevBuf<int32_t> group;                 // [E]
+    GroupTable groups;
     DevBuf<uint32_t> mem_x, mem_y;         // [E][N]
     DevBuf<int32_t> mem_aid;               // [E][N]
     DevBuf<int32_t> mem_episode;           // [E]
@@ -578,7 +592,7 @@ extern "C" int copo_gate_create(copo_sim* sim, const copo_gate_cfg* cfg, const f
     h->at = gate_layout(cfg->G, cfg->L, cfg->S, cfg->T, cfg->HB, cfg->TB);
     h->gates = h->mem.upload(reinterpret_cast<const float4*>(gates), L);
     h->sections = h->mem.upload(reinterpret_cast<const int2*>(sections), S);
-    h->group = h->mem.alloc<int32_t>(E);
+    h->groups.group = h->mem.alloc<int32_t>(E);
     h->mem_x = h->mem.alloc<uint32_t>(E * N);
     h->mem_y = h->mem.alloc<uint32_t>(E * N);
     h->mem_aid = h->mem.alloc<int32_t>(E * N);
@@ -592,11 +606,7 @@ extern "C" int copo_gate_create(copo_sim* sim, const copo_gate_cfg* cfg, const f
 
 extern "C" int copo_gate_destroy(copo_gate* h) { return destroy_handle(h, "copo_gate_destroy"); }
 
-extern "C" int copo_gate_set_groups(copo_gate* h, const int32_t* group_dev, void* stream) {
-    if (!h || !group_dev) return fail(COPO_ERR_NULL, "copo_gate_set_groups: NULL argument");
-    HIP_TRY(h->group.copy_from(group_dev, static_cast<hipStream_t>(stream)));
-    return COPO_OK;
-}
+extern "C" int copo_gate_set_groups(copo_gate* h, const int32_t* group_dev, void* stream) { return GroupTable::set(h, group_dev, stream, "copo_gate_set_groups"); }
 
 extern "C" int copo_gate_record(copo_gate* h, void* stream) {
     if (!h) return fail(COPO_ERR_NULL, "copo_gate_record: NULL handle");
@@ -606,7 +616,7 @@ extern "C" int copo_gate_record(copo_gate* h, void* stream) {
     a.state = p.state; a.env = p.env; a.E = p.E; a.N = p.N;
     a.L = h->cfg.L; a.S = h->cfg.S; a.G = h->cfg.G; a.T = h->cfg.T; a.HB = h->cfg.HB; a.TB = h->cfg.TB; a.tt_bin = h->cfg.tt_bin;
     a.r = h->n_records; a.tbin = std::min(h->n_records / h->cfg.bin_records, h->cfg.T - 1);
-    a.gates = h->gates; a.sections = h->sections; a.group = h->group;
+    a.gates = h->gates; a.sections = h->sections; a.group = h->groups.group;
     a.mem_x = h->mem_x; a.mem_y = h->mem_y; a.mem_aid = h->mem_aid; a.mem_episode = h->mem_episode; a.mem_valid = h->mem_valid;
     a.last_fwd = h->last_fwd; a.entry = h->entry; a.acc = h->acc; a.at = h->at;
     HIP_TRY(launch_gate_record(a, static_cast<hipStream_t>(stream)));
@@ -881,10 +891,10 @@ struct copo_pet {
     copo_sim* sim;
     DevPool mem;
     copo_pet_cfg cfg;
-    float inv_cell;
+    GridSpec grid;
     RowPool rows;
-    DevBuf<int32_t> group;                 // [E]
-    DevBuf<unsigned long long> grid;       // [E][H][W]
+    GroupTable groups;
+    DevBuf<unsigned long long> stamps;     // [E][H][W]
     DevBuf<int32_t> aid;                   // [E][N]
     DevBuf<unsigned long long> met;        // [E][N]
     DevBuf<int32_t> episode, epoch;        // [E]
@@ -899,13 +909,11 @@ extern "C" int copo_pet_create(copo_sim* sim, const copo_pet_cfg* cfg, copo_pet*
     *out = nullptr;
     static_assert(COPO_PET_WORDS == ROWLOG_WORDS && COPO_PET_MAX_WINDOW == PET_MAX_WINDOW && COPO_PET_TYPES == PET_TYPES, "copo_hip.h / encroach_common.h");
     if (int rc = RowPool::check(cfg->max_rows, "copo_pet_create")) return rc;
-    if (cfg->W < 1 || cfg->W > FIELD_MAX_SIDE || cfg->H < 1 || cfg->H > FIELD_MAX_SIDE || cfg->G < 1 || cfg->G > FIELD_MAX_GROUPS ||
-        cfg->window < 1 || cfg->window > PET_MAX_WINDOW || cfg->critical_records < 0 || !(cfg->cell > 0.0f) || !std::isfinite(cfg->cell))
-        return fail(COPO_ERR_DIM, "copo_pet_create: W=%d H=%d (1..%d) G=%d (1..%d) window=%d (1..%d) critical_records=%d (>= 0) cell=%g (> 0, finite)", cfg->W,
-                    cfg->H, FIELD_MAX_SIDE, cfg->G, FIELD_MAX_GROUPS, cfg->window, PET_MAX_WINDOW, cfg->critical_records, (double)cfg->cell);
-    const float inv_cell = (float)(1.0 / (double)cfg->cell);
-    if (!std::isfinite(cfg->x0) || !std::isfinite(cfg->y0) || !std::isfinite(inv_cell))
-        return fail(COPO_ERR_CONFIG, "copo_pet_create: x0=%g y0=%g 1/cell=%g (finite)", (double)cfg->x0, (double)cfg->y0, (double)inv_cell);
+    if (cfg->G < 1 || cfg->G > GRID_MAX_GROUPS || cfg->window < 1 || cfg->window > PET_MAX_WINDOW || cfg->critical_records < 0)
+        return fail(COPO_ERR_DIM, "copo_pet_create: G=%d (1..%d) window=%d (1..%d) critical_records=%d (>= 0)", cfg->G, GRID_MAX_GROUPS, cfg->window,
+                    PET_MAX_WINDOW, cfg->critical_records);
+    GridSpec grid;
+    if (int rc = make_grid(cfg->x0, cfg->y0, cfg->cell, cfg->W, cfg->H, "copo_pet_create", &grid)) return rc;
     // a wider cell lets a body pass between cell centres
     const double widest = 2.0 * (double)sim->p.hw / std::sqrt(2.0);
     if (!((double)cfg->cell <= widest))
@@ -915,9 +923,9 @@ extern "C" int copo_pet_create(copo_sim* sim, const copo_pet_cfg* cfg, copo_pet*
     HIP_TRY(hipSetDevice(sim->device));
     copo_pet* h = new (std::nothrow) copo_pet();
     if (!h) return fail(COPO_ERR_DEVICE, "out of host memory");
-    h->sim = sim; h->mem.device = sim->device; h->cfg = *cfg; h->inv_cell = inv_cell;
-    h->group = h->mem.alloc<int32_t>(E);
-    h->grid = h->mem.alloc<unsigned long long>(E * HW);
+    h->sim = sim; h->mem.device = sim->device; h->cfg = *cfg; h->grid = grid;
+    h->groups.group = h->mem.alloc<int32_t>(E);
+    h->stamps = h->mem.alloc<unsigned long long>(E * HW);
     h->aid = h->mem.alloc<int32_t>(E * N);
     h->met = h->mem.alloc<unsigned long long>(E * N);
     h->episode = h->mem.alloc<int32_t>(E);
@@ -932,11 +940,7 @@ extern "C" int copo_pet_create(copo_sim* sim, const copo_pet_cfg* cfg, copo_pet*
 
 extern "C" int copo_pet_destroy(copo_pet* h) { return destroy_handle(h, "copo_pet_destroy"); }
 
-extern "C" int copo_pet_set_groups(copo_pet* h, const int32_t* group_dev, void* stream) {
-    if (!h || !group_dev) return fail(COPO_ERR_NULL, "copo_pet_set_groups: NULL argument");
-    HIP_TRY(h->group.copy_from(group_dev, static_cast<hipStream_t>(stream)));
-    return COPO_OK;
-}
+extern "C" int copo_pet_set_groups(copo_pet* h, const int32_t* group_dev, void* stream) { return GroupTable::set(h, group_dev, stream, "copo_pet_set_groups"); }
 
 extern "C" int copo_pet_record(copo_pet* h, void* stream) {
     if (!h) return null_handle("copo_pet_record");
@@ -944,9 +948,8 @@ extern "C" int copo_pet_record(copo_pet* h, void* stream) {
     const SimParams& p = h->sim->p;
     PetArgs a;
     a.state = p.state; a.env = p.env; a.E = p.E; a.N = p.N; a.r = h->rows.n_records; a.hl = p.hl; a.hw = p.hw;
-    a.x0 = h->cfg.x0; a.y0 = h->cfg.y0; a.cell = h->cfg.cell; a.inv_cell = h->inv_cell;
-    a.W = h->cfg.W; a.H = h->cfg.H; a.G = h->cfg.G; a.window = h->cfg.window; a.critical_records = h->cfg.critical_records;
-    a.group = h->group; a.grid = h->grid; a.aid = h->aid; a.met = h->met; a.episode = h->episode; a.epoch = h->epoch;
+    a.grid = h->grid; a.window = h->cfg.window; a.critical_records = h->cfg.critical_records;
+    a.groups = h->groups.args(h->cfg.G); a.stamps = h->stamps; a.aid = h->aid; a.met = h->met; a.episode = h->episode; a.epoch = h->epoch;
     a.hist = h->hist; a.critical = h->critical; a.fresh = h->fresh; a.n_fresh = h->n_fresh; a.rows = h->rows.args();
     HIP_TRY(launch_pet_record(a, static_cast<hipStream_t>(stream)));
     h->rows.n_records += 1;
@@ -980,7 +983,7 @@ extern "C" int copo_pet_aggregates(copo_pet* h, int64_t* hist_dev, int64_t* crit
 extern "C" int copo_pet_memory(copo_pet* h, uint64_t* grid_dev, uint64_t* met_dev, void* stream) {
     if (!h || (!grid_dev && !met_dev)) return fail(COPO_ERR_NULL, "copo_pet_memory: NULL argument");
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (grid_dev) HIP_TRY(h->grid.copy_to(grid_dev, st));
+    if (grid_dev) HIP_TRY(h->stamps.copy_to(grid_dev, st));
     if (met_dev) HIP_TRY(h->met.copy_to(met_dev, st));
     return COPO_OK;
 }
@@ -990,7 +993,7 @@ extern "C" int copo_pet_clear(copo_pet* h, void* stream) { return h ? h->rows.cl
 extern "C" int copo_pet_reset(copo_pet* h, void* stream) {
     if (!h) return null_handle("copo_pet_reset");
     hipStream_t st = static_cast<hipStream_t>(stream);
-    HIP_TRY(h->grid.fill(0, st));
+    HIP_TRY(h->stamps.fill(0, st));
     HIP_TRY(h->aid.fill(0, st));
     HIP_TRY(h->met.fill(0, st));
     HIP_TRY(h->episode.fill(0, st));

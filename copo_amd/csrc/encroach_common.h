@@ -1,5 +1,6 @@
 // Shared declarations of the encroachment log (encroach_kernels.hip) and its C entry points (capi_observers.hip).
 #pragma once
+#include "grid_common.h"
 #include "rowlog_common.h"
 
 namespace copo {
@@ -15,11 +16,10 @@ struct PetArgs {
     int32_t E, N;
     int32_t r;                     // this record's number
     float hl, hw;
-    float x0, y0, cell, inv_cell;  // inv_cell = 1 / cell, rounded once to fp32 on the host
-    int32_t W, H, G;
+    GridSpec grid;
     int32_t window, critical_records;
-    const int32_t* group;          // [E]
-    unsigned long long* grid;      // [E][H][W] stamps: rec + 1 << 32 | (aid & 0xffff) << 16 | hq << 8 | slot, 0 = empty
+    SceneGroups groups;
+    unsigned long long* stamps;     // [E][H][W] stamps: rec + 1 << 32 | (aid & 0xffff) << 16 | hq << 8 | slot, 0 = empty
     int32_t* aid;                  // [E][N] the agent id of the previous record
     unsigned long long* met;       // [E][N] slot b: bit a: the encounter of b with the agent in slot a has its row
     int32_t* episode;              // [E] the episode word of the previous record

@@ -15,11 +15,10 @@
 //            integer atomic adds: the sums do not depend on the order)
 //   stamp:   every ALIVE slot writes max(old, its stamp of this record) into the cells of its footprint, a 64-bit atomic max: a later
 //            record always wins, and two bodies over one cell centre in one record resolve by the word's value, not by timing
-// Reads and writes of the grid are in different launches, so no read of a record sees a stamp of that record.  The footprint is the field
-// maps' rule (field_kernels.hip) operation for operation; everything else is integer logic and one fp32 product (the heading's
+// Reads and writes of the grid are in different launches, so no read of a record sees a stamp of that record.  The footprint is `covers`
+// of grid_common.h, the one the field maps count with; everything else is integer logic and one fp32 product (the heading's
 // quantisation), so the numpy restatement (tests/pet_numpy.py) gives the same bits.  The rules are DESIGN.md section 8i.
 #include "sim_device.h"
-#include "field_common.h"
 #include "encroach_common.h"
 
 namespace copo {
@@ -39,13 +38,8 @@ struct Body {
 __device__ __forceinline__ Body body_of(const PetArgs& a, size_t o, size_t EN) {
     Body b;
     b.x = a.state[o]; b.y = (a.state + EN)[o]; b.cs = 1.0f; b.sn = 0.0f;
-    b.lox = b.loy = 0; b.hix = b.hiy = -1;
-    const float r = reach_radius(a.hl, a.hw, a.inv_cell);
-    int lox, hix, loy, hiy;
-    if (reach((b.x - a.x0) * a.inv_cell, r, a.W, lox, hix) && reach((b.y - a.y0) * a.inv_cell, r, a.H, loy, hiy)) {
-        b.lox = lox; b.hix = hix; b.loy = loy; b.hiy = hiy;
-        sincos_det((a.state + 2 * EN)[o], b.sn, b.cs);
-    }
+    if (a.grid.reach_box(b.x, b.y, a.hl, a.hw, b.lox, b.hix, b.loy, b.hiy)) sincos_det((a.state + 2 * EN)[o], b.sn, b.cs);
+    else { b.lox = b.loy = 0; b.hix = b.hiy = -1; }
     return b;
 }
 
@@ -53,12 +47,9 @@ __device__ __forceinline__ Body body_of(const PetArgs& a, size_t o, size_t EN) {
 template <typename F>
 __device__ __forceinline__ void for_cells(const PetArgs& a, const Body& b, F f) {
     for (int iy = b.loy; iy <= b.hiy; ++iy) {
-        const float dy = (a.y0 + ((float)iy + 0.5f) * a.cell) - b.y;
-        for (int ix = b.lox; ix <= b.hix; ++ix) {
-            const float dx = (a.x0 + ((float)ix + 0.5f) * a.cell) - b.x;
-            const float u = fm(dx, b.cs, dy * b.sn), w = fm(dy, b.cs, -(dx * b.sn));
-            if (fabsf(u) <= a.hl && fabsf(w) <= a.hw) f(iy * a.W + ix);
-        }
+        const float dy = a.grid.centre_y(iy) - b.y;
+        for (int ix = b.lox; ix <= b.hix; ++ix)
+            if (covers(a.grid.centre_x(ix) - b.x, dy, b.cs, b.sn, a.hl, a.hw)) f(iy * a.grid.W + ix);
     }
 }
 
@@ -89,7 +80,7 @@ __global__ __launch_bounds__(TB) void pet_scan_kernel(PetArgs a) {
     __shared__ uint32_t sw[NW][64];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int N = a.N;
-    const size_t EN = (size_t)a.E * N, HW = (size_t)a.H * a.W;
+    const size_t EN = (size_t)a.E * N, HW = (size_t)a.grid.H * a.grid.W;
     for (int e0 = blockIdx.x * NW; e0 < a.E; e0 += gridDim.x * NW) {           // (the whole workgroup: the barriers below)
         const int e = e0 + wave;
         const bool in = e < a.E && lane < N;
@@ -116,7 +107,7 @@ __global__ __launch_bounds__(TB) void pet_scan_kernel(PetArgs a) {
         u64 P = 0ull;
         if (alive) {
             const Body b = body_of(a, o, EN);
-            const u64* G = a.grid + (size_t)e * HW;
+            const u64* G = a.stamps + (size_t)e * HW;
             for_cells(a, b, [&](int c) {
                 const u64 s = G[c];
                 if (valid_pet(a, s, lane, epoch, sw[wave])) P |= 1ull << ((uint32_t)s & 63u);
@@ -153,7 +144,7 @@ __global__ __launch_bounds__(TB) void pet_commit_kernel(PetArgs a) {
     __shared__ int32_t said[NW][64];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int N = a.N;
-    const size_t EN = (size_t)a.E * N, HW = (size_t)a.H * a.W;
+    const size_t EN = (size_t)a.E * N, HW = (size_t)a.grid.H * a.grid.W;
     const uint32_t* su = reinterpret_cast<const uint32_t*>(a.state);
     for (int e0 = blockIdx.x * NW; e0 < a.E; e0 += gridDim.x * NW) {           // (the whole workgroup: the barriers below)
         const int e = e0 + wave;
@@ -175,10 +166,9 @@ __global__ __launch_bounds__(TB) void pet_commit_kernel(PetArgs a) {
         }
         if (fresh) {                                   // (a subset of the ALIVE lanes of a scene below E)
             const Body b = body_of(a, o, EN);
-            const u64* G = a.grid + (size_t)e * HW;
+            const u64* G = a.stamps + (size_t)e * HW;
             const int32_t epoch = a.epoch[e], ep = a.env[(size_t)e * 4 + 1];
-            const int g = a.group[e];
-            const bool routed = g >= 0 && g < a.G;
+            const int g = a.groups.of(e);
             const uint32_t th = (su + 2 * EN)[o], hq_b = heading_q(__uint_as_float(th));
             long long id = (long long)a.rows.base[e] + (inc - c);
             for (u64 m = fresh; m; m &= m - 1ull, ++id) {
@@ -202,7 +192,7 @@ __global__ __launch_bounds__(TB) void pet_commit_kernel(PetArgs a) {
                     R[2] = make_uint4((uint32_t)n_cells, sv[wave][s], su[o], (su + EN)[o]);
                     R[3] = make_uint4(th, sv[wave][lane], hq_a, hq_b);
                 }
-                if (routed && n_cells) {               // (pet is in 1..window then)
+                if (g >= 0 && n_cells) {               // (pet is in 1..window then)
                     const uint32_t rel = (hq_b - hq_a) & 255u, d = rel < 256u - rel ? rel : 256u - rel;
                     const int type = d <= (uint32_t)PET_FOLLOW_Q ? 0 : (d >= (uint32_t)PET_OPPOSE_Q ? 2 : 1);
                     atomicAdd(reinterpret_cast<u64*>(a.hist) + ((size_t)g * PET_TYPES + type) * a.window + (pet - 1), 1ull);
@@ -217,7 +207,7 @@ __global__ __launch_bounds__(TB) void pet_commit_kernel(PetArgs a) {
 __global__ __launch_bounds__(TB) void pet_stamp_kernel(PetArgs a) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int N = a.N;
-    const size_t EN = (size_t)a.E * N, HW = (size_t)a.H * a.W;
+    const size_t EN = (size_t)a.E * N, HW = (size_t)a.grid.H * a.grid.W;
     for (int e = blockIdx.x * NW + wave; e < a.E; e += gridDim.x * NW) {
         if (lane >= N) continue;
         const size_t o = (size_t)e * N + lane;
@@ -227,7 +217,7 @@ __global__ __launch_bounds__(TB) void pet_stamp_kernel(PetArgs a) {
         if (!alive) continue;
         const Body b = body_of(a, o, EN);
         const u64 stamp = ((u64)((uint32_t)a.r + 1u) << 32) | (u64)((((uint32_t)aid & 0xffffu) << 16) | (heading_q((a.state + 2 * EN)[o]) << 8) | (uint32_t)lane);
-        u64* G = a.grid + (size_t)e * HW;
+        u64* G = a.stamps + (size_t)e * HW;
         for_cells(a, b, [&](int c) { atomicMax(G + c, stamp); });
     }
 }

@@ -1,14 +1,12 @@
-// Shared declarations of the traffic field maps (field_kernels.hip) and their C entry points (capi.hip).
+// Shared declarations of the traffic field maps (field_kernels.hip) and their C entry points (capi_observers.hip).
 #pragma once
-#include <hip/hip_runtime.h>
-#include <stdint.h>
+#include "grid_common.h"
 
 namespace copo {
 
 constexpr int FIELD_LAYERS = 10;           // int64 [G][FIELD_LAYERS][H][W]
 enum : int { FL_OCCUPANCY = 0, FL_WRECK, FL_VISITS, FL_SPEED_Q, FL_VX_Q, FL_VY_Q, FL_CRASH, FL_OUT, FL_ARRIVE, FL_CRITICAL };
-constexpr int FIELD_MAX_SIDE = 1024;       // cells per side
-constexpr int FIELD_MAX_GROUPS = 64;
+constexpr int FIELD_MAX_SIDE = GRID_MAX_SIDE, FIELD_MAX_GROUPS = GRID_MAX_GROUPS;
 constexpr int FIELD_TILE = 32;             // cells per tile side: one workgroup sums a FIELD_TILE x FIELD_TILE tile on chip
 constexpr int FIELD_MASK_WORDS = (FIELD_MAX_SIDE / FIELD_TILE) * (FIELD_MAX_SIDE / FIELD_TILE) / 32;      // tile bits per scene block
 
@@ -17,11 +15,10 @@ struct FieldArgs {
     const float* state;            // [COPO_STATE_FIELDS][E][N]
     int32_t E, N;
     float hl, hw;
-    float x0, y0, cell, inv_cell;  // inv_cell = 1 / cell, rounded once to fp32 on the host
-    int32_t W, H, G;
+    GridSpec grid;
     int32_t block;                 // scenes per workgroup of the tile pass (a multiple of 4)
     float ttc_below;               // 0: the critical layer is off
-    const int32_t* group;          // [E]
+    SceneGroups groups;
     const uint8_t* flags;          // [E][N] or NULL
     const float* ttc;              // [E][N] or NULL
     int32_t* last;                 // [E][N] centre cell iy * W + ix of the slot in the previous record when it was ALIVE inside the grid, else -1
@@ -35,20 +32,5 @@ struct FieldArgs {
 hipError_t launch_field_events(const FieldArgs& a, int accumulate, hipStream_t stream);
 // occupancy, wreck, visits, speed, flow and critical layers of the current state (one launch; reads the tile bits of launch_field_events)
 hipError_t launch_field_tiles(const FieldArgs& a, hipStream_t stream);
-
-#ifdef __HIPCC__
-// What the kernels over a grid of cells share (field_kernels.hip, encroach_kernels.hip).
-// cells [lo, hi] of an axis of n cells that a footprint around coordinate f (in cells) can reach, r cells to either side
-__device__ __forceinline__ bool reach(float f, float r, int n, int& lo, int& hi) {
-    const float a = floorf(f - r), b = floorf(f + r);
-    if (!(b >= 0.0f) || !(a < (float)n)) return false;      // (NaN reaches nothing)
-    lo = (int)fmaxf(a, 0.0f);
-    hi = (int)fminf(b, (float)(n - 1));
-    return true;
-}
-
-// half a body's diagonal stays below hl + hw; one cell on top for the rounding of the cell coordinates
-__device__ __forceinline__ float reach_radius(float hl, float hw, float inv_cell) { return (hl + hw) * inv_cell + 1.0f; }
-#endif
 
 }  // namespace copo

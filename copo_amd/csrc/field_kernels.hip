@@ -11,7 +11,7 @@
 //            depends on scheduling); centre-cell layers go by LDS integer atomics into the tile.  At the end the non-zero cells go out
 //            as 64-bit integer atomic adds, eight lanes to a row of the tile.  A per-launch partial fits 32 bits (at most 64 scenes x 64
 //            slots x 65 280); the maps are int64.
-// The rules are restated in numpy by tests/field_numpy.py.
+// The grid and the footprint rule are grid_common.h.  The rules are restated in numpy by tests/field_numpy.py.
 #include "sim_device.h"
 #include "field_common.h"
 
@@ -25,15 +25,6 @@ static_assert(FIELD_MASK_WORDS <= FB, "one lane per word of the tile bits");
 
 typedef unsigned long long u64;
 
-// iy * W + ix of the cell that holds (x, y), -1 outside the grid: subtraction, product and floor rounded one by one
-__device__ __forceinline__ int centre_cell(const FieldArgs& a, float x, float y) {
-    const float fx = floorf((x - a.x0) * a.inv_cell), fy = floorf((y - a.y0) * a.inv_cell);
-    if (!(fx >= 0.0f && fx < (float)a.W && fy >= 0.0f && fy < (float)a.H)) return -1;
-    return (int)fy * a.W + (int)fx;
-}
-
-__device__ __forceinline__ float reach_cells(const FieldArgs& a) { return reach_radius(a.hl, a.hw, a.inv_cell); }
-
 }  // namespace
 
 __global__ __launch_bounds__(FB) void field_events_kernel(FieldArgs a, int accumulate) {
@@ -43,9 +34,9 @@ __global__ __launch_bounds__(FB) void field_events_kernel(FieldArgs a, int accum
     __syncthreads();
     const int e = blockIdx.x * NW + wave;
     if (e < a.E && lane < a.N) {
-        const size_t EN = (size_t)a.E * a.N, o = (size_t)e * a.N + lane, HW = (size_t)a.H * a.W;
-        const int g = a.group[e];
-        const bool routed = g >= 0 && g < a.G;
+        const size_t EN = (size_t)a.E * a.N, o = (size_t)e * a.N + lane, HW = (size_t)a.grid.H * a.grid.W;
+        const int g = a.groups.of(e);
+        const bool routed = g >= 0;
         const int was = a.last[o];
         if (a.flags && routed && was >= 0 && (size_t)was < HW) {
             const uint32_t f = a.flags[o];
@@ -58,12 +49,11 @@ __global__ __launch_bounds__(FB) void field_events_kernel(FieldArgs a, int accum
         }
         const float x = a.state[o], y = (a.state + EN)[o];
         const int st = st_status((reinterpret_cast<const int32_t*>(a.state) + 13 * EN)[o]);
-        a.last[o] = st == ST_ALIVE ? centre_cell(a, x, y) : -1;
+        a.last[o] = st == ST_ALIVE ? a.grid.cell_of(x, y) : -1;
         if (accumulate && routed && (st == ST_ALIVE || st == ST_WRECK)) {
-            const float r = reach_cells(a);
             int lox, hix, loy, hiy;
-            if (reach((x - a.x0) * a.inv_cell, r, a.W, lox, hix) && reach((y - a.y0) * a.inv_cell, r, a.H, loy, hiy)) {
-                const int tiles_x = (a.W + T - 1) / T;
+            if (a.grid.reach_box(x, y, a.hl, a.hw, lox, hix, loy, hiy)) {
+                const int tiles_x = (a.grid.W + T - 1) / T;
                 for (int ty = loy / T; ty <= hiy / T; ++ty)
                     for (int tx = lox / T; tx <= hix / T; ++tx) {
                         const int t = ty * tiles_x + tx;
@@ -85,7 +75,7 @@ __global__ __launch_bounds__(FB) void field_tiles_kernel(FieldArgs a) {
     __shared__ int wcnt[NW];
     __shared__ int s_scenes;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int tiles_x = (a.W + T - 1) / T;
+    const int tiles_x = (a.grid.W + T - 1) / T;
     const int tile = blockIdx.x, tx = tile % tiles_x, ty = tile / tiles_x, sb = blockIdx.y, g = blockIdx.z;
     // tile 0 counts the scene-records of its group whether a body reaches it or not
     if (tile != 0 && !((a.mask[(size_t)sb * FIELD_MASK_WORDS + (tile >> 5)] >> (tile & 31)) & 1u)) return;
@@ -93,22 +83,22 @@ __global__ __launch_bounds__(FB) void field_tiles_kernel(FieldArgs a) {
     if (tid == 0) s_scenes = 0;
     // this lane's cells: four in a row of the tile, eight lanes to a row
     const int cx0 = tx * T + (tid & 7) * 4, cy = ty * T + (tid >> 3);
-    const float py = a.y0 + ((float)cy + 0.5f) * a.cell;
+    const float py = a.grid.centre_y(cy);
     float px[4];
     uint32_t occ[4], wrk[4];
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
-        px[q] = a.x0 + ((float)(cx0 + q) + 0.5f) * a.cell;
+        px[q] = a.grid.centre_x(cx0 + q);
         occ[q] = 0u;
         wrk[q] = 0u;
     }
-    const float r = reach_cells(a), hl = a.hl, hw = a.hw;
+    const float hl = a.hl, hw = a.hw;
     const size_t EN = (size_t)a.E * a.N;
     int n_scenes = 0;
     __syncthreads();
     for (int it = 0; it < a.block; it += NW) {
         const int e = sb * a.block + it + wave;
-        const bool mine = e < a.E && a.group[e] == g;         // (the whole wave)
+        const bool mine = e < a.E && a.groups.group[e] == g;     // (the whole wave; g < G is a group of the launch: no range test)
         n_scenes += mine ? 1 : 0;
         bool keep = false;
         float x = 0.0f, y = 0.0f, sn = 0.0f, cs = 0.0f;
@@ -119,13 +109,13 @@ __global__ __launch_bounds__(FB) void field_tiles_kernel(FieldArgs a) {
             st = st_status((reinterpret_cast<const int32_t*>(a.state) + 13 * EN)[o]);
             if (st == ST_ALIVE || st == ST_WRECK) {
                 int lox, hix, loy, hiy;
-                keep = reach((x - a.x0) * a.inv_cell, r, a.W, lox, hix) && reach((y - a.y0) * a.inv_cell, r, a.H, loy, hiy) &&
+                keep = a.grid.reach_box(x, y, hl, hw, lox, hix, loy, hiy) &&
                        lox <= tx * T + T - 1 && hix >= tx * T && loy <= ty * T + T - 1 && hiy >= ty * T;
             }
             if (keep) {                                        // (a centre inside the tile is within reach of it)
                 sincos_det((a.state + 2 * EN)[o], sn, cs);
-                const int cc = st == ST_ALIVE ? centre_cell(a, x, y) : -1;
-                const int ix = cc >= 0 ? cc % a.W - tx * T : -1, iy = cc >= 0 ? cc / a.W - ty * T : -1;
+                const int cc = st == ST_ALIVE ? a.grid.cell_of(x, y) : -1;
+                const int ix = cc >= 0 ? cc % a.grid.W - tx * T : -1, iy = cc >= 0 ? cc / a.grid.W - ty * T : -1;
                 if (ix >= 0 && ix < T && iy >= 0 && iy < T) {
                     const int c = iy * T + ix;
                     const float v = (a.state + 3 * EN)[o];
@@ -161,8 +151,7 @@ __global__ __launch_bounds__(FB) void field_tiles_kernel(FieldArgs a) {
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 const float dx = px[q] - kx;
-                const float u = fm(dx, kc, dy * ks), w = fm(dy, kc, -(dx * ks));
-                const uint32_t in = (fabsf(u) <= hl && fabsf(w) <= hw) ? 1u : 0u;
+                const uint32_t in = covers(dx, dy, kc, ks, hl, hw) ? 1u : 0u;
                 occ[q] += in & (kw ^ 1u);
                 wrk[q] += in & kw;
             }
@@ -172,13 +161,13 @@ __global__ __launch_bounds__(FB) void field_tiles_kernel(FieldArgs a) {
     if (lane == 0 && n_scenes) atomicAdd(&s_scenes, n_scenes);
     __syncthreads();
     // ---- the tile into the maps: non-zero cells only ----
-    const size_t HW = (size_t)a.H * a.W;
+    const size_t HW = (size_t)a.grid.H * a.grid.W;
     u64* M = reinterpret_cast<u64*>(a.maps) + (size_t)g * FIELD_LAYERS * HW;
-    if (cy < a.H) {
+    if (cy < a.grid.H) {
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-            if (cx0 + q >= a.W) continue;
-            u64* C = M + (size_t)cy * a.W + cx0 + q;
+            if (cx0 + q >= a.grid.W) continue;
+            u64* C = M + (size_t)cy * a.grid.W + cx0 + q;
             const int c = (tid >> 3) * T + (tid & 7) * 4 + q;
             if (occ[q]) atomicAdd(C + FL_OCCUPANCY * HW, (u64)occ[q]);
             if (wrk[q]) atomicAdd(C + FL_WRECK * HW, (u64)wrk[q]);
@@ -203,8 +192,8 @@ hipError_t launch_field_events(const FieldArgs& a, int accumulate, hipStream_t s
 }
 
 hipError_t launch_field_tiles(const FieldArgs& a, hipStream_t stream) {
-    const int tiles = ((a.W + T - 1) / T) * ((a.H + T - 1) / T);
-    hipLaunchKernelGGL(field_tiles_kernel, dim3(tiles, (a.E + a.block - 1) / a.block, a.G), dim3(FB), 0, stream, a);
+    const int tiles = ((a.grid.W + T - 1) / T) * ((a.grid.H + T - 1) / T);
+    hipLaunchKernelGGL(field_tiles_kernel, dim3(tiles, (a.E + a.block - 1) / a.block, a.groups.G), dim3(FB), 0, stream, a);
     return hipGetLastError();
 }
 

@@ -1,13 +1,12 @@
 // Shared declarations of the traffic gates (gate_kernels.hip) and their C entry points (capi.hip).
 #pragma once
-#include <hip/hip_runtime.h>
-#include <stdint.h>
+#include "grid_common.h"
 
 namespace copo {
 
 constexpr int GATE_MAX_GATES = 32;         // (a lane keeps the gates it crossed forward in one 32-bit word)
 constexpr int GATE_MAX_SECTIONS = 64;
-constexpr int GATE_MAX_GROUPS = 64;
+constexpr int GATE_MAX_GROUPS = GRID_MAX_GROUPS;
 constexpr int GATE_MAX_BINS = 256;         // time bins of the series
 constexpr int GATE_MAX_HIST = 64;          // headway bins, travel-time bins
 

@@ -62,8 +62,8 @@ __global__ __launch_bounds__(GB) void gate_record_kernel(GateArgs a) {
         }
         const int32_t ep = a.env[(size_t)e * 4 + 1], pep = a.mem_episode[e];
         const u64 valid = a.mem_valid[e];
-        const int g = a.group[e];
-        const bool routed = g >= 0 && g < a.G;
+        const int g = SceneGroups{a.group, a.G}.of(e);
+        const bool routed = g >= 0;
         const bool alive = in && st == ST_ALIVE;
         const bool followed = alive && ((valid >> lane) & 1ull) && paid == aid && pep == ep;
         const float cx = __uint_as_float(xb), cy = __uint_as_float(yb), px = __uint_as_float(pxb), py = __uint_as_float(pyb);

@@ -13,13 +13,14 @@ plus 20 B per slot, 16 B per scene, 8 B per histogram bin and map cell of a grou
 """
 import ctypes as C
 import dataclasses
-import json
 import math
 
 import numpy as np
 
-from . import fields
+from . import _npz, fields      # noqa: F401 (a public name: `encroach.fields`)
 from ._abi import FIELD_MAX_GROUPS as MAX_GROUPS, PET_MAX_WINDOW as MAX_WINDOW, PET_WORDS as WORDS      # noqa: F401
+from ._grid import SceneGrid
+from ._handle import Grouped
 from ._rowlog import RowLog, RowTable
 
 ROW_KEYS = ("scene", "pair", "aid_b", "aid_a", "episode", "rec", "pet", "cell", "n_cells", "speed_a", "x_b", "y_b", "heading_b", "speed_b", "hq_a", "hq_b")
@@ -135,15 +136,12 @@ def aggregates_dict(hist, critical, meta):
 
 def save(path, data):
     """One `.npz` without pickled objects of an `aggregates()` dict: `hist`, `critical` and `meta` as JSON."""
-    np.savez_compressed(path, hist=np.asarray(data["hist"], np.int64), critical=np.asarray(data["critical"], np.int64),
-                        meta=np.array(json.dumps(data["meta"], sort_keys=True)))
-    return path
+    return _npz.save(path, data["meta"], hist=np.asarray(data["hist"], np.int64), critical=np.asarray(data["critical"], np.int64))
 
 
 def load(path):
     """The `aggregates()` dict of a file written by `save`."""
-    with np.load(path, allow_pickle=False) as f:
-        return aggregates_dict(f["hist"], f["critical"], json.loads(str(f["meta"][()])))
+    return aggregates_dict(*_npz.load(path, "hist", "critical"))
 
 
 def pet_meta(cfg, N, grid, window, critical_records, groups, max_rows, dropped=0, n_records=0):
@@ -160,7 +158,7 @@ def state_bytes(E, N, W, H, window, groups, max_rows):
     return 8 * E * W * H + 20 * E * N + 16 * E + 8 * int(groups) * (3 * int(window) + W * H) + 64 * int(max_rows) + 16
 
 
-class EncroachmentLog(RowLog):
+class EncroachmentLog(SceneGrid, Grouped, RowLog):
     """PET rows and aggregates of a `VecSim` on a grid of `W` x `H` cells of `cell` metres with the origin (`x0`, `y0`) per scene: a stamp
     stays valid for `window` records; encounters with a PET of at most `critical_s` seconds (rounded to records) count in the critical map;
     `groups` scene groups (`set_groups`: scene e adds to the aggregates of group[e], a value outside 0..groups-1 to none; all 0 at first);
@@ -169,12 +167,12 @@ class EncroachmentLog(RowLog):
     other call once the simulator is closed); every call is asynchronous on torch's current stream except `count()` and what reads to the
     host (`table()`, `drain()`, `aggregates()`, `memory()`)."""
 
-    _destroy, _prefix, _table_cls = "copo_pet_destroy", "copo_pet_", EncroachmentTable
+    _prefix, _table_cls = "copo_pet_", EncroachmentTable
 
     def __init__(self, sim, x0, y0, W, H, cell=1.0, window=50, critical_s=1.0, groups=1, max_rows=65536):
         self._attach(sim)
-        self.x0, self.y0, self.cell = float(np.float32(x0)), float(np.float32(y0)), float(np.float32(cell))
-        self.W, self.H, self.groups, self.window, self.max_rows = int(W), int(H), int(groups), int(window), int(max_rows)
+        self._set_grid(x0, y0, W, H, cell)
+        self.groups, self.window, self.max_rows = int(groups), int(window), int(max_rows)
         self.critical_s = float(critical_s)
         self.critical_records = int(math.floor(self.critical_s / float(sim.cfg.dt) + 0.5))
         cfg = self._capi.PetCfg(self.x0, self.y0, self.cell, self.W, self.H, self.groups, self.window, self.critical_records, self.max_rows)
@@ -182,32 +180,12 @@ class EncroachmentLog(RowLog):
         self.n_records = 0
         self.state_bytes = state_bytes(sim.E, sim.N, self.W, self.H, self.window, self.groups, self.max_rows)
 
-    @classmethod
-    def for_map(cls, sim, cell=1.0, margin=5.0, **kwargs):
-        """Grid over the bounding box of the simulator's road tables plus `margin` metres."""
-        x0, y0, W, H = fields.grid_for_map(sim.tables, cell, margin)
-        return cls(sim, x0, y0, W, H, cell=cell, **kwargs)
-
-    @classmethod
-    def from_env(cls, sim, value):
-        """The env's log (`env.encroachment_log(**value)`: the arguments of `EncroachmentLog` -- with x0, y0, W, H an explicit grid, else
-        `for_map`)."""
-        kwargs = dict(value or {})
-        explicit = all(k in kwargs for k in ("x0", "y0", "W", "H"))
-        return cls(sim, **kwargs) if explicit else cls.for_map(sim, **kwargs)
-
     def env_record(self, feed):
         """One record of the state after reset and after every step.  After a reset by hand nothing written before may count: `forget()`
         first (a scene's own reset changes its episode word, which the record sees by itself)."""
         if feed.after_reset:
             self.forget()
         self.record()
-
-    grid = property(lambda self: (self.x0, self.y0, self.cell))
-
-    def set_groups(self, group):
-        """Scene groups: int32 [E] (torch tensor on the simulator's device, or anything numpy reads)."""
-        self._call("set_groups", self._groups(group).data_ptr())
 
     def record(self):
         """One record of the current state."""
@@ -249,6 +227,3 @@ class EncroachmentLog(RowLog):
         return save(path, self.aggregates())
 
     load = staticmethod(load)
-
-    def heat_overlay(self, frame_rgb, layer2d, view, lo=None, hi=None, alpha=160):
-        return fields.heat_overlay(frame_rgb, layer2d, view, lo, hi, alpha, grid=self.grid)

@@ -9,13 +9,14 @@ top-down renderer.  The definitions are DESIGN.md section 8e; `tests/field_numpy
 """
 import ctypes as C
 import dataclasses
-import json
 import math
 
 import numpy as np
 
+from . import _npz
 from ._abi import FIELD_MAX_GROUPS as MAX_GROUPS, FIELD_MAX_SIDE as MAX_SIDE
-from ._handle import Handle
+from ._grid import SceneGrid
+from ._handle import Grouped, Handle
 
 LAYERS = ("occupancy", "wreck", "visits", "speed_q", "vx_q", "vy_q", "crash", "out", "arrive", "critical")
 DERIVED = ("mean_speed", "flow", "occupancy_s", "occupancy_frac")
@@ -59,18 +60,13 @@ def save(path, data):
     """One `.npz` without pickled objects (`np.load(path, allow_pickle=False)` reads it) of a `read()` dict: the integer maps,
     `scene_records` and `meta` as JSON (the grid and the `SimConfig` fields that rebuild the map)."""
     maps = np.stack([np.asarray(data[k], np.int64) for k in LAYERS], 1)
-    np.savez_compressed(path, maps=maps, scene_records=np.asarray(data["scene_records"], np.int64),
-                        meta=np.array(json.dumps(data["meta"], sort_keys=True)))
-    return path
+    return _npz.save(path, data["meta"], maps=maps, scene_records=np.asarray(data["scene_records"], np.int64))
 
 
 def load(path):
     """The `read()` dict of a file written by `save`."""
-    with np.load(path, allow_pickle=False) as f:
-        meta = json.loads(str(f["meta"][()]))
-        out = derive(f["maps"], f["scene_records"], meta["dt"])
-    out["meta"] = meta
-    return out
+    maps, scene_records, meta = _npz.load(path, "maps", "scene_records")
+    return dict(derive(maps, scene_records, meta["dt"]), meta=meta)
 
 
 def heat_overlay(frame_rgb, layer2d, view, lo=None, hi=None, alpha=160, grid=None):
@@ -108,19 +104,19 @@ def heat_overlay(frame_rgb, layer2d, view, lo=None, hi=None, alpha=160, grid=Non
     return out
 
 
-class FieldMaps(Handle):
+class FieldMaps(SceneGrid, Grouped, Handle):
     """Field maps of a `VecSim` on a grid of `W` x `H` cells of `cell` metres with the origin (`x0`, `y0`), for `groups` scene groups
     (`set_groups`: scene e adds to group[e], a value outside 0..groups-1 to nothing; all 0 at first).  `ttc_below` > 0 switches the
     `critical` layer on (it reads the `ttc` handed to `record`).  Record r adds to the state layers iff `r % stride == 0` (records
     count from 0 since creation / `reset()`); events count in every record.  `close()` it when done (before or after its simulator;
     no other call once the simulator is closed); every call is asynchronous on torch's current stream except `read()` / `save()`."""
 
-    _destroy = "copo_field_destroy"
+    _prefix = "copo_field_"
 
     def __init__(self, sim, x0, y0, W, H, cell=1.0, groups=1, ttc_below=0.0, stride=1):
         self._attach(sim)
-        self.x0, self.y0, self.cell = float(np.float32(x0)), float(np.float32(y0)), float(np.float32(cell))
-        self.W, self.H, self.groups = int(W), int(H), int(groups)
+        self._set_grid(x0, y0, W, H, cell)
+        self.groups = int(groups)
         self.ttc_below, self.stride = float(ttc_below), int(stride)
         if self.stride < 1:
             raise ValueError("stride=%d (>= 1)" % self.stride)
@@ -128,30 +124,10 @@ class FieldMaps(Handle):
         self._create(self._capi.lib.copo_field_create, sim._h, C.byref(cfg))
         self.n_records = 0
 
-    @classmethod
-    def for_map(cls, sim, cell=1.0, margin=5.0, **kwargs):
-        """Grid over the bounding box of the simulator's road tables plus `margin` metres."""
-        x0, y0, W, H = grid_for_map(sim.tables, cell, margin)
-        return cls(sim, x0, y0, W, H, cell=cell, **kwargs)
-
-    @classmethod
-    def from_env(cls, sim, value):
-        """The env's maps (config key `field_maps`: None, or the arguments of `FieldMaps` -- with x0, y0, W, H an explicit grid, else
-        `for_map`)."""
-        kwargs = dict(value)
-        explicit = all(k in kwargs for k in ("x0", "y0", "W", "H"))
-        return cls(sim, **kwargs) if explicit else cls.for_map(sim, **kwargs)
-
     def env_record(self, feed):
         """One record of the state after reset (no flags: no event) and after every step, fed with the step's flags and, for the
         critical layer, the meter's ttc of that state.  The maps are kept over resets."""
         self.record(flags=feed.flags, ttc=feed.ttc if self.ttc_below > 0.0 else None)
-
-    grid =property(lambda self: (self.x0, self.y0, self.cell))
-
-    def set_groups(self, group):
-        """Scene groups: int32 [E] (torch tensor on the simulator's device, or anything numpy reads)."""
-        self._capi.check(self._capi.lib.copo_field_set_groups(self._h, self._groups(group).data_ptr(), self._stream()))
 
     def record(self, flags=None, ttc=None):
         """One record of the current state.  `flags`: uint8 [E, N], the output of the step that led to this state (None after a reset:
@@ -165,11 +141,11 @@ class FieldMaps(Handle):
 
     def forget(self):
         """Forget where every slot was last seen (after a manual `reset()` / `set_state`): the next record fires no event."""
-        self._capi.check(self._capi.lib.copo_field_forget(self._h, self._stream()))
+        self._call("forget")
 
     def reset(self):
         """Zero the maps, forget the last-seen cells; records count from 0 again.  The groups stay."""
-        self._capi.check(self._capi.lib.copo_field_reset(self._h, self._stream()))
+        self._call("reset")
         self.n_records = 0
 
     def maps(self):
@@ -177,7 +153,7 @@ class FieldMaps(Handle):
         torch = self.sim._torch
         m = torch.empty(self.groups, len(LAYERS), self.H, self.W, dtype=torch.int64, device=self.sim.device)
         r = torch.empty(self.groups, dtype=torch.int64, device=self.sim.device)
-        self._capi.check(self._capi.lib.copo_field_read(self._h, m.data_ptr(), r.data_ptr(), self._stream()))
+        self._call("read", m.data_ptr(), r.data_ptr())
         return m, r
 
     def meta(self):
@@ -197,6 +173,3 @@ class FieldMaps(Handle):
         return save(path, self.read())
 
     load = staticmethod(load)
-
-    def heat_overlay(self, frame_rgb, layer2d, view, lo=None, hi=None, alpha=160):
-        return heat_overlay(frame_rgb, layer2d, view, lo, hi, alpha, grid=self.grid)

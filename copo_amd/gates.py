@@ -11,14 +11,14 @@ one `.npz`; `gate_overlay` draws the gates into a frame of the top-down renderer
 """
 import ctypes as C
 import dataclasses
-import json
 import math
 
 import numpy as np
 
 from ._abi import (GATE_MAX_BINS as MAX_BINS, GATE_MAX_GATES as MAX_GATES, GATE_MAX_GROUPS as MAX_GROUPS, GATE_MAX_HIST as MAX_HIST,
                    GATE_MAX_SECTIONS as MAX_SECTIONS)
-from ._handle import Handle
+from . import _npz
+from ._handle import Grouped, Handle
 
 QUANT = 256
 RAW = ("count", "speed_q", "series", "headway", "sec_count", "sec_sum", "sec_hist", "scene_records", "alive")
@@ -64,17 +64,13 @@ def derive(raw, dt):
 def save(path, data):
     """One `.npz` without pickled objects (`np.load(path, allow_pickle=False)` reads it) of a `read()` dict: the integer accumulators
     and `meta` as JSON (gates, sections, bins and the `SimConfig` fields that rebuild the map)."""
-    np.savez_compressed(path, meta=np.array(json.dumps(data["meta"], sort_keys=True)), **{k: np.asarray(data[k], np.int64) for k in RAW})
-    return path
+    return _npz.save(path, data["meta"], **{k: np.asarray(data[k], np.int64) for k in RAW})
 
 
 def load(path):
     """The `read()` dict of a file written by `save`."""
-    with np.load(path, allow_pickle=False) as f:
-        meta = json.loads(str(f["meta"][()]))
-        out = derive({k: f[k] for k in RAW}, meta["dt"])
-    out["meta"] = meta
-    return out
+    *raw, meta = _npz.load(path, *RAW)
+    return dict(derive(dict(zip(RAW, raw)), meta["dt"]), meta=meta)
 
 
 def route_pose(tables, route, s):
@@ -166,7 +162,7 @@ def gate_overlay(frame_rgb, view, gates, colour=GATE_COLOUR, tick=TICK_COLOUR, t
     return out
 
 
-class TrafficGates(Handle):
+class TrafficGates(Grouped, Handle):
     """Gates of a `VecSim`: `gates` [L, 4] = {ax, ay, bx, by} (1..32), `sections` = pairs (gate_in, gate_out) (0..64), `groups` scene
     groups (`set_groups`: scene e adds to group[e], a value outside 0..groups-1 to nothing; all 0 at first), `bins` = (T, records per
     bin) of the time series, `headway_bins` bins of one record each, `tt_bins` = (TB, records per bin) of the travel times; the last bin
@@ -174,7 +170,7 @@ class TrafficGates(Handle):
     simulator; no other call once the simulator is closed); every call is asynchronous on torch's current stream except `read()` /
     `save()`."""
 
-    _destroy = "copo_gate_destroy"
+    _prefix = "copo_gate_"
 
     def __init__(self, sim, gates, sections=(), groups=1, bins=(1, 1), headway_bins=32, tt_bins=(32, 10)):
         self._attach(sim)
@@ -215,10 +211,6 @@ class TrafficGates(Handle):
 
     dims =property(lambda self: (self.groups, self.L, self.S, self.T, self.HB, self.TB))
 
-    def set_groups(self, group):
-        """Scene groups: int32 [E] (torch tensor on the simulator's device, or anything numpy reads)."""
-        self._capi.check(self._capi.lib.copo_gate_set_groups(self._h, self._groups(group).data_ptr(), self._stream()))
-
     def record(self):
         """One record of the current state (it reads simulator state only)."""
         self._capi.check(self._capi.lib.copo_gate_record(self._h, self._stream()))
@@ -227,18 +219,18 @@ class TrafficGates(Handle):
     def forget(self):
         """Forget every slot, last forward crossing and section entry (after a manual `reset()` / `set_state`): the next record fires
         nothing."""
-        self._capi.check(self._capi.lib.copo_gate_forget(self._h, self._stream()))
+        self._call("forget")
 
     def reset(self):
         """`forget()`, zero the accumulators; records count from 0 again.  The groups stay."""
-        self._capi.check(self._capi.lib.copo_gate_reset(self._h, self._stream()))
+        self._call("reset")
         self.n_records = 0
 
     def counters(self):
         """dict of device int64 tensors by name (`RAW`), views of one copy of the accumulators"""
         torch = self.sim._torch
         block = torch.empty(self._words, dtype=torch.int64, device=self.sim.device)
-        self._capi.check(self._capi.lib.copo_gate_read(self._h, block.data_ptr(), None, self._stream()))
+        self._call("read", block.data_ptr(), None)
         return split(block, *self.dims)
 
     def meta(self):

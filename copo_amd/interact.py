@@ -39,7 +39,7 @@ class InteractionMeter(Handle):
     (before or after its simulator; no other call once the simulator is closed); every call is asynchronous on torch's current
     stream."""
 
-    _destroy = "copo_interact_destroy"
+    _prefix = "copo_interact_"
 
     def __init__(self, sim, horizon=6.0, ttc_crit=1.5, gap_near=0.5, brake=4.0):
         self._attach(sim)
@@ -73,8 +73,7 @@ class InteractionMeter(Handle):
         torch = self.sim._torch
         counts = torch.empty(self.sim.E, len(COUNT_KEYS), dtype=torch.int64, device=self.sim.device)
         sums = torch.empty(self.sim.E, len(SUM_KEYS), dtype=torch.float64, device=self.sim.device)
-        self._capi.check(self._capi.lib.copo_interact_totals(self._h, counts.data_ptr(), sums.data_ptr(), 1 if flush_open else 0,
-                                                             self._stream()))
+        self._call("totals", counts.data_ptr(), sums.data_ptr(), 1 if flush_open else 0)
         return counts, sums
 
     def summary(self, flush_open=False):
@@ -86,4 +85,4 @@ class InteractionMeter(Handle):
 
     def reset(self):
         """Empty every accumulator and the totals (after a manual reset or set_state)."""
-        self._capi.check(self._capi.lib.copo_interact_reset(self._h, self._stream()))
+        self._call("reset")

@@ -34,7 +34,7 @@ class TopDownRenderer(Handle):
     when done (before or after its simulator; no other call once the simulator is closed); every call is asynchronous on torch's
     current stream."""
 
-    _destroy = "copo_render_destroy"
+    _prefix = "copo_render_"
 
     def __init__(self, sim, width=512, height=512, trail=0):
         self._attach(sim)
@@ -56,7 +56,7 @@ class TopDownRenderer(Handle):
 
     def clear(self):
         """Empty the trail ring (after a manual reset or set_state)."""
-        self._capi.check(self._capi.lib.copo_render_clear(self._h, self._stream()))
+        self._call("clear")
         self.recorded = 0
 
     def views(self, scenes, view="map", m_per_px=None, follow_slot=0):
@@ -92,8 +92,7 @@ class TopDownRenderer(Handle):
         sc = torch.from_numpy(scenes.astype(np.int32)).to(dev)
         vt = torch.from_numpy(np.ascontiguousarray(v)).to(dev)
         out = torch.empty(scenes.size, self.H, self.W, dtype=torch.int32, device=dev)
-        self._capi.check(self._capi.lib.copo_render_frames(self._h, sc.data_ptr(), int(scenes.size), vt.data_ptr(), trail,
-                                                           out.data_ptr(), self._stream()))
+        self._call("frames", sc.data_ptr(), int(scenes.size), vt.data_ptr(), trail, out.data_ptr())
         return out.view(torch.uint8).view(scenes.size, self.H, self.W, 4)
 
 

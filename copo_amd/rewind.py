@@ -42,7 +42,7 @@ class RewindBuffer(Handle):
     when done (before or after its simulator; no other call once the simulator is closed); `record` and `fork` are asynchronous on
     torch's current stream."""
 
-    _destroy = "copo_rewind_destroy"
+    _prefix = "copo_rewind_"
 
     def __init__(self, sim, depth=8, stride=4, keep_obs=False):
         self._attach(sim)
@@ -94,7 +94,7 @@ class RewindBuffer(Handle):
 
     def reset(self):
         """Forget everything; records count from 0 again."""
-        self._capi.check(self._capi.lib.copo_rewind_reset(self._h))
+        self._capi.check(self._capi.lib.copo_rewind_reset(self._h))           # (takes no stream)
         self._floor = 0
 
     def invalidate(self):
@@ -136,8 +136,7 @@ class RewindBuffer(Handle):
         status = torch.empty(T, dtype=torch.int32, device=dev)
         aid = torch.empty(T, dtype=torch.int32, device=dev) if t_ws is not None else None
         p = self._capi.ptr
-        self._capi.check(self._capi.lib.copo_rewind_fork(self._h, target._h, int(first), T, p(t_sc), p(t_rc), p(t_lcf), p(t_seeds), p(t_ws),
-                                                         p(status), p(aid), self._stream()))
+        self._call("fork", target._h, int(first), T, p(t_sc), p(t_rc), p(t_lcf), p(t_seeds), p(t_ws), p(status), p(aid))
         self._last_fork = dict(scene=t_sc, lcf=t_lcf, watch_slot=t_ws)
         return status if aid is None else (status, aid)
 

@@ -211,7 +211,7 @@ class VecSim(Handle):
 
     OUT_FIELDS = ("obs", "rew", "nei_rew", "glob_rew", "flags", "nbr_idx", "nbr_cnt", "mf_cnt", "nbr_dist", "lcf",
                   "info", "agent_id")
-    _destroy = "copo_sim_destroy"
+    _prefix = "copo_sim_"
 
     def __init__(self, cfg: SimConfig, device=0, with_info=True):
         import torch

@@ -124,7 +124,7 @@ class TripLog(RowLog):
     simulator; no other call once the simulator is closed); every call is asynchronous on torch's current stream except `count()` and
     what reads rows to the host (`table()`, `drain()`)."""
 
-    _destroy, _prefix, _table_cls = "copo_trip_destroy", "copo_trip_", TripTable
+    _prefix, _table_cls = "copo_trip_", TripTable
 
     def __init__(self, sim, max_rows=65536, stop_speed=0.5):
         self._attach(sim)
