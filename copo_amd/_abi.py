@@ -118,3 +118,4 @@ class PetCfg(C.Structure):
 
 
 PET_WORDS, PET_MAX_WINDOW, PET_TYPES = 16, 4096, 3
+RECORDER_NCOL, RECORDER_MAX_SLOTS = 31, 256

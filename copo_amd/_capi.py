@@ -183,6 +183,14 @@ _SIGS = {
     "copo_pet_clear": (C.c_int, [C.c_void_p, C.c_void_p]),
     "copo_pet_reset": (C.c_int, [C.c_void_p, C.c_void_p]),
     "copo_pet_destroy": (C.c_int, [C.c_void_p]),
+    "copo_recorder_create": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]),
+    "copo_recorder_add": (C.c_int, [C.c_void_p] * 6 + [C.c_int32, C.c_void_p]),
+    "copo_recorder_count": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.c_void_p]),
+    "copo_recorder_read": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "copo_recorder_episodes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "copo_recorder_clear": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "copo_recorder_reset": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "copo_recorder_destroy": (C.c_int, [C.c_void_p]),
     "copo_neighbours_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_float,
                                       C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                       C.c_void_p, C.c_void_p]),

@@ -96,14 +96,18 @@ def evaluate_population(algo, env, weights=None, lcf=None, num_envs=64, num_agen
 
 
 def evaluate_population_rows(algo, env, weights=None, lcf=None, num_envs=64, num_agents=40, scene_episodes=1, seed=0,
-                             recorder_distance=20.0, **extra):
+                             recorder_distance=20.0, recorder="torch", **extra):
     """The reference's per-episode evaluation table (`evaluate_once`, eval/evaluate_population.py:21-99: one row of
     `RecorderEnv.get_episode_result` per whole scene episode) for `num_envs` scenes at once: a pandas DataFrame with the
     reference's column names (`vec_recorder.COLUMNS`).  The recorder counts neighbours within its own radius (20 m,
-    recoder.py:76), so the scenes are built with that `neighbours_distance` -- the policies do not read it."""
+    recoder.py:76), so the scenes are built with that `neighbours_distance` -- the policies do not read it.
+    `recorder`: "torch" = `VecRecorder`; "device" = `DeviceRecorder`, which adds the SVO columns (`device_recorder.COLUMNS`), folds a
+    fragment in three launches and leaves the loop one host read per fragment, the episode counter."""
     import torch
     from .checkpoint_io import load_policy_weights
     from .vec_recorder import F_ENV_RESET, VecRecorder
+    if recorder not in ("torch", "device"):
+        raise ValueError("recorder=%r: 'torch' or 'device'" % (recorder,))
     extra = dict(extra)
     env_config = dict(extra.pop("env_config", None) or {}, neighbours_distance=float(recorder_distance))
     t = make_eval_trainer(algo, env, num_envs, num_agents, seed, lcf, env_config=env_config, **extra)
@@ -112,9 +116,22 @@ def evaluate_population_rows(algo, env, weights=None, lcf=None, num_envs=64, num
         if t.policy.fused is not None:
             t.policy.fused.sync_mirror()
     smp = t.sampler
+    horizon = int(t.env.sim.cfg.horizon)
+    if recorder == "device":
+        from .device_recorder import DeviceRecorder
+        rec = DeviceRecorder(smp.E, smp.N, smp.device, max_rows=smp.E * int(scene_episodes), limit=int(scene_episodes))
+        n_frag = 0
+        while n_frag * smp.T <= 6 * (int(scene_episodes) + 1) * horizon:
+            rec.add(smp.sample())
+            n_frag += 1
+            if int(rec.episodes().min()) >= int(scene_episodes):
+                break
+        df = rec.frame()
+        rec.close()
+        t.stop()
+        return df
     rec = VecRecorder(smp.E, smp.device)
     ep = torch.zeros(smp.E, dtype=torch.int64, device=smp.device)
-    horizon = int(t.env.sim.cfg.horizon)
     n_frag = 0
     while bool((ep < int(scene_episodes)).any()) and n_frag * smp.T <= 6 * (int(scene_episodes) + 1) * horizon:
         b = smp.sample()
@@ -141,6 +158,8 @@ def main():
                     help="write the reference's per-episode evaluation table (RecorderEnv columns, one row per whole scene episode) "
                          "instead of the headline rates")
     ap.add_argument("--scene-episodes", type=int, default=1)
+    ap.add_argument("--recorder", default="torch", choices=["torch", "device"],
+                    help="what folds the table: the torch recorder, or the device recorder (adds the SVO estimate columns)")
     a = ap.parse_args()
     w = None
     if a.npz:
@@ -148,7 +167,7 @@ def main():
             w = {k: f[k] for k in f.files}
     algo = "ippo" if a.algo == "cl" else a.algo
     if a.table:
-        df = evaluate_population_rows(algo, a.env, w, a.lcf, a.num_envs, a.num_agents, scene_episodes=a.scene_episodes)
+        df = evaluate_population_rows(algo, a.env, w, a.lcf, a.num_envs, a.num_agents, scene_episodes=a.scene_episodes, recorder=a.recorder)
         df.to_csv(a.table)
         print(df.mean(numeric_only=True).to_string())
         return

@@ -684,6 +684,51 @@ int copo_pet_clear(copo_pet* h, void* stream);
 int copo_pet_reset(copo_pet* h, void* stream);
 int copo_pet_destroy(copo_pet* h);
 
+/* ---- evaluation recorder: ONE row per finished WHOLE scene episode, the reference's evaluation table (RecorderEnv.get_episode_result,
+ *      copo/eval/recoder.py:188-349, what eval/evaluate_population.py writes out) for E scenes, folded on the device from the sampler's
+ *      fragments.  A handle observes no simulator: it lives on the device that is current at create and reads
+ *      the five tensors of a fragment in place.  Replaces, per step and scene: on_episode_step (recoder.py:107-127: step means of
+ *      velocity and neighbour count, own / neighbourhood reward per agent :49-70), on_episode_end (:129-152: outcome counts) and
+ *      get_episode_result (:188-299 rates, reward / cost / length statistics; :326-347 the SVO estimate).  Energy columns: left out.
+ * State, all fp64, carried across fragments: per scene the accumulators of a row and an int64 count of finished episodes, per slot the
+ * current occupant's cost, own-reward and neighbour-reward sums.
+ * Step t of scene e, ignored once the scene has finished `limit` episodes (limit 0: never).  resetting = any slot carries
+ * COPO_F_ENV_RESET; acted = COPO_F_ACTED; present = acted | (COPO_F_SPAWNED & ~resetting); done = acted & COPO_F_DONE.
+ *   steps += 1; with an acting slot: v = mean velocity over them, vsteps += 1, vsum += v, vmin / vmax; with a present slot: m = mean
+ *   nbr_cnt over them, nsteps += 1, nsum += m, nmax.  Slot: acted: cost += info cost; present: own += rew, nei += (nbr_cnt > 0 ?
+ *   nei_rew : rew).  done: agents, success / crash / out counts by the flags, sum / min / max of info episode_reward and of the slot's
+ *   cost, sum of info episode_length (and over the successful); alpha = degrees(atan2(nei, own)), svo = clamp(alpha, 0, 90): count,
+ *   sum, min, max of svo, svo_reward += hypot(nei, own) * cos(radians(svo - alpha)); then cost = own = nei = 0.  A row with
+ *   COPO_F_DONE | COPO_F_SPAWNED is the acting agent's: the new occupant starts at zero sums.
+ *   resetting: with agents > 0 ONE row; then episodes += 1 and the accumulators start over (the slots' sums stay).
+ * Row, COPO_RECORDER_NCOL fp64 values: the 25 columns of copo_amd/eval/vec_recorder.py COLUMNS in their order, svo_estimate_deg_mean /
+ * _min / _max, svo_reward (sum / agents), scene, episode index of the scene (episodes finished before this one).
+ * Order.  Every sum over slots has ONE fixed order (csrc/recorder_common.h), so rows do not depend on how the steps are cut into
+ * fragments.  The rows of one call take the ids n_rows, n_rows + 1, ... in (scene, step) order; an id >= max_rows is not stored and
+ * counts as dropped.  No atomic decides an id or adds to a sum. ---- */
+#define COPO_RECORDER_NCOL 31
+#define COPO_RECORDER_MAX_SLOTS 256
+typedef struct copo_recorder copo_recorder;
+/* E >= 1, N in 1..COPO_RECORDER_MAX_SLOTS, max_rows >= 1, limit >= 0 (COPO_ERR_DIM, checked before the device is touched).  Allocates
+ * 248 max_rows + 24 E N + 216 E bytes: COPO_ERR_DEVICE when the device refuses */
+int copo_recorder_create(int32_t E, int32_t N, int32_t max_rows, int32_t limit, copo_recorder** out);
+/* one fragment of T >= 1 steps, device arrays: flags u8 [T][E][N], infos fp32 [T][E][N][COPO_INFO_DIM] (16-byte aligned,
+ * COPO_ERR_CONFIG), rewards, nei_rewards fp32 [T][E][N], nbr_cnt int32 [T][E][N].  Three launches on `stream` whatever T is, no
+ * allocation, no host synchronisation; the inputs are only read */
+int copo_recorder_add(copo_recorder* h, const uint8_t* flags, const float* infos, const float* rewards, const float* nei_rewards,
+                      const int32_t* nbr_cnt, int32_t T, void* stream);
+/* HOST output: out[0] = rows stored so far (<= max_rows), out[1] = rows dropped; waits for `stream` */
+int copo_recorder_count(copo_recorder* h, int64_t* out, void* stream);
+/* rows [first, first + n) of the pool, device to device: rows_out [n][COPO_RECORDER_NCOL] fp64; first + n <= max_rows (COPO_ERR_DIM) */
+int copo_recorder_read(copo_recorder* h, int32_t first, int32_t n, double* rows_out, void* stream);
+/* a copy of the finished-episode counts, device to device: episodes_dev int64 [E] */
+int copo_recorder_episodes(copo_recorder* h, int64_t* episodes_dev, void* stream);
+/* n_rows = dropped = 0; the open episodes, the slots' sums and the episode counts stay */
+int copo_recorder_clear(copo_recorder* h, void* stream);
+/* forget everything: rows, counters, accumulators, slot sums, episode counts */
+int copo_recorder_reset(copo_recorder* h, void* stream);
+int copo_recorder_destroy(copo_recorder* h);
+
 /* ---- stateless ops ---- */
 
 /* CCEnv._update_distance_map + _find_in_range (env_wrappers.py:125-158) + LCFEnv reward block (:313-326).
