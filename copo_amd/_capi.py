@@ -76,6 +76,8 @@ _SIGS = {
     "copo_transpose_weights_f32": (C.c_int, [C.POINTER(PpoCfg), C.c_void_p, C.c_void_p, C.c_void_p]),
     "copo_mlp_forward_f32": (C.c_int, [C.POINTER(PpoCfg)] + [C.c_void_p] * 4 + [C.c_int64, C.c_int32, C.c_int32] +
                              [C.c_void_p] * 7),
+    "copo_mlp_forward_bank_f32": (C.c_int, [C.POINTER(PpoCfg), C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int64] +
+                                  [C.c_void_p] * 7),
     "copo_mlp_forward_rows_f32": (C.c_int, [C.POINTER(PpoCfg)] + [C.c_void_p] * 5 + [C.c_int64, C.c_int64, C.c_int32, C.c_int32] +
                                   [C.c_void_p] * 2),
     "copo_adam_step_f32": (C.c_int, [C.POINTER(PpoCfg)] + [C.c_void_p] * 4 + [C.c_int64] + [C.c_void_p] * 5),
@@ -107,6 +109,7 @@ _SIGS = {
     "copo_sim_destroy": (C.c_int, [C.c_void_p]),
     "copo_sim_reset": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(StepOut), C.c_void_p]),
     "copo_sim_set_lcf_dist": (C.c_int, [C.c_void_p, C.c_double, C.c_double]),
+    "copo_sim_set_lcf_table": (C.c_int, [C.c_void_p, C.c_void_p]),
     "copo_sim_set_force_lcf": (C.c_int, [C.c_void_p, C.c_double]),
     "copo_sim_set_capacity": (C.c_int, [C.c_void_p, C.c_int32]),
     "copo_sim_set_block": (C.c_int, [C.c_void_p, C.c_int32]),

@@ -122,6 +122,10 @@ extern "C" int copo_sim_create(const copo_sim_cfg* cfg, int device, copo_sim** o
     s->force_lcf = -100.0;
     s->capacity = cfg->num_agents;
     s->lcf_dirty = true;
+    s->lcf_table.assign((size_t)cfg->num_envs * 2, 0.0f);
+    s->lcf_rows.assign((size_t)cfg->num_envs * 2, 0.0f);
+    s->lcf_table_on = false;
+    s->lcf_rows_dirty = true;
     if (hipSetDevice(device) != hipSuccess) {
         delete s;
         return fail(COPO_ERR_DEVICE, "hipSetDevice(%d) failed", device);
@@ -220,7 +224,7 @@ extern "C" int copo_sim_create(const copo_sim_cfg* cfg, int device, copo_sim** o
     p.state = mem.alloc<float>(COPO_STATE_FIELDS * EN);
     p.env = mem.alloc<int32_t>((size_t)p.E * 4);
     p.seeds = mem.alloc<uint64_t>((size_t)p.E);
-    p.lcf_dist = mem.alloc<float>(4);
+    p.lcf_dist = mem.alloc<float>(4 + (size_t)p.E * 2);
     {   // device table: only as many road records per route as the longest route needs (+ its terminal record)
         int rows = 2;
         for (int r = 0; r < cfg->n_routes; ++r) rows = std::max(rows, (int)cfg->route_meta[r * 4 + 1] + 1);
@@ -279,8 +283,16 @@ static int flush_lcf(copo_sim* s, hipStream_t st) {
     s->lcf_host[1] = (float)s->lcf_std;
     s->lcf_host[2] = (float)s->capacity;
     s->lcf_host[3] = 0.0f;
+    if (s->lcf_rows_dirty) {       // one row per scene: the table, or the single pair (set_force_lcf overrides every scene) in every row
+        if (s->lcf_table_on && s->force_lcf == -100.0) s->lcf_rows = s->lcf_table;
+        else
+            for (size_t e = 0; e < s->lcf_rows.size(); e += 2) { s->lcf_rows[e] = s->lcf_host[0]; s->lcf_rows[e + 1] = s->lcf_host[1]; }
+        HIP_TRY(hipMemcpyAsync(const_cast<float*>(s->p.lcf_dist) + 4, s->lcf_rows.data(), s->lcf_rows.size() * sizeof(float),
+                               hipMemcpyHostToDevice, st));
+    }
     HIP_TRY(hipMemcpyAsync(const_cast<float*>(s->p.lcf_dist), s->lcf_host, 16, hipMemcpyHostToDevice, st));
     s->lcf_dirty = false;
+    s->lcf_rows_dirty = false;
     return COPO_OK;
 }
 
@@ -295,7 +307,22 @@ extern "C" int copo_sim_set_lcf_dist(copo_sim* s, double mean, double std) {
         return fail(COPO_ERR_CONFIG, "set_lcf_dist(mean=%g, std=%g): need -1 <= mean <= 1, std > 0", mean, std);
     s->lcf_mean = mean;
     s->lcf_std = std;
-    s->lcf_dirty = true;
+    s->lcf_dirty = s->lcf_rows_dirty = true;
+    return COPO_OK;
+}
+
+extern "C" int copo_sim_set_lcf_table(copo_sim* s, const float* mean_std) {
+    if (!s) return fail(COPO_ERR_NULL, "copo_sim_set_lcf_table: NULL handle");
+    if (mean_std) {
+        for (int e = 0; e < s->p.E; ++e) {
+            const float mean = mean_std[2 * e], std = mean_std[2 * e + 1];
+            if (!(std > 0.0f) || !(mean >= -1.0f && mean <= 1.0f))
+                return fail(COPO_ERR_CONFIG, "set_lcf_table scene %d (mean=%g, std=%g): need -1 <= mean <= 1, std > 0", e, (double)mean, (double)std);
+        }
+        s->lcf_table.assign(mean_std, mean_std + (size_t)s->p.E * 2);
+    }
+    s->lcf_table_on = mean_std != nullptr;
+    s->lcf_dirty = s->lcf_rows_dirty = true;
     return COPO_OK;
 }
 
@@ -311,7 +338,7 @@ extern "C" int copo_sim_set_force_lcf(copo_sim* s, double v) {
     if (!s) return fail(COPO_ERR_NULL, "copo_sim_set_force_lcf: NULL handle");
     if (v != -100.0 && (v < -1.0 || v > 1.0)) return fail(COPO_ERR_CONFIG, "force_lcf=%g not in [-1,1] (or -100)", v);
     s->force_lcf = v;
-    s->lcf_dirty = true;
+    s->lcf_dirty = s->lcf_rows_dirty = true;
     return COPO_OK;
 }
 

@@ -111,8 +111,13 @@ struct copo_sim {
     bool started;
     double lcf_mean, lcf_std, force_lcf;
     int capacity;              // active agent slots (curriculum), num_agents by default
-    float lcf_host[4];         // {mean, std, capacity, 0}: what the kernels read from p.lcf_dist
+    float lcf_host[4];         // {mean, std, capacity, 0}: the first words of p.lcf_dist (the kernels read the capacity there)
     bool lcf_dirty;
+    // The kernels draw scene e's LCF from row e of [E][2] {mean, std} at p.lcf_dist + 4, always: `lcf_rows` is the host image of those
+    // rows -- `lcf_table` (copo_sim_set_lcf_table) while lcf_table_on and no LCF is forced, else the single pair in every row --
+    // rebuilt and pushed when lcf_rows_dirty.  Both are sized once at create.
+    std::vector<float> lcf_table, lcf_rows;
+    bool lcf_table_on, lcf_rows_dirty;
     copo::DevPool mem;
     // host copies of the map tables for copo_render_create: road records [n_routes][seg_rows][COPO_SEG_STRIDE], route_meta,
     // lane lines (on the device only when a detector reads them) and static boxes

@@ -23,6 +23,7 @@
 // ceil(n_mb / 32) x [gemm_bw_kernel<GA> + fold + rowstat + dot] + meta_seq_kernel, on top of a row store computed once
 // per training iteration (F1, F2, head, Bx over all rows).  DESIGN.md section 4 has the measurements.
 #include <cstring>
+#include <type_traits>
 
 #include "sim_common.h"
 
@@ -79,7 +80,12 @@ static hipError_t gemm_lds_attrs() {
                               reinterpret_cast<const void*>(mlp_fwd_kernel<2, 8>), reinterpret_cast<const void*>(mlp_fwd_kernel<4, 8>),
                               reinterpret_cast<const void*>(mlp_fwd_kernel<1, 4, true>), reinterpret_cast<const void*>(mlp_fwd_kernel<2, 4, true>),
                               reinterpret_cast<const void*>(mlp_fwd_kernel<2, 8, true>), reinterpret_cast<const void*>(mlp_fwd_kernel<4, 8, true>),
-                              reinterpret_cast<const void*>(mlp_fwd_kernel<2, 8, false, 2>), reinterpret_cast<const void*>(mlp_fwd_kernel<2, 8, true, 2>)})
+                              reinterpret_cast<const void*>(mlp_fwd_kernel<2, 8, false, 2>), reinterpret_cast<const void*>(mlp_fwd_kernel<2, 8, true, 2>),
+                              reinterpret_cast<const void*>(mlp_fwd_kernel<1, 4, false, 1, true>), reinterpret_cast<const void*>(mlp_fwd_kernel<2, 4, false, 1, true>),
+                              reinterpret_cast<const void*>(mlp_fwd_kernel<2, 8, false, 1, true>), reinterpret_cast<const void*>(mlp_fwd_kernel<4, 8, false, 1, true>),
+                              reinterpret_cast<const void*>(mlp_fwd_kernel<1, 4, true, 1, true>), reinterpret_cast<const void*>(mlp_fwd_kernel<2, 4, true, 1, true>),
+                              reinterpret_cast<const void*>(mlp_fwd_kernel<2, 8, true, 1, true>), reinterpret_cast<const void*>(mlp_fwd_kernel<4, 8, true, 1, true>),
+                              reinterpret_cast<const void*>(mlp_fwd_kernel<2, 8, false, 2, true>), reinterpret_cast<const void*>(mlp_fwd_kernel<2, 8, true, 2, true>)})
             if ((r = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024)) != hipSuccess) e = r;
         if ((r = hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad_adam_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024)) != hipSuccess) e = r;
         return e;
@@ -379,15 +385,22 @@ extern "C" int copo_dp_status(void* workspace, const copo_ppo_cfg* cfg, int32_t 
     return ctl[0] ? COPO_ERR_DEVICE : COPO_OK;
 }
 
+// n_members = 0: one parameter set, `n_rows` rows.  n_members >= 1 (copo_mlp_forward_bank_f32): that many parameter sets
+// `member_stride` floats apart, `n_rows` rows EACH, the member as the grid's second dimension (policy net only, no row list).  The
+// variant rule below counts a member's rows, not the launch's: the two-tile variant rounds a few rows in ten thousand differently
+// from the one-tile variant (measured: 1 row of 16 536), and a member's rows must hold the bits of a launch of that member alone.
 static int mlp_forward(const copo_ppo_cfg* cfg, const float* theta, const float* theta_t, const float* obs_src,
                        const float* cc_src, int64_t n_rows, int32_t first_net, int32_t n_nets, float* values,
                        float* dist_inputs, const float* eps, float* action, float* logp, float* clipped,
-                       const int64_t* rows, int64_t n_out, void* stream) {
+                       const int64_t* rows, int64_t n_out, void* stream, int32_t n_members = 0, int64_t member_stride = 0) {
     int rc = check_cfg(cfg);
     if (rc != COPO_OK) return rc;
     if (!theta || !theta_t || !obs_src) return COPO_ERR_NULL;
     if (rows && n_out < 1) return COPO_ERR_DIM;
     if (n_rows < 1 || first_net < 0 || n_nets < 1 || first_net + n_nets > 1 + cfg->n_value_heads) return COPO_ERR_DIM;
+    const bool bank = n_members > 0;
+    if (bank && (first_net != 0 || n_nets != 1 || rows || n_members > 65535 || member_stride < cfg->n_params || member_stride % 4 != 0))
+        return COPO_ERR_DIM;
     if (first_net + n_nets > 1 && !values) return COPO_ERR_NULL;
     if (first_net == 0 && eps && (!action || !logp)) return COPO_ERR_NULL;
     const int H = cfg->hidden;
@@ -409,23 +422,25 @@ static int mlp_forward(const copo_ppo_cfg* cfg, const float* theta, const float*
     FwdArgs a{*cfg, theta, theta_t, obs_src, cc_src ? cc_src : obs_src, n_rows, first_net, n_nets, values, dist_inputs, eps,
               action, logp, clipped, rows, rows ? n_out : n_rows};
     const int rws = rt2 ? 2 * HT : HT;
-    const dim3 grid((unsigned)((n_rows + rws - 1) / rws), n_nets);
+    const dim3 grid((unsigned)((n_rows + rws - 1) / rws), bank ? n_members : n_nets);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (rt2) {
-        if (cfg->operand_dtype == COPO_OPERAND_BF16) hipLaunchKernelGGL((mlp_fwd_kernel<2, 8, true, 2>), grid, dim3(512), lds, st, a);
-        else hipLaunchKernelGGL((mlp_fwd_kernel<2, 8, false, 2>), grid, dim3(512), lds, st, a);
-        return hipGetLastError() == hipSuccess ? COPO_OK : COPO_ERR_DEVICE;
-    }
-#define COPO_FWD(NT_, W_)                                                                                       \
-        do {                                                                                                   \
-            if (cfg->operand_dtype == COPO_OPERAND_BF16) hipLaunchKernelGGL((mlp_fwd_kernel<NT_, W_, true>), grid, dim3(64 * W_), lds, st, a); \
-            else hipLaunchKernelGGL((mlp_fwd_kernel<NT_, W_>), grid, dim3(64 * W_), lds, st, a);                 \
+    FwdBankArgs b;
+    static_cast<FwdArgs&>(b) = a;
+    b.member_stride = member_stride;
+    const bool bf = cfg->operand_dtype == COPO_OPERAND_BF16;
+#define COPO_FWD(NT_, W_, RT_)                                                                                                       \
+        do {                                                                                                                        \
+            if (bank && bf) hipLaunchKernelGGL((mlp_fwd_kernel<NT_, W_, true, RT_, true>), grid, dim3(64 * W_), lds, st, b);          \
+            else if (bank) hipLaunchKernelGGL((mlp_fwd_kernel<NT_, W_, false, RT_, true>), grid, dim3(64 * W_), lds, st, b);          \
+            else if (bf) hipLaunchKernelGGL((mlp_fwd_kernel<NT_, W_, true, RT_>), grid, dim3(64 * W_), lds, st, a);                  \
+            else hipLaunchKernelGGL((mlp_fwd_kernel<NT_, W_, false, RT_>), grid, dim3(64 * W_), lds, st, a);                         \
         } while (0)
-    switch (H) {
-        case 64: COPO_FWD(1, 4); break;
-        case 128: COPO_FWD(2, 4); break;
-        case 256: COPO_FWD(2, 8); break;
-        default: COPO_FWD(4, 8); break;
+    if (rt2) COPO_FWD(2, 8, 2);
+    else switch (H) {
+        case 64: COPO_FWD(1, 4, 1); break;
+        case 128: COPO_FWD(2, 4, 1); break;
+        case 256: COPO_FWD(2, 8, 1); break;
+        default: COPO_FWD(4, 8, 1); break;
     }
 #undef COPO_FWD
     return hipGetLastError() == hipSuccess ? COPO_OK : COPO_ERR_DEVICE;
@@ -437,6 +452,14 @@ extern "C" int copo_mlp_forward_f32(const copo_ppo_cfg* cfg, const float* theta,
                                     void* stream) {
     return mlp_forward(cfg, theta, theta_t, obs_src, cc_src, n_rows, first_net, n_nets, values, dist_inputs, eps, action, logp,
                        clipped, nullptr, n_rows, stream);
+}
+
+extern "C" int copo_mlp_forward_bank_f32(const copo_ppo_cfg* cfg, const float* theta, const float* theta_t, int64_t member_stride,
+                                         int32_t n_members, int64_t rows_per_member, const float* obs_src, float* dist_inputs,
+                                         const float* eps, float* action, float* logp, float* clipped, void* stream) {
+    if (n_members < 1) return COPO_ERR_DIM;
+    return mlp_forward(cfg, theta, theta_t, obs_src, nullptr, rows_per_member, 0, 1, nullptr, dist_inputs, eps, action, logp, clipped,
+                       nullptr, rows_per_member, stream, n_members, member_stride);
 }
 
 extern "C" int copo_mlp_forward_rows_f32(const copo_ppo_cfg* cfg, const float* theta, const float* theta_t,

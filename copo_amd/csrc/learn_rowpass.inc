@@ -945,15 +945,35 @@ struct FwdArgs {
     int64_t n_out;            // rows of the sources / outputs (= n_rows without a row list)
 };
 
+// A bank of K policies (copo_mlp_forward_bank_f32, the BANK instantiations of mlp_fwd_kernel): blockIdx.y is the member, which owns rows
+// [y R, (y + 1) R) of the sources and the outputs, R = n_rows = n_out, and the parameters `member_stride` floats into theta / theta_t
+// per member.  Tiles are counted per member, so no tile spans two members and a member's last tile is masked as the last tile of a
+// launch of its R rows alone.  Policy net only (first_net = 0, n_nets = 1), no row list, no values.
+struct FwdBankArgs : FwdArgs {
+    int64_t member_stride;
+};
+
 // RT: 16-row tiles per workgroup.  RT = 2 (launcher: hidden 256, enough rows to fill the chip) halves the weight bytes a row costs and
 // the number of workgroup prologues / epilogues per row; the input rows share LDS with the second hidden layer (dead after layer 1).
-template <int NT, int WAVES, bool BF = false, int RT = 1>
-__global__ void __launch_bounds__(64 * WAVES, RT > 1 ? 4 : 1) mlp_fwd_kernel(FwdArgs a) {      // (RT = 2: four waves per SIMD = two workgroups per CU)
+// BANK: the prologue below moves the member's parameters, sources and outputs into `a`; everything after it is the one body.  (A
+// __device__ function shared by two __global__s changed the register allocation of the single-member hidden-512 kernels, 168 -> 196
+// VGPRs; a template parameter leaves the BANK = false instantiations as they were.)
+template <int NT, int WAVES, bool BF = false, int RT = 1, bool BANK = false>
+__global__ void __launch_bounds__(64 * WAVES, RT > 1 ? 4 : 1) mlp_fwd_kernel(std::conditional_t<BANK, FwdBankArgs, FwdArgs> a) {      // (RT = 2: four waves per SIMD = two workgroups per CU)
     extern __shared__ float4 fwd_lds[];
     constexpr int H = 16 * NT * WAVES, HP = H + 4, TH = 64 * WAVES, RWS = HT * RT, TPR = TH / RWS;
     constexpr int DB = NT >= 8 ? 4 : (H / 16 >= 8 ? 8 : H / 16);
     const copo_ppo_cfg& c = a.c;
-    const int g = a.first_net + blockIdx.y;
+    const int g = BANK ? 0 : a.first_net + blockIdx.y;
+    if constexpr (BANK) {
+        const size_t k = blockIdx.y, r0 = k * (size_t)a.n_rows;
+        a.theta += k * a.member_stride;
+        a.theta_t += k * a.member_stride;
+        a.obs_src += r0 * c.pol.in_dim;
+        if (a.dist_inputs) a.dist_inputs += r0 * 4;
+        if (a.eps) { a.eps += r0 * 2; a.action += r0 * 2; a.logp += r0; }
+        if (a.clipped) a.clipped += r0 * 2;
+    }
     const int64_t m0 = (int64_t)blockIdx.x * RWS;
     const copo_net_layout L = g == 0 ? c.pol : c.val[g - 1];
     const float* src = g == 0 ? a.obs_src : a.cc_src;

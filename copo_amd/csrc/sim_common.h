@@ -62,7 +62,9 @@ struct SimParams {
     const float* lines;            // [n_lines][COPO_LINE_STRIDE]
     const float* boxes;            // [n_boxes][COPO_BOX_STRIDE] static boxes {x, y, cos, sin, half_len, half_wid}
     long long* dbg;                // optional [E][8] phase timestamps (clock64) of the step kernel; NULL = off
-    const float* lcf_dist;         // [4] = {mean (force_lcf folded in), std, capacity, 0}: device memory so that captured graphs see updates
+    const float* lcf_dist;         // [4 + 2 E] = {mean (force_lcf folded in), std, capacity, 0}, then one row per scene [E][2] = {mean, std},
+                                   // which is what spawns draw from (the single pair in every row unless a table is set): device
+                                   // memory so that captured graphs see updates
 };
 
 using StepOut = copo_step_out;

@@ -135,7 +135,10 @@ __device__ __forceinline__ void spawn_pose(const SimParams& p, const float* rseg
 
 // Spawn a fresh agent into this lane's slot at spawn slot sp.  `aid` is the env-wide id.
 // the random draws of the `cnt`-th spawn in slot n: route hash, LCF sample (LCFEnv._add_lcf: normal(mean, std) clipped to [-1, 1])
-__device__ __forceinline__ void spawn_draws(const SimParams& p, uint64_t seed, uint32_t episode, int n, uint32_t cnt,
+// Scene e draws from row e of the [E][2] {mean, std} rows behind the four words of p.lcf_dist.  The host keeps the single
+// distribution in every row until copo_sim_set_lcf_table gives the scenes their own, so the kernel has one path: the read of the
+// pair it always made, at the scene's row.
+__device__ __forceinline__ void spawn_draws(const SimParams& p, int e, uint64_t seed, uint32_t episode, int n, uint32_t cnt,
                                             uint32_t& h_route, float& lcf) {
     h_route = hash_rng(seed, (uint32_t)n, cnt, episode, RNG_ROUTE);
     lcf = 0.0f;
@@ -145,7 +148,8 @@ __device__ __forceinline__ void spawn_draws(const SimParams& p, uint64_t seed, u
         float sn, cs;
         sincos_det(kTwoPi * u2 - kPi, sn, cs);
         const float z = sqrtf(-2.0f * log_det(u1)) * cs;
-        lcf = clipf(p.lcf_dist[0] + p.lcf_dist[1] * z, -1.0f, 1.0f);
+        const float* lcf_dist = p.lcf_dist + 4 + 2 * (size_t)e;
+        lcf = clipf(lcf_dist[0] + lcf_dist[1] * z, -1.0f, 1.0f);
     }
 }
 
@@ -187,13 +191,13 @@ __device__ __forceinline__ uint32_t spaces_taken(const SimParams& p, const float
 
 // `pre`: the draws were made ahead of time (step kernel, several waves per scene: a wave that idles during P0 makes them for
 // every slot, so that a spawn costs wave 0 -- the critical path of the launch -- two LDS reads instead of ~200 instructions)
-__device__ __forceinline__ void spawn_slot(const SimParams& p, const float* rsegs, const int32_t* stab, const float* sps,
+__device__ __forceinline__ void spawn_slot(const SimParams& p, int e, const float* rsegs, const int32_t* stab, const float* sps,
                                            uint64_t seed, uint32_t episode, int n, int sp, int32_t aid, Slot& s,
                                            bool pre = false, uint32_t pre_h = 0, float pre_lcf = 0.0f, int route_fixed = -1) {
     const uint32_t cnt = (uint32_t)s.spawncnt & 0xffffu;
     uint32_t h = pre_h;
     float lcf = pre_lcf;
-    if (!pre) spawn_draws(p, seed, episode, n, cnt, h, lcf);
+    if (!pre) spawn_draws(p, e, seed, episode, n, cnt, h, lcf);
     const int route = route_fixed >= 0 ? route_fixed : stab[sp * 4 + 0] + (int)(h % (uint32_t)stab[sp * 4 + 1]);
     const float* g = rsegs + (size_t)route * p.seg_rows * COPO_SEG_STRIDE;
     spawn_pose(p, rsegs, stab, sps, sp, s.x, s.y);

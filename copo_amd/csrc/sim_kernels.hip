@@ -80,7 +80,7 @@ __device__ __host__ inline int route_table_floats(int n_routes, int seg_rows) {
 
 
 // Full reset of one env by wave 0 (all lanes call; lane n < N owns slot n).
-__device__ __forceinline__ void reset_env_wave0(const SimParams& p, EnvLds& L, uint64_t seed, uint32_t episode, int lane,
+__device__ __forceinline__ void reset_env_wave0(const SimParams& p, int e, EnvLds& L, uint64_t seed, uint32_t episode, int lane,
                                                 Slot& s) {
     int16_t* perm = lds_perm(p);
     if (lane == 0) {
@@ -109,7 +109,7 @@ __device__ __forceinline__ void reset_env_wave0(const SimParams& p, EnvLds& L, u
             if (lane == n) route_fixed = r;
         }
     }
-    if (lane < cap) spawn_slot(p, L.rsegs, L.stab, L.sps, seed, episode, lane, (int)perm[lane], lane, s, false, 0u, 0.0f, route_fixed);
+    if (lane < cap) spawn_slot(p, e, L.rsegs, L.stab, L.sps, seed, episode, lane, (int)perm[lane], lane, s, false, 0u, 0.0f, route_fixed);
     else if (lane < p.N) s.status = st_pack(ST_EMPTY, 0, 0);
 }
 
@@ -896,7 +896,7 @@ __global__ void __launch_bounds__(COPO_SIM_MAX_BLOCK) sim_reset_kernel(const Sim
     if (wave == 0) {
         const uint64_t seed = p.seeds[e];
         s = Slot{};
-        reset_env_wave0(p, L, seed, 0u, lane, s);
+        reset_env_wave0(p, e, L, seed, 0u, lane, s);
         const int cap = capacity_of(p);
         if (lane < N) {
             stage_pose(L, lane, s);
@@ -972,7 +972,7 @@ __global__ void __launch_bounds__(ONE ? 64 : COPO_SIM_MAX_BLOCK, (ONE && !EXT) ?
             const uint32_t cnt = (uint32_t)reinterpret_cast<const int32_t*>(p.state)[(size_t)15 * p.E * N + (size_t)e * N + lane] & 0xffffu;
             uint32_t h;
             float lcf;
-            spawn_draws(p, p.seeds[e], (uint32_t)p.env[(size_t)e * 4 + 1], lane, cnt, h, lcf);
+            spawn_draws(p, e, p.seeds[e], (uint32_t)p.env[(size_t)e * 4 + 1], lane, cnt, h, lcf);
             hr_pre[lane] = h;
             lcf_pre[lane] = lcf;
         }
@@ -1227,8 +1227,8 @@ __global__ void __launch_bounds__(ONE ? 64 : COPO_SIM_MAX_BLOCK, (ONE && !EXT) ?
                     next_aid += 1;
                 }
                 if (my_q >= 0) {
-                    if (copy_apart) spawn_slot(p, L.rsegs, L.stab, L.sps, seed, (uint32_t)episode, lane, p.safe_ids[my_q], my_aid, s, true, hr_pre[lane], lcf_pre[lane], my_route);
-                    else spawn_slot(p, L.rsegs, L.stab, L.sps, seed, (uint32_t)episode, lane, p.safe_ids[my_q], my_aid, s, false, 0u, 0.0f, my_route);
+                    if (copy_apart) spawn_slot(p, e, L.rsegs, L.stab, L.sps, seed, (uint32_t)episode, lane, p.safe_ids[my_q], my_aid, s, true, hr_pre[lane], lcf_pre[lane], my_route);
+                    else spawn_slot(p, e, L.rsegs, L.stab, L.sps, seed, (uint32_t)episode, lane, p.safe_ids[my_q], my_aid, s, false, 0u, 0.0f, my_route);
                     present = true;
                     fl = COPO_F_SPAWNED;
                     lcf_row = s.lcf;
@@ -1290,7 +1290,7 @@ __global__ void __launch_bounds__(ONE ? 64 : COPO_SIM_MAX_BLOCK, (ONE && !EXT) ?
         if (ending) {
             episode += 1;
             next_aid = 0;
-            reset_env_wave0(p, L, seed, (uint32_t)episode, lane, s);
+            reset_env_wave0(p, e, L, seed, (uint32_t)episode, lane, s);
             const int cap = capacity_of(p);
             next_aid = cap;
             present = lane < cap;

@@ -394,7 +394,7 @@ __global__ void __launch_bounds__(COPO_SIM_MAX_BLOCK) sim_step_packed_kernel(con
         const bool ending_a = sc_a[Y.o_scal + PK_ENDING] != 0u;
         if (dw > 0 && dw < 0x20000000) {
             const int q = (dw & 0xff) - 1, route = (dw >> 8) - 1;
-            spawn_slot(p, p.route_segs, p.spawn_tab, p.spawn_s, seed_a, (uint32_t)episode_a, n_a, p.safe_ids[q],
+            spawn_slot(p, e_a, p.route_segs, p.spawn_tab, p.spawn_s, seed_a, (uint32_t)episode_a, n_a, p.safe_ids[q],
                        reinterpret_cast<const int32_t*>(sc_a + Y.o_aid)[n_a], s, false, 0u, 0.0f, route);
             present = true;
             fl = COPO_F_SPAWNED;
@@ -501,7 +501,7 @@ __global__ void __launch_bounds__(COPO_SIM_MAX_BLOCK) sim_step_packed_kernel(con
             episode_a += 1;
             if (dw & 0x40000000) {
                 const int sp = dw & 0xffff, rf = ((dw >> 16) & 0x1fff) - 1;
-                spawn_slot(p, p.route_segs, p.spawn_tab, p.spawn_s, seed_a, (uint32_t)episode_a, n_a, sp, n_a, s, false, 0u, 0.0f, rf);
+                spawn_slot(p, e_a, p.route_segs, p.spawn_tab, p.spawn_s, seed_a, (uint32_t)episode_a, n_a, sp, n_a, s, false, 0u, 0.0f, rf);
                 present = true;
                 fl_out |= COPO_F_SPAWNED;
                 if (!acted) lcf_out = s.lcf;

@@ -1,0 +1,118 @@
+"""A bank of K policies of one layout that act in one batch: the rollout side of a checkpoint sweep.
+
+The reference's `copo/eval.py:93-241` evaluates every checkpoint of every trial one after the other.  Here K checkpoints of one algorithm
+and scene drive E / K scenes each of ONE simulator batch: `PolicyBank` holds their flat parameter sets (and transposed mirrors) in one
+buffer and acts through `copo_mlp_forward_bank_f32`, in which row m belongs to member m / rows_per_member and no tile of rows spans two
+members; `BankSampler` is `VecSampler` with the bank in the policy's place, so the rollout stays one captured graph of one forward and
+one step per env step.  Every member sees the same scene seeds and the same action noise: two members differ by their weights (and,
+with `VecSim.set_lcf_table`, their LCF distribution) only.
+
+One bank is one layout: members of other observation widths or algorithms belong to another bank (`evaluate.sweep_trials` groups by it).
+"""
+import ctypes as C
+
+import numpy as np
+import torch
+
+from ..trainer import VecSampler
+
+
+class PolicyBank:
+    """K flat parameter sets of `layout_from`'s model.  `layout_from`: a trainer policy with a fused learner (`policy.fused`), whose
+    model each member is loaded into once, as `load_policy_weights` loads it (either reference key layout), and copied out of; the
+    model's own weights are put back afterwards.  Members whose shapes differ from the model's are refused.  A member is the model's
+    whole flat buffer, so that the policy's own layout and `copo_transpose_weights_f32` serve it unchanged; the value nets in it
+    are never read."""
+
+    def __init__(self, layout_from, weights):
+        from .. import _capi
+        from .checkpoint_io import load_policy_state_dict, policy_state_dict
+        weights = list(weights)
+        if not weights:
+            raise ValueError("PolicyBank: no members")
+        fz = getattr(layout_from, "fused", None)
+        if fz is None or not fz.can_forward:
+            raise ValueError("PolicyBank needs a policy with a fused learner whose layout the forward kernel covers (hidden 64 / 128 / "
+                             "256 / 512): there is no framework fallback")
+        model = layout_from.model
+        own = model.state_dict()
+        sds = [policy_state_dict(w) for w in weights]
+        for k, sd in enumerate(sds):             # every member is checked before the first is loaded
+            for name, v in sd.items():
+                if name not in own or tuple(own[name].shape) != tuple(v.shape):
+                    raise ValueError("PolicyBank member %d: %s has shape %s, the model's is %s" % (
+                        k, name, tuple(v.shape), tuple(own[name].shape) if name in own else None))
+        self._capi, self.cfg, self.K = _capi, fz.cfg, len(weights)
+        self.stride = int(fz.flat.numel)
+        flat = fz.flat.flat
+        self.theta = torch.empty(self.K, self.stride, dtype=torch.float32, device=flat.device)
+        self.theta_t = torch.zeros_like(self.theta)
+        keep = flat.clone()
+        for k, sd in enumerate(sds):
+            load_policy_state_dict(model, sd)
+            self.theta[k].copy_(flat)
+        with torch.no_grad():
+            flat.copy_(keep)
+        fz.invalidate_mirror()
+        self._mirror_ok = False
+
+    @property
+    def can_forward(self):
+        return True
+
+    def invalidate_mirror(self):
+        self._mirror_ok = False
+
+    def sync_mirror(self):
+        """The transposed mirror of every member: `copo_transpose_weights_f32` once per member on its slice.  Outside captured graphs."""
+        if self._mirror_ok:
+            return
+        st = self._capi.current_stream()
+        for k in range(self.K):
+            self._capi.check(self._capi.lib.copo_transpose_weights_f32(C.byref(self.cfg), self.theta[k].data_ptr(),
+                                                                      self.theta_t[k].data_ptr(), st))
+        self._mirror_ok = True
+
+    def act(self, obs, eps, action, logp, dist_inputs, clipped=None):
+        """`FusedLearner.act` for dense obs [K * R, O]: rows [k R, (k + 1) R) are member k's."""
+        rows = int(obs.shape[0])
+        if rows % self.K:
+            raise ValueError("PolicyBank.act: %d rows for %d members" % (rows, self.K))
+        self._capi.check(self._capi.lib.copo_mlp_forward_bank_f32(
+            C.byref(self.cfg), self.theta.data_ptr(), self.theta_t.data_ptr(), self.stride, self.K, rows // self.K, obs.data_ptr(),
+            dist_inputs.data_ptr(), eps.data_ptr(), action.data_ptr(), logp.data_ptr(),
+            None if clipped is None else clipped.data_ptr(), self._capi.current_stream()))
+
+
+class _BankPolicy:
+    """What `VecSampler` reads of a policy, with the bank as its fused learner."""
+
+    def __init__(self, policy, bank):
+        self.fused, self.config, self.device = bank, {"use_fused_inference": True}, policy.device
+
+
+def members_of_scenes(num_envs, n_members):
+    """Scenes per member; scene e belongs to member e // that."""
+    if n_members < 1 or num_envs % n_members:
+        raise ValueError("num_envs=%d is not a multiple of the %d members of the bank" % (num_envs, n_members))
+    return num_envs // n_members
+
+
+class BankSampler(VecSampler):
+    """`VecSampler` whose scenes [k E / K, (k + 1) E / K) are driven by member k of `bank`.  Every fragment draws noise for
+    [T, E / K, N, 2] and copies it to every member's scenes, and `reset` gives every member the seeds start_seed + arange(E / K)."""
+
+    def __init__(self, vec_env, policy, bank, T, use_graph=True):
+        self.bank = bank
+        self.per_member = members_of_scenes(vec_env.sim.E, bank.K)
+        super().__init__(vec_env, _BankPolicy(policy, bank), T, use_graph=use_graph, stagger_episodes=False)
+        self._eps_member = torch.zeros(self.T, self.per_member, self.N, 2, dtype=torch.float32, device=self.device)
+
+    def reset(self, seeds=None):
+        if seeds is None:
+            seeds = np.tile(np.arange(self.per_member, dtype=np.uint64) + np.uint64(self.sim.cfg.start_seed), self.bank.K)
+        super().reset(seeds)
+
+    def _draw_noise(self):
+        self._eps_member.normal_()
+        self.eps.view(self.T, self.bank.K, self.per_member, self.N, 2).copy_(self._eps_member.unsqueeze(1))

@@ -29,7 +29,11 @@ def policy_state_dict(weights, policy_name="default", layer_name_suffix=None):
 
 def load_policy_weights(model, weights, **kw):
     """Copy a population's policy into `model` (value nets / LCF parameters are left as they are)."""
-    sd = policy_state_dict(weights, **kw)
+    return load_policy_state_dict(model, policy_state_dict(weights, **kw))
+
+
+def load_policy_state_dict(model, sd):
+    """`load_policy_weights` for entries that `policy_state_dict` has already made."""
     own = model.state_dict()
     for k, v in sd.items():
         assert own[k].shape == v.shape, (k, tuple(own[k].shape), tuple(v.shape))
@@ -59,12 +63,17 @@ def export_policy_npz(model, path, layout="torch", policy_name="default", layer_
     return sorted(out)
 
 
-def get_policy_function_from_checkpoint(algo, ckpt, deterministic=False, policy_name="default"):
+def checkpoint_policy_weights(ckpt, policy_name="default"):
+    """The policy's weights of a Tune checkpoint file, in whichever key layout it was written."""
     assert os.path.isfile(ckpt), ckpt
     with open(ckpt, "rb") as f:
         blob = pickle.loads(f.read())
     weights = pickle.loads(blob.pop("worker"))["state"][policy_name]
-    weights = {k: v for k, v in weights.items() if k != "_optimizer_variables" and "value" not in k}
+    return {k: v for k, v in weights.items() if k != "_optimizer_variables" and "value" not in k}
+
+
+def get_policy_function_from_checkpoint(algo, ckpt, deterministic=False, policy_name="default"):
+    weights = checkpoint_policy_weights(ckpt, policy_name)
     # the key layout decides the reader (this build's own checkpoints are torch-layout for every algorithm); the `_1`
     # suffix is the TF-era CoPO convention only (get_policy_function_from_checkpoint.py:15-29)
     layout = detect_layout(weights)

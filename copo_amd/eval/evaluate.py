@@ -4,6 +4,11 @@ checkpoint), roll it in E parallel scenes without learning, report the reference
 (success / crash / out-of-road / max-step rates, episode reward and length, velocity ...).
 
     python -m copo_amd.eval.evaluate --algo copo --env inter --npz path/to/copo_inter.npz --lcf 0.368 0.088
+
+The sweep of `copo/eval.py:93-241` -- every checkpoint of every trial of an experiment folder, one table -- is `sweep_trials`: the
+checkpoints of one algorithm and scene drive their scenes of ONE simulator batch as a policy bank (`evaluate_bank_rows`, eval/bank.py).
+
+    python -m copo_amd.eval.evaluate --root path/to/experiment --num-episodes 20 --table sweep.csv
 """
 import argparse
 import json
@@ -145,8 +150,120 @@ def evaluate_population_rows(algo, env, weights=None, lcf=None, num_envs=64, num
     return rec.frame()
 
 
+def evaluate_bank_rows(algo, env, weights_list, lcfs=None, num_envs=64, num_agents=40, scene_episodes=1, seed=0, labels=None,
+                       recorder_distance=20.0, **extra):
+    """`evaluate_population_rows(recorder="device")` for K populations of one algorithm and scene in one batch: member k drives scenes
+    [k E / K, (k + 1) E / K) of `num_envs` = E scenes (`num_envs % K` must be 0) through one eval trainer, one `PolicyBank`, one
+    captured rollout and one `DeviceRecorder`; with `algo == "copo"` member k's scenes draw their LCF from `lcfs[k]` = (mean, std)
+    (`VecSim.set_lcf_table`).  Every member gets the scene seeds start_seed + arange(E / K) and the same action noise, so the
+    evaluation is paired.  Returns the recorder's frame sorted by (scene, episode of the scene), plus `member` = scene // (E / K) and
+    `label` = labels[member] (default: the member index)."""
+    from .bank import BankSampler, PolicyBank, members_of_scenes
+    from .device_recorder import COLUMNS, DeviceRecorder
+    import pandas as pd
+    weights_list = list(weights_list)
+    K = len(weights_list)
+    per = members_of_scenes(int(num_envs), K)
+    labels = list(range(K)) if labels is None else list(labels)
+    if len(labels) != K:
+        raise ValueError("%d labels for %d members" % (len(labels), K))
+    table = None
+    if algo == "copo":
+        if lcfs is None or len(lcfs) != K:
+            raise ValueError("a CoPO bank needs one (mean, std) per member in `lcfs`")
+        from copo_amd.sim import lcf_table_array
+        table = np.asarray([(float(m), max(float(s), 1e-6)) for m, s in lcfs], np.float32)       # (the floor of `get_env`)
+        table = lcf_table_array(np.repeat(table, per, axis=0), num_envs)
+    extra = dict(extra)
+    env_config = dict(extra.pop("env_config", None) or {}, neighbours_distance=float(recorder_distance))
+    t = make_eval_trainer(algo, env, num_envs, num_agents, seed, None, env_config=env_config, **extra)
+    try:
+        if table is not None:
+            t.env.sim.set_lcf_table(table)
+        bank = PolicyBank(t.policy, weights_list)
+        smp = BankSampler(t.env, t.policy, bank, t.sampler.T, use_graph=t.config.get("use_hip_graphs", True))
+        horizon = int(t.env.sim.cfg.horizon)
+        rec = DeviceRecorder(smp.E, smp.N, smp.device, max_rows=smp.E * int(scene_episodes), limit=int(scene_episodes))
+        n_frag = 0
+        while n_frag * smp.T <= 6 * (int(scene_episodes) + 1) * horizon:
+            rec.add(smp.sample())
+            n_frag += 1
+            if int(rec.episodes().min()) >= int(scene_episodes):
+                break
+        r = rec.rows().cpu().numpy()
+        rec.close()
+    finally:
+        t.stop()
+    r = r[np.lexsort((r[:, len(COLUMNS) + 1], r[:, len(COLUMNS)]))]
+    df = pd.DataFrame(r[:, :len(COLUMNS)], columns=list(COLUMNS))
+    df["scene"] = r[:, len(COLUMNS)].astype(np.int64)
+    df["member"] = df["scene"] // per
+    df["label"] = [labels[k] for k in df["member"]]
+    return df
+
+
+def list_checkpoints(root):
+    """One dict per checkpoint of every trial folder under `root`, trial by trial and by checkpoint count within a trial
+    (copo/eval.py:96-139): path, count, algo (the folder's name), env (the trial's RLlib env name), seed, trial, trial_path and the
+    wrapper choice, "CoPO" / "CCPPO" in the trial's name."""
+    import os
+    root = os.path.abspath(root)
+    infos = []
+    for trial in sorted(p for p in os.listdir(root) if os.path.isdir(os.path.join(root, p))):
+        trial_path = os.path.join(root, trial)
+        raw_env, start_seed, _ = get_env_and_start_seed(trial_path)
+        ckpts = sorted(((c, int(c.split("_")[1])) for c in os.listdir(trial_path) if "checkpoint" in c), key=lambda p: p[1])
+        for ckpt, count in ckpts:
+            infos.append(dict(path=os.path.join(trial_path, ckpt, ckpt.replace("_", "-")), count=count, algo=os.path.basename(root),
+                              env=raw_env, seed=start_seed, trial=trial, trial_path=trial_path,
+                              should_wrap_copo_env="CoPO" in trial, should_wrap_cc_env="CCPPO" in trial))
+    return infos
+
+
+def sweep_trials(root, num_episodes=20, max_members=16, num_agents=40, seed=0, evaluator=None, **extra):
+    """The reference's checkpoint sweep (copo/eval.py:93-241) as banks: the checkpoints of `list_checkpoints(root)` are grouped by
+    (algorithm, scene) in their listed order, and each group is evaluated `max_members` checkpoints at a time by
+    `evaluator` (default `evaluate_bank_rows`) with `num_episodes` scenes of one whole scene episode per checkpoint -- the scene seeds
+    start_seed + 0 .. num_episodes - 1, as the reference's env walks them episode after episode.  CoPO trials take their LCF
+    distribution from the trial's progress.csv.  Returns one frame: the evaluator's rows with the reference's extra columns `count`,
+    `algo`, `env` (the short scene name), `seed`, `trial`; `label` is the checkpoint's path."""
+    import pandas as pd
+    from .checkpoint_io import checkpoint_policy_weights, get_lcf_from_checkpoint
+    evaluator = evaluate_bank_rows if evaluator is None else evaluator
+    if int(max_members) < 1 or int(num_episodes) < 1:
+        raise ValueError("max_members and num_episodes must be at least 1")
+    by_cls = {cls: key for key, cls in ENVS.items()}
+    groups = {}
+    for info in list_checkpoints(root):
+        for needle, cls_name, short in _SCENE_OF:
+            if needle in info["env"]:
+                break
+        else:
+            raise ValueError("trial %s: unknown scene %r" % (info["trial"], info["env"]))
+        algo = "copo" if info["should_wrap_copo_env"] else ("ccppo" if info["should_wrap_cc_env"] else "ippo")
+        groups.setdefault((algo, by_cls[cls_name], short), []).append(info)
+    frames = []
+    for (algo, env, short), infos in groups.items():
+        for lo in range(0, len(infos), int(max_members)):
+            chunk = infos[lo:lo + int(max_members)]
+            weights = [checkpoint_policy_weights(i["path"]) for i in chunk]
+            lcfs = [tuple(float(v) for v in get_lcf_from_checkpoint(i["trial_path"])) for i in chunk] if algo == "copo" else None
+            df = evaluator(algo, env, weights, lcfs=lcfs, num_envs=len(chunk) * int(num_episodes), num_agents=num_agents,
+                           scene_episodes=1, seed=seed, labels=[i["path"] for i in chunk], **extra)
+            member = df["member"].to_numpy()
+            for col in ("count", "algo", "seed", "trial"):
+                df[col] = [chunk[k][col] for k in member]
+            df["env"] = short
+            frames.append(df)
+    return pd.concat(frames, ignore_index=True) if frames else pd.DataFrame()
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--root", default=None, help="experiment folder of Tune trial folders: evaluate every checkpoint of every trial "
+                                                 "(the reference's copo/eval.py) into --table")
+    ap.add_argument("--num-episodes", type=int, default=20, help="with --root: whole scene episodes per checkpoint")
+    ap.add_argument("--max-members", type=int, default=16, help="with --root: checkpoints per simulator batch")
     ap.add_argument("--algo", default="copo", choices=["ippo", "ccppo", "copo", "cl"])
     ap.add_argument("--env", default="inter", choices=sorted(ENVS))
     ap.add_argument("--npz", default=None, help="population file in the reference's key layout")
@@ -161,6 +278,13 @@ def main():
     ap.add_argument("--recorder", default="torch", choices=["torch", "device"],
                     help="what folds the table: the torch recorder, or the device recorder (adds the SVO estimate columns)")
     a = ap.parse_args()
+    if a.root:
+        if not a.table:
+            ap.error("--root needs --table")
+        df = sweep_trials(a.root, a.num_episodes, a.max_members, num_agents=a.num_agents)
+        df.to_csv(a.table)
+        print(df.groupby(["trial", "count"])[["success_rate", "crash_rate", "out_rate", "episode_reward_mean"]].mean().to_string())
+        return
     w = None
     if a.npz:
         with np.load(a.npz) as f:

@@ -206,6 +206,18 @@ def fill_cfg_struct(cfg: SimConfig, struct_cls):
     return c, keep
 
 
+def lcf_table_array(table, num_envs):
+    """float32 [num_envs, 2] of per-scene (mean, std), checked as `copo_sim_set_lcf_table` checks it."""
+    table = np.ascontiguousarray(np.asarray(table, np.float32))
+    if table.shape != (int(num_envs), 2):
+        raise ValueError("lcf table: shape %s, need (%d, 2) = (mean, std) per scene" % (table.shape, num_envs))
+    bad = ~((table[:, 1] > 0.0) & (table[:, 0] >= -1.0) & (table[:, 0] <= 1.0))
+    if bad.any():
+        e = int(np.argmax(bad))
+        raise ValueError("lcf table scene %d (mean=%g, std=%g): need -1 <= mean <= 1, std > 0" % (e, table[e, 0], table[e, 1]))
+    return table
+
+
 class VecSim(Handle):
     """E independent scenes x N agent slots on one GPU; every call is asynchronous on torch's current stream."""
 
@@ -264,6 +276,15 @@ class VecSim(Handle):
 
     def set_lcf_dist(self, mean, std):
         self._capi.check(self._capi.lib.copo_sim_set_lcf_dist(self._h, float(mean), float(std)))
+
+    def set_lcf_table(self, table):
+        """One LCF distribution per scene for agents spawned from now on: `table` [E, 2] = (mean, std) of scene e, or None to
+        return to the single distribution of `set_lcf_dist`.  `set_force_lcf` still overrides every scene."""
+        if table is None:
+            self._capi.check(self._capi.lib.copo_sim_set_lcf_table(self._h, None))
+            return
+        table = lcf_table_array(table, self.E)
+        self._capi.check(self._capi.lib.copo_sim_set_lcf_table(self._h, table.ctypes.data))      # (copied by the library)
 
     def set_force_lcf(self, v):
         self._capi.check(self._capi.lib.copo_sim_set_force_lcf(self._h, float(v)))

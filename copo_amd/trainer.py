@@ -179,13 +179,17 @@ class VecSampler:
                 torch.clamp(a.view(self.E, self.N, 2), -1.0, 1.0, out=self.clipped[t])
             sim._capi.check(lib.copo_sim_step(h, self.clipped[t].data_ptr(), C.byref(self._outs[t]), stream))
 
+    def _draw_noise(self):
+        """The fragment's action noise (eval/bank.py draws one member's and copies it to the others)."""
+        self.eps.normal_()
+
     def sample(self):
         """One fragment of T env steps on every scene; returns the dense SampleBatch (views, no copies)."""
         if not self._started:
             self.reset()
         else:
             self.obs[0].copy_(self.obs[self.T])
-        self.eps.normal_()
+        self._draw_noise()
         self.sim.flush()
         if self.policy.fused is not None:
             self.policy.fused.sync_mirror()      # the captured rollout reads the transposed weight mirror

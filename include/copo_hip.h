@@ -244,6 +244,14 @@ int copo_sim_destroy(copo_sim* sim);
 int copo_sim_reset(copo_sim* sim, const uint64_t* seeds, const copo_step_out* out, void* stream);
 /* LCFEnv.set_lcf_dist (env_wrappers.py:420-426): affects agents spawned from now on */
 int copo_sim_set_lcf_dist(copo_sim* sim, double mean, double std);
+/* One distribution per scene: mean_std is HOST [E][2] = {mean, std} of scene e for agents spawned from now on, each row validated as
+ * set_lcf_dist validates (COPO_ERR_CONFIG names the first bad scene, nothing is changed then); NULL returns to the single
+ * distribution of set_lcf_dist.  The reference gives every env of a worker one distribution (env_wrappers.py:420-426) and evaluates
+ * checkpoints one at a time; a table lets the scenes of one batch belong to different checkpoints.  set_force_lcf still overrides
+ * every scene (mean = the forced value, std = set_lcf_dist's).  The kernels always draw scene e from row e of [E][2] device words
+ * behind the four words of the single distribution -- without a table every row holds the single pair, so there is one kernel path --
+ * and the rows are pushed like it: by the next reset / step / flush after a change, not while the stream is capturing. */
+int copo_sim_set_lcf_table(copo_sim* sim, const float* mean_std);
 /* The LCF distribution lives in device memory (launches captured in a hipGraph keep seeing updates).
  * set_lcf_dist/set_force_lcf mark it dirty; the next reset/step pushes it on its stream, except while that
  * stream is capturing -- replay-only callers push explicitly with copo_sim_flush before the replay. */
@@ -381,7 +389,8 @@ int copo_clip_scatter(copo_sim* target, const uint32_t* snaps, const int32_t* en
  * with env words {0, 0, 0, 1} (its seed is left alone unless `seeds` is given).
  *   lcf[j]         NaN keeps the snapshot's LCF; any other value v sets field 10 of every slot of that scene whose status byte is ALIVE
  *                  to min(max(v, -1), 1).  Slots that are not ALIVE keep their bits, and agents spawned after the fork draw their LCF
- *                  from the TARGET's own distribution (the set_lcf_dist / set_force_lcf values of the target handle).
+ *                  from the TARGET's own distribution (the set_lcf_dist / set_force_lcf values of the target handle; with a
+ *                  copo_sim_set_lcf_table on the target, the row of the target scene first + j).
  *   watch_slot[j]  watch_aid[j] = field 14 (agent id) of slot watch_slot[j] in the snapshot when that slot is ALIVE there, else -1 (also
  *                  for a slot outside 0..N-1, an invalid request, or watch_slot == NULL).
  * Tally, stateless: one step's flags [B][N] are added to the rows tally[B][COPO_REWIND_TALLY], which the caller initialises to
@@ -863,6 +872,17 @@ int copo_transpose_weights_f32(const copo_ppo_cfg* cfg, const float* theta, floa
 int copo_mlp_forward_f32(const copo_ppo_cfg* cfg, const float* theta, const float* theta_t, const float* obs_src,
                          const float* cc_src, int64_t n_rows, int32_t first_net, int32_t n_nets, float* values,
                          float* dist_inputs, const float* eps, float* action, float* logp, float* clipped, void* stream);
+/* The policy net of a BANK of n_members parameter sets over n_members * rows_per_member dense rows in one launch: the rollout of a
+ * checkpoint sweep (the reference's copo/eval.py:93-241 evaluates its checkpoints one after the other).  Member k's parameters are
+ * theta + k * member_stride and its mirror theta_t + k * member_stride (member_stride >= n_params, a multiple of 4; build the mirror
+ * with copo_transpose_weights_f32 once per member on its slice); row m of obs_src and of every output belongs to member
+ * m / rows_per_member.  No tile of rows spans two members -- tiles are counted per member, the member is a grid dimension and a
+ * member's last tile is masked -- so member k's rows hold the bits copo_mlp_forward_f32 writes for that member's parameters on that
+ * slice alone; for that the kernel variant is the one copo_mlp_forward_f32 takes for rows_per_member rows.  Outputs as above
+ * (dist_inputs, clipped may be NULL; eps NULL = no sampling); no value nets, no row list.  n_members in 1..65535. */
+int copo_mlp_forward_bank_f32(const copo_ppo_cfg* cfg, const float* theta, const float* theta_t, int64_t member_stride,
+                              int32_t n_members, int64_t rows_per_member, const float* obs_src, float* dist_inputs,
+                              const float* eps, float* action, float* logp, float* clipped, void* stream);
 /* The same pass over a LIST of rows: launch row m reads row rows[m] of the sources ([n_src_rows][..]) and writes
  * values[net][rows[m]] (values is [n_nets][n_src_rows]; entries of unlisted rows are left alone).  The dense postprocess
  * of a rollout buffer uses it with the rows that hold an agent -- about half of the slots. */
