@@ -214,6 +214,8 @@ _SIGS = {
     "copo_debug_peer_allreduce_all_ranks": (C.c_int, [C.POINTER(C.c_void_p), C.c_int64, C.c_int32, C.c_void_p]),
     "copo_debug_rowpass_stamps": (C.c_int, [C.c_void_p]),
     "copo_debug_wg_times": (C.c_int, [C.c_void_p]),
+    "copo_debug_learner_plan": (C.c_int, [C.POINTER(PpoCfg), C.c_int32, C.c_int32, C.c_int64] + [C.c_int32] * 5 + [C.c_void_p, C.c_int32]),
+    "copo_debug_learner_kernel": (C.c_char_p, [C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)

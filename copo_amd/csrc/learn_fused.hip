@@ -17,7 +17,12 @@
 //      Adam steps of a pass in one workgroup)
 //   6. reduce_adam_kernel (fold of row-split partials + Adam; legacy two-net meta step), wgrad_adam_kernel (weight
 //      gradients + fold + Adam in one kernel), adam_flat_kernel (after a gradient all-reduce), transposes
-//   7. launch_fused_step and the C ABI
+//   7. learn_plan.inc, host only: the kernel table (every instantiation of the kernels above that the learner launches: id, name,
+//      function, workgroup size, dynamic-LDS ceiling) and the launch plan -- plan_step / plan_forward decide, from the configuration,
+//      the caller's mode and a few facts about its pointers, which table entries run with which grid, and the fold geometry
+//   8. here: gemm_lds_attrs (the ceilings of the table as attributes), launch_kernel (the one launch, by table id),
+//      launch_fused_step (walks a plan) and the C ABI; copo_debug_learner_plan returns a plan without touching the device, and the
+//      size queries (exchange workspace, fold length, batched workspace) read their geometry from the same plan
 //
 // One PPO minibatch step = rowpass_kernel + wgrad_adam_kernel (2 launches).  One LCF meta pass over n_mb minibatches =
 // ceil(n_mb / 32) x [gemm_bw_kernel<GA> + fold + rowstat + dot] + meta_seq_kernel, on top of a row store computed once
@@ -35,240 +40,69 @@ namespace copo {
 #include "learn_rowpass.inc"
 #include "learn_meta.inc"
 #include "learn_update.inc"
+#include "learn_plan.inc"
 
 // ------------------------------------------------------------------------------------------------------------
 // host launchers
 // ------------------------------------------------------------------------------------------------------------
-size_t fused_ws_floats(const copo_ppo_cfg& c) {
-    return WsLay(c, 4, 2).total();
-}
-
-static int pick_ksplit(int mb) {
-    int s = mb / 128;
-    if (s < 1) s = 1;
-    if (s > COPO_PPO_MAX_KSPLIT) s = COPO_PPO_MAX_KSPLIT;
-    return s;
-}
-
-struct MetaTail { MetaArgs lcf; MetaFinishArgs fin; };
-
-// the GEMM workgroups use more than the default 64 KB of dynamic LDS (gfx950 has 160 KB per CU)
-template <class F> static hipError_t allow_big_lds(F* f) {
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(f), hipFuncAttributeMaxDynamicSharedMemorySize, (int)GEMM_LDS_BYTES);
-}
+// entries above the default limit get their ceiling as an attribute, once per process; a launch beyond an entry's ceiling is refused
+// here, not by the runtime
 static hipError_t gemm_lds_attrs() {
     static hipError_t once = [] {
         hipError_t e = hipSuccess, r;
-#define COPO_ATTR(K) if ((r = allow_big_lds(K)) != hipSuccess) e = r
-        COPO_ATTR((gemm_kernel<FwdOpT<1>, true>)); COPO_ATTR((gemm_kernel<FwdOpT<1>, false>));
-        COPO_ATTR((gemm_kernel<FwdOpT<2>, true>)); COPO_ATTR((gemm_kernel<FwdOpT<2>, false>));
-        COPO_ATTR((gemm_kernel<BxOp, true>)); COPO_ATTR((gemm_kernel<BxOp, false>));
-        COPO_ATTR((gemm_bw_kernel<true>)); COPO_ATTR((gemm_bw_kernel<false>));
-        COPO_ATTR((gemm_bw_kernel<true, true>)); COPO_ATTR((gemm_bw_kernel<false, true>));
-#undef COPO_ATTR
-        for (const void* f : {reinterpret_cast<const void*>(rowpass_kernel<1, 4, false>), reinterpret_cast<const void*>(rowpass_kernel<2, 4, false>),
-                              reinterpret_cast<const void*>(rowpass_kernel<2, 8, false>), reinterpret_cast<const void*>(rowpass_kernel<4, 8, false>),
-                              reinterpret_cast<const void*>(rowpass_kernel<1, 4, true>), reinterpret_cast<const void*>(rowpass_kernel<2, 4, true>),
-                              reinterpret_cast<const void*>(rowpass_kernel<2, 8, true>), reinterpret_cast<const void*>(rowpass_kernel<4, 8, true>),
-                              reinterpret_cast<const void*>(rowpass_kernel<1, 4, true, true>), reinterpret_cast<const void*>(rowpass_kernel<2, 4, true, true>),
-                              reinterpret_cast<const void*>(rowpass_kernel<2, 8, true, true>), reinterpret_cast<const void*>(rowpass_kernel<4, 8, true, true>),
-                              reinterpret_cast<const void*>(rowpass_kernel<2, 8, true, false, true>),
-                              reinterpret_cast<const void*>(rowpass_kernel<2, 8, true, false, true, 8>), reinterpret_cast<const void*>(rowpass_kernel<2, 8, true, false, false, 8>),
-                              reinterpret_cast<const void*>(rowpass8_kernel<4>), reinterpret_cast<const void*>(rowpass8_kernel<4, true>)})
-            if ((r = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024)) != hipSuccess) e = r;
-        for (const void* f : {reinterpret_cast<const void*>(mlp_fwd_kernel<1, 4>), reinterpret_cast<const void*>(mlp_fwd_kernel<2, 4>),
-                              reinterpret_cast<const void*>(mlp_fwd_kernel<2, 8>), reinterpret_cast<const void*>(mlp_fwd_kernel<4, 8>),
-                              reinterpret_cast<const void*>(mlp_fwd_kernel<1, 4, true>), reinterpret_cast<const void*>(mlp_fwd_kernel<2, 4, true>),
-                              reinterpret_cast<const void*>(mlp_fwd_kernel<2, 8, true>), reinterpret_cast<const void*>(mlp_fwd_kernel<4, 8, true>),
-                              reinterpret_cast<const void*>(mlp_fwd_kernel<2, 8, false, 2>), reinterpret_cast<const void*>(mlp_fwd_kernel<2, 8, true, 2>),
-                              reinterpret_cast<const void*>(mlp_fwd_kernel<1, 4, false, 1, true>), reinterpret_cast<const void*>(mlp_fwd_kernel<2, 4, false, 1, true>),
-                              reinterpret_cast<const void*>(mlp_fwd_kernel<2, 8, false, 1, true>), reinterpret_cast<const void*>(mlp_fwd_kernel<4, 8, false, 1, true>),
-                              reinterpret_cast<const void*>(mlp_fwd_kernel<1, 4, true, 1, true>), reinterpret_cast<const void*>(mlp_fwd_kernel<2, 4, true, 1, true>),
-                              reinterpret_cast<const void*>(mlp_fwd_kernel<2, 8, true, 1, true>), reinterpret_cast<const void*>(mlp_fwd_kernel<4, 8, true, 1, true>),
-                              reinterpret_cast<const void*>(mlp_fwd_kernel<2, 8, false, 2, true>), reinterpret_cast<const void*>(mlp_fwd_kernel<2, 8, true, 2, true>)})
-            if ((r = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024)) != hipSuccess) e = r;
-        if ((r = hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad_adam_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024)) != hipSuccess) e = r;
+        for (const KernelEntry& k : g_kernels)
+            if (k.lds_cap > LDS_DEFAULT && (r = hipFuncSetAttribute(k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, k.lds_cap)) != hipSuccess) e = r;
         return e;
     }();
     return once;
 }
-
-// part: 0 = the whole chain; 1 = row-local kernels only (fill the meta row store); 2 = weight-gradient GEMMs that
-// gather from the row store + fold (a meta pass over precomputed rows)
-struct MetaBatch { int nb; float* g_out; double* dot_out; float* stats_out; int part; };
-
-// The shipped library takes no environment variables: one code path, all of the work, every time.  Profiling builds
-// (`make prof`, -DCOPO_PROFILE_SKIP=<mask>, a separate .so that the package never loads) read COPO_RP_DBG for the
-// phase-stamp / phase-skip bits of the row pass and can fall back to the older kernel chains for A/B measurements.
-#ifdef COPO_PROFILE_SKIP
-static const bool g_rowpass_4x4 = [] { const char* e = getenv("COPO_ROWPASS_4X4"); return !(e && e[0] == '0'); }();
-static const bool g_rowpass_rt8 = [] { const char* e = getenv("COPO_ROWPASS_RT8"); return !(e && e[0] == '0'); }();
-static const int g_wgrad_ot = [] { const char* e = getenv("COPO_WGRAD_OT"); return (e && e[0] == '2') ? 2 : 1; }();
-static const bool g_use_wgrad = [] { const char* e = getenv("COPO_FUSED_WGRAD"); return !(e && e[0] == '0'); }();
-static const bool g_use_rowpass = [] { const char* e = getenv("COPO_FUSED_ROWPASS"); return !(e && e[0] == '0'); }();
-static int profile_dbg_bits() { static const int dbg = [] { const char* e = getenv("COPO_RP_DBG"); return e ? atoi(e) : 0; }(); return dbg; }
-#else
-static constexpr bool g_rowpass_4x4 = true;
-static constexpr bool g_rowpass_rt8 = true;
-static constexpr int g_wgrad_ot = 1;
-static constexpr bool g_use_wgrad = true;
-static constexpr bool g_use_rowpass = true;
-static constexpr int profile_dbg_bits() { return 0; }
-#endif
-
-// [lo, lo + n): the span of the flat parameter buffer that the first `nets` networks of the layout occupy
-static void fold_range(const copo_ppo_cfg& c, int nets_n, int64_t* lo_out, int* n_out) {
-    const copo_net_layout* nets[4] = {&c.pol, &c.val[0], &c.val[1], &c.val[2]};
-    int64_t lo = c.pol.w1, hi = 0;
-    for (int g = 0; g < nets_n; ++g) {
-        const int64_t offs[6] = {nets[g]->w1, nets[g]->b1, nets[g]->w2, nets[g]->b2, nets[g]->w3, nets[g]->b3};
-        const int64_t szs[6] = {(int64_t)c.hidden * nets[g]->in_dim, c.hidden, (int64_t)c.hidden * c.hidden, c.hidden,
-                                (int64_t)nets[g]->out_dim * c.hidden, nets[g]->out_dim};
-        for (int t = 0; t < 6; ++t) {
-            lo = offs[t] < lo ? offs[t] : lo;
-            hi = offs[t] + szs[t] > hi ? offs[t] + szs[t] : hi;
-        }
-    }
-    *lo_out = lo;
-    *n_out = (int)(hi - lo);
+static hipError_t launch_kernel(const Launch& l, void** args, hipStream_t s) {
+    if (l.id < 0 || l.id >= K_COUNT || l.lds > g_kernels[l.id].lds_cap) return hipErrorInvalidValue;
+    return hipLaunchKernel(g_kernels[l.id].fn, dim3(l.gx, l.gy, l.gz), dim3(l.block), args, (size_t)l.lds, s);
 }
 
-hipError_t launch_fused_step(FusedArgs a, hipStream_t s, const MetaTail* mt_ = nullptr, const MetaBatch* mbatch = nullptr,
-                             int* fold_blocks_out = nullptr, int* n_fold_out = nullptr) {
+struct MetaTail { MetaArgs lcf; MetaFinishArgs fin; };
+// what the fold of a meta mode writes besides the gradients: the batched fold's exports, or the LCF step of PLAN_META_PAIR_TAIL
+struct FoldSink { float* g_out; double* dot_out; float* stats_out; const MetaTail* tail; };
+
+static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+static int facts_of(const FusedArgs& a) {
     const copo_ppo_cfg& c = a.c;
-    if (hipError_t e = gemm_lds_attrs(); e != hipSuccess) return e;
-    a.ksplit = mbatch ? 1 : pick_ksplit(c.mb);
-    a.dbg = profile_dbg_bits();
-    a.stat_tiles = head_tiles(c);
-    const int G = a.groups, mt = (c.mb + TM - 1) / TM, ht = (c.hidden + TN - 1) / TN;
-    int kmax1 = c.pol.in_dim;
-    if (a.head_mode == COPO_HEAD_PPO)
-        for (int g = 1; g < G; ++g) kmax1 = c.val[g - 1].in_dim > kmax1 ? c.val[g - 1].in_dim : kmax1;
-    // vector path: every row the kernels touch is 16-byte aligned and a multiple of 4 floats long
-    bool vec = (c.hidden % 4 == 0) && (c.pol.in_dim % 4 == 0) && ((reinterpret_cast<uintptr_t>(a.obs_src) & 15) == 0) &&
-               ((reinterpret_cast<uintptr_t>(a.cc_src) & 15) == 0) && ((reinterpret_cast<uintptr_t>(a.theta) & 15) == 0) &&
-               ((reinterpret_cast<uintptr_t>(a.ws) & 15) == 0) && (!a.theta2 || (reinterpret_cast<uintptr_t>(a.theta2) & 15) == 0);
-    const copo_net_layout* nets[4] = {&c.pol, &c.val[0], &c.val[1], &c.val[2]};
-    for (int g = 0; g < (a.head_mode == COPO_HEAD_PPO ? G : 1); ++g)
-        vec = vec && (nets[g]->in_dim % 4 == 0) && (nets[g]->w1 % 4 == 0) && (nets[g]->w2 % 4 == 0);
-#define COPO_GEMM(OP, grid, op, K)                                                                     \
-    do {                                                                                               \
-        if (vec) hipLaunchKernelGGL((gemm_kernel<OP, true>), grid, dim3(256), gemm_lds_bytes(a.c.mb), s, a, K);   \
-        else hipLaunchKernelGGL((gemm_kernel<OP, false>), grid, dim3(256), gemm_lds_bytes(a.c.mb), s, a, K);      \
-    } while (0)
-    // row pass (one kernel for F1, F2, heads, B2x) when the shapes allow it; else the four separate kernels
-    // shapes with a row-pass instantiation: hidden = 16 * NT * WAVES
-    const int rp_h = c.hidden;
-    const size_t rp_lds = rowpass_lds_floats(c.hidden, rowpass_k1p(kmax1)) * sizeof(float);
-    // with the transposed mirror the row pass reads no k-contiguous weight rows, so input widths that are not a
-    // multiple of 4 (the 91-dim observation of IPPO / CCPPO) only cost a scalar input gather
-    const bool tw = a.theta_t != nullptr && a.head_mode != MODE_META_BOTH;
-    bool tw_ok = tw && (c.hidden % 4 == 0) && ((reinterpret_cast<uintptr_t>(a.theta) & 15) == 0) &&
-                 ((reinterpret_cast<uintptr_t>(a.theta_t) & 15) == 0) && ((reinterpret_cast<uintptr_t>(a.ws) & 15) == 0);
-    for (int g = 0; g < (a.head_mode == COPO_HEAD_PPO ? G : 1); ++g)
-        tw_ok = tw_ok && (nets[g]->w1 % 4 == 0) && (nets[g]->w2 % 4 == 0);
-    const int part = mbatch ? mbatch->part : 0;
-    if (part == 2) {
-        // the gather-all tiles address the row store with 32-bit byte offsets (buffer loads): every operand slab must stay below 4 GB
-        const uint64_t widest = (uint64_t)(c.hidden > c.pol.in_dim ? c.hidden : c.pol.in_dim);
-        vec = vec && ((reinterpret_cast<uintptr_t>(a.ws0) & 15) == 0) && ((uint64_t)a.gcap0 * (uint64_t)c.mb * widest * 4u < 0xfffffff0ull);
-    }
-    const bool rowpass = (vec || tw_ok) && !mbatch && g_use_rowpass && (rp_h == 64 || rp_h == 128 || rp_h == 256 || rp_h == 512) &&
-                         rp_lds <= 150 * 1024;
-    // bfloat16 operands: only the row pass + fused weight-gradient kernels round where torch.autocast rounds
-    const bool bf = c.operand_dtype == COPO_OPERAND_BF16;
-    if (bf && !(rowpass && tw && tw_ok && a.head_mode == COPO_HEAD_PPO && g_use_wgrad)) return hipErrorInvalidValue;
-    if (rowpass) {
-        // 8-row tiles where 16-row tiles would leave compute units without a workgroup (rowpass_kernel, RT): the production
-        // shape only (hidden 256 through the transposed mirror)
-        const bool rt8 = tw && rp_h == 256 && head_tiles(c) * G <= 160 && g_rowpass_rt8 && (!bf || g_rowpass_4x4);
-        if (rt8) a.stat_tiles = (c.mb + 7) / 8;
-        const dim3 grid(a.stat_tiles, G);
-#define COPO_RP(NT_, W_, HO_)                                                                                     \
-        do {                                                                                                   \
-            if (bf && rt8 && g_rowpass_4x4) hipLaunchKernelGGL((rowpass8_kernel<4, true>), grid, dim3(64 * R8_KS * 4), rowpass8_lds_floats(256, rowpass8_k1p(kmax1)) * sizeof(float), s, a); \
-            else if (bf) hipLaunchKernelGGL((rowpass_kernel<NT_, W_, true, true>), grid, dim3(64 * W_), rp_lds, s, a); \
-            else if (rt8 && g_rowpass_4x4) hipLaunchKernelGGL((rowpass8_kernel<4>), grid, dim3(64 * R8_KS * 4), rowpass8_lds_floats(256, rowpass8_k1p(kmax1)) * sizeof(float), s, a); \
-            else if (rt8 && HO_ && kmax1 <= 128) hipLaunchKernelGGL((rowpass_kernel<2, 8, true, false, true, 8>), grid, dim3(64 * W_), rp_lds, s, a); \
-            else if (rt8) hipLaunchKernelGGL((rowpass_kernel<2, 8, true, false, false, 8>), grid, dim3(64 * W_), rp_lds, s, a); \
-            else if (tw && HO_ && kmax1 <= 128) hipLaunchKernelGGL((rowpass_kernel<NT_, W_, true, false, HO_>), grid, dim3(64 * W_), rp_lds, s, a); \
-            else if (tw) hipLaunchKernelGGL((rowpass_kernel<NT_, W_, true>), grid, dim3(64 * W_), rp_lds, s, a); \
-            else hipLaunchKernelGGL((rowpass_kernel<NT_, W_, false>), grid, dim3(64 * W_), rp_lds, s, a);        \
-        } while (0)
-        switch (rp_h) {
-            case 64: COPO_RP(1, 4, false); break;
-            case 128: COPO_RP(2, 4, false); break;
-            case 256: COPO_RP(2, 8, true); break;       // hidden 256: layer 2 is two ring turns -> hand-over variant for narrow inputs
-            default: COPO_RP(4, 8, false); break;
-        }
-#undef COPO_RP
-    } else if (part != 2) {
-        COPO_GEMM(FwdOpT<1>, dim3(ht, mt, G), f1, kmax1);
-        COPO_GEMM(FwdOpT<2>, dim3(ht, mt, G), f2, c.hidden);
-        const size_t lds = (size_t)(HT * (c.hidden + 1) + 4 * c.hidden + HT * 4 + 32) * sizeof(float);
-        hipLaunchKernelGGL(head_kernel, dim3(head_tiles(c), G), dim3(256), lds, s, a);
-        COPO_GEMM(BxOp, dim3(ht, mt, G), bx, c.hidden);
-    }
-#undef COPO_GEMM
-    if (part == 1) return hipGetLastError();
-    if (a.dp_world > 1 && (mbatch || a.head_mode == MODE_META_BOTH || !g_use_wgrad || g_wgrad_ot != 1 || !a.apply_adam)) return hipErrorInvalidValue;
-    if (!mbatch && a.head_mode != MODE_META_BOTH && g_use_wgrad) {
-        // weight gradients, fold and Adam in one kernel: the SGD step ends here
-        const int ot = g_wgrad_ot;
-        const int nty = (c.hidden + 32 * ot - 1) / (32 * ot), wx2 = (c.hidden + 1 + 31) / 32, wx1 = (kmax1 + 1 + 31) / 32;
-        const dim3 grid((wx2 + wx1) * nty + wx2, G);      // (wgrad_tiles() below: the exchange workspace is sized by this grid)
-        const size_t lds = (size_t)WG_WAVES * 32 * ot * 33 * sizeof(float);
-        const bool fastk = c.mb == 2 * WG_RING * WG_WAVES && (bf || ot == 1);      // buffer-load operand ring (learn_update.inc)
-        if (bf && fastk) hipLaunchKernelGGL((wgrad_adam_kernel<1, true, true>), grid, dim3(64 * WG_WAVES), (size_t)WG_WAVES * 32 * 33 * sizeof(float), s, a, nty, (c.hidden + 1 + 31) / 32, wx1);
-        else if (bf) hipLaunchKernelGGL((wgrad_adam_kernel<1, true>), grid, dim3(64 * WG_WAVES), (size_t)WG_WAVES * 32 * 33 * sizeof(float), s, a, nty, (c.hidden + 1 + 31) / 32, wx1);
-        else if (ot == 2) hipLaunchKernelGGL((wgrad_adam_kernel<2>), grid, dim3(64 * WG_WAVES), lds, s, a, nty, wx2, wx1);
-        else if (fastk) hipLaunchKernelGGL((wgrad_adam_kernel<1, false, true>), grid, dim3(64 * WG_WAVES), lds, s, a, nty, wx2, wx1);
-        else hipLaunchKernelGGL((wgrad_adam_kernel<1>), grid, dim3(64 * WG_WAVES), lds, s, a, nty, wx2, wx1);
-        return hipGetLastError();
-    }
-    {
-        // layers 2 / 3: no tile for the bias column alone when the hidden width fills whole tiles (BwOpT::bias_by_rowsum)
-        const int nx2 = (c.hidden % TN == 0) ? c.hidden / TN : (c.hidden + 1 + TN - 1) / TN, nx1 = (kmax1 + 1 + TN - 1) / TN;
-        dim3 grid((nx2 + nx1) * ht + nx2, G * a.ksplit);
-        if (part == 2) {
-            if (vec) grid.x = (nx2 + nx1) * ht + 1;          // gather-all mode, vector rows: the head layer is one workgroup on the lanes (head_wgrad_lanes)
-            if (vec) hipLaunchKernelGGL((gemm_bw_kernel<true, true>), grid, dim3(256), gemm_lds_bytes(a.c.mb), s, a, c.mb, nx2, nx1, ht);
-            else hipLaunchKernelGGL((gemm_bw_kernel<false, true>), grid, dim3(256), gemm_lds_bytes(a.c.mb), s, a, c.mb, nx2, nx1, ht);
-        } else if (vec) hipLaunchKernelGGL((gemm_bw_kernel<true>), grid, dim3(256), gemm_lds_bytes(a.c.mb), s, a, c.mb, nx2, nx1, ht);
-        else hipLaunchKernelGGL((gemm_bw_kernel<false>), grid, dim3(256), gemm_lds_bytes(a.c.mb), s, a, c.mb, nx2, nx1, ht);
-    }
-    // parameter range the fold covers: every net of this call (the policy only in the meta modes)
-    int64_t lo;
-    int n_fold;
-    fold_range(c, a.head_mode == COPO_HEAD_PPO ? G : 1, &lo, &n_fold);
-    const int fold_blocks = (n_fold + 256 * FOLD_EPT - 1) / (256 * FOLD_EPT);
-    if (a.head_mode == MODE_META_BOTH && fold_blocks > COPO_META_DOT_PARTIALS) return hipErrorInvalidValue;
-    if (fold_blocks_out) *fold_blocks_out = fold_blocks;
-    if (n_fold_out) *n_fold_out = n_fold;
-    if (mbatch) {
-        hipLaunchKernelGGL(meta_batch_fold_kernel, dim3(fold_blocks, mbatch->nb), dim3(256), 0, s, a, lo, n_fold, mbatch->g_out,
-                           mbatch->dot_out, mbatch->stats_out);
-        return hipGetLastError();
-    }
-    MetaTail tailv{};
-    if (mt_) {
-        tailv = *mt_;
-        tailv.fin.n_partials = fold_blocks;      // only the partials this launch writes
-    }
-    hipLaunchKernelGGL(reduce_adam_kernel, dim3(fold_blocks), dim3(256), 0, s, a, lo, n_fold, mt_ ? 1 : 0, tailv.lcf, tailv.fin);
-    // this Adam does not write the transposed mirror (the fused weight-gradient kernel does): bring it up to date, or
-    // the next row pass would read stale weights
-    if (a.apply_adam && a.theta_t && a.head_mode == COPO_HEAD_PPO) return launch_refresh_transposed(c, a.theta, a.theta_t, s);
-    return hipGetLastError();
+    // the gather-all tiles address the row store with 32-bit byte offsets (buffer loads): every operand slab must stay below 4 GB
+    const uint64_t widest = (uint64_t)(c.hidden > c.pol.in_dim ? c.hidden : c.pol.in_dim);
+    return (aligned16(a.obs_src) && aligned16(a.cc_src) && aligned16(a.theta) && aligned16(a.ws) && aligned16(a.theta2) ? FACT_ALIGNED : 0) |
+           (a.theta_t ? FACT_MIRROR : 0) | (aligned16(a.theta) && aligned16(a.theta_t) && aligned16(a.ws) ? FACT_MIRROR_ALIGNED : 0) |
+           (aligned16(a.ws0) && (uint64_t)a.gcap0 * (uint64_t)c.mb * widest * 4u < 0xfffffff0ull ? FACT_STORE_OK : 0);
 }
 
-// tiles of the weight-gradient kernel's grid for a PPO step over all nets of `c` (= workgroups; launch_fused_step)
-static int wgrad_tiles(const copo_ppo_cfg& c) {
-    const int G = 1 + c.n_value_heads;
-    int kmax1 = c.pol.in_dim;
-    for (int g = 1; g < G; ++g) kmax1 = c.val[g - 1].in_dim > kmax1 ? c.val[g - 1].in_dim : kmax1;
-    const int nty = (c.hidden + 31) / 32, wx2 = (c.hidden + 1 + 31) / 32, wx1 = (kmax1 + 1 + 31) / 32;
-    return ((wx2 + wx1) * nty + wx2) * G;
+// walks the plan of `mode` for these arguments; plan_out: the plan it walked (its fold geometry, for the kernels a caller adds)
+hipError_t launch_fused_step(FusedArgs a, PlanMode mode, int nb, hipStream_t s, FoldSink sink = {}, Plan* plan_out = nullptr) {
+    if (hipError_t e = gemm_lds_attrs(); e != hipSuccess) return e;
+    const Plan p = plan_step(a.c, mode, a.head_mode, nb, a.dp_world, facts_of(a), switches());
+    if (p.refused) return hipErrorInvalidValue;
+    if (plan_out) *plan_out = p;
+    a.groups = p.groups;
+    a.ksplit = p.ksplit;
+    a.dbg = profile_dbg_bits();
+    a.stat_tiles = p.stat_tiles;
+    MetaTail tail{};
+    if (sink.tail) {
+        tail = *sink.tail;
+        tail.fin.n_partials = p.fold_blocks;      // only the partials this launch writes
+    }
+    int64_t lo = p.lo;
+    int n_fold = p.n_fold, meta_tail = sink.tail ? 1 : 0;
+    for (int i = 0; i < p.n; ++i) {
+        Launch l = p.l[i];
+        void* step_args[] = {&a, &l.arg[0], &l.arg[1], &l.arg[2], &l.arg[3]};
+        void* batch_fold_args[] = {&a, &lo, &n_fold, &sink.g_out, &sink.dot_out, &sink.stats_out};
+        void* fold_args[] = {&a, &lo, &n_fold, &meta_tail, &tail.lcf, &tail.fin};
+        if (hipError_t e = launch_kernel(l, l.id == K_META_FOLD ? batch_fold_args : l.id == K_REDUCE_ADAM ? fold_args : step_args, s); e != hipSuccess)
+            return e;
+    }
+    // the next row pass would read stale weights otherwise (the fused weight-gradient kernel keeps the mirror itself)
+    if (p.refresh_mirror) return launch_refresh_transposed(a.c, a.theta, a.theta_t, s);
+    return hipGetLastError();
 }
 
 hipError_t launch_adam_flat(const FusedArgs& a, long long n, hipStream_t s) {
@@ -336,11 +170,15 @@ extern "C" int copo_ppo_fused_step_f32(const copo_ppo_cfg* cfg, float* theta, fl
     fill_common(a, cfg, obs_src, cc_src, pack_src, rows, w, denom, workspace, mb_index);
     a.theta = theta; a.adam_m = adam_m; a.adam_v = adam_v; a.grad = grad;
     a.kl_coeff = kl_coeff; a.step = step; a.stats = stats; a.apply_adam = apply_adam; a.head_mode = head_mode;
-    a.groups = (head_mode == COPO_HEAD_PPO) ? 1 + cfg->n_value_heads : 1;
     a.bump_k = (mb_index && bump_index) ? 1 : 0;
     a.theta_t = theta_t;
-    hipError_t e = launch_fused_step(a, static_cast<hipStream_t>(stream));
+    hipError_t e = launch_fused_step(a, apply_adam ? PLAN_PPO_STEP : PLAN_PPO_GRADS, 0, static_cast<hipStream_t>(stream));
     return e == hipSuccess ? COPO_OK : COPO_ERR_DEVICE;
+}
+
+// workgroups of the weight-gradient kernel of a PPO step over all nets of `c`: the tiles of the data-parallel exchange
+static int wgrad_tiles(const copo_ppo_cfg& c) {
+    return plan_step(c, PLAN_DP_STEP, COPO_HEAD_PPO, 0, 1, FACT_ALIGNED | FACT_MIRROR | FACT_MIRROR_ALIGNED, switches()).wgrad_tiles;
 }
 
 extern "C" int64_t copo_dp_workspace_bytes(const copo_ppo_cfg* cfg, int32_t world) {
@@ -363,7 +201,6 @@ extern "C" int copo_ppo_fused_step_dp_f32(const copo_ppo_cfg* cfg, float* theta,
     fill_common(a, cfg, obs_src, cc_src, pack_src, rows, w, denom, workspace, mb_index);
     a.theta = theta; a.adam_m = adam_m; a.adam_v = adam_v;
     a.kl_coeff = kl_coeff; a.step = step; a.stats = stats; a.apply_adam = 1; a.head_mode = COPO_HEAD_PPO;
-    a.groups = 1 + cfg->n_value_heads;
     a.bump_k = (mb_index && bump_index) ? 1 : 0;
     a.theta_t = theta_t;
     a.dp_rank = rank; a.dp_world = world;
@@ -371,7 +208,7 @@ extern "C" int copo_ppo_fused_step_dp_f32(const copo_ppo_cfg* cfg, float* theta,
         if (!dp_workspaces[r]) return COPO_ERR_NULL;
         a.dp_ws[r] = static_cast<float*>(dp_workspaces[r]);
     }
-    hipError_t e = launch_fused_step(a, static_cast<hipStream_t>(stream));
+    hipError_t e = launch_fused_step(a, PLAN_DP_STEP, 0, static_cast<hipStream_t>(stream));
     return e == hipSuccess ? COPO_OK : COPO_ERR_DEVICE;
 }
 
@@ -385,10 +222,6 @@ extern "C" int copo_dp_status(void* workspace, const copo_ppo_cfg* cfg, int32_t 
     return ctl[0] ? COPO_ERR_DEVICE : COPO_OK;
 }
 
-// n_members = 0: one parameter set, `n_rows` rows.  n_members >= 1 (copo_mlp_forward_bank_f32): that many parameter sets
-// `member_stride` floats apart, `n_rows` rows EACH, the member as the grid's second dimension (policy net only, no row list).  The
-// variant rule below counts a member's rows, not the launch's: the two-tile variant rounds a few rows in ten thousand differently
-// from the one-tile variant (measured: 1 row of 16 536), and a member's rows must hold the bits of a launch of that member alone.
 static int mlp_forward(const copo_ppo_cfg* cfg, const float* theta, const float* theta_t, const float* obs_src,
                        const float* cc_src, int64_t n_rows, int32_t first_net, int32_t n_nets, float* values,
                        float* dist_inputs, const float* eps, float* action, float* logp, float* clipped,
@@ -403,47 +236,47 @@ static int mlp_forward(const copo_ppo_cfg* cfg, const float* theta, const float*
         return COPO_ERR_DIM;
     if (first_net + n_nets > 1 && !values) return COPO_ERR_NULL;
     if (first_net == 0 && eps && (!action || !logp)) return COPO_ERR_NULL;
-    const int H = cfg->hidden;
-    if (!(H == 64 || H == 128 || H == 256 || H == 512) || (reinterpret_cast<uintptr_t>(theta_t) & 15) != 0) return COPO_ERR_DIM;
+    Launch l;
+    rc = plan_forward(*cfg, n_rows, first_net, n_nets, n_members, aligned16(theta_t) ? FACT_MIRROR_ALIGNED : 0, &l);
+    if (rc != COPO_OK) return rc;
     if (gemm_lds_attrs() != hipSuccess) return COPO_ERR_DEVICE;
-    int kmax = 0;
-    const copo_net_layout* nets[4] = {&cfg->pol, &cfg->val[0], &cfg->val[1], &cfg->val[2]};
-    for (int g = first_net; g < first_net + n_nets; ++g) {
-        kmax = nets[g]->in_dim > kmax ? nets[g]->in_dim : kmax;
-        if (nets[g]->w1 % 4 != 0 || nets[g]->w2 % 4 != 0) return COPO_ERR_DIM;
+    FwdBankArgs a;      // (the single-member kernels take its FwdArgs base)
+    static_cast<FwdArgs&>(a) = FwdArgs{*cfg, theta, theta_t, obs_src, cc_src ? cc_src : obs_src, n_rows, first_net, n_nets, values, dist_inputs, eps,
+                                       action, logp, clipped, rows, rows ? n_out : n_rows};
+    a.member_stride = member_stride;
+    void* args[] = {static_cast<FwdArgs*>(&a)};
+    return launch_kernel(l, args, static_cast<hipStream_t>(stream)) == hipSuccess ? COPO_OK : COPO_ERR_DEVICE;
+}
+
+// ---- plan query (tests): what a configuration would launch; the device is not touched ---------------------------------
+extern "C" const char* copo_debug_learner_kernel(int32_t id, int32_t* block_out, int32_t* lds_cap_out) {
+    if (id < 0 || id >= K_COUNT) return nullptr;
+    if (block_out) *block_out = g_kernels[id].block;
+    if (lds_cap_out) *lds_cap_out = g_kernels[id].lds_cap;
+    return g_kernels[id].name;
+}
+
+extern "C" int copo_debug_learner_plan(const copo_ppo_cfg* cfg, int32_t mode, int32_t head_mode, int64_t n, int32_t world, int32_t facts,
+                                       int32_t first_net, int32_t n_nets, int32_t n_members, int32_t* out, int32_t cap) {
+    int rc = check_cfg(cfg);
+    if (rc != COPO_OK) return rc;
+    if (!out) return COPO_ERR_NULL;
+    if (mode < 0 || mode > PLAN_FORWARD || head_mode < COPO_HEAD_PPO || head_mode > COPO_HEAD_META_OLD || world < 1 || world > COPO_PEER_MAX_WORLD ||
+        n_members < 0 || n_members > 65535 || (mode >= PLAN_META_BATCH && mode < PLAN_FORWARD && (n < 1 || 2 * n > 65535)))
+        return COPO_ERR_DIM;
+    Plan p{};
+    if (mode == PLAN_FORWARD) {
+        if ((rc = plan_forward(*cfg, n, first_net, n_nets, n_members, facts, &p.l[0])) != COPO_OK) return rc;
+        p.n = 1;
+    } else {
+        p = plan_step(*cfg, (PlanMode)mode, head_mode, (int)n, world, facts, switches());
+        if (p.refused) return COPO_ERR_DEVICE;      // (what the entry points answer)
     }
-    // hidden 256 with at least two rounds of 256 workgroups of 32 rows per net: two 16-row tiles per workgroup (learn_rowpass.inc:
-    // RT).  Measured: the critic heads on 72 k rows 580 -> 478 us; a rollout step's 10 240 rows (320 workgroups of 32 rows on 256
-    // CUs) 39.5 -> 43.8 us, hence the threshold
-    const bool rt2 = H == 256 && n_rows >= 2 * 32 * 256 && rowpass_k1p(kmax) <= H;
-    const size_t lds = rt2 ? ((size_t)2 * 2 * HT * (H + 4) + 4 * H) * sizeof(float)
-                           : ((size_t)HT * (rowpass_k1p(kmax) + 4) + (size_t)2 * HT * (H + 4) + 4 * H) * sizeof(float);
-    if (lds > 150 * 1024) return COPO_ERR_DIM;
-    FwdArgs a{*cfg, theta, theta_t, obs_src, cc_src ? cc_src : obs_src, n_rows, first_net, n_nets, values, dist_inputs, eps,
-              action, logp, clipped, rows, rows ? n_out : n_rows};
-    const int rws = rt2 ? 2 * HT : HT;
-    const dim3 grid((unsigned)((n_rows + rws - 1) / rws), bank ? n_members : n_nets);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    FwdBankArgs b;
-    static_cast<FwdArgs&>(b) = a;
-    b.member_stride = member_stride;
-    const bool bf = cfg->operand_dtype == COPO_OPERAND_BF16;
-#define COPO_FWD(NT_, W_, RT_)                                                                                                       \
-        do {                                                                                                                        \
-            if (bank && bf) hipLaunchKernelGGL((mlp_fwd_kernel<NT_, W_, true, RT_, true>), grid, dim3(64 * W_), lds, st, b);          \
-            else if (bank) hipLaunchKernelGGL((mlp_fwd_kernel<NT_, W_, false, RT_, true>), grid, dim3(64 * W_), lds, st, b);          \
-            else if (bf) hipLaunchKernelGGL((mlp_fwd_kernel<NT_, W_, true, RT_>), grid, dim3(64 * W_), lds, st, a);                  \
-            else hipLaunchKernelGGL((mlp_fwd_kernel<NT_, W_, false, RT_>), grid, dim3(64 * W_), lds, st, a);                         \
-        } while (0)
-    if (rt2) COPO_FWD(2, 8, 2);
-    else switch (H) {
-        case 64: COPO_FWD(1, 4, 1); break;
-        case 128: COPO_FWD(2, 4, 1); break;
-        case 256: COPO_FWD(2, 8, 1); break;
-        default: COPO_FWD(4, 8, 1); break;
-    }
-#undef COPO_FWD
-    return hipGetLastError() == hipSuccess ? COPO_OK : COPO_ERR_DEVICE;
+    if (cap < 8 + 6 * p.n) return COPO_ERR_DIM;
+    const int32_t head[8] = {p.n, p.fold_blocks, p.n_fold, (int32_t)(p.lo & 0xffffffff), (int32_t)(p.lo >> 32), p.refresh_mirror, p.ksplit, p.wgrad_tiles};
+    memcpy(out, head, sizeof(head));
+    for (int i = 0; i < p.n; ++i) memcpy(out + 8 + 6 * i, &p.l[i], 6 * sizeof(int32_t));      // id, grid x / y / z, block, LDS bytes
+    return COPO_OK;
 }
 
 extern "C" int copo_mlp_forward_f32(const copo_ppo_cfg* cfg, const float* theta, const float* theta_t, const float* obs_src,
@@ -477,6 +310,16 @@ extern "C" int copo_transpose_weights_f32(const copo_ppo_cfg* cfg, const float* 
     return launch_refresh_transposed(*cfg, theta, theta_t, static_cast<hipStream_t>(stream)) == hipSuccess ? COPO_OK : COPO_ERR_DEVICE;
 }
 
+// the meta modes: both policies of the LCF meta update on the policy net
+static void fill_meta(FusedArgs& a, const copo_ppo_cfg* cfg, float* theta, float* theta_target, const float* obs_src, const float* pack_src,
+                      const int64_t* rows, const float* w, const float* denom, float* workspace, int64_t* mb_index) {
+    fill_common(a, cfg, obs_src, nullptr, pack_src, rows, w, denom, workspace, mb_index);
+    a.theta = theta; a.theta2 = theta_target; a.apply_adam = 0; a.head_mode = MODE_META_BOTH;
+}
+static void fill_meta_pair(FusedArgs& a, float* g_new, float* g_old, float* stats_new, float* stats_old, double* dot_partials) {
+    a.grad = g_new; a.grad2 = g_old; a.stats = stats_new; a.stats2 = stats_old; a.dot_partials = dot_partials;
+}
+
 extern "C" int copo_meta_grads_f32(const copo_ppo_cfg* cfg, float* theta, float* theta_target, float* g_new, float* g_old,
                                    const float* obs_src, const float* pack_src, const int64_t* rows, const float* w,
                                    const float* denom, float* workspace, float* stats_new, float* stats_old,
@@ -487,11 +330,9 @@ extern "C" int copo_meta_grads_f32(const copo_ppo_cfg* cfg, float* theta, float*
         !dot_partials)
         return COPO_ERR_NULL;
     FusedArgs a;
-    fill_common(a, cfg, obs_src, nullptr, pack_src, rows, w, denom, workspace, mb_index);
-    a.theta = theta; a.theta2 = theta_target; a.grad = g_new; a.grad2 = g_old;
-    a.stats = stats_new; a.stats2 = stats_old; a.apply_adam = 0; a.head_mode = MODE_META_BOTH; a.groups = 2;
-    a.dot_partials = dot_partials;
-    hipError_t e = launch_fused_step(a, static_cast<hipStream_t>(stream));
+    fill_meta(a, cfg, theta, theta_target, obs_src, pack_src, rows, w, denom, workspace, mb_index);
+    fill_meta_pair(a, g_new, g_old, stats_new, stats_old, dot_partials);
+    hipError_t e = launch_fused_step(a, PLAN_META_PAIR, 0, static_cast<hipStream_t>(stream));
     return e == hipSuccess ? COPO_OK : COPO_ERR_DEVICE;
 }
 
@@ -507,43 +348,39 @@ extern "C" int copo_meta_step_f64(const copo_ppo_cfg* cfg, float* theta, float* 
         !dot_partials || !eps || !lcf_param || !raw_mean_std || !tail || !adam_state)
         return COPO_ERR_NULL;
     FusedArgs a;
-    fill_common(a, cfg, obs_src, nullptr, pack_src, rows, w, denom, workspace, mb_index);
-    a.theta = theta; a.theta2 = theta_target; a.grad = g_new; a.grad2 = g_old;
-    a.stats = stats_new; a.stats2 = stats_old; a.apply_adam = 0; a.head_mode = MODE_META_BOTH; a.groups = 2;
-    a.dot_partials = dot_partials;
+    fill_meta(a, cfg, theta, theta_target, obs_src, pack_src, rows, w, denom, workspace, mb_index);
+    fill_meta_pair(a, g_new, g_old, stats_new, stats_old, dot_partials);
     MetaTail mt;
     mt.lcf = MetaArgs{pack_src, rows, w, denom, eps, mb_index, cfg->mb, cfg->pack_width, col_adv, col_nei_adv, lcf_param,
                       raw_mean_std, tail};
     mt.fin = MetaFinishArgs{g_new, g_old, 0, dot_partials, COPO_META_DOT_PARTIALS, tail, lcf_param, adam_state, lr, stats_new,
                             stats_old, stats, mb_index, (mb_index && bump_index) ? 1 : 0};
-    hipError_t e = launch_fused_step(a, static_cast<hipStream_t>(stream), &mt);
+    hipError_t e = launch_fused_step(a, PLAN_META_PAIR_TAIL, 0, static_cast<hipStream_t>(stream), FoldSink{nullptr, nullptr, nullptr, &mt});
     return e == hipSuccess ? COPO_OK : COPO_ERR_DEVICE;
 }
 
 // ---- batched LCF meta pass --------------------------------------------------------------------------------------
 static size_t batch_ws_base(const copo_ppo_cfg& c, int nb) {     // floats before the fp64 dot-partial scratch (kept even)
-    const int g = 2 * nb > 4 ? 2 * nb : 8;
-    const size_t t = WsLay(c, g, g).total();
+    const size_t t = WsLay(c, batch_gcap(nb), batch_gcap(nb)).total();
     return (t + 1) & ~(size_t)1;
 }
-static int batch_fold_blocks(const copo_ppo_cfg& c) {
-    int64_t lo;
-    int n;
-    fold_range(c, 1, &lo, &n);
-    return (n + 256 * FOLD_EPT - 1) / (256 * FOLD_EPT);
+// the fold geometry of the batched pass (it does not depend on nb or on the pointers)
+static Plan batch_fold_plan(const copo_ppo_cfg& c) {
+    return plan_step(c, PLAN_META_BATCH, COPO_HEAD_PPO, 1, 1, FACT_ALIGNED | FACT_STORE_OK, switches());
+}
+// a chunk of a batched pass: the layout is fixed by nb_cap, so that a short last chunk reuses the same (zero-padded) regions;
+// returns the fp64 dot-partial scratch behind it
+static double* fill_meta_batch(FusedArgs& a, int nb_cap, int64_t mb_first) {
+    a.gcap = a.nreg = batch_gcap(nb_cap);
+    a.k_first = mb_first;
+    return reinterpret_cast<double*>(a.ws + batch_ws_base(a.c, nb_cap));
 }
 
-extern "C" int64_t copo_meta_fold_len(const copo_ppo_cfg* cfg) {
-    if (!cfg) return -1;
-    int64_t lo;
-    int n;
-    fold_range(*cfg, 1, &lo, &n);
-    return n;
-}
+extern "C" int64_t copo_meta_fold_len(const copo_ppo_cfg* cfg) { return cfg ? batch_fold_plan(*cfg).n_fold : -1; }
 
 extern "C" int64_t copo_meta_batch_workspace_floats(const copo_ppo_cfg* cfg, int32_t nb) {
     if (!cfg || nb < 1) return -1;
-    return (int64_t)(batch_ws_base(*cfg, nb) + (size_t)2 * nb * batch_fold_blocks(*cfg));
+    return (int64_t)(batch_ws_base(*cfg, nb) + (size_t)2 * nb * batch_fold_plan(*cfg).fold_blocks);
 }
 
 extern "C" int copo_meta_batch_grads_f32(const copo_ppo_cfg* cfg, float* theta, float* theta_target, const float* obs_src,
@@ -557,28 +394,19 @@ extern "C" int copo_meta_batch_grads_f32(const copo_ppo_cfg* cfg, float* theta, 
     if (nb < 1 || nb > nb_cap || nb_cap > COPO_META_BATCH_MAX || mb_first < 0) return COPO_ERR_DIM;
     if ((reinterpret_cast<uintptr_t>(workspace) & 7) != 0) return COPO_ERR_DIM;
     FusedArgs a;
-    fill_common(a, cfg, obs_src, nullptr, pack_src, rows, w, denom, workspace, nullptr);
-    a.theta = theta; a.theta2 = theta_target; a.apply_adam = 0; a.head_mode = MODE_META_BOTH;
-    a.groups = 2 * nb;
-    a.gcap = a.nreg = 2 * nb_cap > 4 ? 2 * nb_cap : 8;   // > 4: the batched layout (see WsLay); fixed by nb_cap so that
-                                                         // a short last chunk reuses the same (zero-padded) regions
-    a.k_first = mb_first;
-    double* dot = reinterpret_cast<double*>(workspace + batch_ws_base(*cfg, nb_cap));
-    MetaBatch mbt{nb, g_out, dot, stats_out, 0};
-    int fb = 0;
-    hipError_t e = launch_fused_step(a, static_cast<hipStream_t>(stream), nullptr, &mbt, &fb, nullptr);
+    fill_meta(a, cfg, theta, theta_target, obs_src, pack_src, rows, w, denom, workspace, nullptr);
+    double* dot = fill_meta_batch(a, nb_cap, mb_first);
+    Plan p;
+    hipError_t e = launch_fused_step(a, PLAN_META_BATCH, nb, static_cast<hipStream_t>(stream), FoldSink{g_out, dot, stats_out, nullptr}, &p);
     if (e != hipSuccess) return COPO_ERR_DEVICE;
     hipLaunchKernelGGL(meta_batch_dot_kernel, dim3(nb), dim3(256), 0, static_cast<hipStream_t>(stream), dot, nullptr,
-                       (int64_t)fb, gv_out);
+                       (int64_t)p.fold_blocks, gv_out);
     return hipGetLastError() == hipSuccess ? COPO_OK : COPO_ERR_DEVICE;
 }
 
 // ---- meta row store: row-local quantities once per training iteration, regrouped by every meta pass ---------------
 static int rows_blocks(const copo_ppo_cfg& c, int64_t n_rows) { return (int)((n_rows + c.mb - 1) / c.mb); }
-static int rows_gcap(const copo_ppo_cfg& c, int64_t n_rows) {
-    const int g = 2 * rows_blocks(c, n_rows);
-    return g > 4 ? g : 8;
-}
+static int rows_gcap(const copo_ppo_cfg& c, int64_t n_rows) { return batch_gcap(rows_blocks(c, n_rows)); }
 
 extern "C" int64_t copo_meta_rows_workspace_floats(const copo_ppo_cfg* cfg, int64_t n_rows) {
     if (!cfg || n_rows < 1) return -1;
@@ -592,15 +420,12 @@ extern "C" int copo_meta_rows_f32(const copo_ppo_cfg* cfg, float* theta, float* 
     if (!theta || !theta_target || !obs_src || !pack_src || !rows_ws || !rowstat) return COPO_ERR_NULL;
     if (n_rows < 1 || 2 * rows_blocks(*cfg, n_rows) > 65535) return COPO_ERR_DIM;
     FusedArgs a;
-    fill_common(a, cfg, obs_src, nullptr, pack_src, nullptr, nullptr, nullptr, rows_ws, nullptr);
-    a.theta = theta; a.theta2 = theta_target; a.apply_adam = 0; a.head_mode = MODE_META_BOTH;
-    a.groups = 2 * rows_blocks(*cfg, n_rows);
+    fill_meta(a, cfg, theta, theta_target, obs_src, pack_src, nullptr, nullptr, nullptr, rows_ws, nullptr);
     a.gcap = rows_gcap(*cfg, n_rows);
     a.nreg = 0;
     a.identity_rows = n_rows;
     a.rowstat = rowstat;
-    MetaBatch mbt{a.groups / 2, nullptr, nullptr, nullptr, 1};
-    hipError_t e = launch_fused_step(a, static_cast<hipStream_t>(stream), nullptr, &mbt, nullptr, nullptr);
+    hipError_t e = launch_fused_step(a, PLAN_ROW_STORE, rows_blocks(*cfg, n_rows), static_cast<hipStream_t>(stream));
     return e == hipSuccess ? COPO_OK : COPO_ERR_DEVICE;
 }
 
@@ -614,22 +439,17 @@ extern "C" int copo_meta_batch_wgrads_f32(const copo_ppo_cfg* cfg, const float* 
     if (nb < 1 || nb > nb_cap || nb_cap > COPO_META_BATCH_MAX || mb_first < 0 || n_rows < 1) return COPO_ERR_DIM;
     if ((reinterpret_cast<uintptr_t>(workspace) & 7) != 0) return COPO_ERR_DIM;
     FusedArgs a;
-    fill_common(a, cfg, obs_src, nullptr, nullptr, rows, w, denom, workspace, nullptr);
-    a.apply_adam = 0; a.head_mode = MODE_META_BOTH;
-    a.groups = 2 * nb;
-    a.gcap = a.nreg = 2 * nb_cap > 4 ? 2 * nb_cap : 8;
-    a.k_first = mb_first;
+    fill_meta(a, cfg, nullptr, nullptr, obs_src, nullptr, rows, w, denom, workspace, nullptr);
+    double* dot = fill_meta_batch(a, nb_cap, mb_first);
     a.ws0 = rows_ws;
     a.gcap0 = rows_gcap(*cfg, n_rows);
     a.rowstat = const_cast<float*>(rowstat);
-    double* dot = reinterpret_cast<double*>(workspace + batch_ws_base(*cfg, nb_cap));
-    MetaBatch mbt{nb, g_out, dot, nullptr, 2};
-    int fb = 0;
+    Plan p;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    hipError_t e = launch_fused_step(a, st, nullptr, &mbt, &fb, nullptr);
+    hipError_t e = launch_fused_step(a, PLAN_ROW_WGRADS, nb, st, FoldSink{g_out, dot, nullptr, nullptr}, &p);
     if (e != hipSuccess) return COPO_ERR_DEVICE;
     if (stats_out) hipLaunchKernelGGL(meta_rowstat_kernel, dim3(nb), dim3(256), 0, st, a, mb_first, denom, stats_out);
-    hipLaunchKernelGGL(meta_batch_dot_kernel, dim3(nb), dim3(256), 0, st, dot, nullptr, (int64_t)fb, gv_out, denom + mb_first);
+    hipLaunchKernelGGL(meta_batch_dot_kernel, dim3(nb), dim3(256), 0, st, dot, nullptr, (int64_t)p.fold_blocks, gv_out, denom + mb_first);
     return hipGetLastError() == hipSuccess ? COPO_OK : COPO_ERR_DEVICE;
 }
 

@@ -1040,6 +1040,21 @@ int copo_debug_peer_allreduce_all_ranks(void* const* workspaces, int64_t n, int3
  * 16 phase stamps of one row-pass workgroup / [2][1024][2] start-end stamps per workgroup of the two kernels of a step */
 int copo_debug_rowpass_stamps(unsigned long long* out16);
 int copo_debug_wg_times(unsigned long long* out4096);
+/* test entries: the launch plan of the fused learner -- which kernels a configuration would launch, in order, computed by the code
+ * the entry points above launch from.  Pure host code: the device is not touched.
+ *   mode   0 PPO step, 1 PPO gradients only, 2 data-parallel step, 3 step-by-step meta pair, 4 the same with the LCF tail,
+ *          5 batched meta pass, 6 row store, 7 weight gradients from the row store (5..7: n = minibatches / row blocks of the launch),
+ *          8 forward pass (n = rows, nets [first_net, first_net + n_nets), n_members > 0: the bank forward with n rows per member)
+ *   head_mode   COPO_HEAD_* of modes 0..2;  world   data-parallel ranks (1: none)
+ *   facts  what the caller's pointers are: 1 sources, parameters and workspace 16-byte aligned, 2 transposed mirror given,
+ *          4 the mirror (with parameters and workspace) 16-byte aligned, 8 row store aligned with operand slabs below 4 GB
+ * out (HOST, cap int32): {launches, fold workgroups, fold length, fold offset low / high word, mirror refresh after the chain,
+ * row splits, weight-gradient workgroups}, then per launch {kernel id, grid x, y, z, workgroup size, dynamic LDS bytes}.
+ * A configuration the entry points refuse returns their code (COPO_ERR_DEVICE, or COPO_ERR_DIM for a forward shape).
+ * copo_debug_learner_kernel: name of a kernel id (NULL beyond the table), its workgroup size and dynamic-LDS ceiling. */
+int copo_debug_learner_plan(const copo_ppo_cfg* cfg, int32_t mode, int32_t head_mode, int64_t n, int32_t world, int32_t facts,
+                            int32_t first_net, int32_t n_nets, int32_t n_members, int32_t* out, int32_t cap);
+const char* copo_debug_learner_kernel(int32_t id, int32_t* block_out, int32_t* lds_cap_out);
 
 #ifdef __cplusplus
 }

@@ -70,6 +70,10 @@ def _copy_weights(dst, src):
     ("ippo", "none", 91, dict(hiddens=(128, 128), mb=200)),
     ("copo", "none", 92, dict(hiddens=(512, 512), mb=1000)),
     ("ccppo", "mf", 91, dict(hiddens=(48, 48), mb=72)),
+    # hidden 256 beyond 160 workgroups of 16 rows (4 nets need mb > 640): the 16-row tiles of rowpass_kernel<2, 8, true>, with the
+    # hand-over of layer 1 while every input is at most 128 wide, without it for the 260-wide observation
+    ("copo", "none", 92, dict(mb=1024)),
+    ("copo", "none", 260, dict(mb=1024)),
 ])
 def test_fused_sgd_matches_torch(name, fuse, odim, over):
     over = dict(over)
@@ -527,6 +531,7 @@ def test_plan_epoch_kernel_tables(B, B_all, mb):
     ("ippo", "none", 91, dict(hiddens=(128, 128))),
     ("ccppo", "mf", 91, {}),
     ("ccppo", "concat", 91, dict(hiddens=(64, 64))),
+    ("copo", "none", 92, dict(hiddens=(512, 512))),      # mlp_fwd_kernel<4, 8>
 ])
 def test_forward_kernel_matches_torch_models(name, fuse, odim, over):
     """copo_mlp_forward_f32 (rollout inference + dense value heads) == the torch modules: logits, sampled action,
