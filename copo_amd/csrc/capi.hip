@@ -10,6 +10,7 @@
 #include <cmath>
 
 #include "capi_common.h"
+#include "seat_common.h"
 
 using namespace copo;
 
@@ -460,6 +461,16 @@ extern "C" int copo_gae3_f32(const float* rew, const float* val, const uint8_t* 
     if (T < 0 || M < 0 || heads < 1 || heads > 4) return fail(COPO_ERR_DIM, "copo_gae3_f32: T=%d M=%d heads=%d", T, M, heads);
     if (T == 0 || M == 0) return COPO_OK;
     HIP_TRY(launch_gae3(rew, val, flags, T, M, heads, gamma, lam, adv, tgt, static_cast<hipStream_t>(stream)));
+    return COPO_OK;
+}
+
+extern "C" int copo_seat_tally(const uint8_t* flags, const float* rew, const int32_t* seat, const int32_t* group, int32_t E, int32_t N,
+                               int32_t K, int32_t G, int64_t* out, void* stream) {
+    if (!flags || !seat || !group || !out) return fail(COPO_ERR_NULL, "copo_seat_tally: NULL argument");
+    if (E < 0 || N < 1 || N > COPO_SEAT_MAX_SLOTS || K < 1 || K > 65535 || G < 1)
+        return fail(COPO_ERR_DIM, "copo_seat_tally: E=%d N=%d (1..%d) K=%d (1..65535) G=%d (>= 1)", E, N, COPO_SEAT_MAX_SLOTS, K, G);
+    if (E == 0) return COPO_OK;
+    HIP_TRY(launch_seat_tally(flags, rew, seat, group, E, N, K, G, out, static_cast<hipStream_t>(stream)));
     return COPO_OK;
 }
 

@@ -225,25 +225,29 @@ extern "C" int copo_dp_status(void* workspace, const copo_ppo_cfg* cfg, int32_t 
 static int mlp_forward(const copo_ppo_cfg* cfg, const float* theta, const float* theta_t, const float* obs_src,
                        const float* cc_src, int64_t n_rows, int32_t first_net, int32_t n_nets, float* values,
                        float* dist_inputs, const float* eps, float* action, float* logp, float* clipped,
-                       const int64_t* rows, int64_t n_out, void* stream, int32_t n_members = 0, int64_t member_stride = 0) {
+                       const int64_t* rows, int64_t n_out, void* stream, int32_t n_members = 0, int64_t member_stride = 0,
+                       const int32_t* counts = nullptr) {
     int rc = check_cfg(cfg);
     if (rc != COPO_OK) return rc;
     if (!theta || !theta_t || !obs_src) return COPO_ERR_NULL;
     if (rows && n_out < 1) return COPO_ERR_DIM;
     if (n_rows < 1 || first_net < 0 || n_nets < 1 || first_net + n_nets > 1 + cfg->n_value_heads) return COPO_ERR_DIM;
-    const bool bank = n_members > 0;
-    if (bank && (first_net != 0 || n_nets != 1 || rows || n_members > 65535 || member_stride < cfg->n_params || member_stride % 4 != 0))
+    const bool bank = n_members > 0, seats = counts != nullptr;      // seat mode: the bank with a row list per member (n_rows = cap)
+    if (bank && (first_net != 0 || n_nets != 1 || (rows != nullptr) != seats || n_members > 65535 || member_stride < cfg->n_params ||
+                 member_stride % 4 != 0))
         return COPO_ERR_DIM;
+    if (seats && !bank) return COPO_ERR_DIM;
     if (first_net + n_nets > 1 && !values) return COPO_ERR_NULL;
     if (first_net == 0 && eps && (!action || !logp)) return COPO_ERR_NULL;
     Launch l;
-    rc = plan_forward(*cfg, n_rows, first_net, n_nets, n_members, aligned16(theta_t) ? FACT_MIRROR_ALIGNED : 0, &l);
+    rc = plan_forward(*cfg, n_rows, first_net, n_nets, n_members, (aligned16(theta_t) ? FACT_MIRROR_ALIGNED : 0) | (seats ? FACT_SEATS : 0), &l);
     if (rc != COPO_OK) return rc;
     if (gemm_lds_attrs() != hipSuccess) return COPO_ERR_DEVICE;
     FwdBankArgs a;      // (the single-member kernels take its FwdArgs base)
     static_cast<FwdArgs&>(a) = FwdArgs{*cfg, theta, theta_t, obs_src, cc_src ? cc_src : obs_src, n_rows, first_net, n_nets, values, dist_inputs, eps,
                                        action, logp, clipped, rows, rows ? n_out : n_rows};
     a.member_stride = member_stride;
+    a.counts = counts;
     void* args[] = {static_cast<FwdArgs*>(&a)};
     return launch_kernel(l, args, static_cast<hipStream_t>(stream)) == hipSuccess ? COPO_OK : COPO_ERR_DEVICE;
 }
@@ -293,6 +297,16 @@ extern "C" int copo_mlp_forward_bank_f32(const copo_ppo_cfg* cfg, const float* t
     if (n_members < 1) return COPO_ERR_DIM;
     return mlp_forward(cfg, theta, theta_t, obs_src, nullptr, rows_per_member, 0, 1, nullptr, dist_inputs, eps, action, logp, clipped,
                        nullptr, rows_per_member, stream, n_members, member_stride);
+}
+
+extern "C" int copo_mlp_forward_seats_f32(const copo_ppo_cfg* cfg, const float* theta, const float* theta_t, int64_t member_stride,
+                                          int32_t n_members, const int64_t* rows, const int32_t* counts, int64_t cap, int64_t n_out,
+                                          const float* obs_src, float* dist_inputs, const float* eps, float* action, float* logp,
+                                          float* clipped, void* stream) {
+    if (!rows || !counts) return COPO_ERR_NULL;
+    if (n_members < 1 || cap < 1 || n_out < 1) return COPO_ERR_DIM;
+    return mlp_forward(cfg, theta, theta_t, obs_src, nullptr, cap, 0, 1, nullptr, dist_inputs, eps, action, logp, clipped, rows, n_out,
+                       stream, n_members, member_stride, counts);
 }
 
 extern "C" int copo_mlp_forward_rows_f32(const copo_ppo_cfg* cfg, const float* theta, const float* theta_t,

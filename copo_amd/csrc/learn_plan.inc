@@ -102,6 +102,7 @@ enum PlanFacts : int32_t {
     FACT_MIRROR = 2,            // transposed mirror present
     FACT_MIRROR_ALIGNED = 4,    // ... and it, the parameters and the workspace 16-byte aligned
     FACT_STORE_OK = 8,          // row store 16-byte aligned, every operand slab below 4 GB (32-bit byte offsets of the buffer loads)
+    FACT_SEATS = 16,            // PLAN_FORWARD of a bank: seat mode (copo_mlp_forward_seats_f32), `n_rows` is the lists' capacity
 };
 struct Plan {
     bool refused;               // the entry points answer COPO_ERR_DEVICE and launch nothing
@@ -191,6 +192,9 @@ static Plan plan_step(const copo_ppo_cfg& c, PlanMode mode, int head, int nb, in
 // grid's second dimension, `n_rows` rows EACH.  The variant rule counts a member's rows, not the launch's: the two-tile variant rounds a
 // few rows in ten thousand differently from the one-tile variant (measured: 1 row of 16 536), and a member's rows must hold the bits of
 // a launch of that member alone.
+// FACT_SEATS (copo_mlp_forward_seats_f32): every member owns a row list of up to `n_rows` rows.  How many it holds is known on the device
+// only, so the variant cannot follow it: seat mode always takes the one-tile variant, whatever the capacity, and a member's rows hold
+// the bits of the one-tile single-member kernel (at hidden 256: of a single-member launch of fewer than 2 * 32 * 256 rows).
 static int plan_forward(const copo_ppo_cfg& c, int64_t n_rows, int first_net, int n_nets, int n_members, int facts, Launch* out) {
     if (n_rows < 1 || first_net < 0 || n_nets < 1 || first_net + n_nets > 1 + c.n_value_heads) return COPO_ERR_DIM;
     const int H = c.hidden, sh = shape_index(H);
@@ -204,7 +208,9 @@ static int plan_forward(const copo_ppo_cfg& c, int64_t n_rows, int first_net, in
     // hidden 256 with at least two rounds of 256 workgroups of 32 rows per net: two 16-row tiles per workgroup (learn_rowpass.inc:
     // RT).  Measured: the critic heads on 72 k rows 580 -> 478 us; a rollout step's 10 240 rows (320 workgroups of 32 rows on 256
     // CUs) 39.5 -> 43.8 us, hence the threshold
-    const bool rt2 = H == 256 && n_rows >= 2 * 32 * 256 && rowpass_k1p(kmax) <= H;
+    const bool seats = (facts & FACT_SEATS) != 0;
+    if (seats && n_members < 1) return COPO_ERR_DIM;
+    const bool rt2 = !seats && H == 256 && n_rows >= 2 * 32 * 256 && rowpass_k1p(kmax) <= H;
     const size_t lds = rt2 ? ((size_t)2 * 2 * HT * (H + 4) + 4 * H) * sizeof(float)
                            : ((size_t)HT * (rowpass_k1p(kmax) + 4) + (size_t)2 * HT * (H + 4) + 4 * H) * sizeof(float);
     if (lds > (size_t)LDS_ROWPASS) return COPO_ERR_DIM;

@@ -949,8 +949,13 @@ struct FwdArgs {
 // [y R, (y + 1) R) of the sources and the outputs, R = n_rows = n_out, and the parameters `member_stride` floats into theta / theta_t
 // per member.  Tiles are counted per member, so no tile spans two members and a member's last tile is masked as the last tile of a
 // launch of its R rows alone.  Policy net only (first_net = 0, n_nets = 1), no row list, no values.
+// SEAT mode (copo_mlp_forward_seats_f32, `counts` given): member y owns the row list rows[y cap .. y cap + counts[y]) instead of a slice,
+// cap = n_rows of the launch; sources and outputs are the shared [n_out] arrays, read and written at the listed rows only.  A workgroup
+// whose first row is past counts[y] leaves before its first barrier (the test is uniform over the workgroup); from there on the
+// member's list is the row list of a single-member launch of counts[y] rows, last tile masked alike.
 struct FwdBankArgs : FwdArgs {
     int64_t member_stride;
+    const int32_t* counts;    // [n_members] on the device, or NULL: the dense bank
 };
 
 // RT: 16-row tiles per workgroup.  RT = 2 (launcher: hidden 256, enough rows to fill the chip) halves the weight bytes a row costs and
@@ -969,10 +974,17 @@ __global__ void __launch_bounds__(64 * WAVES, RT > 1 ? 4 : 1) mlp_fwd_kernel(std
         const size_t k = blockIdx.y, r0 = k * (size_t)a.n_rows;
         a.theta += k * a.member_stride;
         a.theta_t += k * a.member_stride;
-        a.obs_src += r0 * c.pol.in_dim;
-        if (a.dist_inputs) a.dist_inputs += r0 * 4;
-        if (a.eps) { a.eps += r0 * 2; a.action += r0 * 2; a.logp += r0; }
-        if (a.clipped) a.clipped += r0 * 2;
+        if (a.counts) {       // seat mode: the member's row list takes the slice's place
+            const int64_t n = a.counts[k] < a.n_rows ? a.counts[k] : a.n_rows;      // (a list holds `cap` rows at the most)
+            if ((int64_t)blockIdx.x * RWS >= n) return;
+            a.rows += r0;
+            a.n_rows = n;
+        } else {
+            a.obs_src += r0 * c.pol.in_dim;
+            if (a.dist_inputs) a.dist_inputs += r0 * 4;
+            if (a.eps) { a.eps += r0 * 2; a.action += r0 * 2; a.logp += r0; }
+            if (a.clipped) a.clipped += r0 * 2;
+        }
     }
     const int64_t m0 = (int64_t)blockIdx.x * RWS;
     const copo_net_layout L = g == 0 ? c.pol : c.val[g - 1];

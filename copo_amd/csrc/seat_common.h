@@ -1,0 +1,12 @@
+// Shared declaration of the seat tally (seat_kernels.hip) and its C entry point (capi.hip).
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+namespace copo {
+
+// cross-play: one step's flags / rewards folded per (scene group, bank member) into out[G][K][COPO_SEAT_WORDS] (one launch)
+hipError_t launch_seat_tally(const uint8_t* flags, const float* rew, const int32_t* seat, const int32_t* group, int32_t E, int32_t N,
+                             int32_t K, int32_t G, int64_t* out, hipStream_t stream);
+
+}  // namespace copo

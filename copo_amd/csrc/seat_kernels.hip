@@ -1,0 +1,86 @@
+// Seat tally (copo_seat_tally, include/copo_hip.h): one step's flags and rewards of scenes whose slots ("seats") belong to different
+// members of a policy bank, folded per (scene group, member) into eight int64 words.  Stateless, one launch, no allocation.
+//   one wave per scene, four scenes per 256-thread workgroup, slot = lane + 64 j (up to COPO_SEAT_MAX_SLOTS slots);
+//   per round of 64 slots the wave walks the members present in it: the first lane not yet served names a member, a ballot collects
+//   that member's lanes, popcounts give its counts and an integer butterfly its reward sum; lanes 0..7 then own the eight words and
+//   add the non-zero ones to the output with 64-bit integer atomics.
+// Every word is an integer (the reward in 2^-16 steps, rounded per row), so the sums do not depend on the order the device adds in.
+// The rules are restated as python loops by tests/crossplay_numpy.py.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "sim_common.h"
+#include "seat_common.h"
+
+namespace copo {
+
+namespace {
+
+constexpr int SCENES_PER_WG = 4;       // waves of a 256-thread workgroup
+
+// rint(min(max(r, -1024), 1024) * 65536): the clamp makes the product exact in fp32 (a power of two, no overflow), so the one rounding
+// is rintf's, half to even.  NaN counts as 0.
+__device__ inline int64_t seat_reward_q16(float r) {
+    if (r != r) return 0;
+    return (int64_t)rintf(fminf(fmaxf(r, -1024.0f), 1024.0f) * 65536.0f);
+}
+
+__device__ inline int64_t wave_sum_i64(int64_t v) {
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) {
+        const int32_t lo = __shfl_xor((int32_t)(uint32_t)((uint64_t)v & 0xffffffffu), o);
+        const int32_t hi = __shfl_xor((int32_t)(uint32_t)((uint64_t)v >> 32), o);
+        v += (int64_t)(((uint64_t)(uint32_t)hi << 32) | (uint64_t)(uint32_t)lo);
+    }
+    return v;
+}
+
+}  // namespace
+
+__global__ __launch_bounds__(256) void seat_tally_kernel(const uint8_t* __restrict__ flags, const float* __restrict__ rew,
+                                                         const int32_t* __restrict__ seat, const int32_t* __restrict__ group,
+                                                         int32_t E, int32_t N, int32_t K, int32_t G, int64_t* __restrict__ out) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int e = blockIdx.x * SCENES_PER_WG + wave;
+    if (e >= E) return;                        // (the whole wave; there is no barrier in this kernel)
+    const int g = group[e];
+    if (g < 0 || g >= G) return;               // (the whole wave)
+    for (int j = 0; 64 * j < N; ++j) {
+        const int n = lane + 64 * j;
+        const size_t idx = (size_t)e * N + (n < N ? n : 0);
+        const int s = n < N ? seat[idx] : -1;
+        const bool seated = s >= 0 && s < K;
+        const uint32_t f = seated ? (uint32_t)flags[idx] : 0u;
+        const bool acted = (f & COPO_F_ACTED) != 0u, done = acted && (f & COPO_F_DONE) != 0u;
+        const int64_t q = (rew && acted) ? seat_reward_q16(rew[idx]) : 0;
+        uint64_t todo = __ballot((f & (COPO_F_ACTED | COPO_F_SPAWNED)) != 0u);      // lanes with something to add; uniform over the wave
+        while (todo) {
+            const int m = __shfl(s, __ffsll((unsigned long long)todo) - 1);          // a served lane is seated: 0 <= m < K
+            const bool mine = seated && s == m;
+            todo &= ~__ballot(mine);
+            const int64_t qs = wave_sum_i64(mine ? q : 0);
+            const int c_acted = __popcll(__ballot(mine && acted)), c_done = __popcll(__ballot(mine && done));
+            const int c_arrive = __popcll(__ballot(mine && done && (f & COPO_F_ARRIVE) != 0u));
+            const int c_crash = __popcll(__ballot(mine && done && (f & COPO_F_CRASH) != 0u));
+            const int c_out = __popcll(__ballot(mine && done && (f & COPO_F_OUT) != 0u));
+            const int c_maxstep = __popcll(__ballot(mine && done && (f & COPO_F_MAXSTEP) != 0u));
+            const int c_spawned = __popcll(__ballot(mine && (f & COPO_F_SPAWNED) != 0u));
+            if (lane < COPO_SEAT_WORDS) {
+                const int64_t v = lane == COPO_SEAT_ACTED ? c_acted : lane == COPO_SEAT_DONE ? c_done : lane == COPO_SEAT_ARRIVE ? c_arrive
+                                : lane == COPO_SEAT_CRASH ? c_crash : lane == COPO_SEAT_OUT ? c_out : lane == COPO_SEAT_MAXSTEP ? c_maxstep
+                                : lane == COPO_SEAT_REWARD_Q16 ? qs : c_spawned;
+                if (v != 0)
+                    atomicAdd(reinterpret_cast<unsigned long long*>(out) + ((size_t)g * K + m) * COPO_SEAT_WORDS + lane, (unsigned long long)v);
+            }
+        }
+    }
+}
+
+hipError_t launch_seat_tally(const uint8_t* flags, const float* rew, const int32_t* seat, const int32_t* group, int32_t E, int32_t N,
+                             int32_t K, int32_t G, int64_t* out, hipStream_t stream) {
+    hipLaunchKernelGGL(seat_tally_kernel, dim3((E + SCENES_PER_WG - 1) / SCENES_PER_WG), dim3(256), 0, stream, flags, rew, seat, group, E, N, K,
+                       G, out);
+    return hipGetLastError();
+}
+
+}  // namespace copo

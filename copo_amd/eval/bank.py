@@ -83,6 +83,18 @@ class PolicyBank:
             dist_inputs.data_ptr(), eps.data_ptr(), action.data_ptr(), logp.data_ptr(),
             None if clipped is None else clipped.data_ptr(), self._capi.current_stream()))
 
+    def act_seats(self, plan_buffers, obs, eps, action, logp, dist_inputs, clipped=None):
+        """`FusedLearner.act` with a member per ROW (eval/crossplay.py): obs [n_out, O]; member k reads and writes the rows of its list
+        in `plan_buffers` (`crossplay.PlanBuffers`: rows [K][cap], counts [K] on the device), rows in no list are left alone."""
+        pb = plan_buffers
+        if pb.K != self.K or int(obs.shape[0]) != pb.n_out:
+            raise ValueError("PolicyBank.act_seats: a plan of %d members over %d rows for a bank of %d and %d rows" % (
+                pb.K, pb.n_out, self.K, int(obs.shape[0])))
+        self._capi.check(self._capi.lib.copo_mlp_forward_seats_f32(
+            C.byref(self.cfg), self.theta.data_ptr(), self.theta_t.data_ptr(), self.stride, self.K, pb.rows.data_ptr(), pb.counts.data_ptr(),
+            pb.cap, pb.n_out, obs.data_ptr(), dist_inputs.data_ptr(), eps.data_ptr(), action.data_ptr(), logp.data_ptr(),
+            None if clipped is None else clipped.data_ptr(), self._capi.current_stream()))
+
 
 class _BankPolicy:
     """What `VecSampler` reads of a policy, with the bank as its fused learner."""

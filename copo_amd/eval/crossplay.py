@@ -1,0 +1,239 @@
+"""Cross-play: the slots ("seats") of ONE scene driven by different members of a policy bank, and the outcomes folded per member.
+
+A `PolicyBank` gives every scene to one checkpoint.  Here a seat table [E][N] names, for every slot of every scene, the member that
+drives whatever agent sits in it (-1: nobody; the slot's action is left alone): CoPO next to IPPO in one scene, an early checkpoint
+next to a late one, one seed next to another.  Three pieces:
+
+* `SeatPlan` (numpy only, pure): the seat table turned into what the forward kernel reads -- per member the ascending list of its rows
+  e * N + n, the counts and the lists' capacity -- with the builders `pairs` (one scene group per ordered pair of members) and `uniform`
+  (whole scenes per member: the dense bank).
+* `SeatedBank` / `SeatSampler`: the bank in the policy's place of `VecSampler`, acting through `copo_mlp_forward_seats_f32` (the seat
+  mode of the bank kernels: the member is the grid's second dimension and owns a row list; always the one-tile kernel, so a member's
+  rows hold the bits `FusedLearner.act` writes for it below 2 * 32 * 256 rows), and after every simulator step `copo_seat_tally`,
+  which adds the step's flags and rewards to eight int64 words per (scene group, member).  Forward, step and tally of a fragment are
+  one captured graph where the sampler captures.
+* `cross_play_rows`: every ordered pair (focal, partner) of K populations on the same scenes, as a pandas frame.
+
+Rewards and termination are decided per agent in the simulator, so nothing there knows about seats.  One bank is one layout, as in
+`bank.py`: members of other observation widths are refused by `PolicyBank`.  LCF is out of scope: the simulator draws an agent's LCF
+from its SCENE's distribution (`VecSim.set_lcf_dist` / `set_lcf_table`), whichever member drives the slot; setting it is the caller's
+business, as with banks.
+"""
+import ctypes as C
+
+import numpy as np
+
+from ..trainer import VecSampler
+from .bank import _BankPolicy
+
+SEAT_WORDS = ("acted", "done", "arrive", "crash", "out", "maxstep", "reward_q16", "spawned")
+REWARD_SCALE = 65536.0
+
+
+class SeatPlan:
+    """`seat`: int [E][N], the member of every slot, -1 = nobody.  `n_members`: K (default: the largest member + 1); members beyond K
+    - 1 are refused.  Derived: `rows` int64 [K][cap], row e * N + n in the list of member seat[e][n], ascending, unused tail 0;
+    `counts` int32 [K]; `cap` = the largest count, at least 1.  `group`: int32 [E], the scene group of the tally (default: all 0) and
+    `n_groups`.  Nothing here touches a device."""
+
+    def __init__(self, seat, n_members=None, group=None, n_groups=None):
+        seat = np.ascontiguousarray(seat, np.int32)
+        if seat.ndim != 2 or seat.shape[0] < 1 or seat.shape[1] < 1:
+            raise ValueError("SeatPlan: seat table of shape %s, [E][N] wanted" % (seat.shape,))
+        top = int(seat.max())
+        K = max(top + 1, 1) if n_members is None else int(n_members)
+        if K < 1 or K > 65535 or top >= K or int(seat.min()) < -1:
+            raise ValueError("SeatPlan: members %d .. %d in a table for %d members (-1 = nobody)" % (int(seat.min()), top, K))
+        self.seat, self.E, self.N, self.K = seat, seat.shape[0], seat.shape[1], K
+        flat = seat.reshape(-1)
+        self.counts = np.bincount(flat[flat >= 0], minlength=K).astype(np.int32)
+        self.cap = max(int(self.counts.max()), 1)
+        self.rows = np.zeros((K, self.cap), np.int64)
+        for k in range(K):
+            self.rows[k, :self.counts[k]] = np.nonzero(flat == k)[0]
+        self.group = np.zeros(self.E, np.int32) if group is None else np.ascontiguousarray(group, np.int32)
+        if self.group.shape != (self.E,):
+            raise ValueError("SeatPlan: group of shape %s for %d scenes" % (self.group.shape, self.E))
+        self.n_groups = max(int(self.group.max()) + 1, 1) if n_groups is None else int(n_groups)
+        self.focal = self.partner = None
+        self.share = None
+
+    @classmethod
+    def pairs(cls, K, scenes_per_pair, N, share=0.5):
+        """One scene group per ORDERED pair (i, j) of K members, i = j included: group i * K + j holds scenes [g S, (g + 1) S), S =
+        `scenes_per_pair`; in each the first round(share * N) seats belong to the focal member i, the rest to the partner j."""
+        K, S, N = int(K), int(scenes_per_pair), int(N)
+        if K < 1 or S < 1 or N < 1 or not 0.0 <= float(share) <= 1.0:
+            raise ValueError("SeatPlan.pairs: K=%d scenes_per_pair=%d N=%d share=%r" % (K, S, N, share))
+        nf = int(round(float(share) * N))
+        seat = np.empty((K * K * S, N), np.int32)
+        pair = np.repeat(np.arange(K * K, dtype=np.int32), S)
+        seat[:, :nf] = (pair // K)[:, None]
+        seat[:, nf:] = (pair % K)[:, None]
+        plan = cls(seat, K, pair, K * K)
+        plan.focal, plan.partner = np.arange(K * K) // K, np.arange(K * K) % K
+        plan.share, plan.scenes_per_pair, plan.n_focal = float(share), S, nf
+        return plan
+
+    @classmethod
+    def uniform(cls, member_of_scene, N, n_members=None):
+        """Every seat of scene e belongs to member_of_scene[e]: with e // (E / K) the ownership of the dense bank.  Group = member."""
+        m = np.ascontiguousarray(member_of_scene, np.int32).reshape(-1)
+        return cls(np.repeat(m[:, None], int(N), axis=1), n_members, m, n_members)
+
+
+class PlanBuffers:
+    """A plan's tables on the device, uploaded once: what `PolicyBank.act_seats` and `seat_tally` read."""
+
+    def __init__(self, plan, device):
+        import torch
+        self.device = torch.device(device)
+        self.load(plan)
+
+    def load(self, plan):
+        import torch
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(self.device)  # noqa: E731
+        self.plan, self.K, self.cap, self.n_out, self.E, self.N, self.G = plan, plan.K, plan.cap, plan.E * plan.N, plan.E, plan.N, plan.n_groups
+        self.rows, self.counts, self.seat, self.group = up(plan.rows), up(plan.counts), up(plan.seat), up(plan.group)
+
+    def same_shape(self, plan):
+        return (plan.K, plan.cap, plan.E, plan.N, plan.n_groups) == (self.K, self.cap, self.E, self.N, self.G)
+
+    def copy_in(self, plan):
+        """`plan` into the existing tensors (same shapes): what a captured graph reads stays where it is."""
+        import torch
+        for dst, src in ((self.rows, plan.rows), (self.counts, plan.counts), (self.seat, plan.seat), (self.group, plan.group)):
+            dst.copy_(torch.from_numpy(np.ascontiguousarray(src)))
+        self.plan = plan
+
+
+def seat_tally(flags, rew, buffers, out):
+    """One step's `flags` uint8 [E][N] and `rew` float32 [E][N] (or None) added to `out` int64 [G][K][8] (`SEAT_WORDS`) by the plan's
+    seat and group tables.  `out` accumulates; the caller clears it.  One launch on the current stream."""
+    from .. import _capi
+    _capi.check(_capi.lib.copo_seat_tally(flags.data_ptr(), _capi.ptr(rew), buffers.seat.data_ptr(), buffers.group.data_ptr(), buffers.E,
+                                          buffers.N, buffers.K, buffers.G, out.data_ptr(), _capi.current_stream()))
+
+
+class SeatedBank:
+    """A `PolicyBank` with a seat plan: `.act` has `FusedLearner.act`'s signature over the [E * N] rows of the plan.  The plan's device
+    buffers are uploaded once; `set_plan` replaces them OUTSIDE captured graphs: a plan of the same shapes (K, cap, E, N, groups) is
+    copied into the buffers a captured graph reads, any other allocates new ones and calls `on_replace` (a sampler drops its graph)."""
+
+    def __init__(self, bank, plan):
+        if plan.K != bank.K:
+            raise ValueError("SeatedBank: a plan for %d members and a bank of %d" % (plan.K, bank.K))
+        self.bank, self.K = bank, bank.K
+        self.buffers = PlanBuffers(plan, bank.theta.device)
+        self.on_replace = []
+
+    @property
+    def plan(self):
+        return self.buffers.plan
+
+    @property
+    def can_forward(self):
+        return True
+
+    def invalidate_mirror(self):
+        self.bank.invalidate_mirror()
+
+    def sync_mirror(self):
+        self.bank.sync_mirror()
+
+    def set_plan(self, plan):
+        if plan.K != self.K:
+            raise ValueError("SeatedBank: a plan for %d members and a bank of %d" % (plan.K, self.K))
+        if self.buffers.same_shape(plan):
+            self.buffers.copy_in(plan)
+            return
+        self.buffers = PlanBuffers(plan, self.bank.theta.device)
+        for fn in self.on_replace:
+            fn()
+
+    def act(self, obs, eps, action, logp, dist_inputs, clipped=None):
+        self.bank.act_seats(self.buffers, obs, eps, action, logp, dist_inputs, clipped)
+
+
+class SeatSampler(VecSampler):
+    """`VecSampler` with a `SeatedBank` in the policy's place, as `BankSampler` puts a bank there, and the seat tally behind every
+    simulator step: `tally` int64 [groups][K][8] accumulates until `clear_tally()`.  Forward, step and tally of the fragment's T env
+    steps are one captured graph where the sampler captures.  Ordinary noise (every seat its own draw).  With a `pairs` plan `reset`
+    seeds the scenes start_seed + arange(scenes_per_pair), tiled over the pairs: every pair sees the same scenes."""
+
+    def __init__(self, vec_env, policy, bank, plan, T, use_graph=True):
+        import torch
+        if (plan.E, plan.N) != (vec_env.sim.E, vec_env.sim.N):
+            raise ValueError("SeatSampler: a plan of %d x %d seats for %d scenes of %d slots" % (plan.E, plan.N, vec_env.sim.E, vec_env.sim.N))
+        self.seated = SeatedBank(bank, plan)
+        super().__init__(vec_env, _BankPolicy(policy, self.seated), T, use_graph=use_graph, stagger_episodes=False)
+        self.seated.on_replace.append(self._loop.reset)
+        self.tally = torch.zeros(plan.n_groups, bank.K, len(SEAT_WORDS), dtype=torch.int64, device=self.device)
+
+    def set_plan(self, plan):
+        if plan.n_groups != self.seated.buffers.G:
+            raise ValueError("SeatSampler.set_plan: %d scene groups, the tally holds %d" % (plan.n_groups, self.seated.buffers.G))
+        self.seated.set_plan(plan)
+
+    def clear_tally(self):
+        self.tally.zero_()
+
+    def reset(self, seeds=None):
+        per = getattr(self.seated.plan, "scenes_per_pair", None)
+        if seeds is None and per:
+            seeds = np.tile(np.arange(per, dtype=np.uint64) + np.uint64(self.sim.cfg.start_seed), self.E // per)
+        super().reset(seeds)
+
+    def _rollout(self):
+        sim, EN = self.sim, self.E * self.N
+        lib, h, stream = sim._capi.lib, sim._h, sim._stream()
+        for t in range(self.T):
+            self.seated.act(self.obs[t].view(EN, self.O), self.eps[t].view(EN, 2), self.actions[t], self.logp[t], self.dist_inputs[t],
+                            self.clipped[t])
+            sim._capi.check(lib.copo_sim_step(h, self.clipped[t].data_ptr(), C.byref(self._outs[t]), stream))
+            seat_tally(self.flags[t], self.rew3[0, t], self.seated.buffers, self.tally)
+
+
+def tally_frame(tally, plan, labels=None):
+    """The tally [G][K][8] (numpy int64) of a `pairs` plan as a frame: one row per (pair group, member seated in it), the columns of
+    `cross_play_rows`."""
+    import pandas as pd
+    labels = list(range(plan.K)) if labels is None else list(labels)
+    rows = []
+    for g in range(plan.n_groups):
+        i, j = int(plan.focal[g]), int(plan.partner[g])
+        for k in ([i] if i == j else [i, j]):
+            w = [int(v) for v in tally[g, k]]
+            ratio = lambda a, b: float(a) / float(b) if b else float("nan")  # noqa: E731
+            rows.append(dict(focal=i, partner=j, member=k, label=labels[k], share=plan.share, **dict(zip(SEAT_WORDS, w)),
+                             success=ratio(w[2], w[1]), crash_rate=ratio(w[3], w[1]), out_rate=ratio(w[4], w[1]),
+                             reward_per_step=ratio(w[6] / REWARD_SCALE, w[0])))
+    return pd.DataFrame(rows)
+
+
+def cross_play_rows(algo, env, weights_list, share=0.5, scenes_per_pair=4, num_agents=40, steps=1000, seed=0, labels=None, **extra):
+    """Every ordered pair (focal i, partner j) of the K populations `weights_list` (one layout: one algorithm's observation) on
+    `scenes_per_pair` scenes each, the same scenes for every pair: the first round(share * num_agents) slots of a scene are driven by
+    i, the rest by j, for `steps` env steps (rounded up to whole fragments of the sampler).  Returns a pandas frame, one row per (pair
+    group, member seated in it): `focal`, `partner`, `member`, `label`, `share`, the eight raw words of the tally (`SEAT_WORDS`),
+    `success` = arrive / done, `crash_rate`, `out_rate`, `reward_per_step` = reward_q16 / 65536 / acted; NaN where a denominator is 0."""
+    from .bank import PolicyBank
+    from .evaluate import make_eval_trainer
+    weights_list = list(weights_list)
+    K = len(weights_list)
+    if K < 1:
+        raise ValueError("cross_play_rows: no members")
+    labels = list(range(K)) if labels is None else list(labels)
+    if len(labels) != K:
+        raise ValueError("%d labels for %d members" % (len(labels), K))
+    plan = SeatPlan.pairs(K, scenes_per_pair, num_agents, share)
+    t = make_eval_trainer(algo, env, plan.E, num_agents, seed, None, **extra)
+    try:
+        bank = PolicyBank(t.policy, weights_list)
+        smp = SeatSampler(t.env, t.policy, bank, plan, t.sampler.T, use_graph=t.config.get("use_hip_graphs", True))
+        for _ in range(-(-int(steps) // smp.T)):
+            smp.sample()
+        tally = smp.tally.cpu().numpy()
+    finally:
+        t.stop()
+    return tally_frame(tally, plan, labels)

@@ -277,7 +277,30 @@ def main():
     ap.add_argument("--scene-episodes", type=int, default=1)
     ap.add_argument("--recorder", default="torch", choices=["torch", "device"],
                     help="what folds the table: the torch recorder, or the device recorder (adds the SVO estimate columns)")
+    ap.add_argument("--cross-play", nargs="+", default=None, metavar="CKPT",
+                    help="checkpoints (.npz populations or Tune checkpoint files) of --algo's layout: every ordered pair shares scenes "
+                         "(eval/crossplay.py), one row per (pair, member) into --table")
+    ap.add_argument("--share", type=float, default=0.5, help="with --cross-play: the focal member's share of a scene's slots")
+    ap.add_argument("--scenes-per-pair", type=int, default=4)
+    ap.add_argument("--steps", type=int, default=1000, help="with --cross-play: env steps")
     a = ap.parse_args()
+    if a.cross_play:
+        if not a.table:
+            ap.error("--cross-play needs --table")
+        from .checkpoint_io import checkpoint_policy_weights
+        from .crossplay import cross_play_rows
+        ws = []
+        for path in a.cross_play:
+            if path.endswith(".npz"):
+                with np.load(path) as f:
+                    ws.append({k: f[k] for k in f.files})
+            else:
+                ws.append(checkpoint_policy_weights(path))
+        df = cross_play_rows("ippo" if a.algo == "cl" else a.algo, a.env, ws, share=a.share, scenes_per_pair=a.scenes_per_pair,
+                             num_agents=a.num_agents, steps=a.steps, labels=list(a.cross_play))
+        df.to_csv(a.table)
+        print(df.drop(columns=["label"]).to_string())
+        return
     if a.root:
         if not a.table:
             ap.error("--root needs --table")

@@ -424,6 +424,28 @@ int copo_rewind_fork(copo_rewind* h, copo_sim* target, int32_t first, int32_t S,
 int copo_rewind_tally(const uint8_t* flags, const int32_t* watch_slot, int32_t* tally, int32_t B, int32_t N, void* stream);
 int copo_rewind_destroy(copo_rewind* h);
 
+/* ---- seat tally (cross-play): one step's outcomes folded per (scene group, bank member).  Stateless.
+ * flags device [E][N] uint8 (a step's output), rew device [E][N] fp32 or NULL, seat device [E][N] int32 (the member that drives the
+ * slot), group device [E] int32, out device [G][K][COPO_SEAT_WORDS] int64.  A slot counts only where 0 <= seat < K, 0 <= group[e] < G
+ * and its flags carry COPO_F_ACTED.  Words: ACTED slot-steps; DONE; ARRIVE / CRASH / OUT / MAXSTEP among the rows with DONE (one
+ * count per set bit); REWARD_Q16 = the sum of rint(min(max(rew, -1024), 1024) * 65536) as int64 (NaN counts as 0; the product is
+ * exact in fp32 and rounded once, half to even; NULL rew adds nothing); SPAWNED = rows with COPO_F_SPAWNED and a valid seat and
+ * group, whether or not they acted.  `out` ACCUMULATES (the caller clears it): 64-bit integer atomic adds, so the result does not
+ * depend on the order.  One launch on the caller's stream, no allocation, no host synchronisation; may be captured in a graph.
+ * E >= 0, N in 1..COPO_SEAT_MAX_SLOTS, K in 1..65535, G >= 1 (COPO_ERR_DIM); a refused call launches nothing. */
+#define COPO_SEAT_WORDS 8
+#define COPO_SEAT_MAX_SLOTS 256
+#define COPO_SEAT_ACTED 0
+#define COPO_SEAT_DONE 1
+#define COPO_SEAT_ARRIVE 2
+#define COPO_SEAT_CRASH 3
+#define COPO_SEAT_OUT 4
+#define COPO_SEAT_MAXSTEP 5
+#define COPO_SEAT_REWARD_Q16 6
+#define COPO_SEAT_SPAWNED 7
+int copo_seat_tally(const uint8_t* flags, const float* rew, const int32_t* seat, const int32_t* group, int32_t E, int32_t N, int32_t K,
+                    int32_t G, int64_t* out, void* stream);
+
 /* ---- traffic field maps: where the scenes of a simulator drive, queue, crash and come close, summed on the device over scenes and
  *      records into integer grids.  A handle reads its simulator's state and must be destroyed before it.  Eager
  *      only.  Every accumulator is an integer, so the maps do not depend on the order the device adds in.
@@ -883,6 +905,22 @@ int copo_mlp_forward_f32(const copo_ppo_cfg* cfg, const float* theta, const floa
 int copo_mlp_forward_bank_f32(const copo_ppo_cfg* cfg, const float* theta, const float* theta_t, int64_t member_stride,
                               int32_t n_members, int64_t rows_per_member, const float* obs_src, float* dist_inputs,
                               const float* eps, float* action, float* logp, float* clipped, void* stream);
+/* SEAT mode of the bank (cross-play): every row ("seat") of the shared [n_out] sources and outputs may belong to any member.  Member k
+ * owns the row list rows[k * cap .. k * cap + counts[k]) (rows: device int64 [n_members][cap]; counts: device int32 [n_members], each in
+ * 0..cap, 0 is legal); it reads obs_src / eps at those rows, writes dist_inputs / action / logp / clipped at those rows and uses the
+ * parameters theta + k * member_stride.  Rows in no list are not written.  Row indices (0 <= row < n_out, no row twice) are the
+ * caller's contract, as in copo_mlp_forward_rows_f32.  Grid ceil(cap / 16) x n_members; a workgroup past its member's count leaves at
+ * once, a member's last tile is masked as the last tile of a launch of its rows alone.
+ * Variant: how many rows a member holds is known on the device only, so seat mode ALWAYS takes the one-tile kernel, also at hidden 256
+ * and whatever cap is.  A member's rows therefore hold the bits of the one-tile single-member kernel: what copo_mlp_forward_f32 writes
+ * for that member's parameters on its gathered rows at every hidden width -- at hidden 256 as long as that launch has fewer than
+ * 2 * 32 * 256 rows (from there on copo_mlp_forward_f32 takes the two-tile variant, which rounds a few rows in ten thousand
+ * differently).  NULL rows / counts: COPO_ERR_NULL; cap < 1, n_out < 1, n_members outside 1..65535 or a member_stride the bank entry
+ * refuses: COPO_ERR_DIM; a refused call launches nothing. */
+int copo_mlp_forward_seats_f32(const copo_ppo_cfg* cfg, const float* theta, const float* theta_t, int64_t member_stride,
+                               int32_t n_members, const int64_t* rows, const int32_t* counts, int64_t cap, int64_t n_out,
+                               const float* obs_src, float* dist_inputs, const float* eps, float* action, float* logp, float* clipped,
+                               void* stream);
 /* The same pass over a LIST of rows: launch row m reads row rows[m] of the sources ([n_src_rows][..]) and writes
  * values[net][rows[m]] (values is [n_nets][n_src_rows]; entries of unlisted rows are left alone).  The dense postprocess
  * of a rollout buffer uses it with the rows that hold an agent -- about half of the slots. */
