@@ -83,6 +83,10 @@ _SIGS = {
     "copo_mlp_forward_seats_f32": (C.c_int, [C.POINTER(PpoCfg), C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p,
                                              C.c_int64, C.c_int64] + [C.c_void_p] * 7),
     "copo_seat_tally": (C.c_int, [C.c_void_p] * 4 + [C.c_int32] * 4 + [C.c_void_p, C.c_void_p]),
+    "copo_fault_obs": (C.c_int, [C.c_void_p] * 2 + [C.c_int32] * 5 + [C.c_void_p] * 2 + [C.c_int32] * 2 + [C.c_void_p] * 2 + [C.c_int32, C.c_void_p,
+                                 C.c_uint64, C.c_void_p]),
+    "copo_fault_act": (C.c_int, [C.c_void_p] * 3 + [C.c_int32] * 2 + [C.c_void_p] * 2 + [C.c_int32] * 2 + [C.c_void_p] * 2 + [C.c_int32, C.c_void_p,
+                                 C.c_uint64, C.c_void_p]),
     "copo_adam_step_f32": (C.c_int, [C.POINTER(PpoCfg)] + [C.c_void_p] * 4 + [C.c_int64] + [C.c_void_p] * 5),
     "copo_meta_grads_f32": (C.c_int, [C.POINTER(PpoCfg)] + [C.c_void_p] * 15),
     "copo_meta_lcf_f64": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 4 + [C.c_int32] +

@@ -11,6 +11,7 @@
 
 #include "capi_common.h"
 #include "seat_common.h"
+#include "fault_common.h"
 
 using namespace copo;
 
@@ -471,6 +472,40 @@ extern "C" int copo_seat_tally(const uint8_t* flags, const float* rew, const int
         return fail(COPO_ERR_DIM, "copo_seat_tally: E=%d N=%d (1..%d) K=%d (1..65535) G=%d (>= 1)", E, N, COPO_SEAT_MAX_SLOTS, K, G);
     if (E == 0) return COPO_OK;
     HIP_TRY(launch_seat_tally(flags, rew, seat, group, E, N, K, G, out, static_cast<hipStream_t>(stream)));
+    return COPO_OK;
+}
+
+// what copo_fault_obs and copo_fault_act share: the keys of a row's level.  Every refusal is -1 with the entry point's name.
+static int check_fault(const char* name, int32_t E, int32_t N, const void* seat, const void* group, int32_t K, int32_t G,
+                       const void* level_of, const void* levels, int32_t L, const void* tick) {
+    if (!seat || !group || !level_of || !levels || !tick) return fail(COPO_ERR_NULL, "%s: NULL argument", name);
+    if (E < 0 || N < 1 || (int64_t)E * N > (int64_t(1) << 30) || K < 1 || K > 65535 || G < 1 || L < 1)
+        return fail(COPO_ERR_NULL, "%s: E=%d (>= 0) N=%d (>= 1, E N <= 2^30) K=%d (1..65535) G=%d (>= 1) L=%d (>= 1)", name, E, N, K, G, L);
+    return COPO_OK;
+}
+
+extern "C" int copo_fault_obs(const float* obs, float* obs_seen, int32_t E, int32_t N, int32_t O, int32_t col_lo, int32_t col_hi,
+                              const int32_t* seat, const int32_t* group, int32_t K, int32_t G, const int32_t* level_of,
+                              const uint32_t* levels, int32_t L, const int32_t* tick, uint64_t fault_seed, void* stream) {
+    if (!obs || !obs_seen) return fail(COPO_ERR_NULL, "copo_fault_obs: NULL argument");
+    if (obs == obs_seen) return fail(COPO_ERR_NULL, "copo_fault_obs: obs == obs_seen (the true observation is kept: give another buffer)");
+    if (const int rc = check_fault("copo_fault_obs", E, N, seat, group, K, G, level_of, levels, L, tick)) return rc;
+    if (O < 1 || col_lo < 0 || col_lo > col_hi || col_hi > O)
+        return fail(COPO_ERR_NULL, "copo_fault_obs: O=%d (>= 1) columns [%d, %d) (0 <= col_lo <= col_hi <= O)", O, col_lo, col_hi);
+    if (E == 0) return COPO_OK;
+    HIP_TRY(launch_fault_obs(obs, obs_seen, E, N, O, col_lo, col_hi, seat, group, K, G, level_of, levels, L, tick, fault_seed,
+                             static_cast<hipStream_t>(stream)));
+    return COPO_OK;
+}
+
+extern "C" int copo_fault_act(float* act, float* prev, const uint8_t* flags_prev, int32_t E, int32_t N, const int32_t* seat,
+                              const int32_t* group, int32_t K, int32_t G, const int32_t* level_of, const uint32_t* levels, int32_t L,
+                              int32_t* tick, uint64_t fault_seed, void* stream) {
+    if (!act || !prev) return fail(COPO_ERR_NULL, "copo_fault_act: NULL argument");
+    if (const int rc = check_fault("copo_fault_act", E, N, seat, group, K, G, level_of, levels, L, tick)) return rc;
+    if (E == 0) return COPO_OK;
+    HIP_TRY(launch_fault_act(act, prev, flags_prev, E, N, seat, group, K, G, level_of, levels, L, tick, fault_seed,
+                             static_cast<hipStream_t>(stream)));
     return COPO_OK;
 }
 

@@ -280,24 +280,46 @@ def main():
     ap.add_argument("--cross-play", nargs="+", default=None, metavar="CKPT",
                     help="checkpoints (.npz populations or Tune checkpoint files) of --algo's layout: every ordered pair shares scenes "
                          "(eval/crossplay.py), one row per (pair, member) into --table")
-    ap.add_argument("--share", type=float, default=0.5, help="with --cross-play: the focal member's share of a scene's slots")
-    ap.add_argument("--scenes-per-pair", type=int, default=4)
-    ap.add_argument("--steps", type=int, default=1000, help="with --cross-play: env steps")
+    ap.add_argument("--share", type=float, default=None,
+                    help="with --cross-play: the focal member's share of a scene's slots (default 0.5); with --fault-sweep: the impaired "
+                         "share (default 1: every slot)")
+    ap.add_argument("--scenes-per-pair", type=int, default=4, help="scenes per pair (--cross-play) or per cell (--fault-sweep)")
+    ap.add_argument("--steps", type=int, default=1000, help="with --cross-play / --fault-sweep: env steps")
+    ap.add_argument("--fault-sweep", nargs="+", default=None, metavar="CKPT",
+                    help="checkpoints of --algo's layout, each driven at every level of --fault-levels (eval/faults.py): one row per "
+                         "(checkpoint, level, role) into --table")
+    ap.add_argument("--fault-levels", default=None, metavar="JSON",
+                    help="with --fault-sweep: a JSON list of {lidar_sigma, lidar_dropout, dropout_value, act_sigma, sticky}; the first "
+                         "must be the identity {}")
     a = ap.parse_args()
-    if a.cross_play:
-        if not a.table:
-            ap.error("--cross-play needs --table")
+
+    def load_members(paths):
         from .checkpoint_io import checkpoint_policy_weights
-        from .crossplay import cross_play_rows
         ws = []
-        for path in a.cross_play:
+        for path in paths:
             if path.endswith(".npz"):
                 with np.load(path) as f:
                     ws.append({k: f[k] for k in f.files})
             else:
                 ws.append(checkpoint_policy_weights(path))
-        df = cross_play_rows("ippo" if a.algo == "cl" else a.algo, a.env, ws, share=a.share, scenes_per_pair=a.scenes_per_pair,
-                             num_agents=a.num_agents, steps=a.steps, labels=list(a.cross_play))
+        return ws
+    if a.fault_sweep:
+        if not a.table or not a.fault_levels:
+            ap.error("--fault-sweep needs --fault-levels and --table")
+        from .faults import fault_sweep_rows, load_levels
+        df = fault_sweep_rows("ippo" if a.algo == "cl" else a.algo, a.env, load_members(a.fault_sweep), load_levels(a.fault_levels),
+                              share=1.0 if a.share is None else a.share, scenes_per_cell=a.scenes_per_pair, num_agents=a.num_agents,
+                              steps=a.steps, labels=list(a.fault_sweep))
+        df.to_csv(a.table)
+        print(df.drop(columns=["label"]).to_string())
+        return
+    if a.cross_play:
+        if not a.table:
+            ap.error("--cross-play needs --table")
+        from .crossplay import cross_play_rows
+        ws = load_members(a.cross_play)
+        df = cross_play_rows("ippo" if a.algo == "cl" else a.algo, a.env, ws, share=0.5 if a.share is None else a.share,
+                             scenes_per_pair=a.scenes_per_pair, num_agents=a.num_agents, steps=a.steps, labels=list(a.cross_play))
         df.to_csv(a.table)
         print(df.drop(columns=["label"]).to_string())
         return

@@ -1,0 +1,307 @@
+"""Fault injection: noisy sensors and actuators in batched evaluation.
+
+Every policy of the evaluation pipeline sees a perfect LiDAR and every action reaches the wheels as chosen.  Here a fault LEVEL is
+chosen per (scene group, bank member), the keys of the seat tally (`crossplay.py`), and applied between the simulator and the policy:
+
+* `copo_fault_obs` writes what the policy sees, `obs_seen`, from the true observation: per LiDAR beam a dropout draw (the beam reads
+  `dropout_value`) or Gaussian-like noise of `lidar_sigma`, clamped to [0, 1]; every other column is copied.
+* `copo_fault_act` works on the clipped action the step will read: with probability `sticky` the action of the previous step is
+  repeated (only while the slot holds the agent it held a step ago), then noise of `act_sigma` per component, clamped to [-1, 1].
+
+The simulator, its oracle and the learner know nothing of this: a fault is not part of the scene.  The draws are the simulator's
+counter-based hash on (fault seed, row, the row's step count since `reset`, beam or component, stream), so a run does not depend on how
+its steps are cut into fragments or on whether they are replayed from a graph.  The normal stand-in `z` is the centred, scaled sum of
+four 16-bit uniform halves of two hashes: mean 0, variance 1, and its tails END at +-3.46 (|z| <= 131070 sqrt(3) / 65536): a level of
+`lidar_sigma` s never moves a beam by more than 3.47 s.
+
+Three pieces: `FaultLevel` / `FaultPlan` (numpy only), `FaultySeatSampler` (the `SeatSampler` with the two launches inside its captured
+fragment) and `fault_sweep_rows` (checkpoints x levels x roles as a pandas frame; `evaluate --fault-sweep`).
+"""
+import ctypes as C
+from dataclasses import dataclass
+
+import numpy as np
+
+from .crossplay import REWARD_SCALE, SEAT_WORDS, SeatPlan, SeatSampler, seat_tally
+
+LEVEL_WORDS = 8
+LEVEL_FIELDS = ("lidar_sigma", "lidar_dropout", "dropout_value", "act_sigma", "sticky")
+PROB_ONE = 1 << 24              # a Bernoulli draw is (hash >> 8) < rint(p * 2^24)
+
+
+@dataclass(frozen=True)
+class FaultLevel:
+    """One level of impairment.  `lidar_sigma`: standard deviation of the noise on every LiDAR beam (beams are in [0, 1], 1 = nothing
+    in range); `lidar_dropout`: probability per beam and step that the beam reads `dropout_value` instead; `act_sigma`: standard
+    deviation of the noise on each component of the clipped action; `sticky`: probability per step that the previous action is repeated.
+    `FaultLevel()` is the identity: rows at it pass through bit for bit."""
+    lidar_sigma: float = 0.0
+    lidar_dropout: float = 0.0
+    dropout_value: float = 0.0
+    act_sigma: float = 0.0
+    sticky: float = 0.0
+
+    def __post_init__(self):
+        for name in LEVEL_FIELDS:
+            v = getattr(self, name)
+            if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v):
+                raise ValueError("FaultLevel: %s = %r, a finite number wanted" % (name, v))
+            object.__setattr__(self, name, float(v))
+        for name in ("lidar_sigma", "act_sigma"):
+            if getattr(self, name) < 0.0:
+                raise ValueError("FaultLevel: %s = %r is negative" % (name, getattr(self, name)))
+        for name in ("lidar_dropout", "sticky"):
+            if not 0.0 <= getattr(self, name) <= 1.0:
+                raise ValueError("FaultLevel: %s = %r is no probability" % (name, getattr(self, name)))
+
+    @property
+    def is_identity(self):
+        return self.lidar_sigma == 0.0 and self.lidar_dropout == 0.0 and self.act_sigma == 0.0 and self.sticky == 0.0
+
+    def words(self):
+        """The level as the eight 32-bit words the kernels read."""
+        w = np.zeros(LEVEL_WORDS, np.uint32)
+        w[[0, 2, 3]] = np.array([self.lidar_sigma, self.dropout_value, self.act_sigma], np.float32).view(np.uint32)
+        w[1], w[4] = int(np.rint(self.lidar_dropout * PROB_ONE)), int(np.rint(self.sticky * PROB_ONE))
+        return w
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name in LEVEL_FIELDS}
+
+
+class FaultPlan:
+    """`levels`: a sequence of `FaultLevel` (or dicts of its fields); `level_of`: int [G][K], the level of bank member k in scene group g
+    (an index outside [0, L) leaves the member's rows alone).  Derived: `words` uint32 [L][8].  Nothing here touches a device."""
+
+    def __init__(self, levels, level_of):
+        self.levels = [lv if isinstance(lv, FaultLevel) else FaultLevel(**lv) for lv in levels]
+        if not self.levels:
+            raise ValueError("FaultPlan: no levels")
+        self.level_of = np.ascontiguousarray(level_of, np.int32)
+        if self.level_of.ndim != 2 or self.level_of.shape[0] < 1 or self.level_of.shape[1] < 1:
+            raise ValueError("FaultPlan: level_of of shape %s, [groups][members] wanted" % (self.level_of.shape,))
+        self.L, (self.G, self.K) = len(self.levels), self.level_of.shape
+        self.words = np.stack([lv.words() for lv in self.levels])
+        self.checkpoint = self.level = None
+        self.share = None
+
+    def check(self, seat_plan):
+        if (seat_plan.n_groups, seat_plan.K) != (self.G, self.K):
+            raise ValueError("FaultPlan: level_of is %d groups x %d members, the seat plan has %d x %d" % (
+                self.G, self.K, seat_plan.n_groups, seat_plan.K))
+        return self
+
+    @classmethod
+    def sweep(cls, K, levels, scenes_per_cell, N, share=1.0):
+        """(seat plan, fault plan) of K checkpoints x L levels: one scene group per cell, group k * L + l = scenes [g S, (g + 1) S), S =
+        `scenes_per_cell`.  share == 1: every slot of the cell is member k at level l, a bank of K members.  share < 1: the bank holds
+        every checkpoint TWICE, members k and K + k with the same weights (`sweep_members`); the first round(share * N) slots are member
+        K + k at level l, the rest member k at level 0, which must then be the identity: the tally keeps the impaired and the healthy
+        drivers of a scene apart.  The seat plan carries `scenes_per_pair` = S, so `SeatSampler.reset` gives every cell the same scenes."""
+        levels = [lv if isinstance(lv, FaultLevel) else FaultLevel(**lv) for lv in levels]
+        K, S, N, L, share = int(K), int(scenes_per_cell), int(N), len(levels), float(share)
+        if K < 1 or S < 1 or N < 1 or L < 1 or not 0.0 <= share <= 1.0:
+            raise ValueError("FaultPlan.sweep: K=%d levels=%d scenes_per_cell=%d N=%d share=%r" % (K, L, S, N, share))
+        doubled = share < 1.0
+        if doubled and not levels[0].is_identity:
+            raise ValueError("FaultPlan.sweep: with share < 1 the healthy seats drive at level 0, which must be the identity")
+        n_imp = int(round(share * N))
+        cell = np.repeat(np.arange(K * L, dtype=np.int32), S)
+        k_of, l_of = np.arange(K * L) // L, np.arange(K * L) % L
+        seat = np.empty((K * L * S, N), np.int32)
+        seat[:, :n_imp] = ((cell // L) + (K if doubled else 0))[:, None]
+        seat[:, n_imp:] = (cell // L)[:, None]
+        KB = 2 * K if doubled else K
+        level_of = np.zeros((K * L, KB), np.int32)
+        level_of[np.arange(K * L), k_of + (K if doubled else 0)] = l_of
+        seats = SeatPlan(seat, KB, cell, K * L)
+        seats.scenes_per_pair = S
+        faults = cls(levels, level_of)
+        faults.checkpoint, faults.level, faults.share = k_of, l_of, share
+        faults.n_checkpoints, faults.doubled, faults.n_impaired, faults.scenes_per_cell = K, doubled, n_imp, S
+        return seats, faults
+
+
+def sweep_members(weights_list, faults):
+    """The bank of a `sweep` plan: the checkpoints, twice where the plan doubles them."""
+    weights_list = list(weights_list)
+    return weights_list + weights_list if faults.doubled else weights_list
+
+
+def lidar_columns(cfg):
+    """[col_lo, col_hi) of the LiDAR block in the observation row of a `SimConfig`."""
+    lo = int(cfg.ego_dim) + int(cfg.navi_dim)
+    return lo, lo + int(cfg.num_lasers)
+
+
+class FaultBuffers:
+    """A fault plan's tables on the device."""
+
+    def __init__(self, faults, device):
+        import torch
+        self.faults, self.L, self.G, self.K = faults, faults.L, faults.G, faults.K
+        self.level_of = torch.from_numpy(faults.level_of).to(device)
+        self.words = torch.from_numpy(faults.words.view(np.int32)).to(device)      # (bits; torch has no uint32 arithmetic to need)
+
+    def same_shape(self, faults):
+        return (faults.L, faults.G, faults.K) == (self.L, self.G, self.K)
+
+    def copy_in(self, faults):
+        import torch
+        self.level_of.copy_(torch.from_numpy(faults.level_of))
+        self.words.copy_(torch.from_numpy(faults.words.view(np.int32)))
+        self.faults = faults
+
+
+def fault_obs(obs, obs_seen, col_lo, col_hi, plan_buffers, fault_buffers, tick, fault_seed):
+    """`copo_fault_obs` on the current stream: obs [E N][O] -> obs_seen."""
+    from .. import _capi
+    pb, fb = plan_buffers, fault_buffers
+    _capi.check(_capi.lib.copo_fault_obs(obs.data_ptr(), obs_seen.data_ptr(), pb.E, pb.N, int(obs.shape[-1]), col_lo, col_hi, pb.seat.data_ptr(),
+                                         pb.group.data_ptr(), pb.K, pb.G, fb.level_of.data_ptr(), fb.words.data_ptr(), fb.L, tick.data_ptr(),
+                                         fault_seed, _capi.current_stream()))
+
+
+def fault_act(act, prev, flags_prev, plan_buffers, fault_buffers, tick, fault_seed):
+    """`copo_fault_act` on the current stream: act [E N][2] in place; `flags_prev` = the previous step's flags or None."""
+    from .. import _capi
+    pb, fb = plan_buffers, fault_buffers
+    _capi.check(_capi.lib.copo_fault_act(act.data_ptr(), prev.data_ptr(), _capi.ptr(flags_prev), pb.E, pb.N, pb.seat.data_ptr(),
+                                         pb.group.data_ptr(), pb.K, pb.G, fb.level_of.data_ptr(), fb.words.data_ptr(), fb.L, tick.data_ptr(),
+                                         fault_seed, _capi.current_stream()))
+
+
+class FaultySeatSampler(SeatSampler):
+    """`SeatSampler` with faults: per env step fault_obs, the seated forward on `obs_seen[t]`, fault_act on `clipped[t]`, the simulator
+    step, the seat tally -- the whole fragment is still one captured graph.  The batch's `obs` stays the TRUE observation, so recorders
+    and observers are unaffected; `obs_seen` [T][E][N][O] (also `batch["obs_seen"]`) is what the policy was given.  `actions` and `logp`
+    are the policy's own, `clipped` is what reached the simulator.
+
+    State: `prev` [E][N][2] (the action that reached the simulator a step ago), `tick` int32 [E N] (steps since `reset`, the draws'
+    counter).  The previous step's flags are `flags[t - 1]`; for t = 0 they are `flags[T - 1]`, which still holds the last step of the
+    previous fragment.  `reset` zeroes `tick`, `prev` and `flags[T - 1]`: flags of zero say that nobody acted, so nothing sticks in the
+    first step, as if no flags were given."""
+
+    def __init__(self, vec_env, policy, bank, plan, faults, T, use_graph=True, fault_seed=0):
+        import torch
+        faults.check(plan)
+        super().__init__(vec_env, policy, bank, plan, T, use_graph=use_graph)
+        self.fault_seed = int(fault_seed) & (2 ** 64 - 1)
+        self.col_lo, self.col_hi = lidar_columns(self.sim.cfg)
+        if not 0 <= self.col_lo <= self.col_hi <= self.O:
+            raise ValueError("FaultySeatSampler: LiDAR columns [%d, %d) of an observation of %d" % (self.col_lo, self.col_hi, self.O))
+        self.fault_buffers = FaultBuffers(faults, self.device)
+        self.obs_seen = torch.zeros(self.T, self.E, self.N, self.O, dtype=torch.float32, device=self.device)
+        self.prev = torch.zeros(self.E, self.N, 2, dtype=torch.float32, device=self.device)
+        self.tick = torch.zeros(self.E * self.N, dtype=torch.int32, device=self.device)
+
+    @property
+    def faults(self):
+        return self.fault_buffers.faults
+
+    def set_faults(self, faults):
+        """Another fault plan, OUTSIDE captured graphs: the same shapes (levels, groups, members) are copied into the tables the captured
+        fragment reads, other shapes allocate new ones and drop the graph."""
+        faults.check(self.seated.plan)
+        if self.fault_buffers.same_shape(faults):
+            self.fault_buffers.copy_in(faults)
+            return
+        self.fault_buffers = FaultBuffers(faults, self.device)
+        self._loop.reset()
+
+    def reset(self, seeds=None):
+        super().reset(seeds)
+        self.tick.zero_()
+        self.prev.zero_()
+        self.flags[self.T - 1].zero_()
+
+    def _draw_noise(self):
+        """Ordinary noise; with a `sweep` plan the first cell's draw is copied to every cell, as `BankSampler` copies one member's: the
+        cells already share their scene seeds, so at the identity level two cells differ by their checkpoint only.  (The fault draws
+        themselves are keyed by the absolute row, so two impaired cells never share those.)"""
+        self.eps.normal_()
+        per = getattr(self.faults, "scenes_per_cell", None)
+        if per and self.E > per and self.E % per == 0:
+            cells = self.eps.view(self.T, self.E // per, per, self.N, 2)
+            cells[:, 1:].copy_(cells[:, :1])
+
+    def sample(self):
+        batch = super().sample()
+        batch["obs_seen"] = self.obs_seen
+        return batch
+
+    def _rollout(self):
+        sim, EN = self.sim, self.E * self.N
+        lib, h, stream = sim._capi.lib, sim._h, sim._stream()
+        pb, fb = self.seated.buffers, self.fault_buffers
+        for t in range(self.T):
+            fault_obs(self.obs[t], self.obs_seen[t], self.col_lo, self.col_hi, pb, fb, self.tick, self.fault_seed)
+            self.seated.act(self.obs_seen[t].view(EN, self.O), self.eps[t].view(EN, 2), self.actions[t], self.logp[t], self.dist_inputs[t],
+                            self.clipped[t])
+            fault_act(self.clipped[t], self.prev, self.flags[t - 1 if t else self.T - 1], pb, fb, self.tick, self.fault_seed)
+            sim._capi.check(lib.copo_sim_step(h, self.clipped[t].data_ptr(), C.byref(self._outs[t]), stream))
+            seat_tally(self.flags[t], self.rew3[0, t], pb, self.tally)
+
+
+def sweep_frame(tally, seats, faults, labels=None):
+    """The tally [G][K][8] (numpy int64) of a `sweep` plan as a frame: one row per (checkpoint, level, role), the columns of
+    `fault_sweep_rows`."""
+    import pandas as pd
+    labels = list(range(faults.n_checkpoints)) if labels is None else list(labels)
+    K, N, n_imp = faults.n_checkpoints, seats.N, faults.n_impaired
+    ratio = lambda a, b: float(a) / float(b) if b else float("nan")  # noqa: E731
+    rows = []
+    for g in range(seats.n_groups):
+        k, lv = int(faults.checkpoint[g]), int(faults.level[g])
+        roles = ([("impaired", k + K if faults.doubled else k, lv)] if n_imp > 0 else []) + ([("healthy", k, 0)] if n_imp < N else [])
+        for role, member, own in roles:
+            w = [int(v) for v in tally[g, member]]
+            rows.append(dict(checkpoint=k, label=labels[k], level=lv, role=role, member=member, share=faults.share, seats=n_imp if role == "impaired"
+                             else N - n_imp, own_level=own, **faults.levels[lv].as_dict(), **dict(zip(SEAT_WORDS, w)), success=ratio(w[2], w[1]),
+                             crash_rate=ratio(w[3], w[1]), out_rate=ratio(w[4], w[1]), reward_per_step=ratio(w[6] / REWARD_SCALE, w[0])))
+    return pd.DataFrame(rows)
+
+
+def fault_sweep_rows(algo, env, weights_list, levels, share=1.0, scenes_per_cell=4, num_agents=40, steps=1000, seed=0, labels=None,
+                     fault_seed=None, **extra):
+    """K populations `weights_list` (one layout) x the fault `levels` (level 0 must be the identity, so that every table carries its
+    own baseline), `scenes_per_cell` scenes per cell, the same scenes and the same action noise for every cell, for `steps` env steps
+    (rounded up to whole fragments).  The first round(share * num_agents) slots of a scene are impaired at the cell's level, the rest are healthy drivers of
+    the same checkpoint (`FaultPlan.sweep`).  Returns a pandas frame, one row per (checkpoint, level, role): `checkpoint`, `label`,
+    `level`, `role` ("impaired" / "healthy"; a role without seats has no row), `member`, `share`, `seats`, `own_level` (the level the
+    row's drivers are at: 0 for the healthy), the five parameters of the CELL's level, the eight raw words of the seat tally and
+    `success`, `crash_rate`, `out_rate`, `reward_per_step` as in `cross_play_rows`.  `fault_seed` defaults to `seed`."""
+    from .bank import PolicyBank
+    from .evaluate import make_eval_trainer
+    weights_list = list(weights_list)
+    K = len(weights_list)
+    if K < 1:
+        raise ValueError("fault_sweep_rows: no members")
+    levels = [lv if isinstance(lv, FaultLevel) else FaultLevel(**lv) for lv in levels]
+    if not levels or not levels[0].is_identity:
+        raise ValueError("fault_sweep_rows: level 0 must be the identity FaultLevel(), the table's own baseline")
+    labels = list(range(K)) if labels is None else list(labels)
+    if len(labels) != K:
+        raise ValueError("%d labels for %d members" % (len(labels), K))
+    seats, faults = FaultPlan.sweep(K, levels, scenes_per_cell, num_agents, share)
+    t = make_eval_trainer(algo, env, seats.E, num_agents, seed, None, **extra)
+    try:
+        bank = PolicyBank(t.policy, sweep_members(weights_list, faults))
+        smp = FaultySeatSampler(t.env, t.policy, bank, seats, faults, t.sampler.T, use_graph=t.config.get("use_hip_graphs", True),
+                                fault_seed=seed if fault_seed is None else fault_seed)
+        for _ in range(-(-int(steps) // smp.T)):
+            smp.sample()
+        tally = smp.tally.cpu().numpy()
+    finally:
+        t.stop()
+    return sweep_frame(tally, seats, faults, labels)
+
+
+def load_levels(path):
+    """A JSON list of objects with `FaultLevel`'s fields (missing fields are 0) -> [FaultLevel]."""
+    import json
+    with open(path) as f:
+        raw = json.load(f)
+    if not isinstance(raw, list) or not all(isinstance(r, dict) for r in raw):
+        raise ValueError("%s: a JSON list of objects wanted" % path)
+    return [FaultLevel(**r) for r in raw]

@@ -446,6 +446,37 @@ int copo_rewind_destroy(copo_rewind* h);
 int copo_seat_tally(const uint8_t* flags, const float* rew, const int32_t* seat, const int32_t* group, int32_t E, int32_t N, int32_t K,
                     int32_t G, int64_t* out, void* stream);
 
+/* ---- fault injection: noisy sensors between the simulator's observation and the policy, noisy and sticky
+ *      actuators between the policy's action and the simulator.  Two stateless entry points; each is one launch on the caller's stream,
+ *      allocates nothing and reads nothing on the host, so both may be captured in a graph.  The simulator knows nothing of them.
+ * Keys: seat device [E][N] int32 and group device [E] int32 are the tables of the seat tally; level_of device [G][K] int32; levels device
+ * [L][COPO_FAULT_LEVEL_WORDS] 32-bit words: [0] f32 lidar_sigma, [1] u32 dropout_thr, [2] f32 dropout_value, [3] f32 act_sigma, [4] u32
+ * sticky_thr, [5..7] zero; a threshold is rint(p * 2^24) for a probability p.  Row r = e N + n has level level_of[group[e]][seat[e][n]];
+ * where the seat is outside [0, K), the group outside [0, G) or the level outside [0, L) the row passes through unchanged, bit for bit.
+ * Draws: every one is hash_rng(fault_seed, r, tick[r], c, stream) of the simulator's counter-based generator on streams it does not use
+ * (32..37, csrc/fault_common.h); tick device [E N] int32 is the caller's.  A Bernoulli draw is (h >> 8) < thr.  The standard-normal
+ * stand-in z of two hashes: S = the sum of their four 16-bit halves, z = ((float)S - 131070.0f) * (float)(sqrt(3) / 65536): conversion
+ * and subtraction exact, the product rounded once; mean 0, variance 1 - 2^-32, |z| <= 3.4641 (the tails END there).  A clamp to [lo, hi]
+ * is v < lo ? lo : (v > hi ? hi : v); every product and sum is rounded on its own.
+ * Both refuse with -1 and their name in copo_last_error(): a NULL pointer (flags_prev may be NULL), obs == obs_seen, E < 0, N < 1, O < 1,
+ * E N > 2^30, not 0 <= col_lo <= col_hi <= O, K outside 1..65535, G < 1, L < 1.  A refused call launches nothing; E == 0 is COPO_OK.
+ *
+ * copo_fault_obs: obs device [E N][O] fp32 -> obs_seen (another buffer of that shape; every column is written).  Column c of
+ * [col_lo, col_hi) is beam b = c - col_lo: if the dropout draw (r, tick, b) fires the value is dropout_value; else, if lidar_sigma != 0,
+ * clamp(x + lidar_sigma * z(r, tick, b), 0, 1); else x.  Every other column is copied.  tick is read only.
+ * copo_fault_act: act device [E N][2] fp32, the clipped action the step will read, in place.  If flags_prev (device [E N] uint8, the
+ * PREVIOUS step's flags) is given and the row's previous flags carry COPO_F_ACTED and none of COPO_F_DONE, COPO_F_SPAWNED,
+ * COPO_F_ENV_RESET -- the slot holds the agent it held a step ago -- and the sticky draw (r, tick) fires, act = prev[r].  Then, if
+ * act_sigma != 0, component j becomes clamp(a + act_sigma * z(r, tick, j), -1, 1).  Then, for EVERY row, pass-through rows included,
+ * prev[r] = act (device [E N][2] fp32) and tick[r] += 1: the tick is the number of steps since the caller cleared it. */
+#define COPO_FAULT_LEVEL_WORDS 8
+int copo_fault_obs(const float* obs, float* obs_seen, int32_t E, int32_t N, int32_t O, int32_t col_lo, int32_t col_hi,
+                   const int32_t* seat, const int32_t* group, int32_t K, int32_t G, const int32_t* level_of, const uint32_t* levels,
+                   int32_t L, const int32_t* tick, uint64_t fault_seed, void* stream);
+int copo_fault_act(float* act, float* prev, const uint8_t* flags_prev, int32_t E, int32_t N, const int32_t* seat, const int32_t* group,
+                   int32_t K, int32_t G, const int32_t* level_of, const uint32_t* levels, int32_t L, int32_t* tick, uint64_t fault_seed,
+                   void* stream);
+
 /* ---- traffic field maps: where the scenes of a simulator drive, queue, crash and come close, summed on the device over scenes and
  *      records into integer grids.  A handle reads its simulator's state and must be destroyed before it.  Eager
  *      only.  Every accumulator is an integer, so the maps do not depend on the order the device adds in.
