@@ -8,6 +8,11 @@ one step per env step.  Every member sees the same scene seeds and the same acti
 with `VecSim.set_lcf_table`, their LCF distribution) only.
 
 One bank is one layout: members of other observation widths or algorithms belong to another bank (`evaluate.sweep_trials` groups by it).
+
+The samplers of `eval/` keep no rollout loop of their own.  `VecSampler._rollout` is the one loop, `for t: _act(t); _step(t)`, with three
+hooks: `_policy_obs(t)` (what the policy reads), `_act(t)` (the forward) and `_step(t)` (the simulator step).  `BankSampler` overrides
+none of them: `_BankPolicy` puts the bank where `_act` looks for the fused learner.  Two helpers that every sampler here shares also live
+in this module: `replica_seeds` (replicas of S scenes see the same scenes) and `DeviceTables` (tables that a captured graph reads).
 """
 import ctypes as C
 
@@ -103,6 +108,46 @@ class _BankPolicy:
         self.fused, self.config, self.device = bank, {"use_fused_inference": True}, policy.device
 
 
+class DeviceTables:
+    """Tables of a numpy-only `source` (a plan) on the device, where a captured graph may read them.  A subclass declares `tables(source)`
+    -> (named numpy arrays, shape key) and `KEY`, the names under which the key's entries become attributes.  `replace` is the one
+    protocol, OUTSIDE captured graphs: a source of the same shape key is copied into the existing tensors (their addresses are what a
+    graph holds), any other key allocates new tensors and calls the `on_replace` callbacks (a sampler drops its graph)."""
+    KEY = ()
+
+    def __init__(self, source, device):
+        self.device, self.on_replace = torch.device(device), []
+        self.load(source)
+
+    def load(self, source):
+        arrays, key = self.tables(source)
+        self.key, self.source = tuple(key), source
+        for name, v in zip(self.KEY, self.key):
+            setattr(self, name, v)
+        for name, a in arrays.items():
+            setattr(self, name, torch.from_numpy(np.ascontiguousarray(a)).to(self.device, copy=True))      # (never the source's own memory)
+
+    def same_shape(self, key):
+        return tuple(key) == self.key
+
+    def copy_in(self, source):
+        for name, a in self.tables(source)[0].items():
+            getattr(self, name).copy_(torch.from_numpy(np.ascontiguousarray(a)))
+        self.source = source
+
+    def replace(self, source):
+        if self.same_shape(self.tables(source)[1]):
+            return self.copy_in(source)
+        self.load(source)
+        for fn in self.on_replace:
+            fn()
+
+
+def replica_seeds(start_seed, S, E):
+    """Scene seeds start_seed + arange(S), tiled E // S times: scenes [r S, (r + 1) S) of every replica r are the same scenes."""
+    return np.tile(np.arange(S, dtype=np.uint64) + np.uint64(start_seed), E // S)
+
+
 def members_of_scenes(num_envs, n_members):
     """Scenes per member; scene e belongs to member e // that."""
     if n_members < 1 or num_envs % n_members:
@@ -122,7 +167,7 @@ class BankSampler(VecSampler):
 
     def reset(self, seeds=None):
         if seeds is None:
-            seeds = np.tile(np.arange(self.per_member, dtype=np.uint64) + np.uint64(self.sim.cfg.start_seed), self.bank.K)
+            seeds = replica_seeds(self.sim.cfg.start_seed, self.per_member, self.E)
         super().reset(seeds)
 
     def _draw_noise(self):

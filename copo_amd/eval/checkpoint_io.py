@@ -72,6 +72,18 @@ def checkpoint_policy_weights(ckpt, policy_name="default"):
     return {k: v for k, v in weights.items() if k != "_optimizer_variables" and "value" not in k}
 
 
+def load_members(paths):
+    """One weights dict per path: an `.npz` population as it is, anything else as a Tune checkpoint file."""
+    ws = []
+    for path in paths:
+        if path.endswith(".npz"):
+            with np.load(path) as f:
+                ws.append({k: f[k] for k in f.files})
+        else:
+            ws.append(checkpoint_policy_weights(path))
+    return ws
+
+
 def get_policy_function_from_checkpoint(algo, ckpt, deterministic=False, policy_name="default"):
     weights = checkpoint_policy_weights(ckpt, policy_name)
     # the key layout decides the reader (this build's own checkpoints are torch-layout for every algorithm); the `_1`

@@ -11,7 +11,8 @@ next to a late one, one seed next to another.  Three pieces:
   mode of the bank kernels: the member is the grid's second dimension and owns a row list; always the one-tile kernel, so a member's
   rows hold the bits `FusedLearner.act` writes for it below 2 * 32 * 256 rows), and after every simulator step `copo_seat_tally`,
   which adds the step's flags and rewards to eight int64 words per (scene group, member).  Forward, step and tally of a fragment are
-  one captured graph where the sampler captures.
+  one captured graph where the sampler captures.  The loop is `VecSampler._rollout`: `_BankPolicy` makes its `_act` call
+  `SeatedBank.act`, and `SeatSampler._step` is the base's step followed by the tally.
 * `cross_play_rows`: every ordered pair (focal, partner) of K populations on the same scenes, as a pandas frame.
 
 Rewards and termination are decided per agent in the simulator, so nothing there knows about seats.  One bank is one layout, as in
@@ -19,12 +20,10 @@ Rewards and termination are decided per agent in the simulator, so nothing there
 from its SCENE's distribution (`VecSim.set_lcf_dist` / `set_lcf_table`), whichever member drives the slot; setting it is the caller's
 business, as with banks.
 """
-import ctypes as C
-
 import numpy as np
 
 from ..trainer import VecSampler
-from .bank import _BankPolicy
+from .bank import DeviceTables, _BankPolicy, replica_seeds
 
 SEAT_WORDS = ("acted", "done", "arrive", "crash", "out", "maxstep", "reward_q16", "spawned")
 REWARD_SCALE = 65536.0
@@ -34,9 +33,10 @@ class SeatPlan:
     """`seat`: int [E][N], the member of every slot, -1 = nobody.  `n_members`: K (default: the largest member + 1); members beyond K
     - 1 are refused.  Derived: `rows` int64 [K][cap], row e * N + n in the list of member seat[e][n], ascending, unused tail 0;
     `counts` int32 [K]; `cap` = the largest count, at least 1.  `group`: int32 [E], the scene group of the tally (default: all 0) and
-    `n_groups`.  Nothing here touches a device."""
+    `n_groups`.  `replica_scenes` = S declares that scenes [r S, (r + 1) S) of every replica r are the same scenes (`SeatSampler.reset`
+    seeds them so); None: every scene its own.  Nothing here touches a device."""
 
-    def __init__(self, seat, n_members=None, group=None, n_groups=None):
+    def __init__(self, seat, n_members=None, group=None, n_groups=None, replica_scenes=None):
         seat = np.ascontiguousarray(seat, np.int32)
         if seat.ndim != 2 or seat.shape[0] < 1 or seat.shape[1] < 1:
             raise ValueError("SeatPlan: seat table of shape %s, [E][N] wanted" % (seat.shape,))
@@ -55,6 +55,9 @@ class SeatPlan:
         if self.group.shape != (self.E,):
             raise ValueError("SeatPlan: group of shape %s for %d scenes" % (self.group.shape, self.E))
         self.n_groups = max(int(self.group.max()) + 1, 1) if n_groups is None else int(n_groups)
+        self.replica_scenes = None if replica_scenes is None else int(replica_scenes)
+        if self.replica_scenes is not None and (self.replica_scenes < 1 or self.E % self.replica_scenes):
+            raise ValueError("SeatPlan: replicas of %d scenes in %d scenes" % (self.replica_scenes, self.E))
         self.focal = self.partner = None
         self.share = None
 
@@ -70,9 +73,9 @@ class SeatPlan:
         pair = np.repeat(np.arange(K * K, dtype=np.int32), S)
         seat[:, :nf] = (pair // K)[:, None]
         seat[:, nf:] = (pair % K)[:, None]
-        plan = cls(seat, K, pair, K * K)
+        plan = cls(seat, K, pair, K * K, replica_scenes=S)
         plan.focal, plan.partner = np.arange(K * K) // K, np.arange(K * K) % K
-        plan.share, plan.scenes_per_pair, plan.n_focal = float(share), S, nf
+        plan.share, plan.n_focal = float(share), nf
         return plan
 
     @classmethod
@@ -82,29 +85,15 @@ class SeatPlan:
         return cls(np.repeat(m[:, None], int(N), axis=1), n_members, m, n_members)
 
 
-class PlanBuffers:
+class PlanBuffers(DeviceTables):
     """A plan's tables on the device, uploaded once: what `PolicyBank.act_seats` and `seat_tally` read."""
+    KEY = ("K", "cap", "E", "N", "G")
+    plan = property(lambda self: self.source)
+    n_out = property(lambda self: self.E * self.N)
 
-    def __init__(self, plan, device):
-        import torch
-        self.device = torch.device(device)
-        self.load(plan)
-
-    def load(self, plan):
-        import torch
-        up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(self.device)  # noqa: E731
-        self.plan, self.K, self.cap, self.n_out, self.E, self.N, self.G = plan, plan.K, plan.cap, plan.E * plan.N, plan.E, plan.N, plan.n_groups
-        self.rows, self.counts, self.seat, self.group = up(plan.rows), up(plan.counts), up(plan.seat), up(plan.group)
-
-    def same_shape(self, plan):
-        return (plan.K, plan.cap, plan.E, plan.N, plan.n_groups) == (self.K, self.cap, self.E, self.N, self.G)
-
-    def copy_in(self, plan):
-        """`plan` into the existing tensors (same shapes): what a captured graph reads stays where it is."""
-        import torch
-        for dst, src in ((self.rows, plan.rows), (self.counts, plan.counts), (self.seat, plan.seat), (self.group, plan.group)):
-            dst.copy_(torch.from_numpy(np.ascontiguousarray(src)))
-        self.plan = plan
+    @staticmethod
+    def tables(plan):
+        return dict(rows=plan.rows, counts=plan.counts, seat=plan.seat, group=plan.group), (plan.K, plan.cap, plan.E, plan.N, plan.n_groups)
 
 
 def seat_tally(flags, rew, buffers, out):
@@ -117,15 +106,16 @@ def seat_tally(flags, rew, buffers, out):
 
 class SeatedBank:
     """A `PolicyBank` with a seat plan: `.act` has `FusedLearner.act`'s signature over the [E * N] rows of the plan.  The plan's device
-    buffers are uploaded once; `set_plan` replaces them OUTSIDE captured graphs: a plan of the same shapes (K, cap, E, N, groups) is
-    copied into the buffers a captured graph reads, any other allocates new ones and calls `on_replace` (a sampler drops its graph)."""
+    buffers are uploaded once; `set_plan` replaces them OUTSIDE captured graphs by `DeviceTables.replace`: a plan of the same shapes (K,
+    cap, E, N, groups) is copied into the tensors a captured graph reads, any other allocates new ones and calls `on_replace` (a sampler
+    drops its graph)."""
 
     def __init__(self, bank, plan):
         if plan.K != bank.K:
             raise ValueError("SeatedBank: a plan for %d members and a bank of %d" % (plan.K, bank.K))
         self.bank, self.K = bank, bank.K
         self.buffers = PlanBuffers(plan, bank.theta.device)
-        self.on_replace = []
+        self.on_replace = self.buffers.on_replace
 
     @property
     def plan(self):
@@ -144,12 +134,7 @@ class SeatedBank:
     def set_plan(self, plan):
         if plan.K != self.K:
             raise ValueError("SeatedBank: a plan for %d members and a bank of %d" % (plan.K, self.K))
-        if self.buffers.same_shape(plan):
-            self.buffers.copy_in(plan)
-            return
-        self.buffers = PlanBuffers(plan, self.bank.theta.device)
-        for fn in self.on_replace:
-            fn()
+        self.buffers.replace(plan)
 
     def act(self, obs, eps, action, logp, dist_inputs, clipped=None):
         self.bank.act_seats(self.buffers, obs, eps, action, logp, dist_inputs, clipped)
@@ -158,8 +143,8 @@ class SeatedBank:
 class SeatSampler(VecSampler):
     """`VecSampler` with a `SeatedBank` in the policy's place, as `BankSampler` puts a bank there, and the seat tally behind every
     simulator step: `tally` int64 [groups][K][8] accumulates until `clear_tally()`.  Forward, step and tally of the fragment's T env
-    steps are one captured graph where the sampler captures.  Ordinary noise (every seat its own draw).  With a `pairs` plan `reset`
-    seeds the scenes start_seed + arange(scenes_per_pair), tiled over the pairs: every pair sees the same scenes."""
+    steps are one captured graph where the sampler captures.  Ordinary noise (every seat its own draw).  A plan that declares
+    `replica_scenes` = S (`pairs` does) has `reset` seed the scenes `replica_seeds(start_seed, S, E)`: every pair sees the same scenes."""
 
     def __init__(self, vec_env, policy, bank, plan, T, use_graph=True):
         import torch
@@ -179,19 +164,23 @@ class SeatSampler(VecSampler):
         self.tally.zero_()
 
     def reset(self, seeds=None):
-        per = getattr(self.seated.plan, "scenes_per_pair", None)
-        if seeds is None and per:
-            seeds = np.tile(np.arange(per, dtype=np.uint64) + np.uint64(self.sim.cfg.start_seed), self.E // per)
+        S = self.seated.plan.replica_scenes
+        if seeds is None and S:
+            seeds = replica_seeds(self.sim.cfg.start_seed, S, self.E)
         super().reset(seeds)
 
-    def _rollout(self):
-        sim, EN = self.sim, self.E * self.N
-        lib, h, stream = sim._capi.lib, sim._h, sim._stream()
-        for t in range(self.T):
-            self.seated.act(self.obs[t].view(EN, self.O), self.eps[t].view(EN, 2), self.actions[t], self.logp[t], self.dist_inputs[t],
-                            self.clipped[t])
-            sim._capi.check(lib.copo_sim_step(h, self.clipped[t].data_ptr(), C.byref(self._outs[t]), stream))
-            seat_tally(self.flags[t], self.rew3[0, t], self.seated.buffers, self.tally)
+    def _step(self, t):
+        super()._step(t)
+        seat_tally(self.flags[t], self.rew3[0, t], self.seated.buffers, self.tally)
+
+
+def tally_rates(words):
+    """The derived columns of one tally cell (the eight `SEAT_WORDS`): `success` = arrive / done, `crash_rate`, `out_rate`,
+    `reward_per_step` = reward_q16 / 65536 / acted; NaN where a denominator is 0."""
+    w = dict(zip(SEAT_WORDS, (int(v) for v in words)))
+    ratio = lambda a, b: float(a) / float(b) if b else float("nan")  # noqa: E731
+    return dict(success=ratio(w["arrive"], w["done"]), crash_rate=ratio(w["crash"], w["done"]), out_rate=ratio(w["out"], w["done"]),
+                reward_per_step=ratio(w["reward_q16"] / REWARD_SCALE, w["acted"]))
 
 
 def tally_frame(tally, plan, labels=None):
@@ -204,10 +193,7 @@ def tally_frame(tally, plan, labels=None):
         i, j = int(plan.focal[g]), int(plan.partner[g])
         for k in ([i] if i == j else [i, j]):
             w = [int(v) for v in tally[g, k]]
-            ratio = lambda a, b: float(a) / float(b) if b else float("nan")  # noqa: E731
-            rows.append(dict(focal=i, partner=j, member=k, label=labels[k], share=plan.share, **dict(zip(SEAT_WORDS, w)),
-                             success=ratio(w[2], w[1]), crash_rate=ratio(w[3], w[1]), out_rate=ratio(w[4], w[1]),
-                             reward_per_step=ratio(w[6] / REWARD_SCALE, w[0])))
+            rows.append(dict(focal=i, partner=j, member=k, label=labels[k], share=plan.share, **dict(zip(SEAT_WORDS, w)), **tally_rates(w)))
     return pd.DataFrame(rows)
 
 
@@ -218,22 +204,14 @@ def cross_play_rows(algo, env, weights_list, share=0.5, scenes_per_pair=4, num_a
     group, member seated in it): `focal`, `partner`, `member`, `label`, `share`, the eight raw words of the tally (`SEAT_WORDS`),
     `success` = arrive / done, `crash_rate`, `out_rate`, `reward_per_step` = reward_q16 / 65536 / acted; NaN where a denominator is 0."""
     from .bank import PolicyBank
-    from .evaluate import make_eval_trainer
+    from .evaluate import check_labels, eval_session, graph_flag, run_steps
     weights_list = list(weights_list)
     K = len(weights_list)
     if K < 1:
         raise ValueError("cross_play_rows: no members")
-    labels = list(range(K)) if labels is None else list(labels)
-    if len(labels) != K:
-        raise ValueError("%d labels for %d members" % (len(labels), K))
+    labels = check_labels(labels, K)
     plan = SeatPlan.pairs(K, scenes_per_pair, num_agents, share)
-    t = make_eval_trainer(algo, env, plan.E, num_agents, seed, None, **extra)
-    try:
-        bank = PolicyBank(t.policy, weights_list)
-        smp = SeatSampler(t.env, t.policy, bank, plan, t.sampler.T, use_graph=t.config.get("use_hip_graphs", True))
-        for _ in range(-(-int(steps) // smp.T)):
-            smp.sample()
-        tally = smp.tally.cpu().numpy()
-    finally:
-        t.stop()
+    with eval_session(algo, env, plan.E, num_agents, seed, **extra) as t:
+        smp = SeatSampler(t.env, t.policy, PolicyBank(t.policy, weights_list), plan, t.sampler.T, use_graph=graph_flag(t))
+        tally = run_steps(smp, steps).tally.cpu().numpy()
     return tally_frame(tally, plan, labels)

@@ -11,6 +11,7 @@ checkpoints of one algorithm and scene drive their scenes of ONE simulator batch
     python -m copo_amd.eval.evaluate --root path/to/experiment --num-episodes 20 --table sweep.csv
 """
 import argparse
+import contextlib
 import json
 
 import numpy as np
@@ -24,16 +25,20 @@ _SCENE_OF = (("Roundabout", "MultiAgentRoundaboutEnv", "Round"), ("Intersection"
              ("Tollgate", "MultiAgentTollgateEnv", "Tollgate"))
 
 
+def scene_of(env_name, *error):
+    """(wrapper class name, short scene name) of an RLlib env name; an unknown one raises ValueError(*error)."""
+    for needle, cls_name, short in _SCENE_OF:
+        if needle in env_name:
+            return cls_name, short
+    raise ValueError(*error)
+
+
 def get_env(env, should_wrap_copo_env, should_wrap_cc_env, svo_mean=0.0, svo_std=0.0):
     """(RecorderEnv(single-scene env), short scene name) from an RLlib env name, as `copo/eval.py:27-64` builds it: the
     CoPO env gets the population's LCF distribution, the CC env only the neighbour lists."""
     from copo_amd.torch_copo.utils import env_wrappers as W
     from .recoder import RecorderEnv
-    for needle, cls_name, short in _SCENE_OF:
-        if needle in env:
-            break
-    else:
-        raise ValueError()
+    cls_name, short = scene_of(env)
     cls = getattr(W, cls_name)
     if should_wrap_copo_env:
         assert should_wrap_cc_env is False
@@ -80,24 +85,67 @@ def make_eval_trainer(algo, env, num_envs=64, num_agents=40, seed=0, lcf=None, *
     return t
 
 
+@contextlib.contextmanager
+def eval_session(algo, env, num_envs, num_agents, seed, lcf=None, weights=None, **extra):
+    """One evaluation session: `make_eval_trainer`, with the population `weights` loaded where given (and the fused learner's mirror in
+    step with them), yielded, and stopped whatever the body did."""
+    t = make_eval_trainer(algo, env, num_envs, num_agents, seed, lcf, **extra)
+    try:
+        if weights is not None:
+            from .checkpoint_io import load_policy_weights
+            load_policy_weights(t.policy.model, weights)
+            if t.policy.fused is not None:
+                t.policy.fused.sync_mirror()
+        yield t
+    finally:
+        t.stop()
+
+
+def graph_flag(t):
+    """Whether a sampler built next to trainer `t`'s own captures its fragment."""
+    return t.config.get("use_hip_graphs", True)
+
+
+def record_scene_episodes(smp, scene_episodes, horizon):
+    """Fragments of `smp` folded by a `DeviceRecorder` until every scene has finished `scene_episodes` whole episodes (or six times their
+    length has passed); one host read per fragment, the episode counter.  Returns the recorder: the caller reads it and closes it."""
+    from .device_recorder import DeviceRecorder
+    n = int(scene_episodes)
+    rec = DeviceRecorder(smp.E, smp.N, smp.device, max_rows=smp.E * n, limit=n)
+    n_frag = 0
+    while n_frag * smp.T <= 6 * (n + 1) * horizon:
+        rec.add(smp.sample())
+        n_frag += 1
+        if int(rec.episodes().min()) >= n:
+            break
+    return rec
+
+
+def run_steps(smp, steps):
+    """`steps` env steps of `smp`, rounded up to whole fragments.  Returns `smp`."""
+    for _ in range(-(-int(steps) // smp.T)):
+        smp.sample()
+    return smp
+
+
+def check_labels(labels, K):
+    """One label per member; default: the member index."""
+    labels = list(range(K)) if labels is None else list(labels)
+    if len(labels) != K:
+        raise ValueError("%d labels for %d members" % (len(labels), K))
+    return labels
+
+
 def evaluate_population(algo, env, weights=None, lcf=None, num_envs=64, num_agents=40, episodes=2000, seed=0,
                         scene_episodes=None, **extra):
     """Roll a population in `num_envs` scenes.  `scene_episodes` = whole scene episodes (until done["__all__"]: `horizon`
     env steps of respawning, then the scene drains -- the unit of the reference's evaluation,
     eval/evaluate_population.py:57-76) -- every agent that terminates inside them counts; otherwise stop after `episodes`
     terminated agents (quick, but the first agents to terminate are the ones that fail early)."""
-    from .checkpoint_io import load_policy_weights
-    t = make_eval_trainer(algo, env, num_envs, num_agents, seed, lcf, **extra)
-    if weights is not None:
-        load_policy_weights(t.policy.model, weights)
-        if t.policy.fused is not None:
-            t.policy.fused.sync_mirror()
-    if scene_episodes:
-        res = t.evaluate(scene_episodes=int(scene_episodes))
-    else:
-        res = t.evaluate(num_fragments=1, min_episodes=episodes)
-    t.stop()
-    return res
+    with eval_session(algo, env, num_envs, num_agents, seed, lcf, weights, **extra) as t:
+        if scene_episodes:
+            return t.evaluate(scene_episodes=int(scene_episodes))
+        return t.evaluate(num_fragments=1, min_episodes=episodes)
 
 
 def evaluate_population_rows(algo, env, weights=None, lcf=None, num_envs=64, num_agents=40, scene_episodes=1, seed=0,
@@ -109,45 +157,31 @@ def evaluate_population_rows(algo, env, weights=None, lcf=None, num_envs=64, num
     `recorder`: "torch" = `VecRecorder`; "device" = `DeviceRecorder`, which adds the SVO columns (`device_recorder.COLUMNS`), folds a
     fragment in three launches and leaves the loop one host read per fragment, the episode counter."""
     import torch
-    from .checkpoint_io import load_policy_weights
     from .vec_recorder import F_ENV_RESET, VecRecorder
     if recorder not in ("torch", "device"):
         raise ValueError("recorder=%r: 'torch' or 'device'" % (recorder,))
     extra = dict(extra)
     env_config = dict(extra.pop("env_config", None) or {}, neighbours_distance=float(recorder_distance))
-    t = make_eval_trainer(algo, env, num_envs, num_agents, seed, lcf, env_config=env_config, **extra)
-    if weights is not None:
-        load_policy_weights(t.policy.model, weights)
-        if t.policy.fused is not None:
-            t.policy.fused.sync_mirror()
-    smp = t.sampler
-    horizon = int(t.env.sim.cfg.horizon)
-    if recorder == "device":
-        from .device_recorder import DeviceRecorder
-        rec = DeviceRecorder(smp.E, smp.N, smp.device, max_rows=smp.E * int(scene_episodes), limit=int(scene_episodes))
+    with eval_session(algo, env, num_envs, num_agents, seed, lcf, weights, env_config=env_config, **extra) as t:
+        smp = t.sampler
+        horizon = int(t.env.sim.cfg.horizon)
+        if recorder == "device":
+            rec = record_scene_episodes(smp, scene_episodes, horizon)
+            df = rec.frame()
+            rec.close()
+            return df
+        rec = VecRecorder(smp.E, smp.device)
+        ep = torch.zeros(smp.E, dtype=torch.int64, device=smp.device)
         n_frag = 0
-        while n_frag * smp.T <= 6 * (int(scene_episodes) + 1) * horizon:
-            rec.add(smp.sample())
+        while bool((ep < int(scene_episodes)).any()) and n_frag * smp.T <= 6 * (int(scene_episodes) + 1) * horizon:
+            b = smp.sample()
+            fl = b["flags"]
+            ended = ((fl & F_ENV_RESET) > 0).any(-1).to(torch.int64)            # [T, E]
+            before = ep[None] + torch.cumsum(ended, 0) - ended                   # whole episodes finished before step t
+            rec.add(dict(flags=fl, infos=b["infos"], nbr_cnt=b["nbr_cnt"]), keep=before < int(scene_episodes))
+            ep = ep + ended.sum(0)
             n_frag += 1
-            if int(rec.episodes().min()) >= int(scene_episodes):
-                break
-        df = rec.frame()
-        rec.close()
-        t.stop()
-        return df
-    rec = VecRecorder(smp.E, smp.device)
-    ep = torch.zeros(smp.E, dtype=torch.int64, device=smp.device)
-    n_frag = 0
-    while bool((ep < int(scene_episodes)).any()) and n_frag * smp.T <= 6 * (int(scene_episodes) + 1) * horizon:
-        b = smp.sample()
-        fl = b["flags"]
-        ended = ((fl & F_ENV_RESET) > 0).any(-1).to(torch.int64)            # [T, E]
-        before = ep[None] + torch.cumsum(ended, 0) - ended                   # whole episodes finished before step t
-        rec.add(dict(flags=fl, infos=b["infos"], nbr_cnt=b["nbr_cnt"]), keep=before < int(scene_episodes))
-        ep = ep + ended.sum(0)
-        n_frag += 1
-    t.stop()
-    return rec.frame()
+        return rec.frame()
 
 
 def evaluate_bank_rows(algo, env, weights_list, lcfs=None, num_envs=64, num_agents=40, scene_episodes=1, seed=0, labels=None,
@@ -159,14 +193,12 @@ def evaluate_bank_rows(algo, env, weights_list, lcfs=None, num_envs=64, num_agen
     evaluation is paired.  Returns the recorder's frame sorted by (scene, episode of the scene), plus `member` = scene // (E / K) and
     `label` = labels[member] (default: the member index)."""
     from .bank import BankSampler, PolicyBank, members_of_scenes
-    from .device_recorder import COLUMNS, DeviceRecorder
+    from .device_recorder import COLUMNS
     import pandas as pd
     weights_list = list(weights_list)
     K = len(weights_list)
     per = members_of_scenes(int(num_envs), K)
-    labels = list(range(K)) if labels is None else list(labels)
-    if len(labels) != K:
-        raise ValueError("%d labels for %d members" % (len(labels), K))
+    labels = check_labels(labels, K)
     table = None
     if algo == "copo":
         if lcfs is None or len(lcfs) != K:
@@ -176,24 +208,13 @@ def evaluate_bank_rows(algo, env, weights_list, lcfs=None, num_envs=64, num_agen
         table = lcf_table_array(np.repeat(table, per, axis=0), num_envs)
     extra = dict(extra)
     env_config = dict(extra.pop("env_config", None) or {}, neighbours_distance=float(recorder_distance))
-    t = make_eval_trainer(algo, env, num_envs, num_agents, seed, None, env_config=env_config, **extra)
-    try:
+    with eval_session(algo, env, num_envs, num_agents, seed, env_config=env_config, **extra) as t:
         if table is not None:
             t.env.sim.set_lcf_table(table)
-        bank = PolicyBank(t.policy, weights_list)
-        smp = BankSampler(t.env, t.policy, bank, t.sampler.T, use_graph=t.config.get("use_hip_graphs", True))
-        horizon = int(t.env.sim.cfg.horizon)
-        rec = DeviceRecorder(smp.E, smp.N, smp.device, max_rows=smp.E * int(scene_episodes), limit=int(scene_episodes))
-        n_frag = 0
-        while n_frag * smp.T <= 6 * (int(scene_episodes) + 1) * horizon:
-            rec.add(smp.sample())
-            n_frag += 1
-            if int(rec.episodes().min()) >= int(scene_episodes):
-                break
+        smp = BankSampler(t.env, t.policy, PolicyBank(t.policy, weights_list), t.sampler.T, use_graph=graph_flag(t))
+        rec = record_scene_episodes(smp, scene_episodes, int(t.env.sim.cfg.horizon))
         r = rec.rows().cpu().numpy()
         rec.close()
-    finally:
-        t.stop()
     r = r[np.lexsort((r[:, len(COLUMNS) + 1], r[:, len(COLUMNS)]))]
     df = pd.DataFrame(r[:, :len(COLUMNS)], columns=list(COLUMNS))
     df["scene"] = r[:, len(COLUMNS)].astype(np.int64)
@@ -235,11 +256,7 @@ def sweep_trials(root, num_episodes=20, max_members=16, num_agents=40, seed=0, e
     by_cls = {cls: key for key, cls in ENVS.items()}
     groups = {}
     for info in list_checkpoints(root):
-        for needle, cls_name, short in _SCENE_OF:
-            if needle in info["env"]:
-                break
-        else:
-            raise ValueError("trial %s: unknown scene %r" % (info["trial"], info["env"]))
+        cls_name, short = scene_of(info["env"], "trial %s: unknown scene %r" % (info["trial"], info["env"]))
         algo = "copo" if info["should_wrap_copo_env"] else ("ccppo" if info["should_wrap_cc_env"] else "ippo")
         groups.setdefault((algo, by_cls[cls_name], short), []).append(info)
     frames = []
@@ -292,17 +309,7 @@ def main():
                     help="with --fault-sweep: a JSON list of {lidar_sigma, lidar_dropout, dropout_value, act_sigma, sticky}; the first "
                          "must be the identity {}")
     a = ap.parse_args()
-
-    def load_members(paths):
-        from .checkpoint_io import checkpoint_policy_weights
-        ws = []
-        for path in paths:
-            if path.endswith(".npz"):
-                with np.load(path) as f:
-                    ws.append({k: f[k] for k in f.files})
-            else:
-                ws.append(checkpoint_policy_weights(path))
-        return ws
+    from .checkpoint_io import load_members
     if a.fault_sweep:
         if not a.table or not a.fault_levels:
             ap.error("--fault-sweep needs --fault-levels and --table")
@@ -330,10 +337,7 @@ def main():
         df.to_csv(a.table)
         print(df.groupby(["trial", "count"])[["success_rate", "crash_rate", "out_rate", "episode_reward_mean"]].mean().to_string())
         return
-    w = None
-    if a.npz:
-        with np.load(a.npz) as f:
-            w = {k: f[k] for k in f.files}
+    w = load_members([a.npz])[0] if a.npz else None
     algo = "ippo" if a.algo == "cl" else a.algo
     if a.table:
         df = evaluate_population_rows(algo, a.env, w, a.lcf, a.num_envs, a.num_agents, scene_episodes=a.scene_episodes, recorder=a.recorder)

@@ -15,14 +15,16 @@ four 16-bit uniform halves of two hashes: mean 0, variance 1, and its tails END 
 `lidar_sigma` s never moves a beam by more than 3.47 s.
 
 Three pieces: `FaultLevel` / `FaultPlan` (numpy only), `FaultySeatSampler` (the `SeatSampler` with the two launches inside its captured
-fragment) and `fault_sweep_rows` (checkpoints x levels x roles as a pandas frame; `evaluate --fault-sweep`).
+fragment: it keeps no loop, `_policy_obs` launches `copo_fault_obs` in front of the forward of `VecSampler._act` and `_step` launches
+`copo_fault_act` in front of the step and its tally) and `fault_sweep_rows` (checkpoints x levels x roles as a pandas frame; `evaluate
+--fault-sweep`).
 """
-import ctypes as C
 from dataclasses import dataclass
 
 import numpy as np
 
-from .crossplay import REWARD_SCALE, SEAT_WORDS, SeatPlan, SeatSampler, seat_tally
+from .bank import DeviceTables
+from .crossplay import SEAT_WORDS, SeatPlan, SeatSampler, tally_rates
 
 LEVEL_WORDS = 8
 LEVEL_FIELDS = ("lidar_sigma", "lidar_dropout", "dropout_value", "act_sigma", "sticky")
@@ -83,7 +85,7 @@ class FaultPlan:
         self.L, (self.G, self.K) = len(self.levels), self.level_of.shape
         self.words = np.stack([lv.words() for lv in self.levels])
         self.checkpoint = self.level = None
-        self.share = None
+        self.share = self.scenes_per_cell = None          # (`sweep` sets them: cells of that many scenes share their action noise)
 
     def check(self, seat_plan):
         if (seat_plan.n_groups, seat_plan.K) != (self.G, self.K):
@@ -97,7 +99,7 @@ class FaultPlan:
         `scenes_per_cell`.  share == 1: every slot of the cell is member k at level l, a bank of K members.  share < 1: the bank holds
         every checkpoint TWICE, members k and K + k with the same weights (`sweep_members`); the first round(share * N) slots are member
         K + k at level l, the rest member k at level 0, which must then be the identity: the tally keeps the impaired and the healthy
-        drivers of a scene apart.  The seat plan carries `scenes_per_pair` = S, so `SeatSampler.reset` gives every cell the same scenes."""
+        drivers of a scene apart.  The seat plan declares `replica_scenes` = S, so `SeatSampler.reset` gives every cell the same scenes."""
         levels = [lv if isinstance(lv, FaultLevel) else FaultLevel(**lv) for lv in levels]
         K, S, N, L, share = int(K), int(scenes_per_cell), int(N), len(levels), float(share)
         if K < 1 or S < 1 or N < 1 or L < 1 or not 0.0 <= share <= 1.0:
@@ -114,8 +116,7 @@ class FaultPlan:
         KB = 2 * K if doubled else K
         level_of = np.zeros((K * L, KB), np.int32)
         level_of[np.arange(K * L), k_of + (K if doubled else 0)] = l_of
-        seats = SeatPlan(seat, KB, cell, K * L)
-        seats.scenes_per_pair = S
+        seats = SeatPlan(seat, KB, cell, K * L, replica_scenes=S)
         faults = cls(levels, level_of)
         faults.checkpoint, faults.level, faults.share = k_of, l_of, share
         faults.n_checkpoints, faults.doubled, faults.n_impaired, faults.scenes_per_cell = K, doubled, n_imp, S
@@ -134,41 +135,36 @@ def lidar_columns(cfg):
     return lo, lo + int(cfg.num_lasers)
 
 
-class FaultBuffers:
+class FaultBuffers(DeviceTables):
     """A fault plan's tables on the device."""
+    KEY = ("L", "G", "K")
+    faults = property(lambda self: self.source)
 
-    def __init__(self, faults, device):
-        import torch
-        self.faults, self.L, self.G, self.K = faults, faults.L, faults.G, faults.K
-        self.level_of = torch.from_numpy(faults.level_of).to(device)
-        self.words = torch.from_numpy(faults.words.view(np.int32)).to(device)      # (bits; torch has no uint32 arithmetic to need)
+    @staticmethod
+    def tables(faults):          # (the level words as bits; torch has no uint32 arithmetic to need)
+        return dict(level_of=faults.level_of, words=faults.words.view(np.int32)), (faults.L, faults.G, faults.K)
 
-    def same_shape(self, faults):
-        return (faults.L, faults.G, faults.K) == (self.L, self.G, self.K)
 
-    def copy_in(self, faults):
-        import torch
-        self.level_of.copy_(torch.from_numpy(faults.level_of))
-        self.words.copy_(torch.from_numpy(faults.words.view(np.int32)))
-        self.faults = faults
+def _fault_launch(name, head, pb, fb, tick, fault_seed):
+    """Entry point `name` on its own arguments `head` and on what both launches end in: the seat and group tables, the levels, the tick,
+    the seed and the current stream."""
+    from .. import _capi
+    _capi.check(getattr(_capi.lib, name)(*head, pb.seat.data_ptr(), pb.group.data_ptr(), pb.K, pb.G, fb.level_of.data_ptr(), fb.words.data_ptr(),
+                                         fb.L, tick.data_ptr(), fault_seed, _capi.current_stream()))
 
 
 def fault_obs(obs, obs_seen, col_lo, col_hi, plan_buffers, fault_buffers, tick, fault_seed):
     """`copo_fault_obs` on the current stream: obs [E N][O] -> obs_seen."""
-    from .. import _capi
-    pb, fb = plan_buffers, fault_buffers
-    _capi.check(_capi.lib.copo_fault_obs(obs.data_ptr(), obs_seen.data_ptr(), pb.E, pb.N, int(obs.shape[-1]), col_lo, col_hi, pb.seat.data_ptr(),
-                                         pb.group.data_ptr(), pb.K, pb.G, fb.level_of.data_ptr(), fb.words.data_ptr(), fb.L, tick.data_ptr(),
-                                         fault_seed, _capi.current_stream()))
+    pb = plan_buffers
+    _fault_launch("copo_fault_obs", (obs.data_ptr(), obs_seen.data_ptr(), pb.E, pb.N, int(obs.shape[-1]), col_lo, col_hi), pb, fault_buffers,
+                  tick, fault_seed)
 
 
 def fault_act(act, prev, flags_prev, plan_buffers, fault_buffers, tick, fault_seed):
     """`copo_fault_act` on the current stream: act [E N][2] in place; `flags_prev` = the previous step's flags or None."""
-    from .. import _capi
-    pb, fb = plan_buffers, fault_buffers
-    _capi.check(_capi.lib.copo_fault_act(act.data_ptr(), prev.data_ptr(), _capi.ptr(flags_prev), pb.E, pb.N, pb.seat.data_ptr(),
-                                         pb.group.data_ptr(), pb.K, pb.G, fb.level_of.data_ptr(), fb.words.data_ptr(), fb.L, tick.data_ptr(),
-                                         fault_seed, _capi.current_stream()))
+    pb = plan_buffers
+    _fault_launch("copo_fault_act", (act.data_ptr(), prev.data_ptr(), None if flags_prev is None else flags_prev.data_ptr(), pb.E, pb.N), pb,
+                  fault_buffers, tick, fault_seed)
 
 
 class FaultySeatSampler(SeatSampler):
@@ -191,6 +187,7 @@ class FaultySeatSampler(SeatSampler):
         if not 0 <= self.col_lo <= self.col_hi <= self.O:
             raise ValueError("FaultySeatSampler: LiDAR columns [%d, %d) of an observation of %d" % (self.col_lo, self.col_hi, self.O))
         self.fault_buffers = FaultBuffers(faults, self.device)
+        self.fault_buffers.on_replace.append(self._loop.reset)
         self.obs_seen = torch.zeros(self.T, self.E, self.N, self.O, dtype=torch.float32, device=self.device)
         self.prev = torch.zeros(self.E, self.N, 2, dtype=torch.float32, device=self.device)
         self.tick = torch.zeros(self.E * self.N, dtype=torch.int32, device=self.device)
@@ -202,12 +199,7 @@ class FaultySeatSampler(SeatSampler):
     def set_faults(self, faults):
         """Another fault plan, OUTSIDE captured graphs: the same shapes (levels, groups, members) are copied into the tables the captured
         fragment reads, other shapes allocate new ones and drop the graph."""
-        faults.check(self.seated.plan)
-        if self.fault_buffers.same_shape(faults):
-            self.fault_buffers.copy_in(faults)
-            return
-        self.fault_buffers = FaultBuffers(faults, self.device)
-        self._loop.reset()
+        self.fault_buffers.replace(faults.check(self.seated.plan))
 
     def reset(self, seeds=None):
         super().reset(seeds)
@@ -220,7 +212,7 @@ class FaultySeatSampler(SeatSampler):
         cells already share their scene seeds, so at the identity level two cells differ by their checkpoint only.  (The fault draws
         themselves are keyed by the absolute row, so two impaired cells never share those.)"""
         self.eps.normal_()
-        per = getattr(self.faults, "scenes_per_cell", None)
+        per = self.faults.scenes_per_cell
         if per and self.E > per and self.E % per == 0:
             cells = self.eps.view(self.T, self.E // per, per, self.N, 2)
             cells[:, 1:].copy_(cells[:, :1])
@@ -230,17 +222,14 @@ class FaultySeatSampler(SeatSampler):
         batch["obs_seen"] = self.obs_seen
         return batch
 
-    def _rollout(self):
-        sim, EN = self.sim, self.E * self.N
-        lib, h, stream = sim._capi.lib, sim._h, sim._stream()
-        pb, fb = self.seated.buffers, self.fault_buffers
-        for t in range(self.T):
-            fault_obs(self.obs[t], self.obs_seen[t], self.col_lo, self.col_hi, pb, fb, self.tick, self.fault_seed)
-            self.seated.act(self.obs_seen[t].view(EN, self.O), self.eps[t].view(EN, 2), self.actions[t], self.logp[t], self.dist_inputs[t],
-                            self.clipped[t])
-            fault_act(self.clipped[t], self.prev, self.flags[t - 1 if t else self.T - 1], pb, fb, self.tick, self.fault_seed)
-            sim._capi.check(lib.copo_sim_step(h, self.clipped[t].data_ptr(), C.byref(self._outs[t]), stream))
-            seat_tally(self.flags[t], self.rew3[0, t], pb, self.tally)
+    def _policy_obs(self, t):
+        fault_obs(self.obs[t], self.obs_seen[t], self.col_lo, self.col_hi, self.seated.buffers, self.fault_buffers, self.tick, self.fault_seed)
+        return self.obs_seen[t]
+
+    def _step(self, t):
+        fault_act(self.clipped[t], self.prev, self.flags[t - 1 if t else self.T - 1], self.seated.buffers, self.fault_buffers, self.tick,
+                  self.fault_seed)
+        super()._step(t)
 
 
 def sweep_frame(tally, seats, faults, labels=None):
@@ -249,7 +238,6 @@ def sweep_frame(tally, seats, faults, labels=None):
     import pandas as pd
     labels = list(range(faults.n_checkpoints)) if labels is None else list(labels)
     K, N, n_imp = faults.n_checkpoints, seats.N, faults.n_impaired
-    ratio = lambda a, b: float(a) / float(b) if b else float("nan")  # noqa: E731
     rows = []
     for g in range(seats.n_groups):
         k, lv = int(faults.checkpoint[g]), int(faults.level[g])
@@ -257,8 +245,7 @@ def sweep_frame(tally, seats, faults, labels=None):
         for role, member, own in roles:
             w = [int(v) for v in tally[g, member]]
             rows.append(dict(checkpoint=k, label=labels[k], level=lv, role=role, member=member, share=faults.share, seats=n_imp if role == "impaired"
-                             else N - n_imp, own_level=own, **faults.levels[lv].as_dict(), **dict(zip(SEAT_WORDS, w)), success=ratio(w[2], w[1]),
-                             crash_rate=ratio(w[3], w[1]), out_rate=ratio(w[4], w[1]), reward_per_step=ratio(w[6] / REWARD_SCALE, w[0])))
+                             else N - n_imp, own_level=own, **faults.levels[lv].as_dict(), **dict(zip(SEAT_WORDS, w)), **tally_rates(w)))
     return pd.DataFrame(rows)
 
 
@@ -272,7 +259,7 @@ def fault_sweep_rows(algo, env, weights_list, levels, share=1.0, scenes_per_cell
     row's drivers are at: 0 for the healthy), the five parameters of the CELL's level, the eight raw words of the seat tally and
     `success`, `crash_rate`, `out_rate`, `reward_per_step` as in `cross_play_rows`.  `fault_seed` defaults to `seed`."""
     from .bank import PolicyBank
-    from .evaluate import make_eval_trainer
+    from .evaluate import check_labels, eval_session, graph_flag, run_steps
     weights_list = list(weights_list)
     K = len(weights_list)
     if K < 1:
@@ -280,20 +267,13 @@ def fault_sweep_rows(algo, env, weights_list, levels, share=1.0, scenes_per_cell
     levels = [lv if isinstance(lv, FaultLevel) else FaultLevel(**lv) for lv in levels]
     if not levels or not levels[0].is_identity:
         raise ValueError("fault_sweep_rows: level 0 must be the identity FaultLevel(), the table's own baseline")
-    labels = list(range(K)) if labels is None else list(labels)
-    if len(labels) != K:
-        raise ValueError("%d labels for %d members" % (len(labels), K))
+    labels = check_labels(labels, K)
     seats, faults = FaultPlan.sweep(K, levels, scenes_per_cell, num_agents, share)
-    t = make_eval_trainer(algo, env, seats.E, num_agents, seed, None, **extra)
-    try:
+    with eval_session(algo, env, seats.E, num_agents, seed, **extra) as t:
         bank = PolicyBank(t.policy, sweep_members(weights_list, faults))
-        smp = FaultySeatSampler(t.env, t.policy, bank, seats, faults, t.sampler.T, use_graph=t.config.get("use_hip_graphs", True),
+        smp = FaultySeatSampler(t.env, t.policy, bank, seats, faults, t.sampler.T, use_graph=graph_flag(t),
                                 fault_seed=seed if fault_seed is None else fault_seed)
-        for _ in range(-(-int(steps) // smp.T)):
-            smp.sample()
-        tally = smp.tally.cpu().numpy()
-    finally:
-        t.stop()
+        tally = run_steps(smp, steps).tally.cpu().numpy()
     return sweep_frame(tally, seats, faults, labels)
 
 

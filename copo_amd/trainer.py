@@ -10,6 +10,7 @@
 Reference call sites being replaced: `synchronous_parallel_sample` (algo_copo.py:519-525), `train_one_step` /
 `multi_gpu_train_one_step` (:555-558), `minibatches` (:585), `update_kl` (:631-632).
 """
+import ctypes as C
 import math
 import os
 import time
@@ -148,7 +149,6 @@ class VecSampler:
         self.env_steps_total = 0
 
     def reset(self, seeds=None):
-        import ctypes as C
         sim = self.sim
         if seeds is None:
             seeds = np.arange(sim.E, dtype=np.uint64) + np.uint64(sim.cfg.start_seed + 1000003 * D.rank())
@@ -162,22 +162,36 @@ class VecSampler:
         self._started = True
 
     def _rollout(self):
-        import ctypes as C
-        sim, pol = self.sim, self.policy
-        EN = self.E * self.N
-        lib, h, stream = sim._capi.lib, sim._h, sim._stream()
-        fz = pol.fused if (pol.fused is not None and pol.fused.can_forward and pol.config.get("use_fused_inference", True)) else None
+        """The one rollout loop.  A subclass changes what a step does through the three hooks below, never the loop.  What holds for
+        the whole rollout is looked up once, here: the fused learner if the forward goes through it, and the stream."""
+        pol = self.policy
+        fused = pol.fused is not None and pol.fused.can_forward and pol.config.get("use_fused_inference", True)
+        self._fz, self._sim_stream = pol.fused if fused else None, self.sim._stream()
         for t in range(self.T):
-            if fz is not None:        # one kernel: both layers, head, sampling, log-probability, clipping
-                fz.act(self.obs[t].view(EN, self.O), self.eps[t].view(EN, 2), self.actions[t], self.logp[t],
-                       self.dist_inputs[t], self.clipped[t])
-            else:
-                a, lp, di = pol.compute_actions(self.obs[t].view(EN, self.O), self.eps[t].view(EN, 2))
-                self.actions[t].view(EN, 2).copy_(a)
-                self.logp[t].view(EN).copy_(lp)
-                self.dist_inputs[t].view(EN, 4).copy_(di)
-                torch.clamp(a.view(self.E, self.N, 2), -1.0, 1.0, out=self.clipped[t])
-            sim._capi.check(lib.copo_sim_step(h, self.clipped[t].data_ptr(), C.byref(self._outs[t]), stream))
+            self._act(t)
+            self._step(t)
+
+    def _policy_obs(self, t):
+        """[E, N, O]: what the policy reads at step t (eval/faults.py hands it an impaired copy)."""
+        return self.obs[t]
+
+    def _act(self, t):
+        """Step t's actions, log-probabilities, distribution inputs and clipped actions from `_policy_obs(t)` and `eps[t]`."""
+        EN = self.E * self.N
+        obs, eps = self._policy_obs(t).view(EN, self.O), self.eps[t].view(EN, 2)
+        if self._fz is not None:      # one kernel: both layers, head, sampling, log-probability, clipping
+            self._fz.act(obs, eps, self.actions[t], self.logp[t], self.dist_inputs[t], self.clipped[t])
+        else:
+            a, lp, di = self.policy.compute_actions(obs, eps)
+            self.actions[t].view(EN, 2).copy_(a)
+            self.logp[t].view(EN).copy_(lp)
+            self.dist_inputs[t].view(EN, 4).copy_(di)
+            torch.clamp(a.view(self.E, self.N, 2), -1.0, 1.0, out=self.clipped[t])
+
+    def _step(self, t):
+        """The simulator step on `clipped[t]`, writing row t of the buffers and `obs[t + 1]`."""
+        sim = self.sim
+        sim._capi.check(sim._capi.lib.copo_sim_step(sim._h, self.clipped[t].data_ptr(), C.byref(self._outs[t]), self._sim_stream))
 
     def _draw_noise(self):
         """The fragment's action noise (eval/bank.py draws one member's and copies it to the others)."""

@@ -61,7 +61,7 @@ def test_sweep_tables(share, n_imp):
     doubled = share < 1.0
     KB = 2 * K if doubled else K
     assert faults.check(seats) is faults and faults.doubled == doubled and faults.n_impaired == n_imp == int(round(share * N))
-    assert (seats.E, seats.N, seats.K, seats.n_groups) == (K * L * S, N, KB, K * L) and seats.scenes_per_pair == S
+    assert (seats.E, seats.N, seats.K, seats.n_groups) == (K * L * S, N, KB, K * L) and seats.replica_scenes == S
     assert faults.level_of.shape == (K * L, KB) and faults.share == share and faults.n_checkpoints == K
     for g in range(K * L):
         k, lv = g // L, g % L

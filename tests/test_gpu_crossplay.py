@@ -289,6 +289,26 @@ def test_captured_fragment_equals_eager_and_the_diagonal_equals_a_dense_bank(e2e
     assert not torch.equal(eager[-1]["actions"][:, :per], eager[-1]["actions"][:, -per:])          # the two members do differ
 
 
+def test_pairs_plan_shares_its_scenes_between_the_pairs_and_not_its_noise(e2e):
+    """A plan that declares `replica_scenes` is seeded one replica's seeds tiled; a `SeatSampler`'s noise stays every seat's own.  On the
+    module's fixture, 4 pairs of 3 scenes x 40 slots, T = 4."""
+    from copo_amd.eval.crossplay import SeatSampler
+    t, plan, ws, bank = e2e
+    K, per, N, _ = cn.E2E_PAIRS
+    assert plan.replica_scenes == per
+    smp = SeatSampler(t.env, t.policy, bank, plan, 4, use_graph=False)
+    torch.manual_seed(3)
+    smp.reset()
+    obs0 = _bits(smp.obs[0]).view(K * K, per, N, smp.O).clone()
+    assert torch.equal(obs0, obs0[:1].expand_as(obs0)) and bool(obs0.any())
+    assert all(not torch.equal(obs0[0, a], obs0[0, b]) for a in range(per) for b in range(a))          # a replica's own scenes differ
+    smp.obs[smp.T].copy_(smp.obs[0])          # (`sample()` after an explicit `reset()` starts from `obs[T]`)
+    smp.sample()
+    torch.cuda.synchronize()
+    eps = smp.eps.view(smp.T, K * K, per, N, 2)
+    assert all(not torch.equal(eps[:, r], eps[:, 0]) for r in range(1, K * K))
+
+
 def test_cross_play_rows_frame(golden_dir):
     from copo_amd.eval.crossplay import SEAT_WORDS, cross_play_rows
     ws = cn.e2e_members(golden_dir)

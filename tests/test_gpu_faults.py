@@ -263,6 +263,37 @@ def test_healthy_seats_next_to_impaired_ones_are_untouched(e2e):
     assert moved_obs > 0 and moved_act > 0
 
 
+def test_sweep_plan_shares_scenes_and_noise_between_its_cells(e2e):
+    from copo_amd.eval.bank import PolicyBank
+    from copo_amd.eval.faults import FaultLevel, FaultPlan, FaultySeatSampler, sweep_members
+    t, ws = e2e
+    E, N, T = E2E
+    seats, faults = FaultPlan.sweep(1, [FaultLevel(), FaultLevel(**HARSH)], 2, N, share=1.0)          # two cells of two scenes
+    assert seats.E == E and seats.replica_scenes == 2 == faults.scenes_per_cell
+    smp = FaultySeatSampler(t.env, t.policy, PolicyBank(t.policy, sweep_members(ws[:1], faults)), seats, faults, T, use_graph=False,
+                            fault_seed=fc.SEED)
+    _fragments(smp, 1, ("eps",))
+    smp.reset()
+    obs0, eps = _bits(smp.obs[0]).view(2, 2, N, smp.O), _bits(smp.eps).view(T, 2, 2, N, 2)
+    assert torch.equal(obs0[1], obs0[0]) and not torch.equal(obs0[0, 0], obs0[0, 1])
+    assert torch.equal(eps[:, 1], eps[:, 0]) and not torch.equal(eps[:, 0, 0], eps[:, 0, 1]) and bool(eps.any())
+
+
+def test_hand_built_plan_without_replica_scenes_gets_the_plain_samplers_seeds(e2e):
+    from copo_amd.eval.bank import PolicyBank
+    from copo_amd.eval.crossplay import SeatPlan, SeatSampler
+    t, ws = e2e
+    E, N, T = E2E
+    plan = SeatPlan(np.arange(E * N).reshape(E, N) % 2, n_members=2)
+    assert plan.replica_scenes is None
+    smp = SeatSampler(t.env, t.policy, PolicyBank(t.policy, ws), plan, T, use_graph=False)
+    smp.reset()
+    obs0 = _bits(smp.obs[0]).clone()
+    assert all(not torch.equal(obs0[a], obs0[b]) for a in range(E) for b in range(a))          # every scene its own
+    t.sampler.reset()
+    assert _same(t.sampler.obs[0], smp.obs[0]) and torch.equal(_bits(smp.obs[0]), obs0)
+
+
 def test_fault_sweep_rows_frame(golden_dir):
     import bank_cases as bc
     from copo_amd.eval.bank import PolicyBank
