@@ -12,7 +12,8 @@
 //      -- the path of shapes without a row-pass instantiation, of the batched meta pass and of the row store
 //   3. head_row_terms (PPO / value / meta loss terms + analytic gradient), head_kernel
 //   4. rowpass_kernel: layers 1-2, heads, dz2, dz1 of 16 rows in one workgroup (v_mfma_f32_16x16x4_f32, weights
-//      streamed through BRing register rings); mlp_fwd_kernel: its forward-only sibling (rollouts, critic heads)
+//      streamed through BRing register rings); mlp_fwd_kernel: its forward-only sibling (rollouts, critic heads);
+//      learn_inputgrad.inc: adv_obs_kernel, the forward plus the backward pass down to the INPUT row of a seated bank (evaluation)
 //   5. LCF meta kernels: meta_lcf / meta_finish (step by step), meta_batch_fold / dot / rowstat, meta_seq (all LCF
 //      Adam steps of a pass in one workgroup)
 //   6. reduce_adam_kernel (fold of row-split partials + Adam; legacy two-net meta step), wgrad_adam_kernel (weight
@@ -38,6 +39,7 @@ namespace copo {
 #include "learn_args.inc"
 #include "learn_gemm.inc"
 #include "learn_rowpass.inc"
+#include "learn_inputgrad.inc"
 #include "learn_meta.inc"
 #include "learn_update.inc"
 #include "learn_plan.inc"
@@ -254,7 +256,7 @@ static int mlp_forward(const copo_ppo_cfg* cfg, const float* theta, const float*
 
 // ---- plan query (tests): what a configuration would launch; the device is not touched ---------------------------------
 extern "C" const char* copo_debug_learner_kernel(int32_t id, int32_t* block_out, int32_t* lds_cap_out) {
-    if (id < 0 || id >= K_COUNT) return nullptr;
+    if (id < 0 || id >= K_LEARNER_COUNT) return nullptr;
     if (block_out) *block_out = g_kernels[id].block;
     if (lds_cap_out) *lds_cap_out = g_kernels[id].lds_cap;
     return g_kernels[id].name;
@@ -307,6 +309,27 @@ extern "C" int copo_mlp_forward_seats_f32(const copo_ppo_cfg* cfg, const float* 
     if (n_members < 1 || cap < 1 || n_out < 1) return COPO_ERR_DIM;
     return mlp_forward(cfg, theta, theta_t, obs_src, nullptr, cap, 0, 1, nullptr, dist_inputs, eps, action, logp, clipped, rows, n_out,
                        stream, n_members, member_stride, counts);
+}
+
+extern "C" int copo_adv_obs_seats_f32(const copo_ppo_cfg* cfg, const float* theta, const float* theta_t, int64_t member_stride,
+                                      int32_t n_members, const int64_t* rows, const int32_t* counts, int64_t cap, int64_t n_out,
+                                      const float* obs_src, float* obs_seen, float* grad, int32_t col_lo, int32_t col_hi, int32_t n_slots,
+                                      const int32_t* group, int32_t n_groups, const int32_t* level_of, const float* levels,
+                                      int32_t n_levels, void* stream) {
+    int rc = check_cfg(cfg);
+    if (rc != COPO_OK) return rc;
+    if (!theta || !theta_t || !rows || !counts || !obs_src || !obs_seen || !group || !level_of || !levels) return COPO_ERR_NULL;
+    if (n_out < 1 || n_slots < 1 || n_out % n_slots != 0 || n_groups < 1 || n_levels < 1 || member_stride < cfg->n_params || member_stride % 4 != 0 ||
+        col_lo < 0 || col_lo > col_hi || col_hi > cfg->pol.in_dim)
+        return COPO_ERR_DIM;
+    Launch l;
+    rc = plan_adversary(*cfg, cap, n_members, aligned16(theta_t) ? FACT_MIRROR_ALIGNED : 0, &l);
+    if (rc != COPO_OK) return rc;
+    if (gemm_lds_attrs() != hipSuccess) return COPO_ERR_DEVICE;
+    AdvArgs a{*cfg, theta, theta_t, member_stride, rows, counts, cap, n_out, obs_src, obs_seen, grad, col_lo, col_hi, n_slots,
+              group, n_groups, level_of, levels, n_levels, n_members};
+    void* args[] = {&a};
+    return launch_kernel(l, args, static_cast<hipStream_t>(stream)) == hipSuccess ? COPO_OK : COPO_ERR_DEVICE;
 }
 
 extern "C" int copo_mlp_forward_rows_f32(const copo_ppo_cfg* cfg, const float* theta, const float* theta_t,

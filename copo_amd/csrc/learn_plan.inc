@@ -32,11 +32,18 @@ constexpr int LDS_GEMM = (int)GEMM_LDS_BYTES;
     X(WGRAD_OT2, 64 * WG_WAVES, 80 * 1024, wgrad_adam_kernel<2>)                                                             \
     X(HEAD, 256, LDS_DEFAULT, head_kernel) X(META_FOLD, 256, LDS_DEFAULT, meta_batch_fold_kernel)                            \
     X(REDUCE_ADAM, 256, LDS_DEFAULT, reduce_adam_kernel)
+// rows behind the learner's: kernels of the evaluation side that live in this translation unit (learn_inputgrad.inc).  They are launched
+// through the same launch_kernel and get their LDS ceilings from the same loop; copo_debug_learner_kernel lists the learner's rows only
+// (ids below K_LEARNER_COUNT).  The four shapes in shape_index order.
+#define COPO_EVAL_KERNELS(X)                                                                                                \
+    X(ADV_1_4, 256, LDS_ROWPASS, adv_obs_kernel<1, 4>) X(ADV_2_4, 256, LDS_ROWPASS, adv_obs_kernel<2, 4>)                    \
+    X(ADV_2_8, 512, LDS_ROWPASS, adv_obs_kernel<2, 8>) X(ADV_4_8, 512, LDS_ROWPASS, adv_obs_kernel<4, 8>)
 struct KernelEntry { const char* name; const void* fn; int block, lds_cap; };
 #define COPO_KERNEL_ID(id, block, cap, ...) K_##id,
 #define COPO_KERNEL_ENTRY(id, block, cap, ...) {#__VA_ARGS__, reinterpret_cast<const void*>(__VA_ARGS__), block, cap},
-enum KernelId : int32_t { COPO_KERNELS(COPO_KERNEL_ID) K_COUNT };
-static const KernelEntry g_kernels[K_COUNT] = {COPO_KERNELS(COPO_KERNEL_ENTRY)};
+enum KernelId : int32_t { COPO_KERNELS(COPO_KERNEL_ID) COPO_EVAL_KERNELS(COPO_KERNEL_ID) K_COUNT };
+constexpr int K_LEARNER_COUNT = K_ADV_1_4;
+static const KernelEntry g_kernels[K_COUNT] = {COPO_KERNELS(COPO_KERNEL_ENTRY) COPO_EVAL_KERNELS(COPO_KERNEL_ENTRY)};
 static int shape_index(int hidden) { return hidden == 64 ? 0 : hidden == 128 ? 1 : hidden == 256 ? 2 : hidden == 512 ? 3 : -1; }
 
 struct Launch { int32_t id; uint32_t gx, gy, gz; int32_t block, lds; int32_t arg[4]; };      // arg: the kernel's int arguments after its struct
@@ -219,5 +226,19 @@ static int plan_forward(const copo_ppo_cfg& c, int64_t n_rows, int first_net, in
                        : (bank ? (bf ? K_FWD_BANK_BF_1_4 : K_FWD_BANK_1_4) : bf ? K_FWD_BF_1_4 : K_FWD_1_4) + sh;
     const int rws = rt2 ? 2 * HT : HT;
     *out = Launch{id, (uint32_t)((n_rows + rws - 1) / rws), (uint32_t)(bank ? n_members : n_nets), 1, g_kernels[id].block, (int32_t)lds, {}};
+    return COPO_OK;
+}
+
+// Input-gradient pass of a seated bank (copo_adv_obs_seats_f32, learn_inputgrad.inc): the launch shape of seat mode -- `cap` rows per
+// member at the most, the member as the grid's second dimension -- and always the 16-row tile, at every hidden width.  fp32 operands only.
+static int plan_adversary(const copo_ppo_cfg& c, int64_t cap, int n_members, int facts, Launch* out) {
+    const int H = c.hidden, sh = shape_index(H);
+    if (cap < 1 || n_members < 1 || n_members > 65535 || (cap + HT - 1) / HT > 0x7fffffff) return COPO_ERR_DIM;
+    if (sh < 0 || c.operand_dtype != COPO_OPERAND_F32 || !(facts & FACT_MIRROR_ALIGNED)) return COPO_ERR_DIM;
+    if (c.pol.in_dim < 1 || c.pol.w1 % 4 != 0 || c.pol.w2 % 4 != 0) return COPO_ERR_DIM;
+    const size_t lds = adv_lds_floats(H, rowpass_k1p(c.pol.in_dim)) * sizeof(float);
+    if (lds > (size_t)LDS_ROWPASS) return COPO_ERR_DIM;
+    const int id = K_ADV_1_4 + sh;
+    *out = Launch{id, (uint32_t)((cap + HT - 1) / HT), (uint32_t)n_members, 1, g_kernels[id].block, (int32_t)lds, {}};
     return COPO_OK;
 }

@@ -100,6 +100,24 @@ class PolicyBank:
             pb.cap, pb.n_out, obs.data_ptr(), dist_inputs.data_ptr(), eps.data_ptr(), action.data_ptr(), logp.data_ptr(),
             None if clipped is None else clipped.data_ptr(), self._capi.current_stream()))
 
+    def perturb_seats(self, plan_buffers, adv_buffers, obs, obs_seen, col_lo, col_hi, grad=None):
+        """`copo_adv_obs_seats_f32` (eval/adversary.py) on the current stream: obs [n_out, O] -> obs_seen, one gradient-sign step on
+        the columns [col_lo, col_hi) of every seated row against the member that drives it, at the level `adv_buffers`
+        (`adversary.AdversaryBuffers`) gives (scene group, member); `grad` [n_out, O]: the raw gradient, if wanted.  Needs the mirror
+        (`sync_mirror`), as `act_seats`."""
+        pb, ab = plan_buffers, adv_buffers
+        if pb.K != self.K or (ab.G, ab.K) != (pb.G, pb.K):
+            raise ValueError("PolicyBank.perturb_seats: a bank of %d, a plan of %d groups x %d members, levels for %d x %d" % (
+                self.K, pb.G, pb.K, ab.G, ab.K))
+        for name, t in (("obs", obs), ("obs_seen", obs_seen), ("grad", grad)):
+            if t is not None and (tuple(t.shape) != (pb.n_out, int(self.cfg.pol.in_dim)) or not t.is_contiguous() or t.dtype != torch.float32):
+                raise ValueError("PolicyBank.perturb_seats: %s of shape %s, contiguous float32 [%d, %d] wanted" % (
+                    name, tuple(t.shape), pb.n_out, int(self.cfg.pol.in_dim)))
+        self._capi.check(self._capi.lib.copo_adv_obs_seats_f32(
+            C.byref(self.cfg), self.theta.data_ptr(), self.theta_t.data_ptr(), self.stride, self.K, pb.rows.data_ptr(), pb.counts.data_ptr(),
+            pb.cap, pb.n_out, obs.data_ptr(), obs_seen.data_ptr(), None if grad is None else grad.data_ptr(), int(col_lo), int(col_hi), pb.N,
+            pb.group.data_ptr(), pb.G, ab.level_of.data_ptr(), ab.levels.data_ptr(), ab.L, self._capi.current_stream()))
+
 
 class _BankPolicy:
     """What `VecSampler` reads of a policy, with the bank as its fused learner."""
@@ -146,6 +164,18 @@ class DeviceTables:
 def replica_seeds(start_seed, S, E):
     """Scene seeds start_seed + arange(S), tiled E // S times: scenes [r S, (r + 1) S) of every replica r are the same scenes."""
     return np.tile(np.arange(S, dtype=np.uint64) + np.uint64(start_seed), E // S)
+
+
+def draw_cell_noise(eps, scenes_per_cell):
+    """Action noise eps [T][E][N][2] of a sweep whose cells are `scenes_per_cell` scenes each: ordinary noise, then the first cell's draw
+    is copied to every cell, as `BankSampler` copies one member's -- the cells already share their scene seeds, so at the identity
+    level two cells differ by their checkpoint only.  `scenes_per_cell` None (a hand-built plan): every scene its own draw."""
+    eps.normal_()
+    T, E, N = eps.shape[:3]
+    per = scenes_per_cell
+    if per and E > per and E % per == 0:
+        cells = eps.view(T, E // per, per, N, 2)
+        cells[:, 1:].copy_(cells[:, :1])
 
 
 def members_of_scenes(num_envs, n_members):

@@ -79,6 +79,30 @@ class SeatPlan:
         return plan
 
     @classmethod
+    def cells(cls, K, L, scenes_per_cell, N, share=1.0, who="SeatPlan.cells"):
+        """The seat layout of a sweep of K checkpoints x L levels (`FaultPlan.sweep`, `AdversaryPlan.sweep`): one scene group per cell,
+        group k * L + l = scenes [g S, (g + 1) S), S = `scenes_per_cell`.  share == 1: every slot of the cell is member k, a bank of K
+        members.  share < 1: the bank holds every checkpoint TWICE, members k and K + k; the first round(share * N) slots are member K +
+        k (at the cell's level), the rest member k (at level 0).  Returns (plan, level_of int32 [K L][bank members], attrs): `attrs` is
+        what a level plan keeps of the layout (`checkpoint`, `level` per group, `share`, `n_checkpoints`, `doubled`, `n_impaired`,
+        `scenes_per_cell`).  The plan declares `replica_scenes` = S."""
+        K, L, S, N, share = int(K), int(L), int(scenes_per_cell), int(N), float(share)
+        if K < 1 or S < 1 or N < 1 or L < 1 or not 0.0 <= share <= 1.0:
+            raise ValueError("%s: K=%d levels=%d scenes_per_cell=%d N=%d share=%r" % (who, K, L, S, N, share))
+        doubled = share < 1.0
+        n_imp = int(round(share * N))
+        cell = np.repeat(np.arange(K * L, dtype=np.int32), S)
+        k_of, l_of = np.arange(K * L) // L, np.arange(K * L) % L
+        seat = np.empty((K * L * S, N), np.int32)
+        seat[:, :n_imp] = ((cell // L) + (K if doubled else 0))[:, None]
+        seat[:, n_imp:] = (cell // L)[:, None]
+        KB = 2 * K if doubled else K
+        level_of = np.zeros((K * L, KB), np.int32)
+        level_of[np.arange(K * L), k_of + (K if doubled else 0)] = l_of
+        attrs = dict(checkpoint=k_of, level=l_of, share=share, n_checkpoints=K, doubled=doubled, n_impaired=n_imp, scenes_per_cell=S)
+        return cls(seat, KB, cell, K * L, replica_scenes=S), level_of, attrs
+
+    @classmethod
     def uniform(cls, member_of_scene, N, n_members=None):
         """Every seat of scene e belongs to member_of_scene[e]: with e // (E / K) the ownership of the dense bank.  Group = member."""
         m = np.ascontiguousarray(member_of_scene, np.int32).reshape(-1)
@@ -138,6 +162,10 @@ class SeatedBank:
 
     def act(self, obs, eps, action, logp, dist_inputs, clipped=None):
         self.bank.act_seats(self.buffers, obs, eps, action, logp, dist_inputs, clipped)
+
+    def perturb_seats(self, adv_buffers, obs, obs_seen, col_lo, col_hi, grad=None):
+        """`PolicyBank.perturb_seats` over the plan's own buffers (eval/adversary.py)."""
+        self.bank.perturb_seats(self.buffers, adv_buffers, obs, obs_seen, col_lo, col_hi, grad)
 
 
 class SeatSampler(VecSampler):

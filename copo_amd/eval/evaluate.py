@@ -275,7 +275,7 @@ def sweep_trials(root, num_episodes=20, max_members=16, num_agents=40, seed=0, e
     return pd.concat(frames, ignore_index=True) if frames else pd.DataFrame()
 
 
-def main():
+def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--root", default=None, help="experiment folder of Tune trial folders: evaluate every checkpoint of every trial "
                                                  "(the reference's copo/eval.py) into --table")
@@ -298,18 +298,35 @@ def main():
                     help="checkpoints (.npz populations or Tune checkpoint files) of --algo's layout: every ordered pair shares scenes "
                          "(eval/crossplay.py), one row per (pair, member) into --table")
     ap.add_argument("--share", type=float, default=None,
-                    help="with --cross-play: the focal member's share of a scene's slots (default 0.5); with --fault-sweep: the impaired "
-                         "share (default 1: every slot)")
-    ap.add_argument("--scenes-per-pair", type=int, default=4, help="scenes per pair (--cross-play) or per cell (--fault-sweep)")
-    ap.add_argument("--steps", type=int, default=1000, help="with --cross-play / --fault-sweep: env steps")
+                    help="with --cross-play: the focal member's share of a scene's slots (default 0.5); with --fault-sweep / --adversary-sweep: the "
+                         "impaired share (default 1: every slot)")
+    ap.add_argument("--scenes-per-pair", type=int, default=4, help="scenes per pair (--cross-play) or per cell (--fault-sweep, --adversary-sweep)")
+    ap.add_argument("--steps", type=int, default=1000, help="with --cross-play / --fault-sweep / --adversary-sweep: env steps")
     ap.add_argument("--fault-sweep", nargs="+", default=None, metavar="CKPT",
                     help="checkpoints of --algo's layout, each driven at every level of --fault-levels (eval/faults.py): one row per "
                          "(checkpoint, level, role) into --table")
     ap.add_argument("--fault-levels", default=None, metavar="JSON",
                     help="with --fault-sweep: a JSON list of {lidar_sigma, lidar_dropout, dropout_value, act_sigma, sticky}; the first "
                          "must be the identity {}")
-    a = ap.parse_args()
+    ap.add_argument("--adversary-sweep", nargs="+", default=None, metavar="CKPT",
+                    help="checkpoints of --algo's layout, each attacked at every level of --adversary-levels (eval/adversary.py: one "
+                         "gradient-sign step on the LiDAR block): one row per (checkpoint, level, role) into --table")
+    ap.add_argument("--adversary-levels", default=None, metavar="JSON",
+                    help="with --adversary-sweep: a JSON list of {eps, steer, throttle}; the first must be an identity, e.g. {}")
+    a = ap.parse_args(argv)
     from .checkpoint_io import load_members
+    if a.adversary_sweep:
+        if a.cross_play or a.fault_sweep:
+            ap.error("--adversary-sweep excludes --cross-play and --fault-sweep: one table per run")
+        if not a.table or not a.adversary_levels:
+            ap.error("--adversary-sweep needs --adversary-levels and --table")
+        from .adversary import adversary_sweep_rows, load_levels
+        df = adversary_sweep_rows("ippo" if a.algo == "cl" else a.algo, a.env, load_members(a.adversary_sweep), load_levels(a.adversary_levels),
+                                  share=1.0 if a.share is None else a.share, scenes_per_cell=a.scenes_per_pair, num_agents=a.num_agents,
+                                  steps=a.steps, labels=list(a.adversary_sweep))
+        df.to_csv(a.table)
+        print(df.drop(columns=["label"]).to_string())
+        return
     if a.fault_sweep:
         if not a.table or not a.fault_levels:
             ap.error("--fault-sweep needs --fault-levels and --table")

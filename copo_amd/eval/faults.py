@@ -23,7 +23,7 @@ from dataclasses import dataclass
 
 import numpy as np
 
-from .bank import DeviceTables
+from .bank import DeviceTables, draw_cell_noise
 from .crossplay import SEAT_WORDS, SeatPlan, SeatSampler, tally_rates
 
 LEVEL_WORDS = 8
@@ -101,26 +101,18 @@ class FaultPlan:
         K + k at level l, the rest member k at level 0, which must then be the identity: the tally keeps the impaired and the healthy
         drivers of a scene apart.  The seat plan declares `replica_scenes` = S, so `SeatSampler.reset` gives every cell the same scenes."""
         levels = [lv if isinstance(lv, FaultLevel) else FaultLevel(**lv) for lv in levels]
-        K, S, N, L, share = int(K), int(scenes_per_cell), int(N), len(levels), float(share)
-        if K < 1 or S < 1 or N < 1 or L < 1 or not 0.0 <= share <= 1.0:
-            raise ValueError("FaultPlan.sweep: K=%d levels=%d scenes_per_cell=%d N=%d share=%r" % (K, L, S, N, share))
-        doubled = share < 1.0
-        if doubled and not levels[0].is_identity:
-            raise ValueError("FaultPlan.sweep: with share < 1 the healthy seats drive at level 0, which must be the identity")
-        n_imp = int(round(share * N))
-        cell = np.repeat(np.arange(K * L, dtype=np.int32), S)
-        k_of, l_of = np.arange(K * L) // L, np.arange(K * L) % L
-        seat = np.empty((K * L * S, N), np.int32)
-        seat[:, :n_imp] = ((cell // L) + (K if doubled else 0))[:, None]
-        seat[:, n_imp:] = (cell // L)[:, None]
-        KB = 2 * K if doubled else K
-        level_of = np.zeros((K * L, KB), np.int32)
-        level_of[np.arange(K * L), k_of + (K if doubled else 0)] = l_of
-        seats = SeatPlan(seat, KB, cell, K * L, replica_scenes=S)
-        faults = cls(levels, level_of)
-        faults.checkpoint, faults.level, faults.share = k_of, l_of, share
-        faults.n_checkpoints, faults.doubled, faults.n_impaired, faults.scenes_per_cell = K, doubled, n_imp, S
-        return seats, faults
+        return sweep_plan(cls, "FaultPlan.sweep", K, levels, scenes_per_cell, N, share)
+
+
+def sweep_plan(cls, who, K, levels, scenes_per_cell, N, share):
+    """(seat plan, `cls(levels, level_of)`) on the cell layout of `SeatPlan.cells`, the layout's attributes on the level plan: what
+    `FaultPlan.sweep` and `AdversaryPlan.sweep` share.  With share < 1 the healthy seats drive at level 0, which must be the identity."""
+    seats, level_of, attrs = SeatPlan.cells(K, len(levels), scenes_per_cell, N, share, who)
+    if attrs["doubled"] and not levels[0].is_identity:
+        raise ValueError("%s: with share < 1 the healthy seats drive at level 0, which must be the identity" % who)
+    plan = cls(levels, level_of)
+    vars(plan).update(attrs)
+    return seats, plan
 
 
 def sweep_members(weights_list, faults):
@@ -211,11 +203,7 @@ class FaultySeatSampler(SeatSampler):
         """Ordinary noise; with a `sweep` plan the first cell's draw is copied to every cell, as `BankSampler` copies one member's: the
         cells already share their scene seeds, so at the identity level two cells differ by their checkpoint only.  (The fault draws
         themselves are keyed by the absolute row, so two impaired cells never share those.)"""
-        self.eps.normal_()
-        per = self.faults.scenes_per_cell
-        if per and self.E > per and self.E % per == 0:
-            cells = self.eps.view(self.T, self.E // per, per, self.N, 2)
-            cells[:, 1:].copy_(cells[:, :1])
+        draw_cell_noise(self.eps, self.faults.scenes_per_cell)
 
     def sample(self):
         batch = super().sample()
@@ -234,7 +222,8 @@ class FaultySeatSampler(SeatSampler):
 
 def sweep_frame(tally, seats, faults, labels=None):
     """The tally [G][K][8] (numpy int64) of a `sweep` plan as a frame: one row per (checkpoint, level, role), the columns of
-    `fault_sweep_rows`."""
+    `fault_sweep_rows`.  `faults`: the level plan of the sweep -- a `FaultPlan`, or any plan made by `sweep_plan` (an
+    `adversary.AdversaryPlan`): the level's columns are whatever its levels' `as_dict()` names."""
     import pandas as pd
     labels = list(range(faults.n_checkpoints)) if labels is None else list(labels)
     K, N, n_imp = faults.n_checkpoints, seats.N, faults.n_impaired

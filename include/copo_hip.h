@@ -952,6 +952,25 @@ int copo_mlp_forward_seats_f32(const copo_ppo_cfg* cfg, const float* theta, cons
                                int32_t n_members, const int64_t* rows, const int32_t* counts, int64_t cap, int64_t n_out,
                                const float* obs_src, float* dist_inputs, const float* eps, float* action, float* logp, float* clipped,
                                void* stream);
+/* Adversarial observation of a seated bank (eval/adversary.py): one gradient-sign step on the columns
+ * [col_lo, col_hi) of every listed row, against the policy that drives the row.  Member k owns the row list of seat mode (rows, counts,
+ * cap, n_out as in copo_mlp_forward_seats_f32; rows in no list are not written).  A row's level is
+ * levels[level_of[group[row / n_slots]][k]] = (eps, steer, throttle, 0): with mu = the first two outputs of member k's policy net on the
+ * TRUE row o of obs_src and J = steer mu_0 + throttle mu_1, g = dJ/do and
+ *     obs_seen[row][j] = clamp(o[j] + eps sign(g[j]), 0, 1) for col_lo <= j < col_hi (sign(0) = 0), o[j] bit for bit elsewhere.
+ * A row passes through bit for bit, with no arithmetic on it, when its level index or its group is out of range, when eps == 0 or when
+ * steer == throttle == 0.  grad (device [n_out][in_dim] or NULL): g of every listed row, zeros for rows whose level is out of range or
+ * has steer == throttle == 0; with grad given, rows at eps == 0 still get their gradient (a per-beam saliency) and pass through.
+ * One launch, grid ceil(cap / 16) x n_members, always the 16-row tile; forward and backward run in the same workgroup, W1 / W2 of the
+ * forward from the mirror theta_t, those of the backward from theta as stored.  No atomics, fixed summation order: two launches give
+ * the same bits.  fp32 operands and hidden in {64, 128, 256, 512} only (else COPO_ERR_DIM, as for n_out % n_slots != 0, columns
+ * outside [0, in_dim], cap < 1, n_members outside 1..65535, a member_stride the bank entry refuses); NULL theta / theta_t / rows / counts / obs_src /
+ * obs_seen / group / level_of / levels: COPO_ERR_NULL.  A refused call launches nothing. */
+int copo_adv_obs_seats_f32(const copo_ppo_cfg* cfg, const float* theta, const float* theta_t, int64_t member_stride,
+                           int32_t n_members, const int64_t* rows, const int32_t* counts, int64_t cap, int64_t n_out,
+                           const float* obs_src, float* obs_seen, float* grad, int32_t col_lo, int32_t col_hi, int32_t n_slots,
+                           const int32_t* group, int32_t n_groups, const int32_t* level_of, const float* levels,
+                           int32_t n_levels, void* stream);
 /* The same pass over a LIST of rows: launch row m reads row rows[m] of the sources ([n_src_rows][..]) and writes
  * values[net][rows[m]] (values is [n_nets][n_src_rows]; entries of unlisted rows are left alone).  The dense postprocess
  * of a rollout buffer uses it with the rows that hold an agent -- about half of the slots. */

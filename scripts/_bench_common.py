@@ -1,5 +1,6 @@
 """What the observer benchmarks (`bench_interact`, `bench_clips`, `bench_rewind`, `bench_fields`, `bench_gates`, `bench_trips`, `bench_conflicts`, `bench_pet`) share:
-the timing loop, the command line, the scene they measure on and the JSON line they end with."""
+the timing loop, the command line, the scene they measure on and the JSON line they end with; `bench_faults` and `bench_adversary` also
+take the graph-replay timer from here."""
 import argparse
 import json
 import os
@@ -23,6 +24,21 @@ def timed(torch, fn, iters, batch):
         torch.cuda.synchronize()
         times.append(t0.elapsed_time(t1) * 1e3 / batch)
     return float(np.median(times)), float(min(times))
+
+
+def replayed(torch, fn, iters, batch):
+    """median microseconds per call of `batch` calls captured into one graph and replayed: the cost inside the sampler's captured
+    fragment, without the host's share of issuing each launch"""
+    s = torch.cuda.Stream()
+    s.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(s):
+        fn()
+    torch.cuda.current_stream().wait_stream(s)
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        for _ in range(batch):
+            fn()
+    return timed(torch, g.replay, iters, 1)[0] / batch
 
 
 def base_parser(**extra):

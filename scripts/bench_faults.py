@@ -17,22 +17,7 @@ import ctypes as C
 
 import numpy as np
 
-from _bench_common import base_parser, emit, timed
-
-
-def replayed(torch, fn, iters, batch):
-    """median microseconds per call of `batch` calls captured into one graph and replayed: the cost inside the sampler's captured
-    fragment, without the host's share of issuing each launch"""
-    s = torch.cuda.Stream()
-    s.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(s):
-        fn()
-    torch.cuda.current_stream().wait_stream(s)
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g):
-        for _ in range(batch):
-            fn()
-    return timed(torch, g.replay, iters, 1)[0] / batch
+from _bench_common import base_parser, emit, replayed, timed
 
 
 def main():
