@@ -32,12 +32,14 @@ constexpr int LDS_GEMM = (int)GEMM_LDS_BYTES;
     X(WGRAD_OT2, 64 * WG_WAVES, 80 * 1024, wgrad_adam_kernel<2>)                                                             \
     X(HEAD, 256, LDS_DEFAULT, head_kernel) X(META_FOLD, 256, LDS_DEFAULT, meta_batch_fold_kernel)                            \
     X(REDUCE_ADAM, 256, LDS_DEFAULT, reduce_adam_kernel)
-// rows behind the learner's: kernels of the evaluation side that live in this translation unit (learn_inputgrad.inc).  They are launched
+// rows behind the learner's: kernels of the evaluation side that live in this translation unit (learn_inputgrad.inc, learn_pgd.inc).  They are launched
 // through the same launch_kernel and get their LDS ceilings from the same loop; copo_debug_learner_kernel lists the learner's rows only
-// (ids below K_LEARNER_COUNT).  The four shapes in shape_index order.
+// (ids below K_LEARNER_COUNT).  Per kernel the four shapes in shape_index order.
 #define COPO_EVAL_KERNELS(X)                                                                                                \
     X(ADV_1_4, 256, LDS_ROWPASS, adv_obs_kernel<1, 4>) X(ADV_2_4, 256, LDS_ROWPASS, adv_obs_kernel<2, 4>)                    \
-    X(ADV_2_8, 512, LDS_ROWPASS, adv_obs_kernel<2, 8>) X(ADV_4_8, 512, LDS_ROWPASS, adv_obs_kernel<4, 8>)
+    X(ADV_2_8, 512, LDS_ROWPASS, adv_obs_kernel<2, 8>) X(ADV_4_8, 512, LDS_ROWPASS, adv_obs_kernel<4, 8>)                    \
+    X(PGD_1_4, 256, LDS_ROWPASS, pgd_obs_kernel<1, 4>) X(PGD_2_4, 256, LDS_ROWPASS, pgd_obs_kernel<2, 4>)                    \
+    X(PGD_2_8, 512, LDS_ROWPASS, pgd_obs_kernel<2, 8>) X(PGD_4_8, 512, LDS_ROWPASS, pgd_obs_kernel<4, 8>)
 struct KernelEntry { const char* name; const void* fn; int block, lds_cap; };
 #define COPO_KERNEL_ID(id, block, cap, ...) K_##id,
 #define COPO_KERNEL_ENTRY(id, block, cap, ...) {#__VA_ARGS__, reinterpret_cast<const void*>(__VA_ARGS__), block, cap},
@@ -240,5 +242,19 @@ static int plan_adversary(const copo_ppo_cfg& c, int64_t cap, int n_members, int
     if (lds > (size_t)LDS_ROWPASS) return COPO_ERR_DIM;
     const int id = K_ADV_1_4 + sh;
     *out = Launch{id, (uint32_t)((cap + HT - 1) / HT), (uint32_t)n_members, 1, g_kernels[id].block, (int32_t)lds, {}};
+    return COPO_OK;
+}
+
+// Iterated input-gradient pass of a seated bank (copo_pgd_obs_seats_f32, learn_pgd.inc): plan_adversary's launch shape and refusals, the
+// LDS of a second input tile, and the iteration bound of the launch (1 .. PGD_MAX_ITERS).
+static int plan_pgd(const copo_ppo_cfg& c, int64_t cap, int n_members, int max_iters, int facts, Launch* out) {
+    if (max_iters < 1 || max_iters > PGD_MAX_ITERS) return COPO_ERR_DIM;
+    const int rc = plan_adversary(c, cap, n_members, facts, out);
+    if (rc != COPO_OK) return rc;
+    const size_t lds = pgd_lds_floats(c.hidden, rowpass_k1p(c.pol.in_dim)) * sizeof(float);
+    if (lds > (size_t)LDS_ROWPASS) return COPO_ERR_DIM;
+    out->id = K_PGD_1_4 + shape_index(c.hidden);
+    out->block = g_kernels[out->id].block;
+    out->lds = (int32_t)lds;
     return COPO_OK;
 }

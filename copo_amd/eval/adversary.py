@@ -14,8 +14,8 @@ policy then acts on `seen` through the unchanged seat forward.  `copo_adv_obs_se
 8m) does forward and backward-to-input of a seated bank in one launch; its raw gradient is an optional output, the per-beam saliency
 of a checkpoint (`beam_saliency`).
 
-One step, an L-infinity budget, the LiDAR block, fp32 operands.  Multi-step PGD, untargeted objectives, the ego / navigation columns
-and the bfloat16 operand mode are out of scope.
+One step, an L-infinity budget, the LiDAR block, fp32 operands.  Multi-step PGD and untargeted objectives are `pgd.py`'s; the ego /
+navigation columns and the bfloat16 operand mode are out of scope.
 
 Pieces: `AdversaryLevel` / `AdversaryPlan` (numpy only), `AdversaryBuffers`, `AdversarialSeatSampler` (the `SeatSampler` whose
 `_policy_obs` launches the kernel inside the captured fragment), `adversary_sweep_rows` (checkpoints x levels x roles as a pandas frame;

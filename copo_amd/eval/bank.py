@@ -118,6 +118,28 @@ class PolicyBank:
             pb.cap, pb.n_out, obs.data_ptr(), obs_seen.data_ptr(), None if grad is None else grad.data_ptr(), int(col_lo), int(col_hi), pb.N,
             pb.group.data_ptr(), pb.G, ab.level_of.data_ptr(), ab.levels.data_ptr(), ab.L, self._capi.current_stream()))
 
+    def pgd_seats(self, plan_buffers, pgd_buffers, obs, obs_seen, col_lo, col_hi, seed=0, tick=None, trace=None, max_iters=None):
+        """`copo_pgd_obs_seats_f32` (eval/pgd.py) on the current stream: obs [n_out, O] -> obs_seen, the iterated attack on the columns
+        [col_lo, col_hi) of every seated row against the member that drives it, at the level `pgd_buffers` (`pgd.PGDBuffers`) gives
+        (scene group, member).  `tick` int32 [n_out]: the launch counter of the random starts, advanced by the kernel (None: 0);
+        `trace` [max_iters, n_out, O]: the gradient of every iteration, if wanted; `max_iters` defaults to the plan's.  Needs the
+        mirror (`sync_mirror`), as `act_seats`."""
+        pb, gb = plan_buffers, pgd_buffers
+        max_iters = int(gb.max_iters if max_iters is None else max_iters)
+        if pb.K != self.K or (gb.G, gb.K) != (pb.G, pb.K):
+            raise ValueError("PolicyBank.pgd_seats: a bank of %d, a plan of %d groups x %d members, levels for %d x %d" % (
+                self.K, pb.G, pb.K, gb.G, gb.K))
+        O = int(self.cfg.pol.in_dim)
+        for name, t, shape, dtype in (("obs", obs, (pb.n_out, O), torch.float32), ("obs_seen", obs_seen, (pb.n_out, O), torch.float32),
+                                      ("trace", trace, (max_iters, pb.n_out, O), torch.float32), ("tick", tick, (pb.n_out,), torch.int32)):
+            if t is not None and (tuple(t.shape) != shape or not t.is_contiguous() or t.dtype != dtype):
+                raise ValueError("PolicyBank.pgd_seats: %s of shape %s, contiguous %s %s wanted" % (name, tuple(t.shape), dtype, list(shape)))
+        self._capi.check(self._capi.lib.copo_pgd_obs_seats_f32(
+            C.byref(self.cfg), self.theta.data_ptr(), self.theta_t.data_ptr(), self.stride, self.K, pb.rows.data_ptr(), pb.counts.data_ptr(),
+            pb.cap, pb.n_out, obs.data_ptr(), obs_seen.data_ptr(), int(col_lo), int(col_hi), pb.N, pb.group.data_ptr(), pb.G,
+            gb.level_of.data_ptr(), gb.levels.data_ptr(), gb.L, int(seed) & (2 ** 64 - 1), None if tick is None else tick.data_ptr(), max_iters,
+            None if trace is None else trace.data_ptr(), self._capi.current_stream()))
+
 
 class _BankPolicy:
     """What `VecSampler` reads of a policy, with the bank as its fused learner."""

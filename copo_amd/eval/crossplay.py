@@ -167,6 +167,10 @@ class SeatedBank:
         """`PolicyBank.perturb_seats` over the plan's own buffers (eval/adversary.py)."""
         self.bank.perturb_seats(self.buffers, adv_buffers, obs, obs_seen, col_lo, col_hi, grad)
 
+    def pgd_seats(self, pgd_buffers, obs, obs_seen, col_lo, col_hi, seed=0, tick=None, trace=None, max_iters=None):
+        """`PolicyBank.pgd_seats` over the plan's own buffers (eval/pgd.py)."""
+        self.bank.pgd_seats(self.buffers, pgd_buffers, obs, obs_seen, col_lo, col_hi, seed, tick, trace, max_iters)
+
 
 class SeatSampler(VecSampler):
     """`VecSampler` with a `SeatedBank` in the policy's place, as `BankSampler` puts a bank there, and the seat tally behind every

@@ -298,10 +298,10 @@ def main(argv=None):
                     help="checkpoints (.npz populations or Tune checkpoint files) of --algo's layout: every ordered pair shares scenes "
                          "(eval/crossplay.py), one row per (pair, member) into --table")
     ap.add_argument("--share", type=float, default=None,
-                    help="with --cross-play: the focal member's share of a scene's slots (default 0.5); with --fault-sweep / --adversary-sweep: the "
+                    help="with --cross-play: the focal member's share of a scene's slots (default 0.5); with --fault-sweep / --adversary-sweep / --pgd-sweep: the "
                          "impaired share (default 1: every slot)")
-    ap.add_argument("--scenes-per-pair", type=int, default=4, help="scenes per pair (--cross-play) or per cell (--fault-sweep, --adversary-sweep)")
-    ap.add_argument("--steps", type=int, default=1000, help="with --cross-play / --fault-sweep / --adversary-sweep: env steps")
+    ap.add_argument("--scenes-per-pair", type=int, default=4, help="scenes per pair (--cross-play) or per cell (--fault-sweep, --adversary-sweep, --pgd-sweep)")
+    ap.add_argument("--steps", type=int, default=1000, help="with --cross-play / --fault-sweep / --adversary-sweep / --pgd-sweep: env steps")
     ap.add_argument("--fault-sweep", nargs="+", default=None, metavar="CKPT",
                     help="checkpoints of --algo's layout, each driven at every level of --fault-levels (eval/faults.py): one row per "
                          "(checkpoint, level, role) into --table")
@@ -313,8 +313,26 @@ def main(argv=None):
                          "gradient-sign step on the LiDAR block): one row per (checkpoint, level, role) into --table")
     ap.add_argument("--adversary-levels", default=None, metavar="JSON",
                     help="with --adversary-sweep: a JSON list of {eps, steer, throttle}; the first must be an identity, e.g. {}")
+    ap.add_argument("--pgd-sweep", nargs="+", default=None, metavar="CKPT",
+                    help="checkpoints of --algo's layout, each attacked at every level of --pgd-levels (eval/pgd.py: iterated "
+                         "gradient-sign steps on the LiDAR block, projected onto the budget): one row per (checkpoint, level, role) into --table")
+    ap.add_argument("--pgd-levels", default=None, metavar="JSON",
+                    help="with --pgd-sweep: a JSON list of {eps, steer, throttle, alpha, iters, random_start, untargeted}; the first must "
+                         "be an identity, e.g. {}")
     a = ap.parse_args(argv)
     from .checkpoint_io import load_members
+    if a.pgd_sweep:
+        if a.cross_play or a.fault_sweep or a.adversary_sweep:
+            ap.error("--pgd-sweep excludes --cross-play, --fault-sweep and --adversary-sweep: one table per run")
+        if not a.table or not a.pgd_levels:
+            ap.error("--pgd-sweep needs --pgd-levels and --table")
+        from .pgd import load_levels, pgd_sweep_rows
+        df = pgd_sweep_rows("ippo" if a.algo == "cl" else a.algo, a.env, load_members(a.pgd_sweep), load_levels(a.pgd_levels),
+                            share=1.0 if a.share is None else a.share, scenes_per_cell=a.scenes_per_pair, num_agents=a.num_agents,
+                            steps=a.steps, labels=list(a.pgd_sweep))
+        df.to_csv(a.table)
+        print(df.drop(columns=["label"]).to_string())
+        return
     if a.adversary_sweep:
         if a.cross_play or a.fault_sweep:
             ap.error("--adversary-sweep excludes --cross-play and --fault-sweep: one table per run")

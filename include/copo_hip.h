@@ -971,6 +971,31 @@ int copo_adv_obs_seats_f32(const copo_ppo_cfg* cfg, const float* theta, const fl
                            const float* obs_src, float* obs_seen, float* grad, int32_t col_lo, int32_t col_hi, int32_t n_slots,
                            const int32_t* group, int32_t n_groups, const int32_t* level_of, const float* levels,
                            int32_t n_levels, void* stream);
+/* Iterated adversarial observation of a seated bank (eval/pgd.py): projected gradient descent on the columns
+ * [col_lo, col_hi) of every listed row, against the policy that drives the row, all iterations in one launch.  The seat-mode arguments,
+ * obs_src, obs_seen, the columns, n_slots, group and level_of are those of copo_adv_obs_seats_f32.  A level is eight 32-bit words:
+ * eps >= 0, steer, throttle, alpha >= 0 (f32), iters, flags (i32; bit 0 RANDOM_START, bit 1 UNTARGETED), two zeros.  With
+ * it = min(iters, max_iters) and o the TRUE row:
+ *     x_0 = o; under RANDOM_START x_0[j] = clamp(o[j] + eps u, 0, 1) on the columns, u = 2 uniform01(h) - 1,
+ *           h = hash_rng(seed, row, tick[row], j - col_lo, 40) of sim_math.h
+ *     i < it: g = dJ/dx at x_i; J = steer mu_0 + throttle mu_1, or under UNTARGETED J = |mu(x) - mu(o)|^2 / 2;
+ *           y = x_i[j] + alpha sign(g[j]) (sign(0) = 0); y = min(max(y, o[j] - eps), o[j] + eps); x_{i+1}[j] = min(max(y, 0), 1)
+ *     obs_seen[row] = x_it on the columns, o[j] bit for bit elsewhere; every sum and product is rounded once.
+ * A row passes through bit for bit, with no arithmetic on it, when its level index or its group is out of range, when eps == 0, when
+ * it <= 0, or when the level is targeted with steer == throttle == 0; rows in no list are not written.  iters = 1, alpha = eps,
+ * flags = 0 is copo_adv_obs_seats_f32's step.  tick (device int32 [n_out] or NULL, which reads as 0) counts the calls: every listed
+ * valid row reads tick[row] and gets tick[row] + 1 back, at every level, so a captured graph draws fresh starts at every replay (a row
+ * sits in one member's list at the most).  trace (device float [max_iters][n_out][in_dim] or NULL): g of iteration i of every
+ * attacked row for i < it, zeros for later iterations and for listed rows that pass through.  One launch, grid ceil(cap / 16) x
+ * n_members, the 16-row tile with the iterate resident in LDS; no atomics: two launches from equal ticks give the same bits.
+ * Refusals as copo_adv_obs_seats_f32 (NULL theta / theta_t / rows / counts / obs_src / obs_seen / group / level_of / levels:
+ * COPO_ERR_NULL; bad dimensions, bfloat16 operands, a hidden width outside {64, 128, 256, 512}: COPO_ERR_DIM), and max_iters outside
+ * [1, 16]: COPO_ERR_DIM.  A refused call launches nothing. */
+int copo_pgd_obs_seats_f32(const copo_ppo_cfg* cfg, const float* theta, const float* theta_t, int64_t member_stride,
+                           int32_t n_members, const int64_t* rows, const int32_t* counts, int64_t cap, int64_t n_out,
+                           const float* obs_src, float* obs_seen, int32_t col_lo, int32_t col_hi, int32_t n_slots,
+                           const int32_t* group, int32_t n_groups, const int32_t* level_of, const uint32_t* levels,
+                           int32_t n_levels, uint64_t seed, int32_t* tick, int32_t max_iters, float* trace, void* stream);
 /* The same pass over a LIST of rows: launch row m reads row rows[m] of the sources ([n_src_rows][..]) and writes
  * values[net][rows[m]] (values is [n_nets][n_src_rows]; entries of unlisted rows are left alone).  The dense postprocess
  * of a rollout buffer uses it with the rows that hold an agent -- about half of the slots. */
