@@ -475,6 +475,17 @@ extern "C" int copo_seat_tally(const uint8_t* flags, const float* rew, const int
     return COPO_OK;
 }
 
+extern "C" int copo_certify_tally(const uint8_t* flags, const float* bounds, const int32_t* seat, const int32_t* group,
+                                  const int32_t* level_of, const float* levels, int32_t E, int32_t N, int32_t K, int32_t G, int32_t L,
+                                  int64_t* out, void* stream) {
+    if (!flags || !bounds || !seat || !group || !level_of || !levels || !out) return fail(COPO_ERR_NULL, "copo_certify_tally: NULL argument");
+    if (E < 0 || N < 1 || N > COPO_SEAT_MAX_SLOTS || K < 1 || K > 65535 || G < 1 || L < 1)
+        return fail(COPO_ERR_DIM, "copo_certify_tally: E=%d N=%d (1..%d) K=%d (1..65535) G=%d (>= 1) L=%d (>= 1)", E, N, COPO_SEAT_MAX_SLOTS, K, G, L);
+    if (E == 0) return COPO_OK;
+    HIP_TRY(launch_certify_tally(flags, bounds, seat, group, level_of, levels, E, N, K, G, L, out, static_cast<hipStream_t>(stream)));
+    return COPO_OK;
+}
+
 // what copo_fault_obs and copo_fault_act share: the keys of a row's level.  Every refusal is -1 with the entry point's name.
 static int check_fault(const char* name, int32_t E, int32_t N, const void* seat, const void* group, int32_t K, int32_t G,
                        const void* level_of, const void* levels, int32_t L, const void* tick) {

@@ -32,14 +32,16 @@ constexpr int LDS_GEMM = (int)GEMM_LDS_BYTES;
     X(WGRAD_OT2, 64 * WG_WAVES, 80 * 1024, wgrad_adam_kernel<2>)                                                             \
     X(HEAD, 256, LDS_DEFAULT, head_kernel) X(META_FOLD, 256, LDS_DEFAULT, meta_batch_fold_kernel)                            \
     X(REDUCE_ADAM, 256, LDS_DEFAULT, reduce_adam_kernel)
-// rows behind the learner's: kernels of the evaluation side that live in this translation unit (learn_inputgrad.inc, learn_pgd.inc).  They are launched
+// rows behind the learner's: kernels of the evaluation side that live in this translation unit (learn_inputgrad.inc, learn_pgd.inc, learn_certify.inc).  They are launched
 // through the same launch_kernel and get their LDS ceilings from the same loop; copo_debug_learner_kernel lists the learner's rows only
 // (ids below K_LEARNER_COUNT).  Per kernel the four shapes in shape_index order.
 #define COPO_EVAL_KERNELS(X)                                                                                                \
     X(ADV_1_4, 256, LDS_ROWPASS, adv_obs_kernel<1, 4>) X(ADV_2_4, 256, LDS_ROWPASS, adv_obs_kernel<2, 4>)                    \
     X(ADV_2_8, 512, LDS_ROWPASS, adv_obs_kernel<2, 8>) X(ADV_4_8, 512, LDS_ROWPASS, adv_obs_kernel<4, 8>)                    \
     X(PGD_1_4, 256, LDS_ROWPASS, pgd_obs_kernel<1, 4>) X(PGD_2_4, 256, LDS_ROWPASS, pgd_obs_kernel<2, 4>)                    \
-    X(PGD_2_8, 512, LDS_ROWPASS, pgd_obs_kernel<2, 8>) X(PGD_4_8, 512, LDS_ROWPASS, pgd_obs_kernel<4, 8>)
+    X(PGD_2_8, 512, LDS_ROWPASS, pgd_obs_kernel<2, 8>) X(PGD_4_8, 512, LDS_ROWPASS, pgd_obs_kernel<4, 8>)                    \
+    X(CERT_1_4, 256, LDS_ROWPASS, cert_obs_kernel<1, 4>) X(CERT_2_4, 256, LDS_ROWPASS, cert_obs_kernel<2, 4>)                \
+    X(CERT_2_8, 512, LDS_ROWPASS, cert_obs_kernel<2, 8>) X(CERT_4_8, 512, LDS_ROWPASS, cert_obs_kernel<4, 8>)
 struct KernelEntry { const char* name; const void* fn; int block, lds_cap; };
 #define COPO_KERNEL_ID(id, block, cap, ...) K_##id,
 #define COPO_KERNEL_ENTRY(id, block, cap, ...) {#__VA_ARGS__, reinterpret_cast<const void*>(__VA_ARGS__), block, cap},
@@ -254,6 +256,19 @@ static int plan_pgd(const copo_ppo_cfg& c, int64_t cap, int n_members, int max_i
     const size_t lds = pgd_lds_floats(c.hidden, rowpass_k1p(c.pol.in_dim)) * sizeof(float);
     if (lds > (size_t)LDS_ROWPASS) return COPO_ERR_DIM;
     out->id = K_PGD_1_4 + shape_index(c.hidden);
+    out->block = g_kernels[out->id].block;
+    out->lds = (int32_t)lds;
+    return COPO_OK;
+}
+
+// Interval bounds of a seated bank (copo_cert_obs_seats_f32, learn_certify.inc): plan_adversary's launch shape and refusals, the LDS of
+// three input tiles and three h1 tiles (layer 2's output stays on the lanes).
+static int plan_certify(const copo_ppo_cfg& c, int64_t cap, int n_members, int facts, Launch* out) {
+    const int rc = plan_adversary(c, cap, n_members, facts, out);
+    if (rc != COPO_OK) return rc;
+    const size_t lds = cert_lds_floats(c.hidden, rowpass_k1p(c.pol.in_dim)) * sizeof(float);
+    if (lds > (size_t)LDS_ROWPASS) return COPO_ERR_DIM;
+    out->id = K_CERT_1_4 + shape_index(c.hidden);
     out->block = g_kernels[out->id].block;
     out->lds = (int32_t)lds;
     return COPO_OK;

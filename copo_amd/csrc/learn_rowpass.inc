@@ -195,6 +195,48 @@ struct BRing {
         }
     }
 
+    // run_tiles whose row tiles named by the bit mask ABS multiply by |W|: the B fragment a step holds feeds every row tile, the
+    // masked ones through fabsf of the value in its register (interval propagation, learn_certify.inc: centre and radius of a box
+    // against one weight stream).  Per unmasked row tile the instruction sequence is run_tiles', so those results are the same bits.
+    template <int RT, unsigned ABS>
+    __device__ __forceinline__ void run_tiles_abs(const float* As, int astride, int k, int ln, int lj, v4f (*acc)[NT]) {
+        const float* arow = As + ln * astride + 4 * lj;
+        const int ns = k >> 4;
+        for (int s0 = 0; s0 < ns; s0 += D) {
+#pragma unroll
+            for (int u = 0; u < D; ++u) {
+                const int s = s0 + u;
+                if (s >= ns) break;
+                float av[RT][4];
+#pragma unroll
+                for (int rt = 0; rt < RT; ++rt) {
+                    const float4 a4 = *reinterpret_cast<const float4*>(arow + (size_t)rt * 16 * astride + 16 * s);
+                    av[rt][0] = a4.x; av[rt][1] = a4.y; av[rt][2] = a4.z; av[rt][3] = a4.w;
+                }
+                if constexpr (VW > 1) {
+#pragma unroll
+                    for (int e = 0; e < 4; ++e)
+#pragma unroll
+                        for (int q = 0; q < NV; ++q) asm volatile("" : "+v"(b[u][e][q]));
+                }
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+#pragma unroll
+                    for (int t = 0; t < NT; ++t) {
+                        const float bv = opnd<BF>(ColVec<VW>::get(b[u][e][t / VW], t % VW));
+#pragma unroll
+                        for (int rt = 0; rt < RT; ++rt)
+                            acc[rt][t] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[rt][e], (ABS >> rt) & 1u ? fabsf(bv) : bv, acc[rt][t], 0, 0, 0);
+                    }
+                const int sn = s + D < ns ? s + D : ns - 1;
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+#pragma unroll
+                    for (int q = 0; q < NV; ++q) b[u][e][q] = *reinterpret_cast<const vec_t*>(wcol + (size_t)(16 * sn + e) * wstride + VW * q);
+            }
+        }
+    }
+
     template <bool REFILL = true>
     __device__ __forceinline__ void run(const float* As, int astride, int k, int ln, int lj, v4f* acc) {
         const float* arow = As + ln * astride + 4 * lj;

@@ -9,4 +9,8 @@ namespace copo {
 hipError_t launch_seat_tally(const uint8_t* flags, const float* rew, const int32_t* seat, const int32_t* group, int32_t E, int32_t N,
                              int32_t K, int32_t G, int64_t* out, hipStream_t stream);
 
+// certified bounds of one step folded per (scene group, bank member) into out[G][K][COPO_CERT_TALLY_WORDS] (one launch)
+hipError_t launch_certify_tally(const uint8_t* flags, const float* bounds, const int32_t* seat, const int32_t* group, const int32_t* level_of,
+                                const float* levels, int32_t E, int32_t N, int32_t K, int32_t G, int32_t L, int64_t* out, hipStream_t stream);
+
 }  // namespace copo

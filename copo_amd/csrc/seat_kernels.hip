@@ -76,6 +76,88 @@ __global__ __launch_bounds__(256) void seat_tally_kernel(const uint8_t* __restri
     }
 }
 
+// Certify tally (copo_certify_tally): one step's certified bounds (copo_cert_obs_seats_f32) folded per (scene
+// group, member) against the level's deltas.  The wave walk is seat_tally_kernel's; the words are counts, sums of quantised widths
+// (rounded once per row, as the reward above) and one 64-bit atomic max, so the result does not depend on the order either.
+namespace {
+
+// rint(min(max(x, 0), 1024) * 65536): exact product, one rounding (the callers pass finite values)
+__device__ inline int64_t cert_q16(float x) { return (int64_t)rintf(fminf(fmaxf(x, 0.0f), 1024.0f) * 65536.0f); }
+
+__device__ inline int64_t wave_max_i64(int64_t v) {
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) {
+        const int32_t lo = __shfl_xor((int32_t)(uint32_t)((uint64_t)v & 0xffffffffu), o);
+        const int32_t hi = __shfl_xor((int32_t)(uint32_t)((uint64_t)v >> 32), o);
+        const int64_t w = (int64_t)(((uint64_t)(uint32_t)hi << 32) | (uint64_t)(uint32_t)lo);
+        v = w > v ? w : v;
+    }
+    return v;
+}
+
+}  // namespace
+
+__global__ __launch_bounds__(256) void certify_tally_kernel(const uint8_t* __restrict__ flags, const float* __restrict__ bounds,
+                                                            const int32_t* __restrict__ seat, const int32_t* __restrict__ group,
+                                                            const int32_t* __restrict__ level_of, const float* __restrict__ levels,
+                                                            int32_t E, int32_t N, int32_t K, int32_t G, int32_t L, int64_t* __restrict__ out) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int e = blockIdx.x * SCENES_PER_WG + wave;
+    if (e >= E) return;                        // (the whole wave; there is no barrier in this kernel)
+    const int g = group[e];
+    if (g < 0 || g >= G) return;               // (the whole wave)
+    for (int j = 0; 64 * j < N; ++j) {
+        const int n = lane + 64 * j;
+        const size_t idx = (size_t)e * N + (n < N ? n : 0);
+        const int s = n < N ? seat[idx] : -1;
+        const bool seated = s >= 0 && s < K;
+        const int lv = seated ? level_of[(size_t)g * K + s] : -1;
+        const bool counted = seated && lv >= 0 && lv < L && ((uint32_t)flags[idx] & COPO_F_ACTED) != 0u &&
+                             bounds[idx * COPO_CERT_WORDS + 6] == 1.0f;
+        bool finite = false, ok0 = false, ok1 = false;
+        int64_t qw0 = 0, qw1 = 0, qdev = 0;
+        if (counted) {
+            const float* b = bounds + idx * COPO_CERT_WORDS;
+            const float lo0 = b[0], hi0 = b[1], lo1 = b[2], hi1 = b[3], mu0 = b[4], mu1 = b[5];
+            finite = isfinite(lo0) && isfinite(hi0) && isfinite(lo1) && isfinite(hi1) && isfinite(mu0) && isfinite(mu1);
+            if (finite) {
+                const float dev0 = fmaxf(hi0 - mu0, mu0 - lo0), dev1 = fmaxf(hi1 - mu1, mu1 - lo1);
+                ok0 = dev0 <= levels[4 * lv + 1];
+                ok1 = dev1 <= levels[4 * lv + 2];
+                qw0 = cert_q16(hi0 - lo0);
+                qw1 = cert_q16(hi1 - lo1);
+                qdev = cert_q16(fmaxf(dev0, dev1));
+            }
+        }
+        uint64_t todo = __ballot(counted);      // lanes with something to add; uniform over the wave
+        while (todo) {
+            const int m = __shfl(s, __ffsll((unsigned long long)todo) - 1);          // a served lane is seated: 0 <= m < K
+            const bool mine = counted && s == m;
+            todo &= ~__ballot(mine);
+            const int64_t s0 = wave_sum_i64(mine ? qw0 : 0), s1 = wave_sum_i64(mine ? qw1 : 0), mx = wave_max_i64(mine ? qdev : 0);
+            const int c_rows = __popcll(__ballot(mine)), c_both = __popcll(__ballot(mine && ok0 && ok1));
+            const int c_steer = __popcll(__ballot(mine && ok0)), c_throttle = __popcll(__ballot(mine && ok1));
+            const int c_bad = __popcll(__ballot(mine && !finite));
+            if (lane < COPO_CERT_TALLY_WORDS) {
+                const int64_t v = lane == 0 ? c_rows : lane == 1 ? c_both : lane == 2 ? c_steer : lane == 3 ? c_throttle : lane == 4 ? s0
+                                : lane == 5 ? s1 : lane == 6 ? mx : c_bad;
+                unsigned long long* at = reinterpret_cast<unsigned long long*>(out) + ((size_t)g * K + m) * COPO_CERT_TALLY_WORDS + lane;
+                if (v != 0) {
+                    if (lane == 6) atomicMax(at, (unsigned long long)v);
+                    else atomicAdd(at, (unsigned long long)v);
+                }
+            }
+        }
+    }
+}
+
+hipError_t launch_certify_tally(const uint8_t* flags, const float* bounds, const int32_t* seat, const int32_t* group, const int32_t* level_of,
+                                const float* levels, int32_t E, int32_t N, int32_t K, int32_t G, int32_t L, int64_t* out, hipStream_t stream) {
+    hipLaunchKernelGGL(certify_tally_kernel, dim3((E + SCENES_PER_WG - 1) / SCENES_PER_WG), dim3(256), 0, stream, flags, bounds, seat, group,
+                       level_of, levels, E, N, K, G, L, out);
+    return hipGetLastError();
+}
+
 hipError_t launch_seat_tally(const uint8_t* flags, const float* rew, const int32_t* seat, const int32_t* group, int32_t E, int32_t N,
                              int32_t K, int32_t G, int64_t* out, hipStream_t stream) {
     hipLaunchKernelGGL(seat_tally_kernel, dim3((E + SCENES_PER_WG - 1) / SCENES_PER_WG), dim3(256), 0, stream, flags, rew, seat, group, E, N, K,

@@ -141,6 +141,24 @@ class PolicyBank:
             None if trace is None else trace.data_ptr(), self._capi.current_stream()))
 
 
+    def certify_seats(self, plan_buffers, cert_buffers, obs, bounds, col_lo, col_hi, pad=0.0):
+        """`copo_cert_obs_seats_f32` (eval/certify.py) on the current stream: obs [n_out, O] -> bounds [n_out, 8], the interval bounds
+        of the two action means of every seated row over the L-infinity box of its level's `eps` on the columns [col_lo, col_hi), at
+        the level `cert_buffers` (`certify.CertifyBuffers`) gives (scene group, member); `pad` >= 0 widens every bound.  Nothing is
+        perturbed.  Needs the mirror (`sync_mirror`), as `act_seats`."""
+        pb, cb = plan_buffers, cert_buffers
+        if pb.K != self.K or (cb.G, cb.K) != (pb.G, pb.K):
+            raise ValueError("PolicyBank.certify_seats: a bank of %d, a plan of %d groups x %d members, levels for %d x %d" % (
+                self.K, pb.G, pb.K, cb.G, cb.K))
+        for name, t, shape in (("obs", obs, (pb.n_out, int(self.cfg.pol.in_dim))), ("bounds", bounds, (pb.n_out, 8))):
+            if tuple(t.shape) != shape or not t.is_contiguous() or t.dtype != torch.float32:
+                raise ValueError("PolicyBank.certify_seats: %s of shape %s, contiguous float32 %s wanted" % (name, tuple(t.shape), list(shape)))
+        self._capi.check(self._capi.lib.copo_cert_obs_seats_f32(
+            C.byref(self.cfg), self.theta.data_ptr(), self.theta_t.data_ptr(), self.stride, self.K, pb.rows.data_ptr(), pb.counts.data_ptr(),
+            pb.cap, pb.n_out, obs.data_ptr(), bounds.data_ptr(), int(col_lo), int(col_hi), pb.N, pb.group.data_ptr(), pb.G,
+            cb.level_of.data_ptr(), cb.levels.data_ptr(), cb.L, float(pad), self._capi.current_stream()))
+
+
 class _BankPolicy:
     """What `VecSampler` reads of a policy, with the bank as its fused learner."""
 

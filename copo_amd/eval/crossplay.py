@@ -172,6 +172,11 @@ class SeatedBank:
         self.bank.pgd_seats(self.buffers, pgd_buffers, obs, obs_seen, col_lo, col_hi, seed, tick, trace, max_iters)
 
 
+    def certify_seats(self, cert_buffers, obs, bounds, col_lo, col_hi, pad=0.0):
+        """`PolicyBank.certify_seats` over the plan's own buffers (eval/certify.py)."""
+        self.bank.certify_seats(self.buffers, cert_buffers, obs, bounds, col_lo, col_hi, pad)
+
+
 class SeatSampler(VecSampler):
     """`VecSampler` with a `SeatedBank` in the policy's place, as `BankSampler` puts a bank there, and the seat tally behind every
     simulator step: `tally` int64 [groups][K][8] accumulates until `clear_tally()`.  Forward, step and tally of the fragment's T env

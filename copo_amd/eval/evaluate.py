@@ -319,8 +319,24 @@ def main(argv=None):
     ap.add_argument("--pgd-levels", default=None, metavar="JSON",
                     help="with --pgd-sweep: a JSON list of {eps, steer, throttle, alpha, iters, random_start, untargeted}; the first must "
                          "be an identity, e.g. {}")
+    ap.add_argument("--certify-sweep", nargs="+", default=None, metavar="CKPT",
+                    help="checkpoints of --algo's layout, each certified at every level of --certify-levels (eval/certify.py: interval "
+                         "bounds of the action means over the LiDAR budget; nobody's driving changes): one row per (checkpoint, level) "
+                         "into --table; takes --scenes-per-pair and --steps")
+    ap.add_argument("--certify-levels", default=None, metavar="JSON", help="with --certify-sweep: a JSON list of {eps, delta_steer, delta_throttle}")
     a = ap.parse_args(argv)
     from .checkpoint_io import load_members
+    if a.certify_sweep:
+        if a.cross_play or a.fault_sweep or a.adversary_sweep or a.pgd_sweep:
+            ap.error("--certify-sweep excludes --cross-play, --fault-sweep, --adversary-sweep and --pgd-sweep: one table per run")
+        if not a.table or not a.certify_levels:
+            ap.error("--certify-sweep needs --certify-levels and --table")
+        from .certify import certify_sweep_rows, load_levels
+        df = certify_sweep_rows("ippo" if a.algo == "cl" else a.algo, a.env, load_members(a.certify_sweep), load_levels(a.certify_levels),
+                                scenes_per_cell=a.scenes_per_pair, num_agents=a.num_agents, steps=a.steps, labels=list(a.certify_sweep))
+        df.to_csv(a.table)
+        print(df.drop(columns=["label"]).to_string())
+        return
     if a.pgd_sweep:
         if a.cross_play or a.fault_sweep or a.adversary_sweep:
             ap.error("--pgd-sweep excludes --cross-play, --fault-sweep and --adversary-sweep: one table per run")

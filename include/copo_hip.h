@@ -446,6 +446,22 @@ int copo_rewind_destroy(copo_rewind* h);
 int copo_seat_tally(const uint8_t* flags, const float* rew, const int32_t* seat, const int32_t* group, int32_t E, int32_t N, int32_t K,
                     int32_t G, int64_t* out, void* stream);
 
+/* ---- certify tally: one step's certified bounds (copo_cert_obs_seats_f32) folded per (scene group, bank
+ * member) against the level's deltas.  Stateless.  flags device [E][N] uint8 (the step's output), bounds device [E][N][COPO_CERT_WORDS]
+ * fp32, seat / group as copo_seat_tally, level_of device [G][K] int32, levels device [L][4] fp32 (eps, delta_steer, delta_throttle, 0),
+ * out device [G][K][COPO_CERT_TALLY_WORDS] int64.  A slot counts where 0 <= seat < K, 0 <= group[e] < G, 0 <= level_of[group][seat] < L,
+ * its flags carry COPO_F_ACTED and bounds[..][6] == 1.  With dev_a = max(hi_a - mu_a, mu_a - lo_a), width_a = hi_a - lo_a (fp32, each
+ * difference rounded once) and q(x) = rint(min(max(x, 0), 1024) * 65536) as int64 (one rounding, half to even), the words are:
+ * [0] rows counted; [1] rows with dev_0 <= delta_steer and dev_1 <= delta_throttle; [2] / [3] either condition alone; [4] / [5] the
+ * sums of q(width_0) / q(width_1); [6] the largest q(max(dev_0, dev_1)) (a 64-bit atomic max); [7] rows one of whose six numbers is
+ * NaN or infinite (they stay out of the words 1 .. 6).  `out` ACCUMULATES (the caller clears it); integers only, so the result does not
+ * depend on the order.  One launch on the caller's stream, no allocation, no host synchronisation; may be captured in a graph.
+ * NULL flags / bounds / seat / group / level_of / levels / out: COPO_ERR_NULL; E >= 0, N in 1..COPO_SEAT_MAX_SLOTS, K in 1..65535,
+ * G >= 1, L >= 1 (COPO_ERR_DIM); a refused call launches nothing. */
+#define COPO_CERT_TALLY_WORDS 8
+int copo_certify_tally(const uint8_t* flags, const float* bounds, const int32_t* seat, const int32_t* group, const int32_t* level_of,
+                       const float* levels, int32_t E, int32_t N, int32_t K, int32_t G, int32_t L, int64_t* out, void* stream);
+
 /* ---- fault injection: noisy sensors between the simulator's observation and the policy, noisy and sticky
  *      actuators between the policy's action and the simulator.  Two stateless entry points; each is one launch on the caller's stream,
  *      allocates nothing and reads nothing on the host, so both may be captured in a graph.  The simulator knows nothing of them.
@@ -996,6 +1012,28 @@ int copo_pgd_obs_seats_f32(const copo_ppo_cfg* cfg, const float* theta, const fl
                            const float* obs_src, float* obs_seen, int32_t col_lo, int32_t col_hi, int32_t n_slots,
                            const int32_t* group, int32_t n_groups, const int32_t* level_of, const uint32_t* levels,
                            int32_t n_levels, uint64_t seed, int32_t* tick, int32_t max_iters, float* trace, void* stream);
+/* Certified bounds of a seated bank (eval/certify.py): interval bound propagation through the policy net, the
+ * other side of the two attacks above -- for every listed row a box that holds the two action MEANS (before sampling and clipping)
+ * under every perturbation of the columns [col_lo, col_hi) inside an L-infinity budget.  The seat-mode arguments, obs_src, the columns,
+ * n_slots, group and level_of are those of copo_adv_obs_seats_f32.  A level is four f32 words: eps >= 0, delta_steer >= 0,
+ * delta_throttle >= 0, 0 (the deltas are read by copo_certify_tally only).  With o the TRUE row:
+ *     lo[j] = max(o[j] - eps, 0), hi[j] = min(o[j] + eps, 1) on the columns, lo = hi = o[j] elsewhere; c0 = (lo + hi) / 2, r0 = (hi - lo) / 2
+ *     layers i = 1, 2: zc = W_i c + b_i, zr = |W_i| r; l = tanh(zc - zr), u = max(tanh(zc + zr), l); c = (l + u) / 2, r = (u - l) / 2
+ *     heads a = 0, 1:  mc = W3[a] . c + b3[a], mr = |W3[a]| . r; lo_a = (mc - mr) - pad, hi_a = (mc + mr) + pad, each sum rounded once
+ *     bounds[row] = lo_0, hi_0, lo_1, hi_1, mu_0(o), mu_1(o), valid = 1.0, eps   (mu(o): the clean pass of the same launch)
+ * fp32 sums are not rounded outward: the bounds are sound up to fp32 rounding, and pad >= 0 widens every bound by exactly pad.  A listed
+ * row whose level index or group is out of range gets eight zeros (valid = 0); rows in no list are not written.  At eps == 0 and
+ * pad == 0, lo_a == hi_a == mu_a(o) bit for bit.  One launch, grid ceil(cap / 16) x n_members, the 16-row tile three times (clean,
+ * centre, radius) against one weight stream from the mirror theta_t; no atomics, fixed summation order: two launches give the same bits.
+ * Refusals as copo_adv_obs_seats_f32 (NULL theta / theta_t / rows / counts / obs_src / bounds / group / level_of / levels:
+ * COPO_ERR_NULL; bad dimensions, bfloat16 operands, a hidden width outside {64, 128, 256, 512}: COPO_ERR_DIM), and a negative or
+ * non-finite pad: COPO_ERR_DIM.  A refused call launches nothing. */
+#define COPO_CERT_WORDS 8
+int copo_cert_obs_seats_f32(const copo_ppo_cfg* cfg, const float* theta, const float* theta_t, int64_t member_stride,
+                            int32_t n_members, const int64_t* rows, const int32_t* counts, int64_t cap, int64_t n_out,
+                            const float* obs_src, float* bounds, int32_t col_lo, int32_t col_hi, int32_t n_slots,
+                            const int32_t* group, int32_t n_groups, const int32_t* level_of, const float* levels,
+                            int32_t n_levels, float pad, void* stream);
 /* The same pass over a LIST of rows: launch row m reads row rows[m] of the sources ([n_src_rows][..]) and writes
  * values[net][rows[m]] (values is [n_nets][n_src_rows]; entries of unlisted rows are left alone).  The dense postprocess
  * of a rollout buffer uses it with the rows that hold an agent -- about half of the slots. */

@@ -1,5 +1,5 @@
 """What the observer benchmarks (`bench_interact`, `bench_clips`, `bench_rewind`, `bench_fields`, `bench_gates`, `bench_trips`, `bench_conflicts`, `bench_pet`) share:
-the timing loop, the command line, the scene they measure on and the JSON line they end with; `bench_faults`, `bench_adversary` and `bench_pgd` also
+the timing loop, the command line, the scene they measure on and the JSON line they end with; `bench_faults`, `bench_adversary`, `bench_pgd` and `bench_certify` also
 take the graph-replay timer from here."""
 import argparse
 import json
