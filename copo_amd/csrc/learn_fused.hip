@@ -16,6 +16,7 @@
 //      learn_inputgrad.inc: adv_obs_kernel, the forward plus the backward pass down to the INPUT row of a seated bank (evaluation);
 //      learn_pgd.inc: pgd_obs_kernel, that pass iterated in one resident workgroup (projected gradient descent on the input row);
 //      learn_certify.inc: cert_obs_kernel, interval bounds of the action means over an L-infinity box of the input row
+//      learn_linbound.inc: lin_obs_kernel, linear bounds of the same means (one relaxation per tanh unit, carried backward), intersected with them
 //   5. LCF meta kernels: meta_lcf / meta_finish (step by step), meta_batch_fold / dot / rowstat, meta_seq (all LCF
 //      Adam steps of a pass in one workgroup)
 //   6. reduce_adam_kernel (fold of row-split partials + Adam; legacy two-net meta step), wgrad_adam_kernel (weight
@@ -44,6 +45,7 @@ namespace copo {
 #include "learn_inputgrad.inc"
 #include "learn_pgd.inc"
 #include "learn_certify.inc"
+#include "learn_linbound.inc"
 #include "learn_meta.inc"
 #include "learn_update.inc"
 #include "learn_plan.inc"
@@ -374,6 +376,27 @@ extern "C" int copo_cert_obs_seats_f32(const copo_ppo_cfg* cfg, const float* the
     if (gemm_lds_attrs() != hipSuccess) return COPO_ERR_DEVICE;
     CertArgs a{*cfg, theta, theta_t, member_stride, rows, counts, cap, n_out, obs_src, bounds, col_lo, col_hi, n_slots,
                group, n_groups, level_of, levels, n_levels, n_members, pad};
+    void* args[] = {&a};
+    return launch_kernel(l, args, static_cast<hipStream_t>(stream)) == hipSuccess ? COPO_OK : COPO_ERR_DEVICE;
+}
+
+extern "C" int copo_lin_obs_seats_f32(const copo_ppo_cfg* cfg, const float* theta, const float* theta_t, int64_t member_stride,
+                                      int32_t n_members, const int64_t* rows, const int32_t* counts, int64_t cap, int64_t n_out,
+                                      const float* obs_src, float* bounds, float* parts, int32_t col_lo, int32_t col_hi, int32_t n_slots,
+                                      const int32_t* group, int32_t n_groups, const int32_t* level_of, const float* levels,
+                                      int32_t n_levels, float pad, void* stream) {
+    int rc = check_cfg(cfg);
+    if (rc != COPO_OK) return rc;
+    if (!theta || !theta_t || !rows || !counts || !obs_src || !bounds || !group || !level_of || !levels) return COPO_ERR_NULL;
+    if (n_out < 1 || n_slots < 1 || n_out % n_slots != 0 || n_groups < 1 || n_levels < 1 || member_stride < cfg->n_params || member_stride % 4 != 0 ||
+        col_lo < 0 || col_lo > col_hi || col_hi > cfg->pol.in_dim || !(pad >= 0.0f) || !__builtin_isfinite(pad))
+        return COPO_ERR_DIM;
+    Launch l;
+    rc = plan_linbound(*cfg, cap, n_members, aligned16(theta_t) ? FACT_MIRROR_ALIGNED : 0, &l);
+    if (rc != COPO_OK) return rc;
+    if (gemm_lds_attrs() != hipSuccess) return COPO_ERR_DEVICE;
+    LinArgs a{*cfg, theta, theta_t, member_stride, rows, counts, cap, n_out, obs_src, bounds, parts, col_lo, col_hi, n_slots,
+              group, n_groups, level_of, levels, n_levels, n_members, pad};
     void* args[] = {&a};
     return launch_kernel(l, args, static_cast<hipStream_t>(stream)) == hipSuccess ? COPO_OK : COPO_ERR_DEVICE;
 }

@@ -5,6 +5,7 @@
 constexpr int LDS_DEFAULT = 64 * 1024;      // what a kernel may use without an attribute
 constexpr int LDS_ROWPASS = 150 * 1024;     // row-pass / forward workgroups (gfx950 has 160 KB per CU)
 constexpr int LDS_GEMM = (int)GEMM_LDS_BYTES;
+constexpr int LDS_LINBOUND = 136 * 1024;    // lin_obs_kernel keeps 11.5 KB of static partial sums next to its tiles: together under the CU's 160 KB
 // a family of the four row-pass shapes, hidden = 16 NT WAVES = 64, 128, 256, 512: adjacent ids in this order (shape_index)
 #define COPO_SHAPES(X, id, K, ...)                                                                                          \
     X(id##_1_4, 256, LDS_ROWPASS, K<1, 4, __VA_ARGS__>) X(id##_2_4, 256, LDS_ROWPASS, K<2, 4, __VA_ARGS__>)                   \
@@ -32,7 +33,7 @@ constexpr int LDS_GEMM = (int)GEMM_LDS_BYTES;
     X(WGRAD_OT2, 64 * WG_WAVES, 80 * 1024, wgrad_adam_kernel<2>)                                                             \
     X(HEAD, 256, LDS_DEFAULT, head_kernel) X(META_FOLD, 256, LDS_DEFAULT, meta_batch_fold_kernel)                            \
     X(REDUCE_ADAM, 256, LDS_DEFAULT, reduce_adam_kernel)
-// rows behind the learner's: kernels of the evaluation side that live in this translation unit (learn_inputgrad.inc, learn_pgd.inc, learn_certify.inc).  They are launched
+// rows behind the learner's: kernels of the evaluation side that live in this translation unit (learn_inputgrad.inc, learn_pgd.inc, learn_certify.inc, learn_linbound.inc).  They are launched
 // through the same launch_kernel and get their LDS ceilings from the same loop; copo_debug_learner_kernel lists the learner's rows only
 // (ids below K_LEARNER_COUNT).  Per kernel the four shapes in shape_index order.
 #define COPO_EVAL_KERNELS(X)                                                                                                \
@@ -41,7 +42,9 @@ constexpr int LDS_GEMM = (int)GEMM_LDS_BYTES;
     X(PGD_1_4, 256, LDS_ROWPASS, pgd_obs_kernel<1, 4>) X(PGD_2_4, 256, LDS_ROWPASS, pgd_obs_kernel<2, 4>)                    \
     X(PGD_2_8, 512, LDS_ROWPASS, pgd_obs_kernel<2, 8>) X(PGD_4_8, 512, LDS_ROWPASS, pgd_obs_kernel<4, 8>)                    \
     X(CERT_1_4, 256, LDS_ROWPASS, cert_obs_kernel<1, 4>) X(CERT_2_4, 256, LDS_ROWPASS, cert_obs_kernel<2, 4>)                \
-    X(CERT_2_8, 512, LDS_ROWPASS, cert_obs_kernel<2, 8>) X(CERT_4_8, 512, LDS_ROWPASS, cert_obs_kernel<4, 8>)
+    X(CERT_2_8, 512, LDS_ROWPASS, cert_obs_kernel<2, 8>) X(CERT_4_8, 512, LDS_ROWPASS, cert_obs_kernel<4, 8>)              \
+    X(LIN_1_4, 256, LDS_LINBOUND, lin_obs_kernel<1, 4>) X(LIN_2_4, 256, LDS_LINBOUND, lin_obs_kernel<2, 4>)                  \
+    X(LIN_2_8, 512, LDS_LINBOUND, lin_obs_kernel<2, 8>) X(LIN_4_8, 512, LDS_LINBOUND, lin_obs_kernel<4, 8>)
 struct KernelEntry { const char* name; const void* fn; int block, lds_cap; };
 #define COPO_KERNEL_ID(id, block, cap, ...) K_##id,
 #define COPO_KERNEL_ENTRY(id, block, cap, ...) {#__VA_ARGS__, reinterpret_cast<const void*>(__VA_ARGS__), block, cap},
@@ -269,6 +272,20 @@ static int plan_certify(const copo_ppo_cfg& c, int64_t cap, int n_members, int f
     const size_t lds = cert_lds_floats(c.hidden, rowpass_k1p(c.pol.in_dim)) * sizeof(float);
     if (lds > (size_t)LDS_ROWPASS) return COPO_ERR_DIM;
     out->id = K_CERT_1_4 + shape_index(c.hidden);
+    out->block = g_kernels[out->id].block;
+    out->lds = (int32_t)lds;
+    return COPO_OK;
+}
+
+// Linear bounds of a seated bank (copo_lin_obs_seats_f32, learn_linbound.inc): plan_certify's launch shape, refusals and dynamic LDS (the
+// backward pass lives in the dead h1 tiles; layer 1's intervals are recomputed, not kept), so hidden 512 runs at the observation widths of
+// the project (k1p = 128); the ceiling is LDS_LINBOUND, which leaves room for the kernel's static partial sums.
+static int plan_linbound(const copo_ppo_cfg& c, int64_t cap, int n_members, int facts, Launch* out) {
+    const int rc = plan_adversary(c, cap, n_members, facts, out);
+    if (rc != COPO_OK) return rc;
+    const size_t lds = lin_lds_floats(c.hidden, rowpass_k1p(c.pol.in_dim)) * sizeof(float);
+    if (lds > (size_t)LDS_LINBOUND) return COPO_ERR_DIM;      // (hidden 512 with an input wider than 128 columns)
+    out->id = K_LIN_1_4 + shape_index(c.hidden);
     out->block = g_kernels[out->id].block;
     out->lds = (int32_t)lds;
     return COPO_OK;

@@ -21,6 +21,14 @@ import torch
 
 from ..trainer import VecSampler
 
+CERTIFY_METHODS = ("interval", "linear")      # `certify_seats`: copo_cert_obs_seats_f32, copo_lin_obs_seats_f32
+
+
+def check_certify_method(who, method):
+    if method not in CERTIFY_METHODS:
+        raise ValueError("%s: method = %r, one of %s wanted" % (who, method, ", ".join(repr(m) for m in CERTIFY_METHODS)))
+    return method
+
 
 class PolicyBank:
     """K flat parameter sets of `layout_from`'s model.  `layout_from`: a trainer policy with a fused learner (`policy.fused`), whose
@@ -141,22 +149,31 @@ class PolicyBank:
             None if trace is None else trace.data_ptr(), self._capi.current_stream()))
 
 
-    def certify_seats(self, plan_buffers, cert_buffers, obs, bounds, col_lo, col_hi, pad=0.0):
+    def certify_seats(self, plan_buffers, cert_buffers, obs, bounds, col_lo, col_hi, pad=0.0, method="interval", parts=None):
         """`copo_cert_obs_seats_f32` (eval/certify.py) on the current stream: obs [n_out, O] -> bounds [n_out, 8], the interval bounds
         of the two action means of every seated row over the L-infinity box of its level's `eps` on the columns [col_lo, col_hi), at
         the level `cert_buffers` (`certify.CertifyBuffers`) gives (scene group, member); `pad` >= 0 widens every bound.  Nothing is
-        perturbed.  Needs the mirror (`sync_mirror`), as `act_seats`."""
+        perturbed.  Needs the mirror (`sync_mirror`), as `act_seats`.  `method="linear"`: `copo_lin_obs_seats_f32` instead, the linear
+        bounds intersected with the interval box into the same `bounds` layout; `parts` [n_out, 8] (linear only): both boxes before
+        the pad, if wanted."""
         pb, cb = plan_buffers, cert_buffers
+        check_certify_method("PolicyBank.certify_seats", method)
+        if parts is not None and method != "linear":
+            raise ValueError("PolicyBank.certify_seats: `parts` is an output of method=\"linear\" only")
         if pb.K != self.K or (cb.G, cb.K) != (pb.G, pb.K):
             raise ValueError("PolicyBank.certify_seats: a bank of %d, a plan of %d groups x %d members, levels for %d x %d" % (
                 self.K, pb.G, pb.K, cb.G, cb.K))
-        for name, t, shape in (("obs", obs, (pb.n_out, int(self.cfg.pol.in_dim))), ("bounds", bounds, (pb.n_out, 8))):
-            if tuple(t.shape) != shape or not t.is_contiguous() or t.dtype != torch.float32:
+        for name, t, shape in (("obs", obs, (pb.n_out, int(self.cfg.pol.in_dim))), ("bounds", bounds, (pb.n_out, 8)), ("parts", parts, (pb.n_out, 8))):
+            if t is not None and (tuple(t.shape) != shape or not t.is_contiguous() or t.dtype != torch.float32):
                 raise ValueError("PolicyBank.certify_seats: %s of shape %s, contiguous float32 %s wanted" % (name, tuple(t.shape), list(shape)))
-        self._capi.check(self._capi.lib.copo_cert_obs_seats_f32(
-            C.byref(self.cfg), self.theta.data_ptr(), self.theta_t.data_ptr(), self.stride, self.K, pb.rows.data_ptr(), pb.counts.data_ptr(),
-            pb.cap, pb.n_out, obs.data_ptr(), bounds.data_ptr(), int(col_lo), int(col_hi), pb.N, pb.group.data_ptr(), pb.G,
-            cb.level_of.data_ptr(), cb.levels.data_ptr(), cb.L, float(pad), self._capi.current_stream()))
+        head = (C.byref(self.cfg), self.theta.data_ptr(), self.theta_t.data_ptr(), self.stride, self.K, pb.rows.data_ptr(), pb.counts.data_ptr(),
+                pb.cap, pb.n_out, obs.data_ptr(), bounds.data_ptr())
+        tail = (int(col_lo), int(col_hi), pb.N, pb.group.data_ptr(), pb.G, cb.level_of.data_ptr(), cb.levels.data_ptr(), cb.L, float(pad),
+                self._capi.current_stream())
+        if method == "linear":
+            self._capi.check(self._capi.lib.copo_lin_obs_seats_f32(*head, None if parts is None else parts.data_ptr(), *tail))
+        else:
+            self._capi.check(self._capi.lib.copo_cert_obs_seats_f32(*head, *tail))
 
 
 class _BankPolicy:

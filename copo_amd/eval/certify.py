@@ -1,4 +1,5 @@
-"""Certified LiDAR bounds: interval bound propagation (IBP) through the policy net, the guarantee that the attacks cannot give.
+"""Certified LiDAR bounds: interval bound propagation (IBP) through the policy net and, tighter, one linear relaxation per tanh unit
+carried backward from each action mean (`method="linear"`): the guarantee that the attacks cannot give.
 
 `faults.py`, `adversary.py` and `pgd.py` each SHOW a perturbation of the LiDAR block that moves the action: lower bounds on the worst
 case inside an L-infinity budget `eps`.  A table that reads "PGD moved the mean throttle by 0.08 at eps = 0.02" does not say whether
@@ -26,8 +27,20 @@ The bracket: join `certify_sweep_rows` with `pgd.pgd_sweep_rows` on (checkpoint,
 -- then the attack's outcome (from below) and `max_dev` / `certified_rate` (from above) stand in one row: the true worst case lies
 between them.
 
-An L-infinity budget, the LiDAR block, fp32 operands, plain intervals.  Tighter relaxations (CROWN, zonotopes), the ego / navigation
-columns, other norms, the bfloat16 operand mode and bounds on the sampled or clipped action are out of scope.
+METHODS.  `method="interval"` (the default, every path and every bit as before) is the pass above.  Its box widens by about 0.8 sqrt(H)
+per hidden layer and turns trivial (2 |W3[a]|_1) near eps = 0.01, below the budgets at which the attacks move anything.
+`method="linear"` (`copo_lin_obs_seats_f32`, csrc/learn_linbound.inc) bounds every tanh unit on its interval [l, u]
+by two parallel lines of slope lam = min(tanh'(l), tanh'(u)) -- lam z + betaL <= tanh z <= lam z + betaU -- and carries W3[a] backward
+through those lines and the weights to the input box: mu_a(x) lies in [base - rad, base + rad] plus the beta terms.  One slope for
+both sides makes the upper and the lower bound share their backward coefficients, so a head costs one backward pass.  The result is
+intersected with the interval box of the same launch (never looser than it), lands in the same `bounds` layout, and is folded by the
+same `copo_certify_tally`.  On the test nets the box is 8 to 40 times narrower at eps = 0.0005 .. 0.002 and still informative at
+eps = 0.01 for hidden 256; at eps = 0.05 both boxes are trivial.  The launch costs about 2.4 interval launches (DESIGN.md section 8p
+has the measurement and what it is made of).
+
+An L-infinity budget, the LiDAR block, fp32 operands.  Backward bounds for layer 2's pre-activations (full CROWN), per-unit optimised
+slopes, chord / tangent relaxations, zonotopes, branch and bound, the ego / navigation columns, other norms, the bfloat16 operand mode
+and bounds on the sampled or clipped action are out of scope.
 
 Pieces: `CertifyLevel` / `CertifyPlan` (numpy only), `CertifyBuffers`, `certify_tally`, `CertifySeatSampler` (the `SeatSampler` whose
 `_policy_obs` launches the kernel inside the captured fragment), `certify_sweep_rows` (checkpoints x levels as a pandas frame; `evaluate
@@ -37,12 +50,13 @@ from dataclasses import dataclass
 
 import numpy as np
 
-from .bank import DeviceTables, draw_cell_noise
+from .bank import CERTIFY_METHODS, DeviceTables, check_certify_method, draw_cell_noise
 from .crossplay import SEAT_WORDS, SeatSampler, tally_rates
 from .faults import lidar_columns, sweep_plan
 
 LEVEL_WORDS = 4
 LEVEL_FIELDS = ("eps", "delta_steer", "delta_throttle")
+PART_WORDS = ("lo_lin_steer", "hi_lin_steer", "lo_lin_throttle", "hi_lin_throttle", "lo_int_steer", "hi_int_steer", "lo_int_throttle", "hi_int_throttle")
 BOUND_WORDS = ("lo_steer", "hi_steer", "lo_throttle", "hi_throttle", "mu_steer", "mu_throttle", "valid", "eps")
 CERT_WORDS = ("rows", "certified", "certified_steer", "certified_throttle", "width_steer_q16", "width_throttle_q16", "max_dev_q16", "nonfinite")
 Q16 = 65536.0
@@ -134,10 +148,12 @@ class CertifySeatSampler(SeatSampler):
     SAME true observation, the simulator step, the seat tally and the certify tally -- the whole fragment is still one captured graph.
     Actions, flags and the seat tally are a plain `SeatSampler`'s.  `bounds` [T][E][N][8] (also `batch["bounds"]`, zero-initialised: rows
     of seats that nobody drives are never written and read as invalid); `cert_tally` int64 [G][K][8] (`CERT_WORDS`) accumulates until
-    `clear_tally()`.  Cells of a `sweep` plan share their action noise, as in `AdversarialSeatSampler`."""
+    `clear_tally()`.  Cells of a `sweep` plan share their action noise, as in `AdversarialSeatSampler`.  `method`: "interval" or "linear"
+    (the module docstring); the launch is the only difference, the fold and everything else are the same."""
 
-    def __init__(self, vec_env, policy, bank, plan, certify, T, use_graph=True, pad=0.0):
+    def __init__(self, vec_env, policy, bank, plan, certify, T, use_graph=True, pad=0.0, method="interval"):
         import torch
+        self.method = check_certify_method("CertifySeatSampler", method)
         certify.check(plan)
         super().__init__(vec_env, policy, bank, plan, T, use_graph=use_graph)
         self.pad = float(pad)
@@ -174,7 +190,7 @@ class CertifySeatSampler(SeatSampler):
 
     def _policy_obs(self, t):
         self.seated.certify_seats(self.cert_buffers, self.obs[t].view(-1, self.O), self.bounds[t].view(-1, len(BOUND_WORDS)), self.col_lo,
-                                  self.col_hi, self.pad)
+                                  self.col_hi, self.pad, self.method)
         return self.obs[t]
 
     def _step(self, t):
@@ -194,29 +210,32 @@ def cert_rates(words):
                 mean_width_throttle=ratio(w["width_throttle_q16"] / Q16), max_dev=w["max_dev_q16"] / Q16 if good > 0 else float("nan"))
 
 
-def certify_frame(cert_tally, tally, seats, certify, labels=None):
+def certify_frame(cert_tally, tally, seats, certify, labels=None, method=None):
     """Both tallies [G][K][8] (numpy int64) of a `sweep` plan as a frame: one row per (checkpoint, level), the columns of
-    `certify_sweep_rows`."""
+    `certify_sweep_rows`; `method` (not None): a `method` column behind `level`."""
     import pandas as pd
     labels = list(range(certify.n_checkpoints)) if labels is None else list(labels)
     rows = []
     for g in range(seats.n_groups):
         k, lv = int(certify.checkpoint[g]), int(certify.level[g])
         cw, sw = [int(v) for v in cert_tally[g, k]], [int(v) for v in tally[g, k]]
-        rows.append(dict(checkpoint=k, label=labels[k], level=lv, member=k, seats=seats.N, **certify.levels[lv].as_dict(), **dict(zip(CERT_WORDS, cw)),
+        rows.append(dict(checkpoint=k, label=labels[k], level=lv, **({} if method is None else dict(method=method)), member=k, seats=seats.N, **certify.levels[lv].as_dict(), **dict(zip(CERT_WORDS, cw)),
                          **cert_rates(cw), **dict(zip(SEAT_WORDS, sw)), **tally_rates(sw)))
     return pd.DataFrame(rows)
 
 
-def certify_sweep_rows(algo, env, weights_list, levels, scenes_per_cell=4, num_agents=40, steps=1000, seed=0, labels=None, pad=0.0, **extra):
+def certify_sweep_rows(algo, env, weights_list, levels, scenes_per_cell=4, num_agents=40, steps=1000, seed=0, labels=None, pad=0.0,
+                       method="interval", **extra):
     """K populations `weights_list` (one layout) x the certification `levels`, `scenes_per_cell` scenes per cell, the same scenes and the
     same action noise for every cell, for `steps` env steps (rounded up to whole fragments).  Every slot of a cell is driven by the
     cell's checkpoint on the true observation and certified at the cell's level (`CertifyPlan.sweep`).  Returns a pandas frame, one
     row per (checkpoint, level): `checkpoint`, `label`, `level`, `member`, `seats`, the level's `eps`, `delta_steer`, `delta_throttle`,
     the eight raw words of the certify tally (`CERT_WORDS`), `certified_rate`, `certified_rate_steer`, `certified_rate_throttle`,
     `mean_width_steer`, `mean_width_throttle`, `max_dev`, then the eight raw words of the seat tally and its rates as in
-    `cross_play_rows`.  Joined with `pgd_sweep_rows` on (checkpoint, eps) it brackets the worst case (see the module docstring)."""
+    `cross_play_rows`.  Joined with `pgd_sweep_rows` on (checkpoint, eps) it brackets the worst case (see the module docstring).
+    `method="linear"`: the tighter bounds, and a `method` column behind `level` (an interval frame keeps today's columns)."""
     from .bank import PolicyBank
+    check_certify_method("certify_sweep_rows", method)
     from .evaluate import check_labels, eval_session, graph_flag, run_steps
     weights_list = list(weights_list)
     K = len(weights_list)
@@ -228,10 +247,11 @@ def certify_sweep_rows(algo, env, weights_list, levels, scenes_per_cell=4, num_a
     labels = check_labels(labels, K)
     seats, certify = CertifyPlan.sweep(K, levels, scenes_per_cell, num_agents)
     with eval_session(algo, env, seats.E, num_agents, seed, **extra) as t:
-        smp = CertifySeatSampler(t.env, t.policy, PolicyBank(t.policy, weights_list), seats, certify, t.sampler.T, use_graph=graph_flag(t), pad=pad)
+        smp = CertifySeatSampler(t.env, t.policy, PolicyBank(t.policy, weights_list), seats, certify, t.sampler.T, use_graph=graph_flag(t), pad=pad,
+                                 method=method)
         run_steps(smp, steps)
         cert, tally = smp.cert_tally.cpu().numpy(), smp.tally.cpu().numpy()
-    return certify_frame(cert, tally, seats, certify, labels)
+    return certify_frame(cert, tally, seats, certify, labels, None if method == "interval" else method)
 
 
 def load_levels(path):
@@ -244,16 +264,25 @@ def load_levels(path):
     return [CertifyLevel(**r) for r in raw]
 
 
-def certified_bounds(bank, plan_buffers, obs, eps, pad=0.0, *, columns):
+def certified_bounds(bank, plan_buffers, obs, eps, pad=0.0, *, columns, method="interval", parts=False):
     """`bounds` [n_out][8] (`BOUND_WORDS`) of every seated row of obs [n_out][O] at one budget `eps` for every (group, member): one
     launch, like `adversary.beam_saliency`.  `columns` = (col_lo, col_hi), the LiDAR block (`faults.lidar_columns(sim.cfg)`): unlike the
-    saliency, the box needs to know where the beams are.  Rows in no list hold zeros (`valid` = 0)."""
+    saliency, the box needs to know where the beams are.  Rows in no list hold zeros (`valid` = 0).  `method="linear"`: the tighter
+    bounds; with `parts=True` (linear only) returns (bounds, parts), parts [n_out][8] (`PART_WORDS`): the linear and the interval box
+    before the intersection and the pad."""
     import torch
+    check_certify_method("certified_bounds", method)
+    if parts and method != "linear":
+        raise ValueError("certified_bounds: parts=True needs method=\"linear\"")
     pb = plan_buffers
     plan = CertifyPlan([CertifyLevel(eps)], np.zeros((pb.G, pb.K), np.int32))
     col_lo, col_hi = (int(v) for v in columns)
     bounds = torch.zeros(int(obs.shape[0]), len(BOUND_WORDS), dtype=torch.float32, device=obs.device)
+    second = torch.zeros_like(bounds) if parts else None
     bank.sync_mirror()
-    bank.certify_seats(pb, CertifyBuffers(plan, obs.device), obs, bounds, col_lo, col_hi, pad)
+    if method == "interval":
+        bank.certify_seats(pb, CertifyBuffers(plan, obs.device), obs, bounds, col_lo, col_hi, pad)
+    else:
+        bank.certify_seats(pb, CertifyBuffers(plan, obs.device), obs, bounds, col_lo, col_hi, pad, method, second)
     torch.cuda.current_stream().synchronize()          # (the plan's tables die with this call)
-    return bounds
+    return (bounds, second) if parts else bounds

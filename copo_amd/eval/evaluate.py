@@ -324,8 +324,13 @@ def main(argv=None):
                          "bounds of the action means over the LiDAR budget; nobody's driving changes): one row per (checkpoint, level) "
                          "into --table; takes --scenes-per-pair and --steps")
     ap.add_argument("--certify-levels", default=None, metavar="JSON", help="with --certify-sweep: a JSON list of {eps, delta_steer, delta_throttle}")
+    ap.add_argument("--certify-method", default="interval", choices=("interval", "linear"),
+                    help="with --certify-sweep: interval propagation (default) or the tighter linear bounds intersected with it; "
+                         "\"linear\" adds a `method` column to the table")
     a = ap.parse_args(argv)
     from .checkpoint_io import load_members
+    if a.certify_method != "interval" and not a.certify_sweep:
+        ap.error("--certify-method goes with --certify-sweep")
     if a.certify_sweep:
         if a.cross_play or a.fault_sweep or a.adversary_sweep or a.pgd_sweep:
             ap.error("--certify-sweep excludes --cross-play, --fault-sweep, --adversary-sweep and --pgd-sweep: one table per run")
@@ -333,7 +338,8 @@ def main(argv=None):
             ap.error("--certify-sweep needs --certify-levels and --table")
         from .certify import certify_sweep_rows, load_levels
         df = certify_sweep_rows("ippo" if a.algo == "cl" else a.algo, a.env, load_members(a.certify_sweep), load_levels(a.certify_levels),
-                                scenes_per_cell=a.scenes_per_pair, num_agents=a.num_agents, steps=a.steps, labels=list(a.certify_sweep))
+                                scenes_per_cell=a.scenes_per_pair, num_agents=a.num_agents, steps=a.steps, labels=list(a.certify_sweep),
+                                method=a.certify_method)
         df.to_csv(a.table)
         print(df.drop(columns=["label"]).to_string())
         return

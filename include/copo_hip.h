@@ -1034,6 +1034,24 @@ int copo_cert_obs_seats_f32(const copo_ppo_cfg* cfg, const float* theta, const f
                             const float* obs_src, float* bounds, int32_t col_lo, int32_t col_hi, int32_t n_slots,
                             const int32_t* group, int32_t n_groups, const int32_t* level_of, const float* levels,
                             int32_t n_levels, float pad, void* stream);
+/* Linear bounds of a seated bank (eval/certify.py method="linear"): copo_cert_obs_seats_f32's box, tightened by
+ * one linear relaxation per tanh unit that is carried backward from each action mean to the input box.  Arguments, levels, the input
+ * box and the forward pass are copo_cert_obs_seats_f32's; with l = zc - zr, u = zc + zr, tl = tanh(l), tu = max(tanh(u), tl) of a unit:
+ *     lam = max(min(1 - tl^2, 1 - tu^2), 0), betaL = tl - lam l, betaU = tu - lam u   (lam z + betaL <= tanh z <= lam z + betaU on [l, u])
+ *     head a: v2 = W3[a], g2 = v2 lam2; v1 = W2^T g2, g1 = v1 lam1; v0 = W1^T g1; base = b3[a] + g2 . b2 + g1 . b1 + v0 . c0, rad = |v0| . r0
+ *     hiL = base + v2+ . betaU2 + v2- . betaL2 + v1+ . betaU1 + v1- . betaL1 + rad;  loL = the same with betaL / betaU exchanged, - rad
+ *     (loI, hiI) = copo_cert_obs_seats_f32's box before its pad;  lo = max(loL, loI), hi = min(hiL, hiI); lo > hi (rounding): (loI, hiI)
+ *     bounds[row] = lo_0 - pad, hi_0 + pad, lo_1 - pad, hi_1 + pad, mu_0(o), mu_1(o), valid = 1.0, eps   (the layout copo_certify_tally reads)
+ *     parts[row]  = loL_0, hiL_0, loL_1, hiL_1, loI_0, hiI_0, loI_1, hiI_1 before the pad; parts may be NULL
+ * Sound up to fp32 rounding, as the interval pass.  An invalid listed row gets eight zeros in both outputs; rows in no list are not
+ * written.  One launch of copo_cert_obs_seats_f32's shape and LDS at every hidden width (layer 1's intervals are recomputed behind
+ * the W2 pass, not kept); no atomics, fixed summation order: two launches give the same bits.  Refusals are
+ * copo_cert_obs_seats_f32's; a refused call launches nothing. */
+int copo_lin_obs_seats_f32(const copo_ppo_cfg* cfg, const float* theta, const float* theta_t, int64_t member_stride,
+                           int32_t n_members, const int64_t* rows, const int32_t* counts, int64_t cap, int64_t n_out,
+                           const float* obs_src, float* bounds, float* parts, int32_t col_lo, int32_t col_hi, int32_t n_slots,
+                           const int32_t* group, int32_t n_groups, const int32_t* level_of, const float* levels,
+                           int32_t n_levels, float pad, void* stream);
 /* The same pass over a LIST of rows: launch row m reads row rows[m] of the sources ([n_src_rows][..]) and writes
  * values[net][rows[m]] (values is [n_nets][n_src_rows]; entries of unlisted rows are left alone).  The dense postprocess
  * of a rollout buffer uses it with the rows that hold an agent -- about half of the slots. */
