@@ -13,6 +13,7 @@
 //   3. head_row_terms (PPO / value / meta loss terms + analytic gradient), head_kernel
 //   4. rowpass_kernel: layers 1-2, heads, dz2, dz1 of 16 rows in one workgroup (v_mfma_f32_16x16x4_f32, weights
 //      streamed through BRing register rings); mlp_fwd_kernel: its forward-only sibling (rollouts, critic heads);
+//      learn_seat.inc: the argument head and the tile prologue of the four seat passes below;
 //      learn_inputgrad.inc: adv_obs_kernel, the forward plus the backward pass down to the INPUT row of a seated bank (evaluation);
 //      learn_pgd.inc: pgd_obs_kernel, that pass iterated in one resident workgroup (projected gradient descent on the input row);
 //      learn_certify.inc: cert_obs_kernel, interval bounds of the action means over an L-infinity box of the input row
@@ -42,6 +43,7 @@ namespace copo {
 #include "learn_args.inc"
 #include "learn_gemm.inc"
 #include "learn_rowpass.inc"
+#include "learn_seat.inc"
 #include "learn_inputgrad.inc"
 #include "learn_pgd.inc"
 #include "learn_certify.inc"
@@ -317,25 +319,37 @@ extern "C" int copo_mlp_forward_seats_f32(const copo_ppo_cfg* cfg, const float* 
                        stream, n_members, member_stride, counts);
 }
 
+// The one launch path of the four seat passes.  `h`: the head of the pass's argument struct, filled by the entry point but for the
+// configuration, which is copied in here once it is known to be there; `out`: the pass's required output; `own_ok`: the entry point's own
+// dimension checks (pad, max_iters); first_id / lds_floats / lds_cap: plan_seat_pass; `args`: the struct `h` is the head of.
+static int seat_pass_launch(const copo_ppo_cfg* cfg, SeatHead& h, const void* out, bool own_ok, int first_id, size_t (*lds_floats)(int, int),
+                            int lds_cap, void* args, void* stream) {
+    int rc = check_cfg(cfg);
+    if (rc != COPO_OK) return rc;
+    if (!h.theta || !h.theta_t || !h.rows || !h.counts || !h.obs_src || !out || !h.group || !h.level_of || !h.levels) return COPO_ERR_NULL;
+    if (h.n_out < 1 || h.n_slots < 1 || h.n_out % h.n_slots != 0 || h.n_groups < 1 || h.n_levels < 1 || h.member_stride < cfg->n_params ||
+        h.member_stride % 4 != 0 || h.col_lo < 0 || h.col_lo > h.col_hi || h.col_hi > cfg->pol.in_dim || !own_ok)
+        return COPO_ERR_DIM;
+    Launch l;
+    rc = plan_seat_pass(*cfg, h.cap, h.n_members, aligned16(h.theta_t) ? FACT_MIRROR_ALIGNED : 0, first_id,
+                        lds_floats(cfg->hidden, rowpass_k1p(cfg->pol.in_dim)), lds_cap, &l);
+    if (rc != COPO_OK) return rc;
+    if (gemm_lds_attrs() != hipSuccess) return COPO_ERR_DEVICE;
+    h.c = *cfg;
+    return launch_kernel(l, &args, static_cast<hipStream_t>(stream)) == hipSuccess ? COPO_OK : COPO_ERR_DEVICE;
+}
+// the head of a seat pass from the leading arguments of its entry point
+#define COPO_SEAT_HEAD                                                                                                          \
+    SeatHead { {}, theta, theta_t, member_stride, rows, counts, cap, n_out, obs_src, col_lo, col_hi, n_slots, group, n_groups, level_of, \
+               reinterpret_cast<const float*>(levels), n_levels, n_members }
+
 extern "C" int copo_adv_obs_seats_f32(const copo_ppo_cfg* cfg, const float* theta, const float* theta_t, int64_t member_stride,
                                       int32_t n_members, const int64_t* rows, const int32_t* counts, int64_t cap, int64_t n_out,
                                       const float* obs_src, float* obs_seen, float* grad, int32_t col_lo, int32_t col_hi, int32_t n_slots,
                                       const int32_t* group, int32_t n_groups, const int32_t* level_of, const float* levels,
                                       int32_t n_levels, void* stream) {
-    int rc = check_cfg(cfg);
-    if (rc != COPO_OK) return rc;
-    if (!theta || !theta_t || !rows || !counts || !obs_src || !obs_seen || !group || !level_of || !levels) return COPO_ERR_NULL;
-    if (n_out < 1 || n_slots < 1 || n_out % n_slots != 0 || n_groups < 1 || n_levels < 1 || member_stride < cfg->n_params || member_stride % 4 != 0 ||
-        col_lo < 0 || col_lo > col_hi || col_hi > cfg->pol.in_dim)
-        return COPO_ERR_DIM;
-    Launch l;
-    rc = plan_adversary(*cfg, cap, n_members, aligned16(theta_t) ? FACT_MIRROR_ALIGNED : 0, &l);
-    if (rc != COPO_OK) return rc;
-    if (gemm_lds_attrs() != hipSuccess) return COPO_ERR_DEVICE;
-    AdvArgs a{*cfg, theta, theta_t, member_stride, rows, counts, cap, n_out, obs_src, obs_seen, grad, col_lo, col_hi, n_slots,
-              group, n_groups, level_of, levels, n_levels, n_members};
-    void* args[] = {&a};
-    return launch_kernel(l, args, static_cast<hipStream_t>(stream)) == hipSuccess ? COPO_OK : COPO_ERR_DEVICE;
+    AdvArgs a{COPO_SEAT_HEAD, obs_seen, grad};
+    return seat_pass_launch(cfg, a.h, obs_seen, true, K_ADV_1_4, adv_lds_floats, LDS_ROWPASS, &a, stream);
 }
 
 extern "C" int copo_pgd_obs_seats_f32(const copo_ppo_cfg* cfg, const float* theta, const float* theta_t, int64_t member_stride,
@@ -343,41 +357,19 @@ extern "C" int copo_pgd_obs_seats_f32(const copo_ppo_cfg* cfg, const float* thet
                                       const float* obs_src, float* obs_seen, int32_t col_lo, int32_t col_hi, int32_t n_slots,
                                       const int32_t* group, int32_t n_groups, const int32_t* level_of, const uint32_t* levels,
                                       int32_t n_levels, uint64_t seed, int32_t* tick, int32_t max_iters, float* trace, void* stream) {
-    int rc = check_cfg(cfg);
-    if (rc != COPO_OK) return rc;
-    if (!theta || !theta_t || !rows || !counts || !obs_src || !obs_seen || !group || !level_of || !levels) return COPO_ERR_NULL;
-    if (n_out < 1 || n_slots < 1 || n_out % n_slots != 0 || n_groups < 1 || n_levels < 1 || member_stride < cfg->n_params || member_stride % 4 != 0 ||
-        col_lo < 0 || col_lo > col_hi || col_hi > cfg->pol.in_dim)
-        return COPO_ERR_DIM;
-    Launch l;
-    rc = plan_pgd(*cfg, cap, n_members, max_iters, aligned16(theta_t) ? FACT_MIRROR_ALIGNED : 0, &l);
-    if (rc != COPO_OK) return rc;
-    if (gemm_lds_attrs() != hipSuccess) return COPO_ERR_DEVICE;
-    PgdArgs a{*cfg, theta, theta_t, member_stride, rows, counts, cap, n_out, obs_src, obs_seen, trace, col_lo, col_hi, n_slots,
-              group, n_groups, level_of, reinterpret_cast<const float*>(levels), n_levels, n_members, seed, tick, max_iters};
-    void* args[] = {&a};
-    return launch_kernel(l, args, static_cast<hipStream_t>(stream)) == hipSuccess ? COPO_OK : COPO_ERR_DEVICE;
+    PgdArgs a{COPO_SEAT_HEAD, obs_seen, trace, seed, tick, max_iters};
+    return seat_pass_launch(cfg, a.h, obs_seen, max_iters >= 1 && max_iters <= PGD_MAX_ITERS, K_PGD_1_4, pgd_lds_floats, LDS_ROWPASS, &a, stream);
 }
+
+static bool pad_ok(float pad) { return pad >= 0.0f && __builtin_isfinite(pad); }
 
 extern "C" int copo_cert_obs_seats_f32(const copo_ppo_cfg* cfg, const float* theta, const float* theta_t, int64_t member_stride,
                                        int32_t n_members, const int64_t* rows, const int32_t* counts, int64_t cap, int64_t n_out,
                                        const float* obs_src, float* bounds, int32_t col_lo, int32_t col_hi, int32_t n_slots,
                                        const int32_t* group, int32_t n_groups, const int32_t* level_of, const float* levels,
                                        int32_t n_levels, float pad, void* stream) {
-    int rc = check_cfg(cfg);
-    if (rc != COPO_OK) return rc;
-    if (!theta || !theta_t || !rows || !counts || !obs_src || !bounds || !group || !level_of || !levels) return COPO_ERR_NULL;
-    if (n_out < 1 || n_slots < 1 || n_out % n_slots != 0 || n_groups < 1 || n_levels < 1 || member_stride < cfg->n_params || member_stride % 4 != 0 ||
-        col_lo < 0 || col_lo > col_hi || col_hi > cfg->pol.in_dim || !(pad >= 0.0f) || !__builtin_isfinite(pad))
-        return COPO_ERR_DIM;
-    Launch l;
-    rc = plan_certify(*cfg, cap, n_members, aligned16(theta_t) ? FACT_MIRROR_ALIGNED : 0, &l);
-    if (rc != COPO_OK) return rc;
-    if (gemm_lds_attrs() != hipSuccess) return COPO_ERR_DEVICE;
-    CertArgs a{*cfg, theta, theta_t, member_stride, rows, counts, cap, n_out, obs_src, bounds, col_lo, col_hi, n_slots,
-               group, n_groups, level_of, levels, n_levels, n_members, pad};
-    void* args[] = {&a};
-    return launch_kernel(l, args, static_cast<hipStream_t>(stream)) == hipSuccess ? COPO_OK : COPO_ERR_DEVICE;
+    CertArgs a{COPO_SEAT_HEAD, bounds, pad};
+    return seat_pass_launch(cfg, a.h, bounds, pad_ok(pad), K_CERT_1_4, cert_lds_floats, LDS_ROWPASS, &a, stream);
 }
 
 extern "C" int copo_lin_obs_seats_f32(const copo_ppo_cfg* cfg, const float* theta, const float* theta_t, int64_t member_stride,
@@ -385,20 +377,8 @@ extern "C" int copo_lin_obs_seats_f32(const copo_ppo_cfg* cfg, const float* thet
                                       const float* obs_src, float* bounds, float* parts, int32_t col_lo, int32_t col_hi, int32_t n_slots,
                                       const int32_t* group, int32_t n_groups, const int32_t* level_of, const float* levels,
                                       int32_t n_levels, float pad, void* stream) {
-    int rc = check_cfg(cfg);
-    if (rc != COPO_OK) return rc;
-    if (!theta || !theta_t || !rows || !counts || !obs_src || !bounds || !group || !level_of || !levels) return COPO_ERR_NULL;
-    if (n_out < 1 || n_slots < 1 || n_out % n_slots != 0 || n_groups < 1 || n_levels < 1 || member_stride < cfg->n_params || member_stride % 4 != 0 ||
-        col_lo < 0 || col_lo > col_hi || col_hi > cfg->pol.in_dim || !(pad >= 0.0f) || !__builtin_isfinite(pad))
-        return COPO_ERR_DIM;
-    Launch l;
-    rc = plan_linbound(*cfg, cap, n_members, aligned16(theta_t) ? FACT_MIRROR_ALIGNED : 0, &l);
-    if (rc != COPO_OK) return rc;
-    if (gemm_lds_attrs() != hipSuccess) return COPO_ERR_DEVICE;
-    LinArgs a{*cfg, theta, theta_t, member_stride, rows, counts, cap, n_out, obs_src, bounds, parts, col_lo, col_hi, n_slots,
-              group, n_groups, level_of, levels, n_levels, n_members, pad};
-    void* args[] = {&a};
-    return launch_kernel(l, args, static_cast<hipStream_t>(stream)) == hipSuccess ? COPO_OK : COPO_ERR_DEVICE;
+    LinArgs a{COPO_SEAT_HEAD, bounds, parts, pad};
+    return seat_pass_launch(cfg, a.h, bounds, pad_ok(pad), K_LIN_1_4, lin_lds_floats, LDS_LINBOUND, &a, stream);
 }
 
 extern "C" int copo_mlp_forward_rows_f32(const copo_ppo_cfg* cfg, const float* theta, const float* theta_t,

@@ -18,26 +18,15 @@
 //                obs_seen = o bit for bit (no arithmetic), grad = 0
 //     ADV_GRAD   the gradient is needed: for the perturbation (eps != 0) or for `grad` alone (eps == 0: obs_seen = o bit for bit)
 // A tile without an ADV_GRAD row copies and leaves before the GEMMs (uniform over the workgroup).  No atomics, fixed summation order.
+// The argument head and the tile prologue (row and level look-up, the staging of the true rows and of W3) are learn_seat.inc's, shared
+// with pgd_obs_kernel, cert_obs_kernel and lin_obs_kernel; the resource report of all sixteen instantiations is what it was with a copy each.
 // The forward body is a copy of mlp_fwd_kernel's on purpose: a __device__ body shared with it changed the register allocation of the
 // hidden-512 forward kernels (see there).
 // ------------------------------------------------------------------------------------------------------------
 struct AdvArgs {
-    copo_ppo_cfg c;
-    const float* theta;
-    const float* theta_t;
-    int64_t member_stride;
-    const int64_t* rows;      // [n_members][cap]
-    const int32_t* counts;    // [n_members]
-    int64_t cap, n_out;
-    const float* obs_src;     // [n_out][in_dim]
+    SeatHead h;               // levels [n_levels][4]: eps, steer, throttle, 0
     float* obs_seen;          // [n_out][in_dim]
     float* grad;              // [n_out][in_dim] or NULL
-    int32_t col_lo, col_hi, n_slots;
-    const int32_t* group;     // [n_out / n_slots]
-    int32_t n_groups;
-    const int32_t* level_of;  // [n_groups][n_members]
-    const float* levels;      // [n_levels][4]: eps, steer, throttle, 0
-    int32_t n_levels, n_members;
 };
 
 constexpr int ADV_SKIP = 0, ADV_COPY = 1, ADV_GRAD = 2;
@@ -51,14 +40,15 @@ __global__ void __launch_bounds__(64 * WAVES) adv_obs_kernel(AdvArgs a) {
     __shared__ int mode_s[HT];
     constexpr int H = 16 * NT * WAVES, HP = H + 4, TH = 64 * WAVES;
     constexpr int DB = NT >= 8 ? 4 : (H / 16 >= 8 ? 8 : H / 16);
-    const copo_ppo_cfg& c = a.c;
+    const SeatHead& hd = a.h;
+    const copo_ppo_cfg& c = hd.c;
     const size_t k = blockIdx.y;
-    const int64_t n = a.counts[k] < a.cap ? a.counts[k] : a.cap;      // (a list holds `cap` rows at the most)
+    const int64_t n = hd.counts[k] < hd.cap ? hd.counts[k] : hd.cap;      // (a list holds `cap` rows at the most)
     const int64_t m0 = (int64_t)blockIdx.x * HT;
     if (m0 >= n) return;
-    const float* theta = a.theta + k * a.member_stride;
-    const float* theta_t = a.theta_t + k * a.member_stride;
-    const int64_t* rows = a.rows + k * (size_t)a.cap;
+    const float* theta = hd.theta + k * hd.member_stride;
+    const float* theta_t = hd.theta_t + k * hd.member_stride;
+    const int64_t* rows = hd.rows + k * (size_t)hd.cap;
     const copo_net_layout L = c.pol;
     const int K1 = L.in_dim, K1P = rowpass_k1p(K1), XP = K1P + 4;
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), ln = lane & 15, lj = lane >> 4, cb = wave * (16 * NT);
@@ -66,22 +56,16 @@ __global__ void __launch_bounds__(64 * WAVES) adv_obs_kernel(AdvArgs a) {
     float* h2s = h1s + HT * HP;                         // [HT][HP]  h2, then u2
     float* xs = h2s + HT * HP;                          // [HT][XP]  the true observation rows, zero beyond K1
     float* w3s = xs + HT * XP;                          // [2][H]    the two mean rows of W3
-    auto row_at = [&](int64_t mm) -> int64_t {          // -1: no row
-        if (mm >= n) return -1;
-        const int64_t r = rows[mm];
-        return r >= 0 && r < a.n_out ? r : -1;
-    };
     BRing<NT, DB, false> ring;
     ring.start(theta_t + L.w1, H, cb, ln, lj);
     if (tid < HT) {
-        const int64_t r = row_at(m0 + tid);
+        const int64_t r = seat_row_at(hd, rows, n, m0 + tid);
         int mode = r < 0 ? ADV_SKIP : ADV_COPY;
         float e = 0.0f, s = 0.0f, t = 0.0f;
         if (r >= 0) {
-            const int g = a.group[r / a.n_slots];
-            const int lv = g >= 0 && g < a.n_groups ? a.level_of[(size_t)g * a.n_members + k] : -1;
-            if (lv >= 0 && lv < a.n_levels) {
-                e = a.levels[4 * lv]; s = a.levels[4 * lv + 1]; t = a.levels[4 * lv + 2];
+            const int lv = seat_level_at(hd, k, r);
+            if (lv >= 0) {
+                e = hd.levels[4 * lv]; s = hd.levels[4 * lv + 1]; t = hd.levels[4 * lv + 2];
                 if ((s != 0.0f || t != 0.0f) && (e != 0.0f || a.grad)) mode = ADV_GRAD;
             }
         }
@@ -89,25 +73,7 @@ __global__ void __launch_bounds__(64 * WAVES) adv_obs_kernel(AdvArgs a) {
         mode_s[tid] = mode;
         lvl_s[tid][0] = e; lvl_s[tid][1] = mode == ADV_GRAD ? s : 0.0f; lvl_s[tid][2] = mode == ADV_GRAD ? t : 0.0f; lvl_s[tid][3] = 0.0f;
     }
-    if ((K1 & 3) == 0 && (reinterpret_cast<uintptr_t>(a.obs_src) & 15) == 0) {
-        const int qn = K1P >> 2;
-        for (int i = tid; i < HT * qn; i += TH) {
-            const int row = i / qn, kk = (i - row * qn) * 4;
-            const int64_t r = row_at(m0 + row);
-            const bool ok = r >= 0 && kk < K1;
-            const float4 v = *reinterpret_cast<const float4*>(a.obs_src + (size_t)(r < 0 ? 0 : r) * K1 + (kk < K1 ? kk : 0));
-            *reinterpret_cast<float4*>(xs + row * XP + kk) = ok ? v : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-    } else {
-        for (int i = tid; i < HT * K1P; i += TH) {
-            const int row = i / K1P, kk = i - row * K1P;
-            const int64_t r = row_at(m0 + row);
-            const bool ok = r >= 0 && kk < K1;
-            const float v = a.obs_src[(size_t)(r < 0 ? 0 : r) * K1 + (kk < K1 ? kk : 0)];
-            xs[row * XP + kk] = ok ? v : 0.0f;
-        }
-    }
-    for (int i = tid; i < 2 * H; i += TH) w3s[i] = theta[L.w3 + i];
+    seat_stage<TH>(hd, rows, n, m0, theta, H, xs, w3s, tid);
     __syncthreads();
     bool any = false;          // (the same sixteen words for every thread: uniform)
 #pragma unroll
@@ -192,7 +158,7 @@ __global__ void __launch_bounds__(64 * WAVES) adv_obs_kernel(AdvArgs a) {
             }
         }
         if (col >= K1) continue;
-        const bool lidar = col >= a.col_lo && col < a.col_hi;
+        const bool lidar = col >= hd.col_lo && col < hd.col_hi;
 #pragma unroll
         for (int rr = 0; rr < 4; ++rr) {
             const int i = 4 * lj + rr, mode = mode_s[i];

@@ -17,7 +17,8 @@
 //     per axis:                 lo = max(loL, loI), hi = min(hiL, hiI); lo > hi (rounding only, e.g. eps = 0): (loI, hiI); then pad (__fadd_rn)
 //     bounds[r] = lo_0, hi_0, lo_1, hi_1, mu_0(o), mu_1(o), 1.0, eps;  parts[r] (optional) = loL_0, hiL_0, loL_1, hiL_1, loI_0, hiI_0, loI_1,
 //     hiI_1 before the pad.  Invalid listed rows: eight zeros in both; rows in no list are never written.
-// Launch shape, prologue, masking, per-row modes and the three-tile forward are cert_obs_kernel's (copied, as its body is mlp_fwd_kernel's).
+// Launch shape, prologue (learn_seat.inc), masking, per-row modes and the three-tile forward are cert_obs_kernel's (the forward copied, as its
+// body is mlp_fwd_kernel's).
 // LDS is cert_obs_kernel's too -- three input tiles, three h1 tiles, the two mean rows of W3 -- at every hidden width, 512 included: layer
 // 1's (l, u) are NOT kept across layer 2.  Where the backward pass needs them, the layer-1 GEMM of the centre and radius tiles (K = in_dim,
 // the cheapest GEMM of the kernel) runs again, behind the W2 pass, into accumulators whose layout is that of v1: lam1 / beta1 are formed
@@ -28,22 +29,9 @@
 // by one thread per row: no atomics, a fixed order -- two launches give the same bits.
 // ------------------------------------------------------------------------------------------------------------
 struct LinArgs {
-    copo_ppo_cfg c;
-    const float* theta;
-    const float* theta_t;
-    int64_t member_stride;
-    const int64_t* rows;      // [n_members][cap]
-    const int32_t* counts;    // [n_members]
-    int64_t cap, n_out;
-    const float* obs_src;     // [n_out][in_dim]
+    SeatHead h;               // levels [n_levels][4]: eps, delta_steer, delta_throttle, 0
     float* bounds;            // [n_out][8]
     float* parts;             // [n_out][8] or NULL
-    int32_t col_lo, col_hi, n_slots;
-    const int32_t* group;     // [n_out / n_slots]
-    int32_t n_groups;
-    const int32_t* level_of;  // [n_groups][n_members]
-    const float* levels;      // [n_levels][4]: eps, delta_steer, delta_throttle, 0
-    int32_t n_levels, n_members;
     float pad;
 };
 
@@ -89,36 +77,31 @@ __global__ void __launch_bounds__(64 * WAVES) lin_obs_kernel(LinArgs a) {
     __shared__ float part_s[WAVES][HT][LIN_PARTS];
     constexpr int H = 16 * NT * WAVES, HP = H + 4, TH = 64 * WAVES;
     constexpr int DB = NT >= 8 ? 4 : (H / 16 >= 8 ? 8 : H / 16);
-    const copo_ppo_cfg& c = a.c;
+    const SeatHead& hd = a.h;
+    const copo_ppo_cfg& c = hd.c;
     const size_t k = blockIdx.y;
-    const int64_t n = a.counts[k] < a.cap ? a.counts[k] : a.cap;      // (a list holds `cap` rows at the most)
+    const int64_t n = hd.counts[k] < hd.cap ? hd.counts[k] : hd.cap;      // (a list holds `cap` rows at the most)
     const int64_t m0 = (int64_t)blockIdx.x * HT;
     if (m0 >= n) return;
-    const float* theta = a.theta + k * a.member_stride;
-    const float* theta_t = a.theta_t + k * a.member_stride;
-    const int64_t* rows = a.rows + k * (size_t)a.cap;
+    const float* theta = hd.theta + k * hd.member_stride;
+    const float* theta_t = hd.theta_t + k * hd.member_stride;
+    const int64_t* rows = hd.rows + k * (size_t)hd.cap;
     const copo_net_layout L = c.pol;
     const int K1 = L.in_dim, K1P = rowpass_k1p(K1), XP = K1P + 4;
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), ln = lane & 15, lj = lane >> 4, cb = wave * (16 * NT);
     float* h1s = reinterpret_cast<float*>(lin_lds);     // [3][HT][HP]  h1 of the true row, centre and radius; then g2 / g1 of the two heads in [0], [1]
     float* xs = h1s + CERT_PASSES * HT * HP;            // [3][HT][XP]  the true rows (zero beyond K1), c0, r0
     float* w3s = xs + CERT_PASSES * HT * XP;            // [2][H]       the two mean rows of W3
-    auto row_at = [&](int64_t mm) -> int64_t {          // -1: no row
-        if (mm >= n) return -1;
-        const int64_t r = rows[mm];
-        return r >= 0 && r < a.n_out ? r : -1;
-    };
     BRing<NT, DB, false> ring;
     ring.start(theta_t + L.w1, H, cb, ln, lj);
     if (tid < HT) {
-        const int64_t r = row_at(m0 + tid);
+        const int64_t r = seat_row_at(hd, rows, n, m0 + tid);
         int mode = r < 0 ? CERT_SKIP : CERT_ZERO;
         float e = 0.0f;
         if (r >= 0) {
-            const int g = a.group[r / a.n_slots];
-            const int lv = g >= 0 && g < a.n_groups ? a.level_of[(size_t)g * a.n_members + k] : -1;
-            if (lv >= 0 && lv < a.n_levels) {
-                e = a.levels[4 * lv];
+            const int lv = seat_level_at(hd, k, r);
+            if (lv >= 0) {
+                e = hd.levels[4 * lv];
                 mode = CERT_RUN;
             }
         }
@@ -126,25 +109,7 @@ __global__ void __launch_bounds__(64 * WAVES) lin_obs_kernel(LinArgs a) {
         mode_s[tid] = mode;
         eps_s[tid] = mode == CERT_RUN ? e : 0.0f;
     }
-    if ((K1 & 3) == 0 && (reinterpret_cast<uintptr_t>(a.obs_src) & 15) == 0) {
-        const int qn = K1P >> 2;
-        for (int i = tid; i < HT * qn; i += TH) {
-            const int row = i / qn, kk = (i - row * qn) * 4;
-            const int64_t r = row_at(m0 + row);
-            const bool ok = r >= 0 && kk < K1;
-            const float4 v = *reinterpret_cast<const float4*>(a.obs_src + (size_t)(r < 0 ? 0 : r) * K1 + (kk < K1 ? kk : 0));
-            *reinterpret_cast<float4*>(xs + row * XP + kk) = ok ? v : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-    } else {
-        for (int i = tid; i < HT * K1P; i += TH) {
-            const int row = i / K1P, kk = i - row * K1P;
-            const int64_t r = row_at(m0 + row);
-            const bool ok = r >= 0 && kk < K1;
-            const float v = a.obs_src[(size_t)(r < 0 ? 0 : r) * K1 + (kk < K1 ? kk : 0)];
-            xs[row * XP + kk] = ok ? v : 0.0f;
-        }
-    }
-    for (int i = tid; i < 2 * H; i += TH) w3s[i] = theta[L.w3 + i];
+    seat_stage<TH>(hd, rows, n, m0, theta, H, xs, w3s, tid);
     __syncthreads();
     bool any = false;          // (the same sixteen words for every thread: uniform)
 #pragma unroll
@@ -164,7 +129,7 @@ __global__ void __launch_bounds__(64 * WAVES) lin_obs_kernel(LinArgs a) {
         const int row = i / K1P, kk = i - row * K1P;
         const float o = xs[row * XP + kk], e = eps_s[row];
         float c0 = o, r0 = 0.0f;
-        if (kk >= a.col_lo && kk < a.col_hi) {
+        if (kk >= hd.col_lo && kk < hd.col_hi) {
             const float lo = fmaxf(__fadd_rn(o, -e), 0.0f), hi = fminf(__fadd_rn(o, e), 1.0f);
             c0 = __fmul_rn(0.5f, __fadd_rn(lo, hi));
             r0 = __fmul_rn(0.5f, __fadd_rn(hi, -lo));

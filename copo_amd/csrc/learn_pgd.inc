@@ -14,7 +14,7 @@
 // level; a row sits in one member's list at the most (the seat plan's contract), so nothing races.
 // trace (float [max_iters][n_out][in_dim] or NULL): g_i of every attacked row for i < it, zeros for later iterations and for listed
 // rows that pass through.
-// Launch shape, prologue and modes are adv_obs_kernel's: grid ceil(cap / 16) x n_members, 16-row tile, a workgroup past counts[k]
+// Launch shape, prologue (learn_seat.inc) and modes are adv_obs_kernel's: grid ceil(cap / 16) x n_members, 16-row tile, a workgroup past counts[k]
 // leaves before its first barrier, the last tile is masked, modes per ROW:
 //     PGD_SKIP    no row here: nothing is written
 //     PGD_COPY    level or group out of range, eps == 0, it <= 0, or targeted with steer == throttle == 0: obs_seen = o, no arithmetic
@@ -28,22 +28,9 @@
 // The forward body is a copy of mlp_fwd_kernel's, as adv_obs_kernel's is (see there).
 // ------------------------------------------------------------------------------------------------------------
 struct PgdArgs {
-    copo_ppo_cfg c;
-    const float* theta;
-    const float* theta_t;
-    int64_t member_stride;
-    const int64_t* rows;      // [n_members][cap]
-    const int32_t* counts;    // [n_members]
-    int64_t cap, n_out;
-    const float* obs_src;     // [n_out][in_dim]
+    SeatHead h;               // levels [n_levels][8]: eps, steer, throttle, alpha, iters (i32), flags (i32), 0, 0
     float* obs_seen;          // [n_out][in_dim]
     float* trace;             // [max_iters][n_out][in_dim] or NULL
-    int32_t col_lo, col_hi, n_slots;
-    const int32_t* group;     // [n_out / n_slots]
-    int32_t n_groups;
-    const int32_t* level_of;  // [n_groups][n_members]
-    const float* levels;      // [n_levels][8]: eps, steer, throttle, alpha, iters (i32), flags (i32), 0, 0
-    int32_t n_levels, n_members;
     uint64_t seed;
     int32_t* tick;            // [n_out] or NULL
     int32_t max_iters;
@@ -64,14 +51,15 @@ __global__ void __launch_bounds__(64 * WAVES) pgd_obs_kernel(PgdArgs a) {
     __shared__ int mode_s[HT], it_s[HT], flag_s[HT], tick_s[HT];
     constexpr int H = 16 * NT * WAVES, HP = H + 4, TH = 64 * WAVES;
     constexpr int DB = NT >= 8 ? 4 : (H / 16 >= 8 ? 8 : H / 16);
-    const copo_ppo_cfg& c = a.c;
+    const SeatHead& hd = a.h;
+    const copo_ppo_cfg& c = hd.c;
     const size_t k = blockIdx.y;
-    const int64_t n = a.counts[k] < a.cap ? a.counts[k] : a.cap;      // (a list holds `cap` rows at the most)
+    const int64_t n = hd.counts[k] < hd.cap ? hd.counts[k] : hd.cap;      // (a list holds `cap` rows at the most)
     const int64_t m0 = (int64_t)blockIdx.x * HT;
     if (m0 >= n) return;
-    const float* theta = a.theta + k * a.member_stride;
-    const float* theta_t = a.theta_t + k * a.member_stride;
-    const int64_t* rows = a.rows + k * (size_t)a.cap;
+    const float* theta = hd.theta + k * hd.member_stride;
+    const float* theta_t = hd.theta_t + k * hd.member_stride;
+    const int64_t* rows = hd.rows + k * (size_t)hd.cap;
     const copo_net_layout L = c.pol;
     const int K1 = L.in_dim, K1P = rowpass_k1p(K1), XP = K1P + 4;
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), ln = lane & 15, lj = lane >> 4, cb = wave * (16 * NT);
@@ -80,13 +68,8 @@ __global__ void __launch_bounds__(64 * WAVES) pgd_obs_kernel(PgdArgs a) {
     float* xs = h2s + HT * HP;                          // [HT][XP]  the true observation rows, zero beyond K1
     float* w3s = xs + HT * XP;                          // [2][H]    the two mean rows of W3
     float* xp = w3s + 2 * H;                            // [HT][XP]  the iterate
-    auto row_at = [&](int64_t mm) -> int64_t {          // -1: no row
-        if (mm >= n) return -1;
-        const int64_t r = rows[mm];
-        return r >= 0 && r < a.n_out ? r : -1;
-    };
     if (tid < HT) {
-        const int64_t r = row_at(m0 + tid);
+        const int64_t r = seat_row_at(hd, rows, n, m0 + tid);
         int mode = r < 0 ? PGD_SKIP : PGD_COPY, it = 0, flags = 0, tk = 0;
         float e = 0.0f, s = 0.0f, t = 0.0f, al = 0.0f;
         if (r >= 0) {
@@ -94,10 +77,9 @@ __global__ void __launch_bounds__(64 * WAVES) pgd_obs_kernel(PgdArgs a) {
                 tk = a.tick[r];
                 a.tick[r] = tk + 1;
             }
-            const int g = a.group[r / a.n_slots];
-            const int lv = g >= 0 && g < a.n_groups ? a.level_of[(size_t)g * a.n_members + k] : -1;
-            if (lv >= 0 && lv < a.n_levels) {
-                const float* w = a.levels + (size_t)PGD_LEVEL_WORDS * lv;
+            const int lv = seat_level_at(hd, k, r);
+            if (lv >= 0) {
+                const float* w = hd.levels + (size_t)PGD_LEVEL_WORDS * lv;
                 e = w[0]; s = w[1]; t = w[2]; al = w[3];
                 it = __float_as_int(w[4]); flags = __float_as_int(w[5]);
                 it = it < a.max_iters ? it : a.max_iters;
@@ -114,25 +96,7 @@ __global__ void __launch_bounds__(64 * WAVES) pgd_obs_kernel(PgdArgs a) {
         c_s[tid][0] = aimed ? s : 0.0f; c_s[tid][1] = aimed ? t : 0.0f;
         mu0_s[tid][0] = 0.0f; mu0_s[tid][1] = 0.0f;
     }
-    if ((K1 & 3) == 0 && (reinterpret_cast<uintptr_t>(a.obs_src) & 15) == 0) {
-        const int qn = K1P >> 2;
-        for (int i = tid; i < HT * qn; i += TH) {
-            const int row = i / qn, kk = (i - row * qn) * 4;
-            const int64_t r = row_at(m0 + row);
-            const bool ok = r >= 0 && kk < K1;
-            const float4 v = *reinterpret_cast<const float4*>(a.obs_src + (size_t)(r < 0 ? 0 : r) * K1 + (kk < K1 ? kk : 0));
-            *reinterpret_cast<float4*>(xs + row * XP + kk) = ok ? v : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-    } else {
-        for (int i = tid; i < HT * K1P; i += TH) {
-            const int row = i / K1P, kk = i - row * K1P;
-            const int64_t r = row_at(m0 + row);
-            const bool ok = r >= 0 && kk < K1;
-            const float v = a.obs_src[(size_t)(r < 0 ? 0 : r) * K1 + (kk < K1 ? kk : 0)];
-            xs[row * XP + kk] = ok ? v : 0.0f;
-        }
-    }
-    for (int i = tid; i < 2 * H; i += TH) w3s[i] = theta[L.w3 + i];
+    seat_stage<TH>(hd, rows, n, m0, theta, H, xs, w3s, tid);
     __syncthreads();
     int itmax = 0;             // (the same sixteen words for every thread: uniform)
     bool any_unt = false;
@@ -149,7 +113,7 @@ __global__ void __launch_bounds__(64 * WAVES) pgd_obs_kernel(PgdArgs a) {
             const size_t at = (size_t)dst_s[row] * K1 + col;
             a.obs_seen[at] = src[row * XP + col];
             if (a.trace)
-                for (int j = from; j < a.max_iters; ++j) a.trace[(size_t)j * a.n_out * K1 + at] = 0.0f;
+                for (int j = from; j < a.max_iters; ++j) a.trace[(size_t)j * hd.n_out * K1 + at] = 0.0f;
         }
     };
     if (itmax <= 0) {          // every row passes through: copy, no GEMM
@@ -160,8 +124,8 @@ __global__ void __launch_bounds__(64 * WAVES) pgd_obs_kernel(PgdArgs a) {
     for (int i = tid; i < HT * K1P; i += TH) {
         const int row = i / K1P, kk = i - row * K1P;
         float v = xs[row * XP + kk];
-        if ((flag_s[row] & PGD_RANDOM_START) && kk >= a.col_lo && kk < a.col_hi) {      // (flags are zero off the attacked rows)
-            const uint32_t h = hash_rng(a.seed, (uint32_t)dst_s[row], (uint32_t)tick_s[row], (uint32_t)(kk - a.col_lo), PGD_STREAM);
+        if ((flag_s[row] & PGD_RANDOM_START) && kk >= hd.col_lo && kk < hd.col_hi) {      // (flags are zero off the attacked rows)
+            const uint32_t h = hash_rng(a.seed, (uint32_t)dst_s[row], (uint32_t)tick_s[row], (uint32_t)(kk - hd.col_lo), PGD_STREAM);
             const float u = __fadd_rn(__fmul_rn(2.0f, uniform01(h)), -1.0f);
             v = fminf(fmaxf(__fadd_rn(v, __fmul_rn(lvl_s[row][0], u)), 0.0f), 1.0f);
         }
@@ -269,14 +233,14 @@ __global__ void __launch_bounds__(64 * WAVES) pgd_obs_kernel(PgdArgs a) {
                 }
             }
             if (col >= K1) continue;
-            const bool lidar = col >= a.col_lo && col < a.col_hi;
+            const bool lidar = col >= hd.col_lo && col < hd.col_hi;
 #pragma unroll
             for (int rr = 0; rr < 4; ++rr) {
                 const int i = 4 * lj + rr;
                 if (mode_s[i] == PGD_SKIP) continue;
                 const bool on = it < it_s[i];
                 const float gv = on ? g[rr] : 0.0f;
-                if (a.trace) a.trace[((size_t)it * a.n_out + dst_s[i]) * K1 + col] = gv;
+                if (a.trace) a.trace[((size_t)it * hd.n_out + dst_s[i]) * K1 + col] = gv;
                 if (on && lidar) {
                     const float x = xp[i * XP + col], o = xs[i * XP + col], e = lvl_s[i][0], al = lvl_s[i][3];
                     const float sg = gv > 0.0f ? 1.0f : gv < 0.0f ? -1.0f : 0.0f;

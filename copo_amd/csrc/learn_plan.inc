@@ -33,7 +33,7 @@ constexpr int LDS_LINBOUND = 136 * 1024;    // lin_obs_kernel keeps 11.5 KB of s
     X(WGRAD_OT2, 64 * WG_WAVES, 80 * 1024, wgrad_adam_kernel<2>)                                                             \
     X(HEAD, 256, LDS_DEFAULT, head_kernel) X(META_FOLD, 256, LDS_DEFAULT, meta_batch_fold_kernel)                            \
     X(REDUCE_ADAM, 256, LDS_DEFAULT, reduce_adam_kernel)
-// rows behind the learner's: kernels of the evaluation side that live in this translation unit (learn_inputgrad.inc, learn_pgd.inc, learn_certify.inc, learn_linbound.inc).  They are launched
+// rows behind the learner's: kernels of the evaluation side that live in this translation unit (learn_seat.inc, learn_inputgrad.inc, learn_pgd.inc, learn_certify.inc, learn_linbound.inc).  They are launched
 // through the same launch_kernel and get their LDS ceilings from the same loop; copo_debug_learner_kernel lists the learner's rows only
 // (ids below K_LEARNER_COUNT).  Per kernel the four shapes in shape_index order.
 #define COPO_EVAL_KERNELS(X)                                                                                                \
@@ -236,57 +236,20 @@ static int plan_forward(const copo_ppo_cfg& c, int64_t n_rows, int first_net, in
     return COPO_OK;
 }
 
-// Input-gradient pass of a seated bank (copo_adv_obs_seats_f32, learn_inputgrad.inc): the launch shape of seat mode -- `cap` rows per
-// member at the most, the member as the grid's second dimension -- and always the 16-row tile, at every hidden width.  fp32 operands only.
-static int plan_adversary(const copo_ppo_cfg& c, int64_t cap, int n_members, int facts, Launch* out) {
+// The four seat passes of a seated bank (copo_adv / pgd / cert / lin_obs_seats_f32; learn_inputgrad.inc, learn_pgd.inc, learn_certify.inc,
+// learn_linbound.inc): the launch shape of seat mode -- `cap` rows per member at the most, the member as the grid's second dimension --
+// and always the 16-row tile, at every hidden width.  fp32 operands only.  `first_id`: the pass's hidden-64 table entry; `lds_floats`:
+// its dynamic LDS (every pass holds at least adv_obs_kernel's two h tiles, one input tile and the W3 rows: the iterate of the PGD pass is
+// a second input tile, the bound passes hold three of each); `lds_cap`: LDS_ROWPASS, or LDS_LINBOUND for the linear pass, which keeps
+// static partial sums next to its tiles (hidden 512 with an input wider than 128 columns is refused there).
+static int plan_seat_pass(const copo_ppo_cfg& c, int64_t cap, int n_members, int facts, int first_id, size_t lds_floats, int lds_cap, Launch* out) {
     const int H = c.hidden, sh = shape_index(H);
     if (cap < 1 || n_members < 1 || n_members > 65535 || (cap + HT - 1) / HT > 0x7fffffff) return COPO_ERR_DIM;
     if (sh < 0 || c.operand_dtype != COPO_OPERAND_F32 || !(facts & FACT_MIRROR_ALIGNED)) return COPO_ERR_DIM;
     if (c.pol.in_dim < 1 || c.pol.w1 % 4 != 0 || c.pol.w2 % 4 != 0) return COPO_ERR_DIM;
-    const size_t lds = adv_lds_floats(H, rowpass_k1p(c.pol.in_dim)) * sizeof(float);
-    if (lds > (size_t)LDS_ROWPASS) return COPO_ERR_DIM;
-    const int id = K_ADV_1_4 + sh;
+    const size_t lds = lds_floats * sizeof(float);
+    if (lds > (size_t)lds_cap) return COPO_ERR_DIM;
+    const int id = first_id + sh;
     *out = Launch{id, (uint32_t)((cap + HT - 1) / HT), (uint32_t)n_members, 1, g_kernels[id].block, (int32_t)lds, {}};
-    return COPO_OK;
-}
-
-// Iterated input-gradient pass of a seated bank (copo_pgd_obs_seats_f32, learn_pgd.inc): plan_adversary's launch shape and refusals, the
-// LDS of a second input tile, and the iteration bound of the launch (1 .. PGD_MAX_ITERS).
-static int plan_pgd(const copo_ppo_cfg& c, int64_t cap, int n_members, int max_iters, int facts, Launch* out) {
-    if (max_iters < 1 || max_iters > PGD_MAX_ITERS) return COPO_ERR_DIM;
-    const int rc = plan_adversary(c, cap, n_members, facts, out);
-    if (rc != COPO_OK) return rc;
-    const size_t lds = pgd_lds_floats(c.hidden, rowpass_k1p(c.pol.in_dim)) * sizeof(float);
-    if (lds > (size_t)LDS_ROWPASS) return COPO_ERR_DIM;
-    out->id = K_PGD_1_4 + shape_index(c.hidden);
-    out->block = g_kernels[out->id].block;
-    out->lds = (int32_t)lds;
-    return COPO_OK;
-}
-
-// Interval bounds of a seated bank (copo_cert_obs_seats_f32, learn_certify.inc): plan_adversary's launch shape and refusals, the LDS of
-// three input tiles and three h1 tiles (layer 2's output stays on the lanes).
-static int plan_certify(const copo_ppo_cfg& c, int64_t cap, int n_members, int facts, Launch* out) {
-    const int rc = plan_adversary(c, cap, n_members, facts, out);
-    if (rc != COPO_OK) return rc;
-    const size_t lds = cert_lds_floats(c.hidden, rowpass_k1p(c.pol.in_dim)) * sizeof(float);
-    if (lds > (size_t)LDS_ROWPASS) return COPO_ERR_DIM;
-    out->id = K_CERT_1_4 + shape_index(c.hidden);
-    out->block = g_kernels[out->id].block;
-    out->lds = (int32_t)lds;
-    return COPO_OK;
-}
-
-// Linear bounds of a seated bank (copo_lin_obs_seats_f32, learn_linbound.inc): plan_certify's launch shape, refusals and dynamic LDS (the
-// backward pass lives in the dead h1 tiles; layer 1's intervals are recomputed, not kept), so hidden 512 runs at the observation widths of
-// the project (k1p = 128); the ceiling is LDS_LINBOUND, which leaves room for the kernel's static partial sums.
-static int plan_linbound(const copo_ppo_cfg& c, int64_t cap, int n_members, int facts, Launch* out) {
-    const int rc = plan_adversary(c, cap, n_members, facts, out);
-    if (rc != COPO_OK) return rc;
-    const size_t lds = lin_lds_floats(c.hidden, rowpass_k1p(c.pol.in_dim)) * sizeof(float);
-    if (lds > (size_t)LDS_LINBOUND) return COPO_ERR_DIM;      // (hidden 512 with an input wider than 128 columns)
-    out->id = K_LIN_1_4 + shape_index(c.hidden);
-    out->block = g_kernels[out->id].block;
-    out->lds = (int32_t)lds;
     return COPO_OK;
 }

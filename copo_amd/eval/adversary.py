@@ -17,17 +17,16 @@ of a checkpoint (`beam_saliency`).
 One step, an L-infinity budget, the LiDAR block, fp32 operands.  Multi-step PGD and untargeted objectives are `pgd.py`'s; the ego /
 navigation columns and the bfloat16 operand mode are out of scope.
 
-Pieces: `AdversaryLevel` / `AdversaryPlan` (numpy only), `AdversaryBuffers`, `AdversarialSeatSampler` (the `SeatSampler` whose
-`_policy_obs` launches the kernel inside the captured fragment), `adversary_sweep_rows` (checkpoints x levels x roles as a pandas frame;
-`evaluate --adversary-sweep`) and `beam_saliency`.
+Pieces, each on its base in `levels.py`: `AdversaryLevel` / `AdversaryPlan` (numpy only), `AdversaryBuffers`, `AdversarialSeatSampler`
+(whose `_policy_obs` launches the kernel inside the captured fragment), `adversary_sweep_rows` (checkpoints x levels x roles as a pandas
+frame; `evaluate --adversary-sweep`); and `beam_saliency`.
 """
 from dataclasses import dataclass
 
 import numpy as np
 
-from .bank import DeviceTables, draw_cell_noise
-from .crossplay import SeatSampler
-from .faults import lidar_columns, sweep_frame, sweep_members, sweep_plan
+from . import levels as _levels
+from .levels import LevelBuffers, LevelPlan, LevelSeatSampler, baseline_levels, finite_fields, role_frame, run_sweep
 
 LEVEL_WORDS = 4
 LEVEL_FIELDS = ("eps", "steer", "throttle")
@@ -43,11 +42,7 @@ class AdversaryLevel:
     throttle: float = 0.0
 
     def __post_init__(self):
-        for name in LEVEL_FIELDS:
-            v = getattr(self, name)
-            if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v):
-                raise ValueError("AdversaryLevel: %s = %r, a finite number wanted" % (name, v))
-            object.__setattr__(self, name, float(v))
+        finite_fields(self, LEVEL_FIELDS)
         if self.eps < 0.0:
             raise ValueError("AdversaryLevel: eps = %r is negative" % self.eps)
 
@@ -63,83 +58,25 @@ class AdversaryLevel:
         return {name: getattr(self, name) for name in LEVEL_FIELDS}
 
 
-def _levels(levels):
-    return [lv if isinstance(lv, AdversaryLevel) else AdversaryLevel(**lv) for lv in levels]
+class AdversaryPlan(LevelPlan):
+    """`LevelPlan` of `AdversaryLevel`s; `words` float32 [L][4]."""
+    LEVEL = AdversaryLevel
 
 
-class AdversaryPlan:
-    """`levels`: a sequence of `AdversaryLevel` (or dicts of its fields); `level_of`: int [G][K], the level of bank member k in scene
-    group g (an index outside [0, L) leaves the member's rows alone).  Derived: `words` float32 [L][4].  Nothing here touches a device."""
-
-    def __init__(self, levels, level_of):
-        self.levels = _levels(levels)
-        if not self.levels:
-            raise ValueError("AdversaryPlan: no levels")
-        self.level_of = np.ascontiguousarray(level_of, np.int32)
-        if self.level_of.ndim != 2 or self.level_of.shape[0] < 1 or self.level_of.shape[1] < 1:
-            raise ValueError("AdversaryPlan: level_of of shape %s, [groups][members] wanted" % (self.level_of.shape,))
-        self.L, (self.G, self.K) = len(self.levels), self.level_of.shape
-        self.words = np.stack([lv.words() for lv in self.levels])
-        self.checkpoint = self.level = None
-        self.share = self.scenes_per_cell = None          # (`sweep` sets them: cells of that many scenes share their action noise)
-
-    def check(self, seat_plan):
-        if (seat_plan.n_groups, seat_plan.K) != (self.G, self.K):
-            raise ValueError("AdversaryPlan: level_of is %d groups x %d members, the seat plan has %d x %d" % (
-                self.G, self.K, seat_plan.n_groups, seat_plan.K))
-        return self
-
-    @classmethod
-    def sweep(cls, K, levels, scenes_per_cell, N, share=1.0):
-        """(seat plan, adversary plan) of K checkpoints x L levels on the cell layout of `FaultPlan.sweep` (`SeatPlan.cells`): with share
-        < 1 the bank is doubled, the first round(share * N) slots of a cell are attacked at the cell's level and the rest drive at level
-        0, which must then be an identity."""
-        return sweep_plan(cls, "AdversaryPlan.sweep", K, _levels(levels), scenes_per_cell, N, share)
-
-
-class AdversaryBuffers(DeviceTables):
+class AdversaryBuffers(LevelBuffers):
     """An adversary plan's tables on the device."""
-    KEY = ("L", "G", "K")
     adversary = property(lambda self: self.source)
 
-    @staticmethod
-    def tables(plan):
-        return dict(level_of=plan.level_of, levels=plan.words), (plan.L, plan.G, plan.K)
 
-
-class AdversarialSeatSampler(SeatSampler):
+class AdversarialSeatSampler(LevelSeatSampler):
     """`SeatSampler` under attack: per env step `perturb_seats` on the true observation, the seated forward on `obs_seen[t]`, the
     simulator step, the seat tally -- the whole fragment is still one captured graph.  The batch's `obs` stays the TRUE observation;
     `obs_seen` [T][E][N][O] (also `batch["obs_seen"]`, zero-initialised: rows of seats that nobody drives are never written) is what
     the policy was given.  Cells of a `sweep` plan share their action noise, as in `FaultySeatSampler`."""
-
-    def __init__(self, vec_env, policy, bank, plan, adversary, T, use_graph=True):
-        import torch
-        adversary.check(plan)
-        super().__init__(vec_env, policy, bank, plan, T, use_graph=use_graph)
-        self.col_lo, self.col_hi = lidar_columns(self.sim.cfg)
-        if not 0 <= self.col_lo <= self.col_hi <= self.O:
-            raise ValueError("AdversarialSeatSampler: LiDAR columns [%d, %d) of an observation of %d" % (self.col_lo, self.col_hi, self.O))
-        self.adv_buffers = AdversaryBuffers(adversary, self.device)
-        self.adv_buffers.on_replace.append(self._loop.reset)
-        self.obs_seen = torch.zeros(self.T, self.E, self.N, self.O, dtype=torch.float32, device=self.device)
-
-    @property
-    def adversary(self):
-        return self.adv_buffers.adversary
-
-    def set_adversary(self, adversary):
-        """Another adversary plan, OUTSIDE captured graphs: the same shapes (levels, groups, members) are copied into the tables the
-        captured fragment reads, other shapes allocate new ones and drop the graph."""
-        self.adv_buffers.replace(adversary.check(self.seated.plan))
-
-    def _draw_noise(self):
-        draw_cell_noise(self.eps, self.adversary.scenes_per_cell)
-
-    def sample(self):
-        batch = super().sample()
-        batch["obs_seen"] = self.obs_seen
-        return batch
+    BUFFERS = AdversaryBuffers
+    adv_buffers = property(lambda self: self.level_buffers)
+    adversary = property(lambda self: self.level_plan)
+    set_adversary = LevelSeatSampler.set_levels
 
     def _policy_obs(self, t):
         self.seated.perturb_seats(self.adv_buffers, self.obs[t].view(-1, self.O), self.obs_seen[t].view(-1, self.O), self.col_lo, self.col_hi)
@@ -153,32 +90,16 @@ def adversary_sweep_rows(algo, env, weights_list, levels, share=1.0, scenes_per_
     (rounded up to whole fragments).  The first round(share * num_agents) slots of a scene are attacked at the cell's level, the rest
     are unattacked drivers of the same checkpoint (`AdversaryPlan.sweep`).  Returns a pandas frame, one row per (checkpoint, level,
     role), with the columns of `fault_sweep_rows` and the level's three parameters in the place of the fault level's five."""
-    from .bank import PolicyBank
-    from .evaluate import check_labels, eval_session, graph_flag, run_steps
-    weights_list = list(weights_list)
-    K = len(weights_list)
-    if K < 1:
-        raise ValueError("adversary_sweep_rows: no members")
-    levels = _levels(levels)
-    if not levels or not levels[0].is_identity:
-        raise ValueError("adversary_sweep_rows: level 0 must be an identity (eps 0 or no direction), the table's own baseline")
-    labels = check_labels(labels, K)
-    seats, adversary = AdversaryPlan.sweep(K, levels, scenes_per_cell, num_agents, share)
-    with eval_session(algo, env, seats.E, num_agents, seed, **extra) as t:
-        bank = PolicyBank(t.policy, sweep_members(weights_list, adversary))
-        smp = AdversarialSeatSampler(t.env, t.policy, bank, seats, adversary, t.sampler.T, use_graph=graph_flag(t))
-        tally = run_steps(smp, steps).tally.cpu().numpy()
-    return sweep_frame(tally, seats, adversary, labels)
+    return run_sweep("adversary_sweep_rows", AdversaryPlan, algo, env, weights_list,
+                     lambda: baseline_levels("adversary_sweep_rows", AdversaryPlan, levels, "an identity (eps 0 or no direction)"),
+                     lambda t, bank, seats, adversary, use_graph: AdversarialSeatSampler(t.env, t.policy, bank, seats, adversary, t.sampler.T,
+                                                                                         use_graph=use_graph),
+                     role_frame, labels=labels, scenes_per_cell=scenes_per_cell, num_agents=num_agents, steps=steps, seed=seed, extra=extra, share=share)
 
 
 def load_levels(path):
     """A JSON list of objects with `AdversaryLevel`'s fields (missing fields are 0) -> [AdversaryLevel]."""
-    import json
-    with open(path) as f:
-        raw = json.load(f)
-    if not isinstance(raw, list) or not all(isinstance(r, dict) for r in raw):
-        raise ValueError("%s: a JSON list of objects wanted" % path)
-    return [AdversaryLevel(**r) for r in raw]
+    return _levels.load_levels(path, AdversaryLevel)
 
 
 def beam_saliency(bank, plan_buffers, obs, steer, throttle):

@@ -11,8 +11,10 @@ One bank is one layout: members of other observation widths or algorithms belong
 
 The samplers of `eval/` keep no rollout loop of their own.  `VecSampler._rollout` is the one loop, `for t: _act(t); _step(t)`, with three
 hooks: `_policy_obs(t)` (what the policy reads), `_act(t)` (the forward) and `_step(t)` (the simulator step).  `BankSampler` overrides
-none of them: `_BankPolicy` puts the bank where `_act` looks for the fused learner.  Two helpers that every sampler here shares also live
-in this module: `replica_seeds` (replicas of S scenes see the same scenes) and `DeviceTables` (tables that a captured graph reads).
+none of them: `_BankPolicy` puts the bank where `_act` looks for the fused learner.  Helpers that every sampler here shares also live
+in this module: `replica_seeds` (replicas of S scenes see the same scenes), `DeviceTables` (tables that a captured graph reads) and
+`draw_cell_noise`; what the samplers of the LiDAR studies share on top of `crossplay.SeatSampler` is `levels.LevelSeatSampler`.  The
+bank's three seat passes (`perturb_seats`, `pgd_seats`, `certify_seats`) go through one checked launch, `_seat_pass`.
 """
 import ctypes as C
 
@@ -108,23 +110,31 @@ class PolicyBank:
             pb.cap, pb.n_out, obs.data_ptr(), dist_inputs.data_ptr(), eps.data_ptr(), action.data_ptr(), logp.data_ptr(),
             None if clipped is None else clipped.data_ptr(), self._capi.current_stream()))
 
+    def _seat_pass(self, who, entry, pb, lb, tensors, col_lo, col_hi, middle, extra=(), dtype_text=lambda dtype: str(dtype).replace("torch.", "")):
+        """One launch of a seat pass on the current stream (csrc/learn_fused.hip, seat_pass_launch): `entry`(the bank, the plan's row
+        lists, obs, *middle, the columns, the plan's groups, the level tables of `lb`, *extra, stream).  `tensors`: rows (name, tensor or
+        None, shape, dtype), `obs` first, every tensor given must be contiguous of that shape and dtype; `who` opens the messages, `dtype_text`
+        is how they name the dtype that was wanted."""
+        if pb.K != self.K or (lb.G, lb.K) != (pb.G, pb.K):
+            raise ValueError("%s: a bank of %d, a plan of %d groups x %d members, levels for %d x %d" % (who, self.K, pb.G, pb.K, lb.G, lb.K))
+        for name, t, shape, dtype in tensors:
+            if t is not None and (tuple(t.shape) != tuple(shape) or not t.is_contiguous() or t.dtype != dtype):
+                raise ValueError("%s: %s of shape %s, contiguous %s %s wanted" % (
+                    who, name, tuple(t.shape), dtype_text(dtype), list(shape)))
+        self._capi.check(getattr(self._capi.lib, entry)(
+            C.byref(self.cfg), self.theta.data_ptr(), self.theta_t.data_ptr(), self.stride, self.K, pb.rows.data_ptr(), pb.counts.data_ptr(),
+            pb.cap, pb.n_out, tensors[0][1].data_ptr(), *(None if t is None else t.data_ptr() for t in middle), int(col_lo), int(col_hi), pb.N,
+            pb.group.data_ptr(), pb.G, lb.level_of.data_ptr(), lb.levels.data_ptr(), lb.L, *extra, self._capi.current_stream()))
+
     def perturb_seats(self, plan_buffers, adv_buffers, obs, obs_seen, col_lo, col_hi, grad=None):
         """`copo_adv_obs_seats_f32` (eval/adversary.py) on the current stream: obs [n_out, O] -> obs_seen, one gradient-sign step on
         the columns [col_lo, col_hi) of every seated row against the member that drives it, at the level `adv_buffers`
         (`adversary.AdversaryBuffers`) gives (scene group, member); `grad` [n_out, O]: the raw gradient, if wanted.  Needs the mirror
         (`sync_mirror`), as `act_seats`."""
-        pb, ab = plan_buffers, adv_buffers
-        if pb.K != self.K or (ab.G, ab.K) != (pb.G, pb.K):
-            raise ValueError("PolicyBank.perturb_seats: a bank of %d, a plan of %d groups x %d members, levels for %d x %d" % (
-                self.K, pb.G, pb.K, ab.G, ab.K))
-        for name, t in (("obs", obs), ("obs_seen", obs_seen), ("grad", grad)):
-            if t is not None and (tuple(t.shape) != (pb.n_out, int(self.cfg.pol.in_dim)) or not t.is_contiguous() or t.dtype != torch.float32):
-                raise ValueError("PolicyBank.perturb_seats: %s of shape %s, contiguous float32 [%d, %d] wanted" % (
-                    name, tuple(t.shape), pb.n_out, int(self.cfg.pol.in_dim)))
-        self._capi.check(self._capi.lib.copo_adv_obs_seats_f32(
-            C.byref(self.cfg), self.theta.data_ptr(), self.theta_t.data_ptr(), self.stride, self.K, pb.rows.data_ptr(), pb.counts.data_ptr(),
-            pb.cap, pb.n_out, obs.data_ptr(), obs_seen.data_ptr(), None if grad is None else grad.data_ptr(), int(col_lo), int(col_hi), pb.N,
-            pb.group.data_ptr(), pb.G, ab.level_of.data_ptr(), ab.levels.data_ptr(), ab.L, self._capi.current_stream()))
+        row = (plan_buffers.n_out, int(self.cfg.pol.in_dim))
+        self._seat_pass("PolicyBank.perturb_seats", "copo_adv_obs_seats_f32", plan_buffers, adv_buffers,
+                        [(name, t, row, torch.float32) for name, t in (("obs", obs), ("obs_seen", obs_seen), ("grad", grad))], col_lo, col_hi,
+                        (obs_seen, grad))
 
     def pgd_seats(self, plan_buffers, pgd_buffers, obs, obs_seen, col_lo, col_hi, seed=0, tick=None, trace=None, max_iters=None):
         """`copo_pgd_obs_seats_f32` (eval/pgd.py) on the current stream: obs [n_out, O] -> obs_seen, the iterated attack on the columns
@@ -132,22 +142,12 @@ class PolicyBank:
         (scene group, member).  `tick` int32 [n_out]: the launch counter of the random starts, advanced by the kernel (None: 0);
         `trace` [max_iters, n_out, O]: the gradient of every iteration, if wanted; `max_iters` defaults to the plan's.  Needs the
         mirror (`sync_mirror`), as `act_seats`."""
-        pb, gb = plan_buffers, pgd_buffers
-        max_iters = int(gb.max_iters if max_iters is None else max_iters)
-        if pb.K != self.K or (gb.G, gb.K) != (pb.G, pb.K):
-            raise ValueError("PolicyBank.pgd_seats: a bank of %d, a plan of %d groups x %d members, levels for %d x %d" % (
-                self.K, pb.G, pb.K, gb.G, gb.K))
-        O = int(self.cfg.pol.in_dim)
-        for name, t, shape, dtype in (("obs", obs, (pb.n_out, O), torch.float32), ("obs_seen", obs_seen, (pb.n_out, O), torch.float32),
-                                      ("trace", trace, (max_iters, pb.n_out, O), torch.float32), ("tick", tick, (pb.n_out,), torch.int32)):
-            if t is not None and (tuple(t.shape) != shape or not t.is_contiguous() or t.dtype != dtype):
-                raise ValueError("PolicyBank.pgd_seats: %s of shape %s, contiguous %s %s wanted" % (name, tuple(t.shape), dtype, list(shape)))
-        self._capi.check(self._capi.lib.copo_pgd_obs_seats_f32(
-            C.byref(self.cfg), self.theta.data_ptr(), self.theta_t.data_ptr(), self.stride, self.K, pb.rows.data_ptr(), pb.counts.data_ptr(),
-            pb.cap, pb.n_out, obs.data_ptr(), obs_seen.data_ptr(), int(col_lo), int(col_hi), pb.N, pb.group.data_ptr(), pb.G,
-            gb.level_of.data_ptr(), gb.levels.data_ptr(), gb.L, int(seed) & (2 ** 64 - 1), None if tick is None else tick.data_ptr(), max_iters,
-            None if trace is None else trace.data_ptr(), self._capi.current_stream()))
-
+        max_iters = int(pgd_buffers.max_iters if max_iters is None else max_iters)
+        row = (plan_buffers.n_out, int(self.cfg.pol.in_dim))
+        self._seat_pass("PolicyBank.pgd_seats", "copo_pgd_obs_seats_f32", plan_buffers, pgd_buffers,
+                        (("obs", obs, row, torch.float32), ("obs_seen", obs_seen, row, torch.float32),
+                         ("trace", trace, (max_iters,) + row, torch.float32), ("tick", tick, row[:1], torch.int32)), col_lo, col_hi, (obs_seen,),
+                        (int(seed) & (2 ** 64 - 1), None if tick is None else tick.data_ptr(), max_iters, None if trace is None else trace.data_ptr()), dtype_text=str)
 
     def certify_seats(self, plan_buffers, cert_buffers, obs, bounds, col_lo, col_hi, pad=0.0, method="interval", parts=None):
         """`copo_cert_obs_seats_f32` (eval/certify.py) on the current stream: obs [n_out, O] -> bounds [n_out, 8], the interval bounds
@@ -156,24 +156,13 @@ class PolicyBank:
         perturbed.  Needs the mirror (`sync_mirror`), as `act_seats`.  `method="linear"`: `copo_lin_obs_seats_f32` instead, the linear
         bounds intersected with the interval box into the same `bounds` layout; `parts` [n_out, 8] (linear only): both boxes before
         the pad, if wanted."""
-        pb, cb = plan_buffers, cert_buffers
         check_certify_method("PolicyBank.certify_seats", method)
         if parts is not None and method != "linear":
             raise ValueError("PolicyBank.certify_seats: `parts` is an output of method=\"linear\" only")
-        if pb.K != self.K or (cb.G, cb.K) != (pb.G, pb.K):
-            raise ValueError("PolicyBank.certify_seats: a bank of %d, a plan of %d groups x %d members, levels for %d x %d" % (
-                self.K, pb.G, pb.K, cb.G, cb.K))
-        for name, t, shape in (("obs", obs, (pb.n_out, int(self.cfg.pol.in_dim))), ("bounds", bounds, (pb.n_out, 8)), ("parts", parts, (pb.n_out, 8))):
-            if t is not None and (tuple(t.shape) != shape or not t.is_contiguous() or t.dtype != torch.float32):
-                raise ValueError("PolicyBank.certify_seats: %s of shape %s, contiguous float32 %s wanted" % (name, tuple(t.shape), list(shape)))
-        head = (C.byref(self.cfg), self.theta.data_ptr(), self.theta_t.data_ptr(), self.stride, self.K, pb.rows.data_ptr(), pb.counts.data_ptr(),
-                pb.cap, pb.n_out, obs.data_ptr(), bounds.data_ptr())
-        tail = (int(col_lo), int(col_hi), pb.N, pb.group.data_ptr(), pb.G, cb.level_of.data_ptr(), cb.levels.data_ptr(), cb.L, float(pad),
-                self._capi.current_stream())
-        if method == "linear":
-            self._capi.check(self._capi.lib.copo_lin_obs_seats_f32(*head, None if parts is None else parts.data_ptr(), *tail))
-        else:
-            self._capi.check(self._capi.lib.copo_cert_obs_seats_f32(*head, *tail))
+        n_out, linear = plan_buffers.n_out, method == "linear"
+        self._seat_pass("PolicyBank.certify_seats", "copo_lin_obs_seats_f32" if linear else "copo_cert_obs_seats_f32", plan_buffers, cert_buffers,
+                        (("obs", obs, (n_out, int(self.cfg.pol.in_dim)), torch.float32), ("bounds", bounds, (n_out, 8), torch.float32),
+                         ("parts", parts, (n_out, 8), torch.float32)), col_lo, col_hi, (bounds, parts) if linear else (bounds,), (float(pad),))
 
 
 class _BankPolicy:

@@ -42,17 +42,18 @@ An L-infinity budget, the LiDAR block, fp32 operands.  Backward bounds for layer
 slopes, chord / tangent relaxations, zonotopes, branch and bound, the ego / navigation columns, other norms, the bfloat16 operand mode
 and bounds on the sampled or clipped action are out of scope.
 
-Pieces: `CertifyLevel` / `CertifyPlan` (numpy only), `CertifyBuffers`, `certify_tally`, `CertifySeatSampler` (the `SeatSampler` whose
+Pieces, each on its base in `levels.py`: `CertifyLevel` / `CertifyPlan` (numpy only), `CertifyBuffers`, `CertifySeatSampler` (whose
 `_policy_obs` launches the kernel inside the captured fragment), `certify_sweep_rows` (checkpoints x levels as a pandas frame; `evaluate
---certify-sweep`), `load_levels` and `certified_bounds`.
+--certify-sweep`) and `load_levels`; its own: `certify_tally`, `certify_frame` and `certified_bounds`.
 """
 from dataclasses import dataclass
 
 import numpy as np
 
-from .bank import CERTIFY_METHODS, DeviceTables, check_certify_method, draw_cell_noise
-from .crossplay import SEAT_WORDS, SeatSampler, tally_rates
-from .faults import lidar_columns, sweep_plan
+from . import levels as _levels
+from .bank import check_certify_method
+from .crossplay import SEAT_WORDS, tally_rates
+from .levels import LevelBuffers, LevelPlan, LevelSeatSampler, finite_fields, run_sweep
 
 LEVEL_WORDS = 4
 LEVEL_FIELDS = ("eps", "delta_steer", "delta_throttle")
@@ -71,13 +72,10 @@ class CertifyLevel:
     delta_throttle: float = 0.0
 
     def __post_init__(self):
+        finite_fields(self, LEVEL_FIELDS)
         for name in LEVEL_FIELDS:
-            v = getattr(self, name)
-            if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v):
-                raise ValueError("CertifyLevel: %s = %r, a finite number wanted" % (name, v))
-            if v < 0:
-                raise ValueError("CertifyLevel: %s = %r is negative" % (name, v))
-            object.__setattr__(self, name, float(v))
+            if getattr(self, name) < 0:
+                raise ValueError("CertifyLevel: %s = %r is negative" % (name, getattr(self, name)))
 
     def words(self):
         """The level as the four floats the kernels read: eps, delta_steer, delta_throttle, 0."""
@@ -87,48 +85,21 @@ class CertifyLevel:
         return {name: getattr(self, name) for name in LEVEL_FIELDS}
 
 
-def _levels(levels):
-    return [lv if isinstance(lv, CertifyLevel) else CertifyLevel(**lv) for lv in levels]
-
-
-class CertifyPlan:
-    """`levels`: a sequence of `CertifyLevel` (or dicts of its fields); `level_of`: int [G][K], the level of bank member k in scene
-    group g (an index outside [0, L): the member's rows there are not certified, `valid` = 0).  Derived: `words` float32 [L][4].
-    Nothing here touches a device."""
-
-    def __init__(self, levels, level_of):
-        self.levels = _levels(levels)
-        if not self.levels:
-            raise ValueError("CertifyPlan: no levels")
-        self.level_of = np.ascontiguousarray(level_of, np.int32)
-        if self.level_of.ndim != 2 or self.level_of.shape[0] < 1 or self.level_of.shape[1] < 1:
-            raise ValueError("CertifyPlan: level_of of shape %s, [groups][members] wanted" % (self.level_of.shape,))
-        self.L, (self.G, self.K) = len(self.levels), self.level_of.shape
-        self.words = np.stack([lv.words() for lv in self.levels])
-        self.checkpoint = self.level = None
-        self.share = self.scenes_per_cell = None          # (`sweep` sets them: cells of that many scenes share their action noise)
-
-    def check(self, seat_plan):
-        if (seat_plan.n_groups, seat_plan.K) != (self.G, self.K):
-            raise ValueError("CertifyPlan: level_of is %d groups x %d members, the seat plan has %d x %d" % (
-                self.G, self.K, seat_plan.n_groups, seat_plan.K))
-        return self
+class CertifyPlan(LevelPlan):
+    """`LevelPlan` of `CertifyLevel`s; `words` float32 [L][4].  A `level_of` index outside [0, L): the member's rows there are not
+    certified, `valid` = 0."""
+    LEVEL = CertifyLevel
 
     @classmethod
     def sweep(cls, K, levels, scenes_per_cell, N):
-        """(seat plan, certify plan) of K checkpoints x L levels on the cell layout of `AdversaryPlan.sweep` (`SeatPlan.cells`) at share
-        1: every slot of cell (k, l) is member k, certified at level l.  There are no roles: nobody is impaired."""
-        return sweep_plan(cls, "CertifyPlan.sweep", K, _levels(levels), scenes_per_cell, N, 1.0)
+        """(seat plan, certify plan) of K checkpoints x L levels on the cell layout of `LevelPlan.sweep` at share 1: every slot of cell
+        (k, l) is member k, certified at level l.  There are no roles: nobody is impaired."""
+        return super().sweep(K, levels, scenes_per_cell, N, 1.0)
 
 
-class CertifyBuffers(DeviceTables):
+class CertifyBuffers(LevelBuffers):
     """A certify plan's tables on the device."""
-    KEY = ("L", "G", "K")
     certify = property(lambda self: self.source)
-
-    @staticmethod
-    def tables(plan):
-        return dict(level_of=plan.level_of, levels=plan.words), (plan.L, plan.G, plan.K)
 
 
 def certify_tally(flags, bounds, plan_buffers, cert_buffers, out):
@@ -143,7 +114,7 @@ def certify_tally(flags, bounds, plan_buffers, cert_buffers, out):
                                              cb.levels.data_ptr(), pb.E, pb.N, pb.K, pb.G, cb.L, out.data_ptr(), _capi.current_stream()))
 
 
-class CertifySeatSampler(SeatSampler):
+class CertifySeatSampler(LevelSeatSampler):
     """`SeatSampler` with certificates: per env step `certify_seats` on the true observation into `bounds[t]`, the seated forward on the
     SAME true observation, the simulator step, the seat tally and the certify tally -- the whole fragment is still one captured graph.
     Actions, flags and the seat tally are a plain `SeatSampler`'s.  `bounds` [T][E][N][8] (also `batch["bounds"]`, zero-initialised: rows
@@ -151,37 +122,25 @@ class CertifySeatSampler(SeatSampler):
     `clear_tally()`.  Cells of a `sweep` plan share their action noise, as in `AdversarialSeatSampler`.  `method`: "interval" or "linear"
     (the module docstring); the launch is the only difference, the fold and everything else are the same."""
 
+    BUFFERS = CertifyBuffers
+    SEEN = False          # (nothing is perturbed: the policy reads the true observation)
+    cert_buffers = property(lambda self: self.level_buffers)
+    certify = property(lambda self: self.level_plan)
+    set_certify = LevelSeatSampler.set_levels
+
     def __init__(self, vec_env, policy, bank, plan, certify, T, use_graph=True, pad=0.0, method="interval"):
         import torch
         self.method = check_certify_method("CertifySeatSampler", method)
-        certify.check(plan)
-        super().__init__(vec_env, policy, bank, plan, T, use_graph=use_graph)
+        super().__init__(vec_env, policy, bank, plan, certify, T, use_graph=use_graph)
         self.pad = float(pad)
         if not (self.pad >= 0.0 and np.isfinite(self.pad)):
             raise ValueError("CertifySeatSampler: pad = %r, a finite number >= 0 wanted" % (pad,))
-        self.col_lo, self.col_hi = lidar_columns(self.sim.cfg)
-        if not 0 <= self.col_lo <= self.col_hi <= self.O:
-            raise ValueError("CertifySeatSampler: LiDAR columns [%d, %d) of an observation of %d" % (self.col_lo, self.col_hi, self.O))
-        self.cert_buffers = CertifyBuffers(certify, self.device)
-        self.cert_buffers.on_replace.append(self._loop.reset)
         self.bounds = torch.zeros(self.T, self.E, self.N, len(BOUND_WORDS), dtype=torch.float32, device=self.device)
         self.cert_tally = torch.zeros(plan.n_groups, bank.K, len(CERT_WORDS), dtype=torch.int64, device=self.device)
-
-    @property
-    def certify(self):
-        return self.cert_buffers.certify
-
-    def set_certify(self, certify):
-        """Another certify plan, OUTSIDE captured graphs: the same shapes (levels, groups, members) are copied into the tables the
-        captured fragment reads, other shapes allocate new ones and drop the graph."""
-        self.cert_buffers.replace(certify.check(self.seated.plan))
 
     def clear_tally(self):
         super().clear_tally()
         self.cert_tally.zero_()
-
-    def _draw_noise(self):
-        draw_cell_noise(self.eps, self.certify.scenes_per_cell)
 
     def sample(self):
         batch = super().sample()
@@ -234,39 +193,30 @@ def certify_sweep_rows(algo, env, weights_list, levels, scenes_per_cell=4, num_a
     `mean_width_steer`, `mean_width_throttle`, `max_dev`, then the eight raw words of the seat tally and its rates as in
     `cross_play_rows`.  Joined with `pgd_sweep_rows` on (checkpoint, eps) it brackets the worst case (see the module docstring).
     `method="linear"`: the tighter bounds, and a `method` column behind `level` (an interval frame keeps today's columns)."""
-    from .bank import PolicyBank
     check_certify_method("certify_sweep_rows", method)
-    from .evaluate import check_labels, eval_session, graph_flag, run_steps
-    weights_list = list(weights_list)
-    K = len(weights_list)
-    if K < 1:
-        raise ValueError("certify_sweep_rows: no members")
-    levels = _levels(levels)
-    if not levels:
-        raise ValueError("certify_sweep_rows: no levels")
-    labels = check_labels(labels, K)
-    seats, certify = CertifyPlan.sweep(K, levels, scenes_per_cell, num_agents)
-    with eval_session(algo, env, seats.E, num_agents, seed, **extra) as t:
-        smp = CertifySeatSampler(t.env, t.policy, PolicyBank(t.policy, weights_list), seats, certify, t.sampler.T, use_graph=graph_flag(t), pad=pad,
-                                 method=method)
-        run_steps(smp, steps)
-        cert, tally = smp.cert_tally.cpu().numpy(), smp.tally.cpu().numpy()
-    return certify_frame(cert, tally, seats, certify, labels, None if method == "interval" else method)
+    def some_levels():          # (no level-0 rule: nobody is impaired, so there is no baseline to carry)
+        checked = CertifyPlan.as_levels(levels)
+        if not checked:
+            raise ValueError("certify_sweep_rows: no levels")
+        return checked
+
+    def frame(smp, seats, certify, labels):
+        return certify_frame(smp.cert_tally.cpu().numpy(), smp.tally.cpu().numpy(), seats, certify, labels, None if method == "interval" else method)
+
+    return run_sweep("certify_sweep_rows", CertifyPlan, algo, env, weights_list, some_levels,
+                     lambda t, bank, seats, certify, use_graph: CertifySeatSampler(t.env, t.policy, bank, seats, certify, t.sampler.T,
+                                                                                   use_graph=use_graph, pad=pad, method=method),
+                     frame, labels=labels, scenes_per_cell=scenes_per_cell, num_agents=num_agents, steps=steps, seed=seed, extra=extra)
 
 
 def load_levels(path):
     """A JSON list of objects with `CertifyLevel`'s fields (missing fields are 0) -> [CertifyLevel]."""
-    import json
-    with open(path) as f:
-        raw = json.load(f)
-    if not isinstance(raw, list) or not all(isinstance(r, dict) for r in raw):
-        raise ValueError("%s: a JSON list of objects wanted" % path)
-    return [CertifyLevel(**r) for r in raw]
+    return _levels.load_levels(path, CertifyLevel)
 
 
 def certified_bounds(bank, plan_buffers, obs, eps, pad=0.0, *, columns, method="interval", parts=False):
     """`bounds` [n_out][8] (`BOUND_WORDS`) of every seated row of obs [n_out][O] at one budget `eps` for every (group, member): one
-    launch, like `adversary.beam_saliency`.  `columns` = (col_lo, col_hi), the LiDAR block (`faults.lidar_columns(sim.cfg)`): unlike the
+    launch, like `adversary.beam_saliency`.  `columns` = (col_lo, col_hi), the LiDAR block (`levels.lidar_columns(sim.cfg)`): unlike the
     saliency, the box needs to know where the beams are.  Rows in no list hold zeros (`valid` = 0).  `method="linear"`: the tighter
     bounds; with `parts=True` (linear only) returns (bounds, parts), parts [n_out][8] (`PART_WORDS`): the linear and the interval box
     before the intersection and the pad."""

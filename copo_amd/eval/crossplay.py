@@ -171,7 +171,6 @@ class SeatedBank:
         """`PolicyBank.pgd_seats` over the plan's own buffers (eval/pgd.py)."""
         self.bank.pgd_seats(self.buffers, pgd_buffers, obs, obs_seen, col_lo, col_hi, seed, tick, trace, max_iters)
 
-
     def certify_seats(self, cert_buffers, obs, bounds, col_lo, col_hi, pad=0.0, method="interval", parts=None):
         """`PolicyBank.certify_seats` over the plan's own buffers (eval/certify.py)."""
         self.bank.certify_seats(self.buffers, cert_buffers, obs, bounds, col_lo, col_hi, pad, method, parts)

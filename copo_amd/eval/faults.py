@@ -14,17 +14,18 @@ its steps are cut into fragments or on whether they are replayed from a graph.  
 four 16-bit uniform halves of two hashes: mean 0, variance 1, and its tails END at +-3.46 (|z| <= 131070 sqrt(3) / 65536): a level of
 `lidar_sigma` s never moves a beam by more than 3.47 s.
 
-Three pieces: `FaultLevel` / `FaultPlan` (numpy only), `FaultySeatSampler` (the `SeatSampler` with the two launches inside its captured
-fragment: it keeps no loop, `_policy_obs` launches `copo_fault_obs` in front of the forward of `VecSampler._act` and `_step` launches
-`copo_fault_act` in front of the step and its tally) and `fault_sweep_rows` (checkpoints x levels x roles as a pandas frame; `evaluate
---fault-sweep`).
+Pieces, each on its base in `levels.py` (plan, buffers, sampler and sweep session shared with `adversary.py`, `pgd.py` and `certify.py`):
+`FaultLevel` / `FaultPlan` (numpy only), `FaultBuffers`, `FaultySeatSampler` (the two launches inside its captured fragment: it keeps no
+loop, `_policy_obs` launches `copo_fault_obs` in front of the forward of `VecSampler._act` and `_step` launches `copo_fault_act` in front
+of the step and its tally) and `fault_sweep_rows` (checkpoints x levels x roles as a pandas frame; `evaluate --fault-sweep`).
 """
 from dataclasses import dataclass
 
 import numpy as np
 
-from .bank import DeviceTables, draw_cell_noise
-from .crossplay import SEAT_WORDS, SeatPlan, SeatSampler, tally_rates
+from . import levels as _levels
+from .levels import LevelBuffers, LevelPlan, LevelSeatSampler, baseline_levels, finite_fields, role_frame, run_sweep
+from .levels import lidar_columns, sweep_frame, sweep_members, sweep_plan  # noqa: F401  (they lived here first: importable from here as before)
 
 LEVEL_WORDS = 8
 LEVEL_FIELDS = ("lidar_sigma", "lidar_dropout", "dropout_value", "act_sigma", "sticky")
@@ -44,11 +45,7 @@ class FaultLevel:
     sticky: float = 0.0
 
     def __post_init__(self):
-        for name in LEVEL_FIELDS:
-            v = getattr(self, name)
-            if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v):
-                raise ValueError("FaultLevel: %s = %r, a finite number wanted" % (name, v))
-            object.__setattr__(self, name, float(v))
+        finite_fields(self, LEVEL_FIELDS)
         for name in ("lidar_sigma", "act_sigma"):
             if getattr(self, name) < 0.0:
                 raise ValueError("FaultLevel: %s = %r is negative" % (name, getattr(self, name)))
@@ -71,65 +68,13 @@ class FaultLevel:
         return {name: getattr(self, name) for name in LEVEL_FIELDS}
 
 
-class FaultPlan:
-    """`levels`: a sequence of `FaultLevel` (or dicts of its fields); `level_of`: int [G][K], the level of bank member k in scene group g
-    (an index outside [0, L) leaves the member's rows alone).  Derived: `words` uint32 [L][8].  Nothing here touches a device."""
-
-    def __init__(self, levels, level_of):
-        self.levels = [lv if isinstance(lv, FaultLevel) else FaultLevel(**lv) for lv in levels]
-        if not self.levels:
-            raise ValueError("FaultPlan: no levels")
-        self.level_of = np.ascontiguousarray(level_of, np.int32)
-        if self.level_of.ndim != 2 or self.level_of.shape[0] < 1 or self.level_of.shape[1] < 1:
-            raise ValueError("FaultPlan: level_of of shape %s, [groups][members] wanted" % (self.level_of.shape,))
-        self.L, (self.G, self.K) = len(self.levels), self.level_of.shape
-        self.words = np.stack([lv.words() for lv in self.levels])
-        self.checkpoint = self.level = None
-        self.share = self.scenes_per_cell = None          # (`sweep` sets them: cells of that many scenes share their action noise)
-
-    def check(self, seat_plan):
-        if (seat_plan.n_groups, seat_plan.K) != (self.G, self.K):
-            raise ValueError("FaultPlan: level_of is %d groups x %d members, the seat plan has %d x %d" % (
-                self.G, self.K, seat_plan.n_groups, seat_plan.K))
-        return self
-
-    @classmethod
-    def sweep(cls, K, levels, scenes_per_cell, N, share=1.0):
-        """(seat plan, fault plan) of K checkpoints x L levels: one scene group per cell, group k * L + l = scenes [g S, (g + 1) S), S =
-        `scenes_per_cell`.  share == 1: every slot of the cell is member k at level l, a bank of K members.  share < 1: the bank holds
-        every checkpoint TWICE, members k and K + k with the same weights (`sweep_members`); the first round(share * N) slots are member
-        K + k at level l, the rest member k at level 0, which must then be the identity: the tally keeps the impaired and the healthy
-        drivers of a scene apart.  The seat plan declares `replica_scenes` = S, so `SeatSampler.reset` gives every cell the same scenes."""
-        levels = [lv if isinstance(lv, FaultLevel) else FaultLevel(**lv) for lv in levels]
-        return sweep_plan(cls, "FaultPlan.sweep", K, levels, scenes_per_cell, N, share)
+class FaultPlan(LevelPlan):
+    """`LevelPlan` of `FaultLevel`s; `words` uint32 [L][8]."""
+    LEVEL = FaultLevel
 
 
-def sweep_plan(cls, who, K, levels, scenes_per_cell, N, share):
-    """(seat plan, `cls(levels, level_of)`) on the cell layout of `SeatPlan.cells`, the layout's attributes on the level plan: what
-    `FaultPlan.sweep` and `AdversaryPlan.sweep` share.  With share < 1 the healthy seats drive at level 0, which must be the identity."""
-    seats, level_of, attrs = SeatPlan.cells(K, len(levels), scenes_per_cell, N, share, who)
-    if attrs["doubled"] and not levels[0].is_identity:
-        raise ValueError("%s: with share < 1 the healthy seats drive at level 0, which must be the identity" % who)
-    plan = cls(levels, level_of)
-    vars(plan).update(attrs)
-    return seats, plan
-
-
-def sweep_members(weights_list, faults):
-    """The bank of a `sweep` plan: the checkpoints, twice where the plan doubles them."""
-    weights_list = list(weights_list)
-    return weights_list + weights_list if faults.doubled else weights_list
-
-
-def lidar_columns(cfg):
-    """[col_lo, col_hi) of the LiDAR block in the observation row of a `SimConfig`."""
-    lo = int(cfg.ego_dim) + int(cfg.navi_dim)
-    return lo, lo + int(cfg.num_lasers)
-
-
-class FaultBuffers(DeviceTables):
+class FaultBuffers(LevelBuffers):
     """A fault plan's tables on the device."""
-    KEY = ("L", "G", "K")
     faults = property(lambda self: self.source)
 
     @staticmethod
@@ -159,7 +104,7 @@ def fault_act(act, prev, flags_prev, plan_buffers, fault_buffers, tick, fault_se
                   fault_buffers, tick, fault_seed)
 
 
-class FaultySeatSampler(SeatSampler):
+class FaultySeatSampler(LevelSeatSampler):
     """`SeatSampler` with faults: per env step fault_obs, the seated forward on `obs_seen[t]`, fault_act on `clipped[t]`, the simulator
     step, the seat tally -- the whole fragment is still one captured graph.  The batch's `obs` stays the TRUE observation, so recorders
     and observers are unaffected; `obs_seen` [T][E][N][O] (also `batch["obs_seen"]`) is what the policy was given.  `actions` and `logp`
@@ -168,47 +113,26 @@ class FaultySeatSampler(SeatSampler):
     State: `prev` [E][N][2] (the action that reached the simulator a step ago), `tick` int32 [E N] (steps since `reset`, the draws'
     counter).  The previous step's flags are `flags[t - 1]`; for t = 0 they are `flags[T - 1]`, which still holds the last step of the
     previous fragment.  `reset` zeroes `tick`, `prev` and `flags[T - 1]`: flags of zero say that nobody acted, so nothing sticks in the
-    first step, as if no flags were given."""
+    first step, as if no flags were given.  (The fault draws themselves are keyed by the absolute row, so two impaired cells of a `sweep`
+    plan never share those, as they share their action noise.)"""
+
+    BUFFERS = FaultBuffers
+    fault_buffers = property(lambda self: self.level_buffers)
+    faults = property(lambda self: self.level_plan)
+    set_faults = LevelSeatSampler.set_levels
 
     def __init__(self, vec_env, policy, bank, plan, faults, T, use_graph=True, fault_seed=0):
         import torch
-        faults.check(plan)
-        super().__init__(vec_env, policy, bank, plan, T, use_graph=use_graph)
+        super().__init__(vec_env, policy, bank, plan, faults, T, use_graph=use_graph)
         self.fault_seed = int(fault_seed) & (2 ** 64 - 1)
-        self.col_lo, self.col_hi = lidar_columns(self.sim.cfg)
-        if not 0 <= self.col_lo <= self.col_hi <= self.O:
-            raise ValueError("FaultySeatSampler: LiDAR columns [%d, %d) of an observation of %d" % (self.col_lo, self.col_hi, self.O))
-        self.fault_buffers = FaultBuffers(faults, self.device)
-        self.fault_buffers.on_replace.append(self._loop.reset)
-        self.obs_seen = torch.zeros(self.T, self.E, self.N, self.O, dtype=torch.float32, device=self.device)
         self.prev = torch.zeros(self.E, self.N, 2, dtype=torch.float32, device=self.device)
         self.tick = torch.zeros(self.E * self.N, dtype=torch.int32, device=self.device)
-
-    @property
-    def faults(self):
-        return self.fault_buffers.faults
-
-    def set_faults(self, faults):
-        """Another fault plan, OUTSIDE captured graphs: the same shapes (levels, groups, members) are copied into the tables the captured
-        fragment reads, other shapes allocate new ones and drop the graph."""
-        self.fault_buffers.replace(faults.check(self.seated.plan))
 
     def reset(self, seeds=None):
         super().reset(seeds)
         self.tick.zero_()
         self.prev.zero_()
         self.flags[self.T - 1].zero_()
-
-    def _draw_noise(self):
-        """Ordinary noise; with a `sweep` plan the first cell's draw is copied to every cell, as `BankSampler` copies one member's: the
-        cells already share their scene seeds, so at the identity level two cells differ by their checkpoint only.  (The fault draws
-        themselves are keyed by the absolute row, so two impaired cells never share those.)"""
-        draw_cell_noise(self.eps, self.faults.scenes_per_cell)
-
-    def sample(self):
-        batch = super().sample()
-        batch["obs_seen"] = self.obs_seen
-        return batch
 
     def _policy_obs(self, t):
         fault_obs(self.obs[t], self.obs_seen[t], self.col_lo, self.col_hi, self.seated.buffers, self.fault_buffers, self.tick, self.fault_seed)
@@ -220,24 +144,6 @@ class FaultySeatSampler(SeatSampler):
         super()._step(t)
 
 
-def sweep_frame(tally, seats, faults, labels=None):
-    """The tally [G][K][8] (numpy int64) of a `sweep` plan as a frame: one row per (checkpoint, level, role), the columns of
-    `fault_sweep_rows`.  `faults`: the level plan of the sweep -- a `FaultPlan`, or any plan made by `sweep_plan` (an
-    `adversary.AdversaryPlan`): the level's columns are whatever its levels' `as_dict()` names."""
-    import pandas as pd
-    labels = list(range(faults.n_checkpoints)) if labels is None else list(labels)
-    K, N, n_imp = faults.n_checkpoints, seats.N, faults.n_impaired
-    rows = []
-    for g in range(seats.n_groups):
-        k, lv = int(faults.checkpoint[g]), int(faults.level[g])
-        roles = ([("impaired", k + K if faults.doubled else k, lv)] if n_imp > 0 else []) + ([("healthy", k, 0)] if n_imp < N else [])
-        for role, member, own in roles:
-            w = [int(v) for v in tally[g, member]]
-            rows.append(dict(checkpoint=k, label=labels[k], level=lv, role=role, member=member, share=faults.share, seats=n_imp if role == "impaired"
-                             else N - n_imp, own_level=own, **faults.levels[lv].as_dict(), **dict(zip(SEAT_WORDS, w)), **tally_rates(w)))
-    return pd.DataFrame(rows)
-
-
 def fault_sweep_rows(algo, env, weights_list, levels, share=1.0, scenes_per_cell=4, num_agents=40, steps=1000, seed=0, labels=None,
                      fault_seed=None, **extra):
     """K populations `weights_list` (one layout) x the fault `levels` (level 0 must be the identity, so that every table carries its
@@ -247,30 +153,13 @@ def fault_sweep_rows(algo, env, weights_list, levels, share=1.0, scenes_per_cell
     `level`, `role` ("impaired" / "healthy"; a role without seats has no row), `member`, `share`, `seats`, `own_level` (the level the
     row's drivers are at: 0 for the healthy), the five parameters of the CELL's level, the eight raw words of the seat tally and
     `success`, `crash_rate`, `out_rate`, `reward_per_step` as in `cross_play_rows`.  `fault_seed` defaults to `seed`."""
-    from .bank import PolicyBank
-    from .evaluate import check_labels, eval_session, graph_flag, run_steps
-    weights_list = list(weights_list)
-    K = len(weights_list)
-    if K < 1:
-        raise ValueError("fault_sweep_rows: no members")
-    levels = [lv if isinstance(lv, FaultLevel) else FaultLevel(**lv) for lv in levels]
-    if not levels or not levels[0].is_identity:
-        raise ValueError("fault_sweep_rows: level 0 must be the identity FaultLevel(), the table's own baseline")
-    labels = check_labels(labels, K)
-    seats, faults = FaultPlan.sweep(K, levels, scenes_per_cell, num_agents, share)
-    with eval_session(algo, env, seats.E, num_agents, seed, **extra) as t:
-        bank = PolicyBank(t.policy, sweep_members(weights_list, faults))
-        smp = FaultySeatSampler(t.env, t.policy, bank, seats, faults, t.sampler.T, use_graph=graph_flag(t),
-                                fault_seed=seed if fault_seed is None else fault_seed)
-        tally = run_steps(smp, steps).tally.cpu().numpy()
-    return sweep_frame(tally, seats, faults, labels)
+    return run_sweep("fault_sweep_rows", FaultPlan, algo, env, weights_list,
+                     lambda: baseline_levels("fault_sweep_rows", FaultPlan, levels, "the identity FaultLevel()"),
+                     lambda t, bank, seats, faults, use_graph: FaultySeatSampler(
+                         t.env, t.policy, bank, seats, faults, t.sampler.T, use_graph=use_graph, fault_seed=seed if fault_seed is None else fault_seed),
+                     role_frame, labels=labels, scenes_per_cell=scenes_per_cell, num_agents=num_agents, steps=steps, seed=seed, extra=extra, share=share)
 
 
 def load_levels(path):
     """A JSON list of objects with `FaultLevel`'s fields (missing fields are 0) -> [FaultLevel]."""
-    import json
-    with open(path) as f:
-        raw = json.load(f)
-    if not isinstance(raw, list) or not all(isinstance(r, dict) for r in raw):
-        raise ValueError("%s: a JSON list of objects wanted" % path)
-    return [FaultLevel(**r) for r in raw]
+    return _levels.load_levels(path, FaultLevel)

@@ -22,16 +22,15 @@ launches since `reset`, so a captured graph draws fresh starts at every replay.
 An L-infinity budget, the LiDAR block, fp32 operands; the ego / navigation columns, other norms, momentum and restarts and the bfloat16
 operand mode are out of scope.
 
-Pieces: `PGDLevel` / `PGDPlan` (numpy only), `PGDBuffers`, `PGDSeatSampler` (the `SeatSampler` whose `_policy_obs` launches the kernel
-inside the captured fragment) and `pgd_sweep_rows` (checkpoints x levels x roles as a pandas frame; `evaluate --pgd-sweep`).
+Pieces, each on its base in `levels.py`: `PGDLevel` / `PGDPlan` (numpy only), `PGDBuffers`, `PGDSeatSampler` (whose `_policy_obs` launches
+the kernel inside the captured fragment) and `pgd_sweep_rows` (checkpoints x levels x roles as a pandas frame; `evaluate --pgd-sweep`).
 """
 from dataclasses import dataclass
 
 import numpy as np
 
-from .bank import DeviceTables, draw_cell_noise
-from .crossplay import SeatSampler
-from .faults import lidar_columns, sweep_frame, sweep_members, sweep_plan
+from . import levels as _levels
+from .levels import LevelBuffers, LevelPlan, LevelSeatSampler, baseline_levels, finite_fields, role_frame, run_sweep
 
 LEVEL_WORDS = 8
 LEVEL_FIELDS = ("eps", "steer", "throttle", "alpha", "iters", "random_start", "untargeted")
@@ -54,11 +53,7 @@ class PGDLevel:
     untargeted: bool = False
 
     def __post_init__(self):
-        for name in ("eps", "steer", "throttle", "alpha"):
-            v = getattr(self, name)
-            if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v):
-                raise ValueError("PGDLevel: %s = %r, a finite number wanted" % (name, v))
-            object.__setattr__(self, name, float(v))
+        finite_fields(self, ("eps", "steer", "throttle", "alpha"))
         if isinstance(self.iters, bool) or not isinstance(self.iters, (int, np.integer)) or not 0 <= self.iters <= MAX_ITERS:
             raise ValueError("PGDLevel: iters = %r, an integer in [0, %d] wanted" % (self.iters, MAX_ITERS))
         object.__setattr__(self, "iters", int(self.iters))
@@ -91,53 +86,22 @@ class PGDLevel:
         return {name: getattr(self, name) for name in LEVEL_FIELDS}
 
 
-def _levels(levels):
-    return [lv if isinstance(lv, PGDLevel) else PGDLevel(**lv) for lv in levels]
-
-
-class PGDPlan:
-    """`levels`: a sequence of `PGDLevel` (or dicts of its fields); `level_of`: int [G][K], the level of bank member k in scene group g
-    (an index outside [0, L) leaves the member's rows alone).  Derived: `words` int32 [L][8], `max_iters` (the largest `iters`, at
-    least 1: the launch's bound).  Nothing here touches a device."""
+class PGDPlan(LevelPlan):
+    """`LevelPlan` of `PGDLevel`s; `words` int32 [L][8], and `max_iters` (the largest `iters`, at least 1: the launch's bound)."""
+    LEVEL = PGDLevel
 
     def __init__(self, levels, level_of):
-        self.levels = _levels(levels)
-        if not self.levels:
-            raise ValueError("PGDPlan: no levels")
-        self.level_of = np.ascontiguousarray(level_of, np.int32)
-        if self.level_of.ndim != 2 or self.level_of.shape[0] < 1 or self.level_of.shape[1] < 1:
-            raise ValueError("PGDPlan: level_of of shape %s, [groups][members] wanted" % (self.level_of.shape,))
-        self.L, (self.G, self.K) = len(self.levels), self.level_of.shape
-        self.words = np.stack([lv.words() for lv in self.levels])
+        super().__init__(levels, level_of)
         self.max_iters = max(1, max(lv.iters for lv in self.levels))
-        self.checkpoint = self.level = None
-        self.share = self.scenes_per_cell = None          # (`sweep` sets them: cells of that many scenes share their action noise)
-
-    def check(self, seat_plan):
-        if (seat_plan.n_groups, seat_plan.K) != (self.G, self.K):
-            raise ValueError("PGDPlan: level_of is %d groups x %d members, the seat plan has %d x %d" % (
-                self.G, self.K, seat_plan.n_groups, seat_plan.K))
-        return self
-
-    @classmethod
-    def sweep(cls, K, levels, scenes_per_cell, N, share=1.0):
-        """(seat plan, PGD plan) of K checkpoints x L levels on the cell layout of `AdversaryPlan.sweep` (`SeatPlan.cells`): with share
-        < 1 the bank is doubled, the first round(share * N) slots of a cell are attacked at the cell's level and the rest drive at level
-        0, which must then be an identity."""
-        return sweep_plan(cls, "PGDPlan.sweep", K, _levels(levels), scenes_per_cell, N, share)
 
 
-class PGDBuffers(DeviceTables):
+class PGDBuffers(LevelBuffers):
     """A PGD plan's tables on the device.  The iteration bound is part of the shape key: it is an argument of the captured launch."""
     KEY = ("L", "G", "K", "max_iters")
     pgd = property(lambda self: self.source)
 
-    @staticmethod
-    def tables(plan):
-        return dict(level_of=plan.level_of, levels=plan.words), (plan.L, plan.G, plan.K, plan.max_iters)
 
-
-class PGDSeatSampler(SeatSampler):
+class PGDSeatSampler(LevelSeatSampler):
     """`SeatSampler` under an iterated attack: per env step `pgd_seats` on the true observation, the seated forward on `obs_seen[t]`,
     the simulator step, the seat tally -- the whole fragment is still one captured graph.  The batch's `obs` stays the TRUE observation;
     `obs_seen` [T][E][N][O] (also `batch["obs_seen"]`, zero-initialised: rows of seats that nobody drives are never written) is what
@@ -145,39 +109,20 @@ class PGDSeatSampler(SeatSampler):
     starts, advanced by the kernel itself, so every replay of the graph draws new ones; `seed` keys them.  Cells of a `sweep` plan share
     their action noise, as in `AdversarialSeatSampler`."""
 
+    BUFFERS = PGDBuffers
+    pgd_buffers = property(lambda self: self.level_buffers)
+    pgd = property(lambda self: self.level_plan)
+    set_pgd = LevelSeatSampler.set_levels
+
     def __init__(self, vec_env, policy, bank, plan, pgd, T, use_graph=True, seed=0):
         import torch
-        pgd.check(plan)
-        super().__init__(vec_env, policy, bank, plan, T, use_graph=use_graph)
+        super().__init__(vec_env, policy, bank, plan, pgd, T, use_graph=use_graph)
         self.seed = int(seed) & (2 ** 64 - 1)
-        self.col_lo, self.col_hi = lidar_columns(self.sim.cfg)
-        if not 0 <= self.col_lo <= self.col_hi <= self.O:
-            raise ValueError("PGDSeatSampler: LiDAR columns [%d, %d) of an observation of %d" % (self.col_lo, self.col_hi, self.O))
-        self.pgd_buffers = PGDBuffers(pgd, self.device)
-        self.pgd_buffers.on_replace.append(self._loop.reset)
-        self.obs_seen = torch.zeros(self.T, self.E, self.N, self.O, dtype=torch.float32, device=self.device)
         self.tick = torch.zeros(self.E * self.N, dtype=torch.int32, device=self.device)
-
-    @property
-    def pgd(self):
-        return self.pgd_buffers.pgd
-
-    def set_pgd(self, pgd):
-        """Another PGD plan, OUTSIDE captured graphs: the same shapes (levels, groups, members, iteration bound) are copied into the
-        tables the captured fragment reads, other shapes allocate new ones and drop the graph."""
-        self.pgd_buffers.replace(pgd.check(self.seated.plan))
 
     def reset(self, seeds=None):
         super().reset(seeds)
         self.tick.zero_()
-
-    def _draw_noise(self):
-        draw_cell_noise(self.eps, self.pgd.scenes_per_cell)
-
-    def sample(self):
-        batch = super().sample()
-        batch["obs_seen"] = self.obs_seen
-        return batch
 
     def _policy_obs(self, t):
         self.seated.pgd_seats(self.pgd_buffers, self.obs[t].view(-1, self.O), self.obs_seen[t].view(-1, self.O), self.col_lo, self.col_hi,
@@ -193,29 +138,13 @@ def pgd_sweep_rows(algo, env, weights_list, levels, share=1.0, scenes_per_cell=4
     are unattacked drivers of the same checkpoint (`PGDPlan.sweep`).  Returns a pandas frame, one row per (checkpoint, level, role),
     with the columns of `adversary_sweep_rows` and the level's seven parameters in the place of its three.  `pgd_seed` (the random
     starts) defaults to `seed`."""
-    from .bank import PolicyBank
-    from .evaluate import check_labels, eval_session, graph_flag, run_steps
-    weights_list = list(weights_list)
-    K = len(weights_list)
-    if K < 1:
-        raise ValueError("pgd_sweep_rows: no members")
-    levels = _levels(levels)
-    if not levels or not levels[0].is_identity:
-        raise ValueError("pgd_sweep_rows: level 0 must be an identity (eps 0, iters 0 or no direction), the table's own baseline")
-    labels = check_labels(labels, K)
-    seats, pgd = PGDPlan.sweep(K, levels, scenes_per_cell, num_agents, share)
-    with eval_session(algo, env, seats.E, num_agents, seed, **extra) as t:
-        bank = PolicyBank(t.policy, sweep_members(weights_list, pgd))
-        smp = PGDSeatSampler(t.env, t.policy, bank, seats, pgd, t.sampler.T, use_graph=graph_flag(t), seed=seed if pgd_seed is None else pgd_seed)
-        tally = run_steps(smp, steps).tally.cpu().numpy()
-    return sweep_frame(tally, seats, pgd, labels)
+    return run_sweep("pgd_sweep_rows", PGDPlan, algo, env, weights_list,
+                     lambda: baseline_levels("pgd_sweep_rows", PGDPlan, levels, "an identity (eps 0, iters 0 or no direction)"),
+                     lambda t, bank, seats, pgd, use_graph: PGDSeatSampler(t.env, t.policy, bank, seats, pgd, t.sampler.T, use_graph=use_graph,
+                                                                           seed=seed if pgd_seed is None else pgd_seed),
+                     role_frame, labels=labels, scenes_per_cell=scenes_per_cell, num_agents=num_agents, steps=steps, seed=seed, extra=extra, share=share)
 
 
 def load_levels(path):
     """A JSON list of objects with `PGDLevel`'s fields (missing fields are 0 / false) -> [PGDLevel]."""
-    import json
-    with open(path) as f:
-        raw = json.load(f)
-    if not isinstance(raw, list) or not all(isinstance(r, dict) for r in raw):
-        raise ValueError("%s: a JSON list of objects wanted" % path)
-    return [PGDLevel(**r) for r in raw]
+    return _levels.load_levels(path, PGDLevel)

@@ -78,6 +78,8 @@ def adversary(nets, obs, N, rows, counts, group, level_of, levels, col_lo, col_h
     for k in range(len(counts)):
         for r in rows[k][:counts[k]]:
             r = int(r)
+            if not 0 <= r < n_out:          # an index outside the rows is no row (the kernels' row look-up): nothing is written
+                continue
             o = obs[r].astype(np.float64)
             written[r] = True
             lv = level_index(r, N, k, group, level_of, len(levels))

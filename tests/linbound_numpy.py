@@ -76,6 +76,8 @@ def certify(nets, obs, N, rows, counts, group, level_of, levels, col_lo, col_hi,
     for k in range(len(counts)):
         for r in rows[k][:counts[k]]:
             r = int(r)
+            if not 0 <= r < n_out:          # an index outside the rows is no row (the kernels' row look-up): nothing is written
+                continue
             lv = cz.level_of_row(r, N, k, group, level_of, len(levels))
             index[r] = lv
             if lv < 0:

@@ -105,6 +105,8 @@ def pgd(nets, obs, N, rows, counts, group, level_of, levels, col_lo, col_hi, see
     for k in range(len(counts)):
         for r in rows[k][:counts[k]]:
             r = int(r)
+            if not 0 <= r < n_out:          # an index outside the rows is no row (the kernels' row look-up): nothing is written
+                continue
             seen[r], its[r], member[r] = obs[r], 0, k
             lv = level_of_row(r, N, k, group, level_of, len(levels))
             if lv < 0:
