@@ -20,6 +20,7 @@ import torch.nn as nn
 from copo_amd import dist as D
 from copo_amd.engine import (LEARNER_STATS_KEY, NUM_AGENT_STEPS_SAMPLED, NUM_ENV_STEPS_SAMPLED, Postprocessing,
                              SampleBatch, build_mlp, reduce_mean_valid_fn)
+from copo_amd.hostread import HostRead, PendingResult
 from copo_amd.torch_copo.algo_ccppo import (CENTRALIZED_CRITIC_OBS, COUNTERFACTUAL, CCModel, CCPPOConfig, CCPPOPolicy,  # noqa: F401
                                             CCPPOTrainer)
 from copo_amd.torch_copo.algo_ippo import clipped_value_loss
@@ -132,6 +133,29 @@ class CoPOModel(CCModel):
         return None
 
 
+def meta_result(keys, stats, lcf_parameters, raw_ms, distributional, extra=None):
+    """The ONE device -> host read for everything an iteration reports about the meta update, as a `PendingResult`: the mean of every
+    statistic in `keys`, the LCF parameters (one, or two if `distributional`), {mean, std} of the raw coordinated advantage, and the
+    caller's `extra` {name: 1-D device tensor} riding along.  Its result is the meta-update dict; its `parts` hold the host values under
+    "stats", "lcf_parameters", "raw_adv" and the riders' names.  The LCF mean / std are the model's formulas (CoPOModel.lcf_mean /
+    lcf_std) applied to the parameters on the host, in float64 like there."""
+    assert lcf_parameters.numel() == (2 if distributional else 1), lcf_parameters.shape
+    read = HostRead([("stats", stats), ("lcf_parameters", lcf_parameters), ("raw_adv", raw_ms)] + list((extra or {}).items()))
+
+    def build(parts):
+        out = dict(zip(keys, parts["stats"]))
+        p = parts["lcf_parameters"]
+        lm = min(max(math.tanh(p[0]), -1 + 1e-6), 1 - 1e-6)
+        out.update(lcf=lm, lcf_deg=lm * 90, lcf_param=p[0])
+        if distributional:
+            ls = math.exp(min(max(p[1], -20.0), 2.0))
+            out.update(lcf_std=ls, lcf_std_deg=ls * 90, lcf_std_param=p[1])
+        else:
+            out.update(lcf_std=None)
+        return out
+    return PendingResult(read, build)
+
+
 class CoPOPolicy(CCPPOPolicy):
     model_class = CoPOModel
     STAT_KEYS = CCPPOPolicy.STAT_KEYS + ("mean_nei_vf_loss", "mean_global_vf_loss", "normalized_advantages")
@@ -154,6 +178,8 @@ class CoPOPolicy(CCPPOPolicy):
         self._meta_side = None
         self._meta_aux = None           # data-parallel: the small collectives of a pass (row terms, statistics) run here
         self._meta_keep = []
+        self._meta_row_store = False    # this iteration's passes read the row store (decided by run_meta)
+        self._rows_early = False        # ... and `meta_rows_early` has filled it already
 
     # ---- dense postprocess: three critic heads ----------------------------------------------------------
     def gae_heads(self):
@@ -623,10 +649,10 @@ class CoPOPolicy(CCPPOPolicy):
         self._rows_early = True
         return True
 
-    def run_meta(self, valid_idx, B_local, B_all, mb, num_iters, defer=False, extra=()):
+    def run_meta(self, valid_idx, B_local, B_all, mb, num_iters, defer=False, extra=None):
         """`lcf_num_iters` passes of shuffled minibatches through `meta_update` (algo_copo.py:581-589).
-        defer=True: everything is queued and a callable is returned that does the ONE device -> host read and builds the result;
-        `extra`: 1-D device tensors whose values ride along in that read (the callable leaves them in `self._extra_host`), so that an
+        defer=True: everything is queued and the `PendingResult` of `meta_result` is returned, whose call does the ONE device -> host read
+        and builds the result; `extra`: {name: 1-D device tensor} whose values ride along in that read (its `parts`), so that an
         iteration ends with one host stop instead of three (PPO statistics, meta results, episode metrics)."""
         rs = self._row_sources
         dev = self.device
@@ -670,7 +696,7 @@ class CoPOPolicy(CCPPOPolicy):
         steps = 0
         nb_batch = int(self.config.get("meta_batch_size", 32)) if self.fused is not None else 0
         self._meta_row_store = self._wants_row_store(mb, num_iters)
-        early, self._rows_early = getattr(self, "_rows_early", False), False
+        early, self._rows_early = self._rows_early, False
         if self._meta_row_store and not early:
             self.fused.meta_rows(rs)
         perms = self.draw_perms(num_iters, B_local)
@@ -717,31 +743,9 @@ class CoPOPolicy(CCPPOPolicy):
             torch.cuda.current_stream().wait_stream(self._meta_aux)
         self._meta_keep.clear()
         m = self.model
-        # one device -> host read for everything this iteration reports about the meta update (+ the caller's `extra`); the LCF mean /
-        # std are the model's formulas (CoPOModel.lcf_mean / lcf_std) applied to the parameters on the host, in float64 like there
-        extra = [t.detach().reshape(-1).double() for t in extra]
-        packed = torch.cat([mbuf["stats"] / max(1, steps), m.lcf_parameters.detach().double().reshape(-1),
-                            self._raw_ms.double().reshape(-1)] + extra)
-        nk = len(self.META_KEYS)
-        distributional = bool(m.model_config["custom_model_config"][USE_DISTRIBUTIONAL_LCF])
-
-        def resolve():
-            host = packed.tolist()
-            out = dict(zip(self.META_KEYS, host[:nk]))
-            p0, p1, self._raw_host = host[nk], host[nk + 1], (host[nk + 2], host[nk + 3])
-            lm = min(max(math.tanh(p0), -1 + 1e-6), 1 - 1e-6)
-            out.update(lcf=lm, lcf_deg=lm * 90, lcf_param=p0)
-            if distributional:
-                ls = math.exp(min(max(p1, -20.0), 2.0))
-                out.update(lcf_std=ls, lcf_std_deg=ls * 90, lcf_std_param=p1)
-            else:
-                out.update(lcf_std=None)
-            o, self._extra_host = nk + 4, []
-            for t in extra:
-                self._extra_host.append(host[o:o + t.numel()])
-                o += t.numel()
-            return out
-        return resolve if defer else resolve()
+        pending = meta_result(self.META_KEYS, mbuf["stats"] / max(1, steps), m.lcf_parameters, self._raw_ms,
+                              bool(m.model_config["custom_model_config"][USE_DISTRIBUTIONAL_LCF]), extra)
+        return pending if defer else pending()
 
     def update_old_policy(self):
         fz = self.fused
@@ -820,6 +824,7 @@ def _single_traj_gae(rollout, last_r, gamma, lambda_, rk, vk, ak, tk):
 
 class CoPOTrainer(CCPPOTrainer):
     _name = "CoPO"
+    _mix_ws = None      # workspaces of `coordinated_advantage`, sized for the rollout's rows
 
     @classmethod
     def get_default_config(cls):
@@ -836,7 +841,7 @@ class CoPOTrainer(CCPPOTrainer):
         pol = self.policy
         dev = pol.device
         n = batch[SampleBatch.FLAGS].numel()
-        if getattr(self, "_mix_ws", None) is None or self._mix_ws["n"] != n:
+        if self._mix_ws is None or self._mix_ws["n"] != n:
             self._mix_ws = dict(n=n, stats=ops.lcf_stats_workspace(dev), mixed=torch.empty(n, device=dev),
                                 norm=torch.empty(n, device=dev), gstd=torch.empty(n, device=dev),
                                 valid=torch.empty(n, dtype=torch.uint8, device=dev))
@@ -881,20 +886,16 @@ class CoPOTrainer(CCPPOTrainer):
         # copy of the statistics -- the host wakes up on the copy's event while the device is already in the row pass.
         lcf_mb = int(cfg["lcf_sgd_minibatch_size"] or cfg["sgd_minibatch_size"])
         pending = pol.run_sgd(idx, B, B_all, mb, int(cfg["num_sgd_iter"]), defer=True)
-        if hasattr(pending, "start_copy") and not D.is_dist():
-            pending.start_copy()
+        if not D.is_dist():
+            pending.start()
             pol.meta_rows_early(lcf_mb, int(cfg["lcf_num_iters"]))
         stats = pending()
         self._timers["learn_time_ms"] = (time.perf_counter() - t0) * 1e3
         # ---- global coordination: LCF meta update ----
         t0 = time.perf_counter()
-        lcf_mb = int(cfg["lcf_sgd_minibatch_size"] or cfg["sgd_minibatch_size"])
         # ONE host stop at the end of the iteration: the episode-metric sums ride along in the meta pass's read
-        extra = []
-        early = getattr(self, "_metric_sums", None)
-        if early is not None and early[1] is not None:
-            self._wait_metric_sums()
-            extra.append(early[1])
+        sums = self._episode.rider()
+        extra = {} if sums is None else {"episode_sums": sums}
         pending_meta = pol.run_meta(idx, B, B_all, lcf_mb, int(cfg["lcf_num_iters"]), defer=True, extra=extra)
         # the device half of the reference's weight / LCF broadcast (algo_copo.py:555-558, 596-613) is queued BEFORE that read
         lcf_parameters = pol.model.lcf_parameters.detach().clone()
@@ -908,15 +909,14 @@ class CoPOTrainer(CCPPOTrainer):
         self.workers.foreach_worker_with_id(_update_lcf_dev)
         meta = pending_meta()
         self._timers["meta_time_ms"] = (time.perf_counter() - t0) * 1e3
-        host = list(getattr(pol, "_extra_host", []))
-        if early is not None and early[1] is not None:
-            self._metric_sums = (early[0], host.pop(0))
+        if sums is not None:
+            self._episode.accept(pending_meta.parts["episode_sums"])
         train_results = {"default": {LEARNER_STATS_KEY: stats, "custom_metrics": {}}}
         lcf_mean, lcf_std = meta["lcf"], meta["lcf_std"]
         if os.environ.get("COPO_CHECK_ASSIGN_LCF", "0") == "1":     # the reference's sanity check (algo_copo.py:446-471), two device reads
             self.workers.foreach_worker_with_id(lambda w_id, w: w.foreach_policy(lambda pi, pi_id: pi.assign_lcf(lcf_parameters, lcf_mean, lcf_std)))
         self.workers.foreach_worker_with_id(lambda w_id, w: w.foreach_env(lambda e: e.set_lcf_dist(mean=lcf_mean, std=lcf_std)))
-        raw = getattr(pol, "_raw_host", None) or (float(pol._raw_lcf_adv_mean.item()), float(pol._raw_lcf_adv_std.item()))
+        raw = pending_meta.parts["raw_adv"]
         fetches = dict(raw_lcf_adv_mean_value=float(raw[0]), raw_lcf_adv_std_value=float(raw[1]))
         fetches.update(meta)
         train_results["default"]["custom_metrics"]["meta_update"] = fetches

@@ -22,6 +22,7 @@ import torch
 from . import dist as D
 from .engine import (LEARNER_STATS_KEY, NUM_AGENT_STEPS_SAMPLED, NUM_ENV_STEPS_SAMPLED, Postprocessing, SampleBatch,
                      TorchDiagGaussian)
+from .hostread import HostRead, PendingResult, PinnedBuffer
 
 F_ACTED, F_DONE, F_ARRIVE, F_CRASH, F_OUT, F_MAXSTEP, F_SPAWNED, F_ENV_RESET = (1 << i for i in range(8))
 
@@ -250,6 +251,7 @@ class PPOPolicyBase:
         self._flat_grad = None
         self._sgd = None
         self._row_sources = None
+        self._stats_pinned = PinnedBuffer()      # host side of the epochs' statistics read (run_sgd(defer=True).start())
         # fused HIP learner (2 launches per minibatch step instead of ~250 autograd kernels).  A bfloat16 policy
         # (`policy_dtype`, BASELINE configs[3]) runs the same kernels in their bfloat16-operand mode (fp32 parameters, Adam and
         # losses, as torch.autocast keeps them); the LCF meta pass has no such mode, so bfloat16 CoPO stays on autocast
@@ -496,6 +498,9 @@ class PPOPolicyBase:
     _dp_mode = None         # "tile" / "rccl", decided at the first SGD call of a distributed run
 
     _rs_step = None         # what the step kernels read: the epoch's rows in minibatch order (FusedLearner.gather_epoch)
+    _sgd_chain = _sgd_chain_long = None      # captured chains of SGD_CHAIN / SGD_CHAIN_LONG local steps (next to `_sgd`, the single step)
+    _gather_ok = None       # rows gathered into minibatch order?  Decided once: captured chains keep reading the sources they were captured on
+    _dp_fault_injected = False      # the `dp_fault_injection_rank` test hook fires once
 
     def _fused_local(self):
         rs = self._rs_step if self._rs_step is not None else self._row_sources
@@ -573,43 +578,54 @@ class PPOPolicyBase:
         self.fused.adam(self._row_sources)
         self.fused.step(self._row_sources, apply_adam=False, stats=self.fused.stats, bump_index=False)
 
-    def run_sgd_fused(self, valid_idx, B_local, B_all, mb, num_epochs, _perms=None, defer=False):
-        """defer=True: returns a callable that reads the statistics back (the ONE device -> host read of the PPO epochs) instead of the
-        dict itself -- a caller with more device work to queue (CoPO's meta passes) resolves it afterwards, so the host keeps running
-        ahead of the device instead of stopping at the end of the epochs (round 6: ~0.2 ms of launch gaps at the start of the meta phase)."""
-        fz = self.fused
-        assert mb == fz.cfg.mb, "fused learner was built for minibatch %d" % fz.cfg.mb
-        if self._sgd is None and D.is_dist() and self._dp_mode is None:
+    def _build_fused_sgd(self):
+        """The data-parallel mode (decided at the first call of a distributed run) and the captured callables of the step."""
+        if self._sgd is not None:
+            return
+        if D.is_dist() and self._dp_mode is None:
             self._dp_mode = self._pick_dp_mode()
-        tile = self._dp_mode == "tile"
-        if self._sgd is None:
-            if D.is_dist() and not tile:
-                # the RCCL loop: [gradient pass] -> all-reduce -> [Adam + next gradient pass]; the kernels run captured, the collective
-                # between them eager (ONE fallback: the captured-collective and peer-kernel variants of round 4 are gone)
-                self._sgd = (GraphedCallable(self._fused_grads, self.use_graphs),
-                             GraphedCallable(self._fused_apply, self.use_graphs),
-                             GraphedCallable(self._fused_apply_then_grads, self.use_graphs))
-            else:
-                self._sgd = GraphedCallable(self._fused_local, self.use_graphs)
-                self._sgd_chain = GraphedCallable(self._fused_local_chain, self.use_graphs)
-                self._sgd_chain_long = GraphedCallable(self._fused_local_chain_long, self.use_graphs)
-        # the tile exchange has a bounded wait instead of a hang; should one ever time out on the job's links, every rank goes back
-        # to the state this call started from and repeats it through the RCCL loop (unless the exchange was asked for by name)
-        snap = None
-        by_name = os.environ.get("COPO_DP_EXCHANGE", "auto") == "tile"
-        if tile and self._tile is not None and not by_name:
-            snap = (fz.flat.flat.clone(), fz.adam_m.clone(), fz.adam_v.clone(), fz.step_count.clone(), self.num_grad_updates)
-        fz.stats.zero_()
-        fz.sync_mirror()          # graph replays below do not run python: refresh the transposed weights here if needed
-        steps = 0
-        n_epochs_asked = num_epochs
-        perms = _perms if _perms is not None else self.draw_perms(num_epochs, B_local)      # (a retry after a fall-back repeats the SAME epochs)
-        rs0 = self._row_sources
+        if D.is_dist() and self._dp_mode != "tile":
+            # the RCCL loop: [gradient pass] -> all-reduce -> [Adam + next gradient pass]; the kernels run captured, the collective
+            # between them eager (ONE fallback: the captured-collective and peer-kernel variants of round 4 are gone)
+            self._sgd = (GraphedCallable(self._fused_grads, self.use_graphs),
+                         GraphedCallable(self._fused_apply, self.use_graphs),
+                         GraphedCallable(self._fused_apply_then_grads, self.use_graphs))
+        else:
+            self._sgd = GraphedCallable(self._fused_local, self.use_graphs)
+            self._sgd_chain = GraphedCallable(self._fused_local_chain, self.use_graphs)
+            self._sgd_chain_long = GraphedCallable(self._fused_local_chain_long, self.use_graphs)
+
+    def _walk(self, n):
+        """`n` local steps (the device-side minibatch counter walks the plan): captured, most of them in graphs of SGD_CHAIN_LONG and
+        SGD_CHAIN steps -- fewer graph launches, no gap between their kernels -- and the rest one by one."""
+        k = 0
+        if self.use_graphs:
+            while self.SGD_CHAIN_LONG > self.SGD_CHAIN and k + self.SGD_CHAIN_LONG <= n:
+                self._sgd_chain_long()
+                k += self.SGD_CHAIN_LONG
+            while k + self.SGD_CHAIN <= n:
+                self._sgd_chain()
+                k += self.SGD_CHAIN
+        for _ in range(k, n):
+            self._sgd()
+
+    def _rccl_epoch(self, n_mb):
+        """An epoch of the RCCL loop, two host calls per minibatch: [Adam of the previous one + this gradient pass], all-reduce; the
+        last Adam of the epoch is flushed before the next plan resets the minibatch index."""
+        grads, apply, apply_then_grads = self._sgd
+        for k in range(n_mb):
+            (grads if k == 0 else apply_then_grads)()
+            self._grad_all_reduce()
+        apply()
+
+    def _fused_epochs(self, valid_idx, B_local, B_all, mb, num_epochs, perms):
+        """Plan and issue the steps of `num_epochs` epochs; returns how many were taken."""
+        fz, rs0 = self.fused, self._row_sources
+        local = self._dp_mode == "tile" or not D.is_dist()      # (the tile exchange is the local step's two launches)
         n_mb_ep = max(1, math.ceil(max(B_all) / mb))
-        if getattr(self, "_gather_ok", None) is None:      # decided once: captured chains keep reading the sources they were captured on
+        if self._gather_ok is None:
             self._gather_ok = bool(self.config.get("gather_epoch_rows", True) and fz.gather_epoch_ok(rs0))      # (memory for the copy, fp32 sources; else: row tables)
-        gather_ok = self._gather_ok
-        if (tile or not D.is_dist()) and self.use_graphs and gather_ok and self.config.get("plan_all_epochs", True) \
+        if local and self.use_graphs and self._gather_ok and self.config.get("plan_all_epochs", True) \
                 and num_epochs * n_mb_ep <= int(rs0["rows_all"].shape[0]):
             # every epoch's plan up front, back to back in the tables, ONE gather of all planned rows into minibatch order; the
             # device-side minibatch counter then walks all num_epochs x n_mb steps in captured chains without a host stop
@@ -620,98 +636,105 @@ class PPOPolicyBase:
                                 bufs=dict(rows_all=rs0["rows_all"][o:], w_all=rs0["w_all"][o:], denom_all=rs0["denom_all"][o:], k=rs0["k"]))
             total = num_epochs * n_mb_ep
             self._rs_step = fz.gather_epoch(rs0, total)
-            _k0 = 0
-            while self.SGD_CHAIN_LONG > self.SGD_CHAIN and _k0 + self.SGD_CHAIN_LONG <= total:
-                self._sgd_chain_long()
-                _k0 += self.SGD_CHAIN_LONG
-            while _k0 + self.SGD_CHAIN <= total:
-                self._sgd_chain()
-                _k0 += self.SGD_CHAIN
-            for _k in range(_k0, total):
-                self._sgd()
-            steps = total
-            num_epochs = 0          # (the per-epoch loop below has nothing left to do)
+            self._walk(total)
+            return total
+        steps = 0
         for ep in range(num_epochs):
             n_mb = self.plan_epoch(valid_idx, B_local, B_all, mb, perm=None if perms is None else perms[ep])
-            if (tile or not D.is_dist()) and gather_ok:
-                # (persistent buffers: the captured chains keep reading the same addresses)
-                self._rs_step = fz.gather_epoch(self._row_sources, n_mb)
-            _k0 = 0
-            if (tile or not D.is_dist()) and self.use_graphs:
-                # most of an epoch in graphs of SGD_CHAIN steps: fewer graph launches, no gap between their kernels
-                while _k0 + self.SGD_CHAIN <= n_mb:
-                    self._sgd_chain()
-                    _k0 += self.SGD_CHAIN
-                    steps += self.SGD_CHAIN
-            for _k in range(_k0, n_mb):
-                if D.is_dist() and not tile:
-                    # two host calls per minibatch: [Adam of the previous one + this gradient pass], all-reduce; the
-                    # last Adam of the epoch is flushed before the next plan resets the minibatch index
-                    self._sgd[0 if _k == _k0 else 2]()
-                    self._grad_all_reduce()
-                    if _k == n_mb - 1:
-                        self._sgd[1]()
-                else:
-                    self._sgd()
-                steps += 1
-        self.num_grad_updates += steps
-        if self._tile is not None:
-            # every rank learns whether ANY rank's wait timed out (a rank that raised alone would leave its peers hanging in their
-            # next collective with partially summed parameters)
-            ok = self._tile.ok()
-            if int(self.config.get("dp_fault_injection_rank", -1)) == D.rank() and not getattr(self, "_dp_fault_injected", False):
-                # test hook: this rank reports a timed-out wait ONCE (the kernels' own time-out needs starving ranks or dead links;
-                # what follows it -- agreement, restore, the same epochs again through the RCCL loop -- must be covered every time)
-                ok, self._dp_fault_injected = False, True
-            good = torch.tensor([1 if ok else 0], dtype=torch.int32, device=self.device)
-            if D.world_size() > 1:
-                import torch.distributed as td
-                td.all_reduce(good, op=td.ReduceOp.MIN)
-            if not bool(good.item()):
-                if snap is None:          # asked for by name: no fall-back -- close the mappings, raise on every rank
-                    self._tile.close()
-                    self._tile = None
-                    raise RuntimeError("data-parallel tile exchange (COPO_DP_EXCHANGE=tile): a wait for a peer timed out on some rank")
-                else:
-                    import warnings
-                    warnings.warn("data-parallel tile exchange: a wait for a peer timed out; back to the RCCL loop from the state before this call")
-                    fz.flat.flat.copy_(snap[0]); fz.adam_m.copy_(snap[1]); fz.adam_v.copy_(snap[2]); fz.step_count.copy_(snap[3])
-                    self.num_grad_updates = snap[4]
-                    fz.invalidate_mirror()
-                    self._tile.close()
-                    self._tile, self._dp_mode, self._sgd, self._rs_step = None, "rccl", None, None
-                    self.dp_reason = "a wait of the tile exchange timed out during training: RCCL loop from then on"
-                    return self.run_sgd_fused(valid_idx, B_local, B_all, mb, n_epochs_asked, _perms=perms, defer=defer)
-        # a rank's statistics are ITS rows' terms over the GLOBAL row count of each minibatch: the sum over the ranks is the global mean.
-        # Without it the KL coefficient would follow 1 / world of the sampled KL, differently on every rank (found by the two-rank
-        # end-to-end test of round 6: the ranks' parameters stay identical only while their KL coefficients do)
-        D.all_reduce_sum_(fz.stats)
-        means = fz.stats / max(1, steps)          # (its own tensor: the next call zeroes fz.stats)
+            if not local:
+                self._rccl_epoch(n_mb)
+            else:
+                if self._gather_ok:
+                    # (persistent buffers: the captured chains keep reading the same addresses)
+                    self._rs_step = fz.gather_epoch(rs0, n_mb)
+                self._walk(n_mb)
+            steps += n_mb
+        return steps
 
-        copy = {}
+    def _tile_snapshot(self):
+        """The tile exchange has a bounded wait instead of a hang; should one ever time out on the job's links, every rank goes back
+        to the state the call started from -- this snapshot -- and repeats it through the RCCL loop.  None: nothing to go back to
+        (no exchange in use, or it was asked for by name)."""
+        fz = self.fused
+        if self._dp_mode != "tile" or self._tile is None or os.environ.get("COPO_DP_EXCHANGE", "auto") == "tile":
+            return None
+        return fz.flat.flat.clone(), fz.adam_m.clone(), fz.adam_v.clone(), fz.step_count.clone(), self.num_grad_updates
 
-        def start_copy():                  # asynchronous device -> host copy; resolve() then waits for ITS event, not for the stream
-            if means.is_cuda:
-                if getattr(self, "_stats_pin", None) is None:
-                    self._stats_pin = torch.empty(means.numel(), dtype=means.dtype, pin_memory=True)
-                self._stats_pin.copy_(means, non_blocking=True)
-                copy["ev"] = torch.cuda.Event()
-                copy["ev"].record()
+    def _tile_agreed(self, snap):
+        """True if no rank's wait for a peer timed out during the call.  Else the learner is back at `snap` and in the RCCL loop
+        (False: the caller repeats the call), or, without a snapshot, the exchange is closed and every rank raises."""
+        # every rank learns whether ANY rank's wait timed out (a rank that raised alone would leave its peers hanging in their
+        # next collective with partially summed parameters)
+        ok = self._tile.ok()
+        if int(self.config.get("dp_fault_injection_rank", -1)) == D.rank() and not self._dp_fault_injected:
+            # test hook: this rank reports a timed-out wait ONCE (the kernels' own time-out needs starving ranks or dead links;
+            # what follows it -- agreement, restore, the same epochs again through the RCCL loop -- must be covered every time)
+            ok, self._dp_fault_injected = False, True
+        good = torch.tensor([1 if ok else 0], dtype=torch.int32, device=self.device)
+        if D.world_size() > 1:
+            import torch.distributed as td
+            td.all_reduce(good, op=td.ReduceOp.MIN)
+        if bool(good.item()):
+            return True
+        if snap is None:          # asked for by name: no fall-back -- close the mappings, raise on every rank
+            self._tile.close()
+            self._tile = None
+            raise RuntimeError("data-parallel tile exchange (COPO_DP_EXCHANGE=tile): a wait for a peer timed out on some rank")
+        import warnings
+        warnings.warn("data-parallel tile exchange: a wait for a peer timed out; back to the RCCL loop from the state before this call")
+        fz = self.fused
+        fz.flat.flat.copy_(snap[0]); fz.adam_m.copy_(snap[1]); fz.adam_v.copy_(snap[2]); fz.step_count.copy_(snap[3])
+        self.num_grad_updates = snap[4]
+        fz.invalidate_mirror()
+        self._tile.close()
+        self._tile, self._dp_mode, self._sgd, self._rs_step = None, "rccl", None, None
+        self.dp_reason = "a wait of the tile exchange timed out during training: RCCL loop from then on"
+        return False
 
-        def resolve(values=None):          # values: the means, already on the host (they rode along in another read)
-            if values is None and "ev" in copy:
-                copy["ev"].synchronize()
-                values = self._stats_pin.tolist()
-            tot, pol, vf, kl, ent, vfn, vfg, adv = means.tolist() if values is None else values
-            return dict(total_loss=tot, policy_loss=pol, vf_loss=vf, kl=kl, entropy=ent, cur_kl_coeff=self._kl_value,
-                        cur_lr=float(self.config["lr"]), num_sgd_steps=steps, mean_nei_vf_loss=vfn, mean_global_vf_loss=vfg,
-                        normalized_advantages=adv)
-        resolve.means, resolve.start_copy = means, start_copy
-        return resolve if defer else resolve()
+    FUSED_STAT_KEYS = STAT_KEYS + ("mean_nei_vf_loss", "mean_global_vf_loss", "normalized_advantages")      # the fused learner's 8 slots
+
+    def learner_stats(self, keys, means, steps):
+        """The learner-stats dict of `steps` SGD steps from the mean of every statistic in `keys` (names of `tower_stats`)."""
+        rest = dict(zip(keys, means))
+        out = dict(total_loss=rest.pop("total_loss"), policy_loss=rest.pop("mean_policy_loss"), vf_loss=rest.pop("mean_vf_loss"),
+                   kl=rest.pop("mean_kl_loss"), entropy=rest.pop("mean_entropy"), cur_kl_coeff=self._kl_value,
+                   cur_lr=float(self.config["lr"]), num_sgd_steps=steps)
+        out.update(rest)
+        return out
+
+    def _read_stats(self, keys, sums, steps, defer):
+        """The read-back of both SGD paths: the ONE device -> host read of the PPO epochs.  A rank's statistics are ITS rows' terms
+        over the GLOBAL row count of each minibatch: the sum over the ranks is the global mean.  Without it the KL coefficient would
+        follow 1 / world of the sampled KL, differently on every rank (found by the two-rank end-to-end test of round 6: the ranks'
+        parameters stay identical only while their KL coefficients do)."""
+        D.all_reduce_sum_(sums)
+        means = sums / max(1, steps)          # (its own tensor: the next call zeroes the sums)
+        pending = PendingResult(HostRead([("means", means)], pin=self._stats_pinned),
+                                lambda parts: self.learner_stats(keys, parts["means"], steps))
+        return pending if defer else pending()
+
+    def run_sgd_fused(self, valid_idx, B_local, B_all, mb, num_epochs, defer=False):
+        """`run_sgd` on the fused learner: only the order of the pieces above."""
+        fz = self.fused
+        assert mb == fz.cfg.mb, "fused learner was built for minibatch %d" % fz.cfg.mb
+        perms = None
+        while True:
+            self._build_fused_sgd()
+            snap = self._tile_snapshot()
+            fz.stats.zero_()
+            fz.sync_mirror()          # graph replays below do not run python: refresh the transposed weights here if needed
+            if perms is None:         # (a retry after a fall-back repeats the SAME epochs)
+                perms = self.draw_perms(num_epochs, B_local)
+            steps = self._fused_epochs(valid_idx, B_local, B_all, mb, num_epochs, perms)
+            self.num_grad_updates += steps
+            if self._tile is None or self._tile_agreed(snap):
+                return self._read_stats(self.FUSED_STAT_KEYS, fz.stats, steps, defer)
 
     def run_sgd(self, valid_idx, B_local, B_all, mb, num_epochs, defer=False):
-        """`num_sgd_iter` epochs of minibatch SGD; returns the mean learner stats over every step taken (defer=True: a callable
-        that returns them, see run_sgd_fused)."""
+        """`num_sgd_iter` epochs of minibatch SGD; returns the mean learner stats over every step taken.
+        defer=True: returns a `PendingResult` instead, whose call reads the statistics back and gives that dict -- a caller with more
+        device work to queue (CoPO's meta row store) starts its copy, queues the work and resolves it afterwards, so the host keeps
+        running ahead of the device instead of stopping at the end of the epochs."""
         if self.fused is not None:
             return self.run_sgd_fused(valid_idx, B_local, B_all, mb, num_epochs, defer=defer)
         self._ensure_flat_grads()
@@ -736,15 +759,7 @@ class PPOPolicyBase:
                     self._sgd()
                 steps += 1
         self.num_grad_updates += steps
-        D.all_reduce_sum_(rs["stats"])          # (partial sums over this rank's rows -> the global means, as in run_sgd_fused)
-        vals = (rs["stats"] / max(1, steps)).tolist()
-        out = dict(zip(self.STAT_KEYS, vals))
-        res = dict(total_loss=out["total_loss"], policy_loss=out["mean_policy_loss"], vf_loss=out["mean_vf_loss"],
-                   kl=out["mean_kl_loss"], entropy=out["mean_entropy"], cur_kl_coeff=self._kl_value,
-                   cur_lr=float(self.config["lr"]), num_sgd_steps=steps,
-                   **{k: v for k, v in out.items() if k not in ("total_loss", "mean_policy_loss", "mean_vf_loss",
-                                                                "mean_kl_loss", "mean_entropy")})
-        return (lambda: res) if defer else res
+        return self._read_stats(self.STAT_KEYS, rs["stats"], steps, defer)
 
     # ---- postprocess (dense) -----------------------------------------------------------------------------
     def critic_obs_dense(self, batch):
@@ -886,6 +901,57 @@ class PPOPolicyBase:
 # ----------------------------------------------------------------------------------------------------
 # trainer
 # ----------------------------------------------------------------------------------------------------
+class EpisodeSums:
+    """The episode-metric sums (`VecTrainer.episode_sums`) of the latest rollout: queued right behind it and read back at the end of the
+    iteration, so that no kernel launch is left behind the iteration's last host stop.  On one GPU the one-workgroup reduction (70 us)
+    runs on a side stream, under the postprocess; on the CPU and data-parallel (the sums end in an all-reduce) it runs inline."""
+
+    def __init__(self, trainer):
+        self._trainer = trainer
+        self.batch = None            # the rows of the latest rollout
+        self.sums = None             # their sums: a device tensor, a host list once `accept`ed, None once taken
+        self._stream = self._event = None
+
+    def queue(self, batch):
+        tr, dev = self._trainer, self._trainer.policy.device
+        self.batch = batch
+        if dev.type == "cuda" and not D.is_dist():
+            if self._stream is None:
+                self._stream = concurrent_stream(dev)
+            self._stream.wait_stream(torch.cuda.current_stream(dev))
+            with torch.cuda.stream(self._stream):
+                self.sums = tr.episode_sums(batch)
+            self._event = torch.cuda.Event()
+            self._event.record(self._stream)
+        else:
+            self._event, self.sums = None, tr.episode_sums(batch)
+
+    def wait(self):
+        """From here on the current stream may read the queued sums -- and rewrite the rollout buffers they are taken from."""
+        if self._event is not None:
+            torch.cuda.current_stream(self._trainer.policy.device).wait_event(self._event)
+            self._event = None
+
+    def rider(self):
+        """The sums on the device, for a caller whose own host read carries them along (None: there are none)."""
+        if not torch.is_tensor(self.sums):
+            return None
+        self.wait()
+        return self.sums
+
+    def accept(self, values):
+        """The host values of `rider()`'s tensor."""
+        self.sums = list(values)
+
+    def take(self, batch):
+        """The sums of `batch` on the host, handed out once; None: there are none for that batch."""
+        sums, self.sums = self.sums, None
+        self.wait()
+        if sums is None or batch is not self.batch:
+            return None
+        return HostRead([("episode_sums", sums)]).get()["episode_sums"] if torch.is_tensor(sums) else sums
+
+
 class VecTrainer:
     """`Algorithm`-shaped driver: `train()` runs one iteration and returns an RLlib-style result dict."""
     _name = "PPO"
@@ -912,6 +978,8 @@ class VecTrainer:
         self.iteration = 0
         self._t_start = time.time()
         self.callbacks = cfg.callbacks() if isinstance(cfg.callbacks, type) else cfg.callbacks
+        self._episode = EpisodeSums(self)      # (here, not in setup: trainers that replace `setup` and `collect` still go through train())
+        self._last_batch = None
         self.setup(cfg)
 
     def setup(self, cfg):
@@ -944,25 +1012,13 @@ class VecTrainer:
 
     # ---- the iteration ------------------------------------------------------------------------------------
     def collect(self):
+        """One rollout, its episode-metric sums queued (`EpisodeSums`), the dense postprocess.  Data-parallel, the sums' all-reduce is
+        issued HERE, directly behind the rollout: it is the iteration's first collective, ahead of the row counts' all-gather and the
+        advantage statistics of `training_step` -- also for a caller that uses `collect` alone."""
         t0 = time.perf_counter()
-        self._wait_metric_sums()               # (a caller that never read the previous rollout's sums: they read the buffers this rollout rewrites)
+        self._episode.wait()                   # (a caller that never read the previous rollout's sums: they read the buffers this rollout rewrites)
         batch = self.sampler.sample()
-        self._metrics_batch = batch            # the rows of THIS rollout (episode metrics, counters)
-        # its metric sums are queued NOW and read back at the end of train(): no kernel launch behind the iteration's last host stop.
-        # On the GPU the one-workgroup reduction (70 us) runs on a side stream, under the postprocess
-        if self.policy.device.type == "cuda" and not D.is_dist():
-            if getattr(self, "_metric_stream", None) is None:
-                self._metric_stream = concurrent_stream(self.policy.device)
-            ms = self._metric_stream
-            ms.wait_stream(torch.cuda.current_stream(self.policy.device))
-            with torch.cuda.stream(ms):
-                sums = self.episode_sums(batch)
-            self._metric_event = torch.cuda.Event()
-            self._metric_event.record(ms)
-            self._metric_sums = (batch, sums)
-        else:
-            self._metric_event = None
-            self._metric_sums = (batch, self.episode_sums(batch))
+        self._episode.queue(batch)             # read back at the end of train()
         if self.policy.wants_lookahead():
             batch = self._lookahead_batch(batch)
         self.policy.postprocess_trajectory(batch)
@@ -998,13 +1054,6 @@ class VecTrainer:
         out[SampleBatch.REWARDS], out["nei_rewards"], out["global_rewards"] = r3[0], r3[1], r3[2]
         out["_lookahead"] = True
         return out
-
-    def _wait_metric_sums(self):
-        """The current stream may read the sums `collect` queued on the metric stream."""
-        ev = getattr(self, "_metric_event", None)
-        if ev is not None:
-            torch.cuda.current_stream(self.policy.device).wait_event(ev)
-            self._metric_event = None
 
     def valid_rows(self, batch):
         if "_valid_idx" in batch:                          # already listed by the dense postprocess
@@ -1102,6 +1151,7 @@ class VecTrainer:
         eval/evaluate_population.py:57-76) -- rows of a scene's partial first episode and of episodes after its k-th are
         left out, so slow agents and the drain phase of an episode weigh what they weigh in the reference's evaluation."""
         tot, n_frag = {}, 0
+        self._episode.wait()       # (sums queued by a `collect` read the rollout buffers that the fragments below rewrite)
         # [E] episodes completed per scene; -1: still inside the partial episode the call started in
         ep = torch.full((self.sampler.E,), -1 if self.sampler._started else 0, dtype=torch.int64, device=self.sampler.device)
         while True:
@@ -1157,10 +1207,9 @@ class VecTrainer:
         train_results = self.training_step()
         dt = time.perf_counter() - t0
         self.iteration += 1
-        mbatch = getattr(self, "_metrics_batch", None) or self._last_batch
-        early, self._metric_sums = getattr(self, "_metric_sums", None), None
-        self._wait_metric_sums()
-        cm = self._metrics_from_sums(early[1]) if early is not None and early[0] is mbatch else self.episode_metrics(mbatch)
+        mbatch = self._episode.batch or self._last_batch      # the rows of THIS rollout (episode metrics, counters)
+        early = self._episode.take(mbatch)
+        cm = self._metrics_from_sums(early) if early is not None else self.episode_metrics(mbatch)
         agent_steps = self._counters[NUM_AGENT_STEPS_SAMPLED]
         result = dict(
             training_iteration=self.iteration, timesteps_total=self._counters[NUM_ENV_STEPS_SAMPLED],
@@ -1204,11 +1253,9 @@ class VecTrainer:
             self.env.close()
         except Exception:
             pass
-        for name in ("_tile",):
-            peer = getattr(self.policy, name, None)
-            if peer is not None:
-                peer.close()
-                setattr(self.policy, name, None)
+        if self.policy._tile is not None:
+            self.policy._tile.close()
+            self.policy._tile = None
 
 
 class _LocalWorker:

@@ -436,7 +436,7 @@ def test_batched_meta_pass_equals_sequential_steps(nb, store):
 
 def test_run_meta_deferred_read_with_riders_and_early_row_store():
     """Round 6: `run_meta(defer=True, extra=...)` queues everything and returns a callable that does the ONE host read (the riders'
-    values land in `_extra_host`); `meta_rows_early` queues the row store ahead of the call.  Both must give what the plain call gives:
+    values and the raw advantage moments come back in its `parts`, by name); `meta_rows_early` queues the row store ahead of the call.  Both must give what the plain call gives:
     same seeds -> the same LCF parameters, Adam state and reported values, bit for bit (the same kernels in the same order), and the
     reported LCF mean / std are the model's formulas applied to the parameters."""
     import math
@@ -457,11 +457,13 @@ def test_run_meta_deferred_read_with_riders_and_early_row_store():
                 outs.append(pol.run_meta(idx, R, [R], mb, 3))
             else:
                 assert pol.meta_rows_early(mb, 3) == (rep == 1)
-                riders = [torch.arange(3, device="cuda", dtype=torch.float32) + rep, torch.tensor([7.5], device="cuda", dtype=torch.float64)]
+                riders = dict(ramp=torch.arange(3, device="cuda", dtype=torch.float32) + rep,
+                              one=torch.tensor([7.5], device="cuda", dtype=torch.float64))
                 pending = pol.run_meta(idx, R, [R], mb, 3, defer=True, extra=riders)
                 assert callable(pending)
                 outs.append(pending())
-                assert pol._extra_host == [[0.0 + rep, 1.0 + rep, 2.0 + rep], [7.5]]
+                assert [pending.parts[k] for k in riders] == [[0.0 + rep, 1.0 + rep, 2.0 + rep], [7.5]]
+                assert pending.parts["raw_adv"] == [0.1, 1.4] and pending() is outs[-1]
     a, b = pols
     assert torch.equal(a.model.lcf_parameters, b.model.lcf_parameters) and torch.equal(a._lcf_adam, b._lcf_adam)
     for rep in range(2):

@@ -838,11 +838,64 @@ def test_copo_iteration_has_one_host_read_of_results_and_early_metric_sums():
                                    num_sgd_iter=2, lcf_num_iters=2, seed=5))
     for _ in range(4):
         res = algo.train()
-        late = algo.episode_metrics(algo._metrics_batch)
-        assert algo._metric_sums is None                      # consumed by train()
+        late = algo.episode_metrics(algo._episode.batch)
+        assert algo._episode.sums is None and algo._episode.take(algo._episode.batch) is None      # consumed by train()
         for k, v in late.items():
             assert res["custom_metrics"][k] == v, (k, res["custom_metrics"][k], v)
         st = res["info"]["learner"]["default"]["learner_stats"]
         meta = res["info"]["learner"]["default"]["custom_metrics"]["meta_update"]
         assert np.isfinite(st["total_loss"]) and np.isfinite(st["kl"]) and np.isfinite(meta["lcf"]) and meta["lcf_std"] > 0
+    algo.stop()
+
+
+def test_host_reads_of_a_copo_iteration_and_evaluate_behind_collect(monkeypatch):
+    """`hostread.HostRead` on the device, and the two places of an iteration that depend on it.
+    A started read (asynchronous copy into pinned memory, its own event) gives what an unstarted one gives on the same tensors, and
+    writes to its sources on the same stream after `start()` do not reach it.  A single-process CoPO iteration resolves exactly two
+    reads: the PPO statistics, and the meta read with the episode sums riding along.  `evaluate()` directly behind `collect()` waits
+    for the rollout's queued episode sums before its fragments rewrite the rollout buffers: what `train()` would have reported for
+    that rollout is `episode_metrics` of a copy of its rows taken before `evaluate()`."""
+    from copo_amd.hostread import HostRead
+    from copo_amd.torch_copo.algo_copo import CoPOTrainer
+    from copo_amd.torch_copo.utils.env_wrappers import MultiAgentIntersectionEnv, get_lcf_env, get_rllib_compatible_env
+    f64 = dict(device="cuda", dtype=torch.float64)
+    # several parts (packed by one cat) and a single part (the read holds the source tensor itself)
+    for make in (lambda: [("a", torch.arange(5, **f64) * 0.25), ("none", torch.zeros(0, **f64)), ("b", torch.tensor([3.5, -1.0], **f64))],
+                 lambda: [("m", torch.arange(8, device="cuda", dtype=torch.float32) / 3)]):
+        src = make()
+        values = {k: t.tolist() for k, t in src}
+        plain, started = HostRead(src), HostRead(src)
+        want = plain.get()
+        torch.cuda._sleep(2_000_000)             # (about a millisecond: the copy and the writes are both queued before either runs)
+        started.start()
+        for _, t in src:
+            t.add_(100.0)
+        got = started.get()
+        assert got == want == values, (got, want, values)
+        assert started.get() is got and started._pin.buf.is_pinned()
+        assert all(t.tolist() != values[k] for k, t in src if t.numel())
+
+    env = get_rllib_compatible_env(get_lcf_env(MultiAgentIntersectionEnv))
+    algo = CoPOTrainer(config=dict(env=env, env_config=dict(num_agents=10), num_envs=8, train_batch_size=64, sgd_minibatch_size=128,
+                                   num_sgd_iter=2, lcf_num_iters=2, seed=11))
+    reads, real = [], HostRead._read
+    monkeypatch.setattr(HostRead, "_read", lambda self: reads.append(self.names) or real(self))
+    for _ in range(2):
+        del reads[:]
+        res = algo.train()
+        assert reads == [["means"], ["stats", "lcf_parameters", "raw_adv", "episode_sums"]], reads
+        assert res["custom_metrics"]["num_acting_rows"] > 0
+    monkeypatch.undo()
+
+    algo.collect()
+    rollout = algo._episode.batch
+    keys = (SampleBatch.FLAGS, "infos", "nbr_cnt")
+    before = SampleBatch({k: rollout[k].clone() for k in keys})
+    algo.evaluate(num_fragments=2)
+    assert not torch.equal(rollout["infos"], before["infos"])              # (the fragments did rewrite the rollout's buffers)
+    reported = algo._metrics_from_sums(algo._episode.take(rollout))
+    want = algo.episode_metrics(before)
+    assert want["num_acting_rows"] > 0 and reported.keys() == want.keys()
+    for k, v in want.items():
+        assert reported[k] == v, (k, reported[k], v)
     algo.stop()
