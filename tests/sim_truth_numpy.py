@@ -183,13 +183,13 @@ def road_decisions(cfg, tables, route, road, x, y, heading):
     to_left, to_right = 0.5 * w - lat, (lanes - 0.5) * w + lat     # distance of the centre to the two edges of the road
     need_left = cfg.body_margin * across if code & 2 else (-w if code & 1 else 0.0)
     need_right = cfg.body_margin * across if code & 4 else 0.0
-    out_margin = min(to_left - need_left, to_right - need_right)
+    out_margin = out_margin_narrow = min(to_left - need_left, to_right - need_right)      # (narrow: without a funnel's extra width)
     if float(rec[5]) == 0.0 and float(rec[12]) != 0.0:
         out_margin = float("nan")
     lane = min(max(int(math.floor(-lat / w + 0.5)), 0), lanes - 1)
     lane_margin = min([abs(-lat - (i + 0.5) * w) for i in range(lanes - 1)], default=np.inf)
     return dict(road=road, long=lon, lat=lat, psi=psi, lanes=lanes, lane=lane, lane_margin=lane_margin, out_margin=out_margin,
-                long_margin=long_margin, length=float(rec[4]), prog=float(rec[6]) + lon, total=float(tables.route_meta[route, 0]))
+                out_margin_narrow=out_margin_narrow, long_margin=long_margin, length=float(rec[4]), prog=float(rec[6]) + lon, total=float(tables.route_meta[route, 0]))
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
