@@ -94,6 +94,9 @@ _SIGS = {
     "copo_lin_obs_seats_f32": (C.c_int, [C.POINTER(PpoCfg), C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p,
                                          C.c_int64, C.c_int64] + [C.c_void_p] * 3 + [C.c_int32] * 3 + [C.c_void_p, C.c_int32, C.c_void_p,
                                          C.c_void_p, C.c_int32, C.c_float, C.c_void_p]),
+    "copo_jury_obs_seats_f32": (C.c_int, [C.POINTER(PpoCfg), C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p,
+                                          C.c_int64, C.c_int64] + [C.c_void_p] * 3),
+    "copo_jury_tally": (C.c_int, [C.c_void_p] * 6 + [C.c_int32] * 4 + [C.c_float] * 2 + [C.c_void_p, C.c_void_p]),
     "copo_seat_tally": (C.c_int, [C.c_void_p] * 4 + [C.c_int32] * 4 + [C.c_void_p, C.c_void_p]),
     "copo_certify_tally": (C.c_int, [C.c_void_p] * 6 + [C.c_int32] * 5 + [C.c_void_p, C.c_void_p]),
     "copo_fault_obs": (C.c_int, [C.c_void_p] * 2 + [C.c_int32] * 5 + [C.c_void_p] * 2 + [C.c_int32] * 2 + [C.c_void_p] * 2 + [C.c_int32, C.c_void_p,

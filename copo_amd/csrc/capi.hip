@@ -486,6 +486,20 @@ extern "C" int copo_certify_tally(const uint8_t* flags, const float* bounds, con
     return COPO_OK;
 }
 
+extern "C" int copo_jury_tally(const uint8_t* flags, const float* dist, const float* verdict, const int32_t* seat, const int32_t* group,
+                               const int32_t* judges, int32_t E, int32_t N, int32_t K, int32_t G, float delta_steer, float delta_throttle,
+                               int64_t* out, void* stream) {
+    if (!flags || !dist || !verdict || !seat || !group || !judges || !out) return fail(COPO_ERR_NULL, "copo_jury_tally: NULL argument");
+    if (E < 0 || N < 1 || N > COPO_SEAT_MAX_SLOTS || K < 1 || K > 65535 || G < 1)
+        return fail(COPO_ERR_DIM, "copo_jury_tally: E=%d N=%d (1..%d) K=%d (1..65535) G=%d (>= 1)", E, N, COPO_SEAT_MAX_SLOTS, K, G);
+    if (((reinterpret_cast<uintptr_t>(dist) | reinterpret_cast<uintptr_t>(verdict)) & 15) != 0)
+        return fail(COPO_ERR_DIM, "copo_jury_tally: dist and verdict must be 16-byte aligned (their rows are read as one 128-bit word)");
+    if (E == 0) return COPO_OK;
+    HIP_TRY(launch_jury_tally(flags, dist, verdict, seat, group, judges, E, N, K, G, delta_steer, delta_throttle, out,
+                              static_cast<hipStream_t>(stream)));
+    return COPO_OK;
+}
+
 // what copo_fault_obs and copo_fault_act share: the keys of a row's level.  Every refusal is -1 with the entry point's name.
 static int check_fault(const char* name, int32_t E, int32_t N, const void* seat, const void* group, int32_t K, int32_t G,
                        const void* level_of, const void* levels, int32_t L, const void* tick) {

@@ -18,6 +18,7 @@
 //      learn_pgd.inc: pgd_obs_kernel, that pass iterated in one resident workgroup (projected gradient descent on the input row);
 //      learn_certify.inc: cert_obs_kernel, interval bounds of the action means over an L-infinity box of the input row
 //      learn_linbound.inc: lin_obs_kernel, linear bounds of the same means (one relaxation per tanh unit, carried backward), intersected with them
+//      learn_jury.inc: jury_obs_kernel, the forward of every JUDGE of a row into a plane of its own (a row may stand in many members' lists)
 //   5. LCF meta kernels: meta_lcf / meta_finish (step by step), meta_batch_fold / dot / rowstat, meta_seq (all LCF
 //      Adam steps of a pass in one workgroup)
 //   6. reduce_adam_kernel (fold of row-split partials + Adam; legacy two-net meta step), wgrad_adam_kernel (weight
@@ -48,6 +49,7 @@ namespace copo {
 #include "learn_pgd.inc"
 #include "learn_certify.inc"
 #include "learn_linbound.inc"
+#include "learn_jury.inc"
 #include "learn_meta.inc"
 #include "learn_update.inc"
 #include "learn_plan.inc"
@@ -379,6 +381,25 @@ extern "C" int copo_lin_obs_seats_f32(const copo_ppo_cfg* cfg, const float* thet
                                       int32_t n_levels, float pad, void* stream) {
     LinArgs a{COPO_SEAT_HEAD, bounds, parts, pad};
     return seat_pass_launch(cfg, a.h, bounds, pad_ok(pad), K_LIN_1_4, lin_lds_floats, LDS_LINBOUND, &a, stream);
+}
+
+// The jury pass: seat mode's launch shape with a list per JUDGE; none of the level tables of the four passes above, so its checks are its own.
+extern "C" int copo_jury_obs_seats_f32(const copo_ppo_cfg* cfg, const float* theta, const float* theta_t, int64_t member_stride,
+                                       int32_t n_members, const int64_t* rows, const int32_t* counts, int64_t cap, int64_t n_out,
+                                       const float* obs_src, float* verdict, void* stream) {
+    int rc = check_cfg(cfg);
+    if (rc != COPO_OK) return rc;
+    if (!theta || !theta_t || !rows || !counts || !obs_src || !verdict) return COPO_ERR_NULL;
+    if (cap < 1 || n_out < 1 || n_members < 1 || n_members > 65535 || member_stride < cfg->n_params || member_stride % 4 != 0) return COPO_ERR_DIM;
+    Launch l;      // (plan_seat_pass refuses the bfloat16 operand mode, as it does for the adversary pass)
+    rc = plan_seat_pass(*cfg, cap, n_members, aligned16(theta_t) ? FACT_MIRROR_ALIGNED : 0, K_JURY_1_4,
+                        jury_lds_floats(cfg->hidden, rowpass_k1p(cfg->pol.in_dim)), LDS_ROWPASS, &l);
+    if (rc != COPO_OK) return rc;
+    if (gemm_lds_attrs() != hipSuccess) return COPO_ERR_DEVICE;
+    JuryArgs a{SeatHead{*cfg, theta, theta_t, member_stride, rows, counts, cap, n_out, obs_src, 0, 0, 1, nullptr, 0, nullptr, nullptr, 0, n_members},
+               verdict};
+    void* args[] = {&a};
+    return launch_kernel(l, args, static_cast<hipStream_t>(stream)) == hipSuccess ? COPO_OK : COPO_ERR_DEVICE;
 }
 
 extern "C" int copo_mlp_forward_rows_f32(const copo_ppo_cfg* cfg, const float* theta, const float* theta_t,

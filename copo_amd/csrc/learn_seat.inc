@@ -2,6 +2,7 @@
 // (learn_pgd.inc), cert_obs_kernel (learn_certify.inc) and lin_obs_kernel (learn_linbound.inc).  SeatHead is the head of their argument
 // structs (the host fills and checks it once, seat_pass_launch in learn_fused.hip); the functions below are the prologue of a 16-row
 // tile of member k's list.  Each kernel keeps its own mode decision and level-word reads, and everything from its first barrier on.
+// jury_obs_kernel (learn_jury.inc) takes the same head and prologue with the group / level fields unused.
 // ------------------------------------------------------------------------------------------------------------
 struct SeatHead {
     copo_ppo_cfg c;

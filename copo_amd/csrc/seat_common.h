@@ -13,4 +13,9 @@ hipError_t launch_seat_tally(const uint8_t* flags, const float* rew, const int32
 hipError_t launch_certify_tally(const uint8_t* flags, const float* bounds, const int32_t* seat, const int32_t* group, const int32_t* level_of,
                                 const float* levels, int32_t E, int32_t N, int32_t K, int32_t G, int32_t L, int64_t* out, hipStream_t stream);
 
+// one step's jury verdicts folded per (scene group, driving member, judging member) into out[G][K][K][COPO_JURY_WORDS] (one launch)
+hipError_t launch_jury_tally(const uint8_t* flags, const float* dist, const float* verdict, const int32_t* seat, const int32_t* group,
+                             const int32_t* judges, int32_t E, int32_t N, int32_t K, int32_t G, float delta_steer, float delta_throttle,
+                             int64_t* out, hipStream_t stream);
+
 }  // namespace copo

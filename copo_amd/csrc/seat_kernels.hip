@@ -151,6 +151,102 @@ __global__ __launch_bounds__(256) void certify_tally_kernel(const uint8_t* __res
     }
 }
 
+// Jury tally (copo_jury_tally): one step's verdicts (copo_jury_obs_seats_f32) against the driver's own distribution
+// inputs, folded per (scene group, driving member, judging member).  The wave walk is seat_tally_kernel's, once per judge of the scene's
+// group (the judge loop is uniform over the wave: judges[g] is the scene's); the words are counts, sums of values quantised once per
+// pair and one 64-bit atomic max, so the result does not depend on the order.
+namespace {
+
+// q of the header for an fp32 value: NaN counts as 0, the clamp makes the product exact, rintf rounds once
+__device__ inline int64_t jury_q16(float x) {
+    if (x != x) return 0;
+    return (int64_t)rintf(fminf(fmaxf(x, 0.0f), 1024.0f) * 65536.0f);
+}
+// ... and for a float64 value (the two divergences)
+__device__ inline int64_t jury_q16(double x) {
+    if (x != x) return 0;
+    return (int64_t)rint(fmin(fmax(x, 0.0), 1024.0) * 65536.0);
+}
+
+// KL(p || q) of two diagonal Gaussians over the two action axes, (mean, log-std) in fp32, evaluated in float64 as the header states it;
+// no contraction, so that the float64 restatement of the tests differs by the last ulp of exp at the most
+__device__ inline double jury_kl(const float4& p, const float4& q) {
+#pragma clang fp contract(off)
+    const double mp[2] = {p.x, p.y}, sp[2] = {p.z, p.w}, mq[2] = {q.x, q.y}, sq[2] = {q.z, q.w};
+    double kl = 0.0;
+#pragma unroll
+    for (int a = 0; a < 2; ++a) {
+        const double dm = mp[a] - mq[a];
+        kl = kl + ((sq[a] - sp[a]) + (0.5 * (exp(2.0 * (sp[a] - sq[a])) + dm * dm * exp(-2.0 * sq[a])) - 0.5));
+    }
+    return kl;
+}
+
+}  // namespace
+
+__global__ __launch_bounds__(256) void jury_tally_kernel(const uint8_t* __restrict__ flags, const float* __restrict__ dist,
+                                                         const float* __restrict__ verdict, const int32_t* __restrict__ seat,
+                                                         const int32_t* __restrict__ group, const int32_t* __restrict__ judges, int32_t E,
+                                                         int32_t N, int32_t K, int32_t G, float delta_steer, float delta_throttle,
+                                                         int64_t* __restrict__ out) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int e = blockIdx.x * SCENES_PER_WG + wave;
+    if (e >= E) return;                        // (the whole wave; there is no barrier in this kernel)
+    const int g = group[e];
+    if (g < 0 || g >= G) return;               // (the whole wave)
+    for (int j = 0; 64 * j < N; ++j) {
+        const int n = lane + 64 * j;
+        const size_t idx = (size_t)e * N + (n < N ? n : 0);
+        const int s = n < N ? seat[idx] : -1;
+        const bool counted = s >= 0 && s < K && ((uint32_t)flags[idx] & COPO_F_ACTED) != 0u;
+        if (!__ballot(counted)) continue;      // (uniform)
+        const float4 own = counted ? *reinterpret_cast<const float4*>(dist + idx * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
+        for (int jj = 0; jj < K; ++jj) {
+            if (judges[(size_t)g * K + jj] == 0) continue;      // (uniform: one word per wave)
+            int64_t q0 = 0, q1 = 0, qs = 0, qkl = 0, qlk = 0, qmx = 0;
+            bool apart = false;
+            if (counted) {
+                const float4 v = *reinterpret_cast<const float4*>(verdict + (idx * K + jj) * 4);
+                const float d0 = fabsf(__fsub_rn(v.x, own.x)), d1 = fabsf(__fsub_rn(v.y, own.y));
+                const float ds = __fadd_rn(fabsf(__fsub_rn(v.z, own.z)), fabsf(__fsub_rn(v.w, own.w)));
+                apart = d0 > delta_steer || d1 > delta_throttle;
+                q0 = jury_q16(d0);
+                q1 = jury_q16(d1);
+                qs = jury_q16(ds);
+                qkl = jury_q16(jury_kl(own, v));
+                qlk = jury_q16(jury_kl(v, own));
+                qmx = jury_q16(fmaxf(d0, d1));
+            }
+            uint64_t todo = __ballot(counted);      // lanes with something to add; uniform over the wave
+            while (todo) {
+                const int m = __shfl(s, __ffsll((unsigned long long)todo) - 1);          // a served lane is seated: 0 <= m < K
+                const bool mine = counted && s == m;
+                todo &= ~__ballot(mine);
+                const int c_pairs = __popcll(__ballot(mine)), c_apart = __popcll(__ballot(mine && apart));
+                const int64_t s0 = wave_sum_i64(mine ? q0 : 0), s1 = wave_sum_i64(mine ? q1 : 0), ss = wave_sum_i64(mine ? qs : 0);
+                const int64_t skl = wave_sum_i64(mine ? qkl : 0), slk = wave_sum_i64(mine ? qlk : 0), mx = wave_max_i64(mine ? qmx : 0);
+                if (lane < COPO_JURY_WORDS) {
+                    const int64_t v = lane == 0 ? c_pairs : lane == 1 ? c_apart : lane == 2 ? s0 : lane == 3 ? s1 : lane == 4 ? ss
+                                    : lane == 5 ? skl : lane == 6 ? slk : mx;
+                    unsigned long long* at = reinterpret_cast<unsigned long long*>(out) + (((size_t)g * K + m) * K + jj) * COPO_JURY_WORDS + lane;
+                    if (v != 0) {
+                        if (lane == 7) atomicMax(at, (unsigned long long)v);
+                        else atomicAdd(at, (unsigned long long)v);
+                    }
+                }
+            }
+        }
+    }
+}
+
+hipError_t launch_jury_tally(const uint8_t* flags, const float* dist, const float* verdict, const int32_t* seat, const int32_t* group,
+                             const int32_t* judges, int32_t E, int32_t N, int32_t K, int32_t G, float delta_steer, float delta_throttle,
+                             int64_t* out, hipStream_t stream) {
+    hipLaunchKernelGGL(jury_tally_kernel, dim3((E + SCENES_PER_WG - 1) / SCENES_PER_WG), dim3(256), 0, stream, flags, dist, verdict, seat, group,
+                       judges, E, N, K, G, delta_steer, delta_throttle, out);
+    return hipGetLastError();
+}
+
 hipError_t launch_certify_tally(const uint8_t* flags, const float* bounds, const int32_t* seat, const int32_t* group, const int32_t* level_of,
                                 const float* levels, int32_t E, int32_t N, int32_t K, int32_t G, int32_t L, int64_t* out, hipStream_t stream) {
     hipLaunchKernelGGL(certify_tally_kernel, dim3((E + SCENES_PER_WG - 1) / SCENES_PER_WG), dim3(256), 0, stream, flags, bounds, seat, group,

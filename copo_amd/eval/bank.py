@@ -165,6 +165,22 @@ class PolicyBank:
                          ("parts", parts, (n_out, 8), torch.float32)), col_lo, col_hi, (bounds, parts) if linear else (bounds,), (float(pad),))
 
 
+    def jury_seats(self, jury_buffers, obs, verdict):
+        """`copo_jury_obs_seats_f32` (eval/jury.py) on the current stream: obs [n_out, O] -> verdict [n_out, K, 4], the four
+        distribution inputs of every JUDGE j on the rows of its list in `jury_buffers` (`jury.JuryBuffers`: rows [K][cap], counts [K]
+        on the device; a row may stand in many lists), the bits `act_seats` writes to `dist_inputs` for that member on that row.
+        Entries that no list names are left alone.  Needs the mirror (`sync_mirror`), as `act_seats`."""
+        jb = jury_buffers
+        if jb.K != self.K:
+            raise ValueError("PolicyBank.jury_seats: judges' lists for %d members and a bank of %d" % (jb.K, self.K))
+        for name, t, shape in (("obs", obs, (jb.n_out, int(self.cfg.pol.in_dim))), ("verdict", verdict, (jb.n_out, self.K, 4))):
+            if tuple(t.shape) != shape or not t.is_contiguous() or t.dtype != torch.float32:
+                raise ValueError("PolicyBank.jury_seats: %s of shape %s, contiguous float32 %s wanted" % (name, tuple(t.shape), list(shape)))
+        self._capi.check(self._capi.lib.copo_jury_obs_seats_f32(
+            C.byref(self.cfg), self.theta.data_ptr(), self.theta_t.data_ptr(), self.stride, self.K, jb.rows.data_ptr(), jb.counts.data_ptr(),
+            jb.cap, jb.n_out, obs.data_ptr(), verdict.data_ptr(), self._capi.current_stream()))
+
+
 class _BankPolicy:
     """What `VecSampler` reads of a policy, with the bank as its fused learner."""
 

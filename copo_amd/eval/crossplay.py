@@ -175,6 +175,12 @@ class SeatedBank:
         """`PolicyBank.certify_seats` over the plan's own buffers (eval/certify.py)."""
         self.bank.certify_seats(self.buffers, cert_buffers, obs, bounds, col_lo, col_hi, pad, method, parts)
 
+    def jury_seats(self, jury_buffers, obs, verdict):
+        """`PolicyBank.jury_seats` on the rows of the plan (eval/jury.py): the judges' lists must cover the plan's [E * N] rows."""
+        if jury_buffers.n_out != self.buffers.n_out:
+            raise ValueError("SeatedBank.jury_seats: judges' lists over %d rows, the plan has %d" % (jury_buffers.n_out, self.buffers.n_out))
+        self.bank.jury_seats(jury_buffers, obs, verdict)
+
 
 class SeatSampler(VecSampler):
     """`VecSampler` with a `SeatedBank` in the policy's place, as `BankSampler` puts a bank there, and the seat tally behind every

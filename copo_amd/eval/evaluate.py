@@ -327,8 +327,33 @@ def main(argv=None):
     ap.add_argument("--certify-method", default="interval", choices=("interval", "linear"),
                     help="with --certify-sweep: interval propagation (default) or the tighter linear bounds intersected with it; "
                          "\"linear\" adds a `method` column to the table")
+    ap.add_argument("--jury", nargs="+", default=None, metavar="CKPT",
+                    help="checkpoints of --algo's layout on the scenes of --cross-play, each row judged by the others (eval/jury.py: how far "
+                         "apart the drivers' and the judges' action distributions are): one row per (pair, driver, judge) into --table; "
+                         "takes --share, --scenes-per-pair and --steps")
+    ap.add_argument("--jury-plan", default="everyone", choices=("everyone", "seated"),
+                    help="with --jury: every checkpoint judges every row (default), or focal and partner judge the rows of their pair")
+    ap.add_argument("--jury-deltas", type=float, nargs=2, default=None, metavar=("STEER", "THROTTLE"),
+                    help="with --jury: the distances of the two action means above which a pair counts as a disagreement (default 0.05 0.05)")
     a = ap.parse_args(argv)
     from .checkpoint_io import load_members
+    if (a.jury_plan != "everyone" or a.jury_deltas is not None) and not a.jury:
+        ap.error("--jury-plan and --jury-deltas go with --jury")
+    if a.jury:
+        if a.cross_play or a.fault_sweep or a.adversary_sweep or a.pgd_sweep or a.certify_sweep:
+            ap.error("--jury excludes --cross-play, --fault-sweep, --adversary-sweep, --pgd-sweep and --certify-sweep: one table per run")
+        if not a.table:
+            ap.error("--jury needs --table")
+        deltas = (0.05, 0.05) if a.jury_deltas is None else tuple(a.jury_deltas)
+        if not all(d >= 0.0 and d == d and d != float("inf") for d in deltas):
+            ap.error("--jury-deltas: two finite numbers >= 0 wanted")
+        from .jury import jury_matrix, jury_rows
+        df = jury_rows("ippo" if a.algo == "cl" else a.algo, a.env, load_members(a.jury), plan=a.jury_plan, share=0.5 if a.share is None else a.share,
+                       deltas=deltas, scenes_per_pair=a.scenes_per_pair, num_agents=a.num_agents, steps=a.steps, labels=list(a.jury))
+        df.to_csv(a.table)
+        print(df.drop(columns=["driver_label", "judge_label"]).to_string())
+        print(jury_matrix(df, len(a.jury)).to_string())
+        return
     if a.certify_method != "interval" and not a.certify_sweep:
         ap.error("--certify-method goes with --certify-sweep")
     if a.certify_sweep:

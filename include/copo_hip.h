@@ -462,6 +462,29 @@ int copo_seat_tally(const uint8_t* flags, const float* rew, const int32_t* seat,
 int copo_certify_tally(const uint8_t* flags, const float* bounds, const int32_t* seat, const int32_t* group, const int32_t* level_of,
                        const float* levels, int32_t E, int32_t N, int32_t K, int32_t G, int32_t L, int64_t* out, void* stream);
 
+/* ---- jury tally: one step's verdicts (copo_jury_obs_seats_f32) against the driver's own distribution inputs,
+ * folded per (scene group, driving member, judging member).  Stateless.  flags device [E][N] uint8 (the step's output), dist device
+ * [E][N][4] fp32 (mu_steer, mu_throttle, logstd_steer, logstd_throttle of the member that drives the slot: the forward's dist_inputs),
+ * verdict device [E N][K][4] fp32 (the same four numbers by judge j at [row][j]), seat / group as copo_seat_tally, judges device [G][K]
+ * int32 (nonzero: member j judges the rows of group g), out device [G][K][K][COPO_JURY_WORDS] int64.  A (slot, judge j) pair counts
+ * where 0 <= seat < K, 0 <= group[e] < G, the slot's flags carry COPO_F_ACTED and judges[group[e]][j] != 0; it is added at
+ * out[group[e]][k = seat][j].  With d_a = |mu_a(judge) - mu_a(driver)| in fp32 (the difference rounded once) and q(x) =
+ * rint(min(max(x, 0), 1024) * 65536) as int64 (one rounding, half to even; NaN counts as 0) the words are: [0] pairs counted; [1] pairs
+ * with d_0 > delta_steer or d_1 > delta_throttle (a NaN exceeds nothing); [2] / [3] the sums of q(d_0) / q(d_1); [4] the sum of
+ * q(|dlogstd_0| + |dlogstd_1|), either difference and then their sum rounded once in fp32; [5] the sum of q(KL(driver || judge)); [6] the
+ * sum of q(KL(judge || driver)); [7] the largest q(max(d_0, d_1)) (fmaxf: a NaN yields to the other axis; a 64-bit atomic max).
+ * KL of the two diagonal Gaussians, in float64 from the fp32 inputs (m: mean, s: log-std), added over a = 0, 1 in this order and form:
+ *     KL(p || q) = sum_a (s_q - s_p) + (0.5 (exp(2 (s_p - s_q)) + (m_p - m_q)^2 exp(-2 s_q)) - 0.5)
+ * and quantised in float64 by the same q.  Equal bits on both sides give zero in the words 1 .. 7.  `out` ACCUMULATES (the caller clears
+ * it; word 7 keeps the largest); integers only, so the result does not depend on the order.  One launch on the caller's stream, no
+ * allocation, no host synchronisation; may be captured in a graph.  NULL flags / dist / verdict / seat / group / judges / out:
+ * COPO_ERR_NULL; E >= 0, N in 1..COPO_SEAT_MAX_SLOTS, K in 1..65535, G >= 1, dist and verdict 16-byte aligned (COPO_ERR_DIM); a refused
+ * call launches nothing. */
+#define COPO_JURY_WORDS 8
+int copo_jury_tally(const uint8_t* flags, const float* dist, const float* verdict, const int32_t* seat, const int32_t* group,
+                    const int32_t* judges, int32_t E, int32_t N, int32_t K, int32_t G, float delta_steer, float delta_throttle,
+                    int64_t* out, void* stream);
+
 /* ---- fault injection: noisy sensors between the simulator's observation and the policy, noisy and sticky
  *      actuators between the policy's action and the simulator.  Two stateless entry points; each is one launch on the caller's stream,
  *      allocates nothing and reads nothing on the host, so both may be captured in a graph.  The simulator knows nothing of them.
@@ -1052,6 +1075,22 @@ int copo_lin_obs_seats_f32(const copo_ppo_cfg* cfg, const float* theta, const fl
                            const float* obs_src, float* bounds, float* parts, int32_t col_lo, int32_t col_hi, int32_t n_slots,
                            const int32_t* group, int32_t n_groups, const int32_t* level_of, const float* levels,
                            int32_t n_levels, float pad, void* stream);
+/* The jury pass of a seated bank (eval/jury.py): the third mode of the bank's forward.  The dense bank gives every
+ * member its own rows and seat mode gives a row to ONE member; here a row may be judged by many, and each judge's distribution inputs
+ * land in a plane of their own.  Member j is a judge and owns the list rows[j cap .. j cap + counts[j]) of [0, n_out) (rows device
+ * [n_members][cap] int64, counts device [n_members] int32; a row may stand in the lists of several judges, at most once per list; an
+ * index outside [0, n_out) is skipped).  Judge j reads the true row obs_src[r] ([n_out][pol.in_dim]), runs its own policy net on it
+ * (theta + j member_stride, the mirror theta_t alike) and writes mu_steer, mu_throttle, logstd_steer, logstd_throttle to
+ * verdict[r][j][0..4); verdict device fp32 [n_out][n_members][4], 16-byte aligned.  Entries that no list names are not written.
+ * verdict[r][j] holds the bits copo_mlp_forward_seats_f32 writes to dist_inputs[r] when member j's list there contains r, at every
+ * hidden width it supports and whichever other rows share r's tile.  No sampling, no action, no eps.  One launch, grid ceil(cap / 16) x
+ * n_members, always the one-tile kernel, fp32 operands; a workgroup past its judge's count leaves before any weight load; no atomics,
+ * fixed summation order: two launches give the same bits.  NULL theta / theta_t / rows / counts / obs_src / verdict: COPO_ERR_NULL;
+ * cap < 1, n_out < 1, n_members outside 1..65535, member_stride below cfg->n_params or no multiple of 4, bfloat16 operands, a hidden
+ * width outside {64, 128, 256, 512}, a mirror that is not 16-byte aligned: COPO_ERR_DIM.  A refused call launches nothing. */
+int copo_jury_obs_seats_f32(const copo_ppo_cfg* cfg, const float* theta, const float* theta_t, int64_t member_stride,
+                            int32_t n_members, const int64_t* rows, const int32_t* counts, int64_t cap, int64_t n_out,
+                            const float* obs_src, float* verdict, void* stream);
 /* The same pass over a LIST of rows: launch row m reads row rows[m] of the sources ([n_src_rows][..]) and writes
  * values[net][rows[m]] (values is [n_nets][n_src_rows]; entries of unlisted rows are left alone).  The dense postprocess
  * of a rollout buffer uses it with the rows that hold an agent -- about half of the slots. */
