@@ -97,6 +97,10 @@ _SIGS = {
     "copo_jury_obs_seats_f32": (C.c_int, [C.POINTER(PpoCfg), C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p,
                                           C.c_int64, C.c_int64] + [C.c_void_p] * 3),
     "copo_jury_tally": (C.c_int, [C.c_void_p] * 6 + [C.c_int32] * 4 + [C.c_float] * 2 + [C.c_void_p, C.c_void_p]),
+    "copo_influence_heading": (C.c_int, [C.c_void_p] * 4),
+    "copo_influence_obs": (C.c_int, [C.c_void_p] * 4 + [C.c_int32] + [C.c_void_p] * 7),
+    "copo_influence_lists": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_void_p, C.c_int32] + [C.c_void_p] * 3),
+    "copo_influence_tally": (C.c_int, [C.c_void_p] * 8 + [C.c_int32] * 5 + [C.c_float] * 2 + [C.c_void_p] * 3),
     "copo_seat_tally": (C.c_int, [C.c_void_p] * 4 + [C.c_int32] * 4 + [C.c_void_p, C.c_void_p]),
     "copo_certify_tally": (C.c_int, [C.c_void_p] * 6 + [C.c_int32] * 5 + [C.c_void_p, C.c_void_p]),
     "copo_fault_obs": (C.c_int, [C.c_void_p] * 2 + [C.c_int32] * 5 + [C.c_void_p] * 2 + [C.c_int32] * 2 + [C.c_void_p] * 2 + [C.c_int32, C.c_void_p,

@@ -25,16 +25,6 @@ __device__ inline int64_t seat_reward_q16(float r) {
     return (int64_t)rintf(fminf(fmaxf(r, -1024.0f), 1024.0f) * 65536.0f);
 }
 
-__device__ inline int64_t wave_sum_i64(int64_t v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) {
-        const int32_t lo = __shfl_xor((int32_t)(uint32_t)((uint64_t)v & 0xffffffffu), o);
-        const int32_t hi = __shfl_xor((int32_t)(uint32_t)((uint64_t)v >> 32), o);
-        v += (int64_t)(((uint64_t)(uint32_t)hi << 32) | (uint64_t)(uint32_t)lo);
-    }
-    return v;
-}
-
 }  // namespace
 
 __global__ __launch_bounds__(256) void seat_tally_kernel(const uint8_t* __restrict__ flags, const float* __restrict__ rew,
@@ -83,17 +73,6 @@ namespace {
 
 // rint(min(max(x, 0), 1024) * 65536): exact product, one rounding (the callers pass finite values)
 __device__ inline int64_t cert_q16(float x) { return (int64_t)rintf(fminf(fmaxf(x, 0.0f), 1024.0f) * 65536.0f); }
-
-__device__ inline int64_t wave_max_i64(int64_t v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) {
-        const int32_t lo = __shfl_xor((int32_t)(uint32_t)((uint64_t)v & 0xffffffffu), o);
-        const int32_t hi = __shfl_xor((int32_t)(uint32_t)((uint64_t)v >> 32), o);
-        const int64_t w = (int64_t)(((uint64_t)(uint32_t)hi << 32) | (uint64_t)(uint32_t)lo);
-        v = w > v ? w : v;
-    }
-    return v;
-}
 
 }  // namespace
 
@@ -154,36 +133,7 @@ __global__ __launch_bounds__(256) void certify_tally_kernel(const uint8_t* __res
 // Jury tally (copo_jury_tally): one step's verdicts (copo_jury_obs_seats_f32) against the driver's own distribution
 // inputs, folded per (scene group, driving member, judging member).  The wave walk is seat_tally_kernel's, once per judge of the scene's
 // group (the judge loop is uniform over the wave: judges[g] is the scene's); the words are counts, sums of values quantised once per
-// pair and one 64-bit atomic max, so the result does not depend on the order.
-namespace {
-
-// q of the header for an fp32 value: NaN counts as 0, the clamp makes the product exact, rintf rounds once
-__device__ inline int64_t jury_q16(float x) {
-    if (x != x) return 0;
-    return (int64_t)rintf(fminf(fmaxf(x, 0.0f), 1024.0f) * 65536.0f);
-}
-// ... and for a float64 value (the two divergences)
-__device__ inline int64_t jury_q16(double x) {
-    if (x != x) return 0;
-    return (int64_t)rint(fmin(fmax(x, 0.0), 1024.0) * 65536.0);
-}
-
-// KL(p || q) of two diagonal Gaussians over the two action axes, (mean, log-std) in fp32, evaluated in float64 as the header states it;
-// no contraction, so that the float64 restatement of the tests differs by the last ulp of exp at the most
-__device__ inline double jury_kl(const float4& p, const float4& q) {
-#pragma clang fp contract(off)
-    const double mp[2] = {p.x, p.y}, sp[2] = {p.z, p.w}, mq[2] = {q.x, q.y}, sq[2] = {q.z, q.w};
-    double kl = 0.0;
-#pragma unroll
-    for (int a = 0; a < 2; ++a) {
-        const double dm = mp[a] - mq[a];
-        kl = kl + ((sq[a] - sp[a]) + (0.5 * (exp(2.0 * (sp[a] - sq[a])) + dm * dm * exp(-2.0 * sq[a])) - 0.5));
-    }
-    return kl;
-}
-
-}  // namespace
-
+// pair and one 64-bit atomic max, so the result does not depend on the order.  (jury_q16 / jury_kl: seat_common.h)
 __global__ __launch_bounds__(256) void jury_tally_kernel(const uint8_t* __restrict__ flags, const float* __restrict__ dist,
                                                          const float* __restrict__ verdict, const int32_t* __restrict__ seat,
                                                          const int32_t* __restrict__ group, const int32_t* __restrict__ judges, int32_t E,

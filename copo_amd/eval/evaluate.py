@@ -335,8 +335,36 @@ def main(argv=None):
                     help="with --jury: every checkpoint judges every row (default), or focal and partner judge the rows of their pair")
     ap.add_argument("--jury-deltas", type=float, nargs=2, default=None, metavar=("STEER", "THROTTLE"),
                     help="with --jury: the distances of the two action means above which a pair counts as a disagreement (default 0.05 0.05)")
+    ap.add_argument("--influence", nargs="+", default=None, metavar="CKPT",
+                    help="checkpoints of --algo's layout on the scenes of --cross-play, every driver's row re-read with one LiDAR neighbour "
+                         "taken out at a time (eval/influence.py: which neighbour a driver reacts to, and how strongly): one row per (pair, "
+                         "member) into --table; takes --share, --scenes-per-pair and --steps")
+    ap.add_argument("--influence-max", type=int, default=None, metavar="M", help="with --influence: neighbours removed per driver, 1..8 (default 4)")
+    ap.add_argument("--influence-deltas", type=float, nargs=2, default=None, metavar=("STEER", "THROTTLE"),
+                    help="with --influence: the shifts of the two action means above which a neighbour counts as one that moved the driver "
+                         "(default 0.05 0.05)")
     a = ap.parse_args(argv)
     from .checkpoint_io import load_members
+    if (a.influence_max is not None or a.influence_deltas is not None) and not a.influence:
+        ap.error("--influence-max and --influence-deltas go with --influence")
+    if a.influence:
+        if a.cross_play or a.fault_sweep or a.adversary_sweep or a.pgd_sweep or a.certify_sweep or a.jury:
+            ap.error("--influence excludes --cross-play, --fault-sweep, --adversary-sweep, --pgd-sweep, --certify-sweep and --jury: one table per run")
+        if not a.table:
+            ap.error("--influence needs --table")
+        M = 4 if a.influence_max is None else a.influence_max
+        if not 1 <= M <= 8:
+            ap.error("--influence-max: 1..8 wanted")
+        deltas = (0.05, 0.05) if a.influence_deltas is None else tuple(a.influence_deltas)
+        if not all(d >= 0.0 and d == d and d != float("inf") for d in deltas):
+            ap.error("--influence-deltas: two finite numbers >= 0 wanted")
+        from .influence import influence_rows
+        df = influence_rows("ippo" if a.algo == "cl" else a.algo, a.env, load_members(a.influence), share=0.5 if a.share is None else a.share,
+                            max_others=M, deltas=deltas, scenes_per_pair=a.scenes_per_pair, num_agents=a.num_agents, steps=a.steps,
+                            labels=list(a.influence))
+        df.to_csv(a.table)
+        print(df.drop(columns=["label"]).to_string())
+        return
     if (a.jury_plan != "everyone" or a.jury_deltas is not None) and not a.jury:
         ap.error("--jury-plan and --jury-deltas go with --jury")
     if a.jury:

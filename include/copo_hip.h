@@ -485,6 +485,51 @@ int copo_jury_tally(const uint8_t* flags, const float* dist, const float* verdic
                     const int32_t* judges, int32_t E, int32_t N, int32_t K, int32_t G, float delta_steer, float delta_throttle,
                     int64_t* out, void* stream);
 
+/* ---- influence graph (eval/influence.py): which neighbour a driver reacts to, and how strongly.  A policy learns
+ *      of other vehicles through the LiDAR block of its observation row alone, so the effect of vehicle j on ego i has an exact
+ *      counterfactual: i's row with j taken out of the scene.  Stateless entry points, one launch each on the caller's stream, no
+ *      allocation, no host synchronisation; all may be captured in a graph.  Each replaces nothing in the reference.
+ * The scene is the simulator's at the moment the policy reads `obs`: after the step or reset that wrote the row, before the next step.
+ * An EGO is a row r = e N + n with seat[r] >= 0 whose slot is ALIVE.  Per beam b of an ego: d_j(b) = the entering distance of the ray
+ * against the box of slot j != n (alive or lingering wreck) by the step's own pair record and ray / box test, `range` for a miss or a hit
+ * not below the range; s(b) = the same minimum over the static boxes the LiDAR sees; min1 = min(s, min_j d_j).  Slot j OWNS b when d_j(b)
+ * == min1(b) < range, s(b) > min1(b) and no lower slot attains the value; min2(b) = the minimum over everything but the owner.  The
+ * CANDIDATES of an ego are the owners of at least one beam, ordered by (smallest owned distance as fp32 bits, slot); the first M are kept,
+ * the rest only counted.  Variant c of row r is row r M + c of obs_cf: every column of obs[r], the LiDAR block replaced by
+ * (owner(b) == who[r][c] ? min2(b) : min1(b)) * inv_range.
+ *
+ * copo_influence_heading (BEFORE a step, with the action the step will read, act device [E][N][act_dim]): heading device [E N][2] fp32 :=
+ * the heading unit vector the step gives every slot (its own dynamics code).  The step's LiDAR reads that vector and the state does not
+ * keep it; without it copo_influence_obs is exact only for vehicles that stood still in the last step.
+ * copo_influence_obs: seat device [E][N] int32, heading device [E N][2] or NULL (a pair of zeros = nothing kept: sin / cos of the stored
+ * heading; a vehicle the last step spawned has its road's vector either way), obs device [E N][O] -> who device [E N][M] int32 (-1 =
+ * none), ncand device [E N] int32 (kept candidates | truncated << 16), ego device [E N] uint8 (COPO_F_ACTED on an ego, else 0: the `flags`
+ * of copo_influence_tally), obs_cf device [E N M][O] (the variant rows that exist; the others are left alone), hit device [E N][M] or
+ * NULL (the candidate's smallest owned distance over the range), clean device [E N][num_lasers] or NULL (min1 * inv_range: the bits of
+ * the simulator's own LiDAR block).  Rows that are not egos get who = -1, ncand = 0, ego = 0.  One wave per row, lanes over beams.
+ * copo_influence_lists: member k's seat list rows[k][0 .. counts[k]) (the seat forward's tables) -> vrows device [K][cap M] int64, the
+ * variant rows r M + c of its egos, ascending, and vcounts device [K] int32: the lists copo_jury_obs_seats_f32 takes on (obs_cf, vrows,
+ * vcounts, cap M, n_out M).  A prefix over lanes and waves decides every position.
+ * copo_influence_tally: with p = dist[r] (the driver's own distribution inputs on obs[r]) and q = verdict_cf[r M + c][seat[r]], d_a =
+ * |q.mu_a - p.mu_a| in fp32, KL(p || q) and q16 as copo_jury_tally defines them, a pair counts for every who[r][c] >= 0 of a row whose
+ * flags carry COPO_F_ACTED with 0 <= seat < K, 0 <= group[e] < G.  out device [G][K][COPO_INFL_WORDS] int64 ACCUMULATES: [0] egos; [1]
+ * pairs; [2] pairs with d_0 > delta_steer or d_1 > delta_throttle; [3] / [4] the sums of q16(d_0) / q16(d_1); [5] the sum of q16(KL);
+ * [6] the largest q16(max(d_0, d_1)) (atomic max); [7] truncated candidates.  edges device [E N][M][4] fp32 or NULL: d_0, d_1, KL and
+ * hit[r][c] of every pair (hit NULL: 0).  Integer atomics only, so the result does not depend on the order.
+ * Refusals: NULL required pointer COPO_ERR_NULL; a simulator never reset COPO_ERR_STATE; M outside 1..COPO_INFL_MAX, K outside 1..65535,
+ * N outside 1..COPO_SEAT_MAX_SLOTS, G < 1, cap < 1, n_out < 1, obs_cf == obs, dist / verdict_cf / edges not 16-byte aligned
+ * COPO_ERR_DIM; a refused call launches nothing. */
+#define COPO_INFL_MAX 8
+#define COPO_INFL_WORDS 8
+int copo_influence_heading(copo_sim* sim, const float* act, float* heading, void* stream);
+int copo_influence_obs(copo_sim* sim, const int32_t* seat, const float* heading, const float* obs, int32_t M, int32_t* who, float* obs_cf,
+                       int32_t* ncand, uint8_t* ego, float* hit, float* clean, void* stream);
+int copo_influence_lists(const int64_t* rows, const int32_t* counts, int32_t K, int64_t cap, int64_t n_out, const int32_t* ncand, int32_t M,
+                         int64_t* vrows, int32_t* vcounts, void* stream);
+int copo_influence_tally(const uint8_t* flags, const float* dist, const float* verdict_cf, const int32_t* who, const int32_t* ncand,
+                         const float* hit, const int32_t* seat, const int32_t* group, int32_t E, int32_t N, int32_t K, int32_t G, int32_t M,
+                         float delta_steer, float delta_throttle, int64_t* out, float* edges, void* stream);
+
 /* ---- fault injection: noisy sensors between the simulator's observation and the policy, noisy and sticky
  *      actuators between the policy's action and the simulator.  Two stateless entry points; each is one launch on the caller's stream,
  *      allocates nothing and reads nothing on the host, so both may be captured in a graph.  The simulator knows nothing of them.

@@ -1,6 +1,6 @@
 """What the observer benchmarks (`bench_interact`, `bench_clips`, `bench_rewind`, `bench_fields`, `bench_gates`, `bench_trips`, `bench_conflicts`, `bench_pet`) share:
 the timing loop, the command line, the scene they measure on and the JSON line they end with; `bench_faults`, `bench_adversary`, `bench_pgd`, `bench_certify` and
-`bench_jury` also take the graph-replay timer from here."""
+`bench_jury` and `bench_influence` also take the graph-replay timer from here."""
 import argparse
 import json
 import os
