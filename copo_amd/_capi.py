@@ -59,6 +59,7 @@ class PpoCfg(C.Structure):
 
 HEAD_PPO, HEAD_META_NEW, HEAD_META_OLD = 0, 1, 2
 OPERAND_F32, OPERAND_BF16 = 0, 1
+LOWP_BF16, LOWP_E4M3 = 1, 2
 PPO_STATS = 8
 META_DOT_PARTIALS = 8192
 
@@ -97,6 +98,11 @@ _SIGS = {
     "copo_jury_obs_seats_f32": (C.c_int, [C.POINTER(PpoCfg), C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p,
                                           C.c_int64, C.c_int64] + [C.c_void_p] * 3),
     "copo_jury_tally": (C.c_int, [C.c_void_p] * 6 + [C.c_int32] * 4 + [C.c_float] * 2 + [C.c_void_p, C.c_void_p]),
+    "copo_lowp_pack": (C.c_int, [C.POINTER(PpoCfg), C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]),
+    "copo_lowp_forward_seats": (C.c_int, [C.POINTER(PpoCfg), C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64,
+                                          C.c_int64] + [C.c_void_p] * 7),
+    "copo_debug_lowp_round": (C.c_int, [C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]),
+    "copo_debug_lowp_scale": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p]),
     "copo_influence_heading": (C.c_int, [C.c_void_p] * 4),
     "copo_influence_obs": (C.c_int, [C.c_void_p] * 4 + [C.c_int32] + [C.c_void_p] * 7),
     "copo_influence_lists": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_void_p, C.c_int32] + [C.c_void_p] * 3),

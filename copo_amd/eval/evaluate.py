@@ -343,8 +343,35 @@ def main(argv=None):
     ap.add_argument("--influence-deltas", type=float, nargs=2, default=None, metavar=("STEER", "THROTTLE"),
                     help="with --influence: the shifts of the two action means above which a neighbour counts as one that moved the driver "
                          "(default 0.05 0.05)")
+    ap.add_argument("--precision-sweep", nargs="+", default=None, metavar="CKPT",
+                    help="checkpoints of --algo's layout, each driven in float32 and in every precision of --precisions (eval/precision.py: "
+                         "the policy net on the bfloat16 / float8 matrix instructions, its float32 twin judging the states it drives): one row "
+                         "per (checkpoint, precision) into --table; takes --share (default 1), --jury-deltas, --scenes-per-pair and --steps")
+    ap.add_argument("--precisions", nargs="+", default=None, choices=("bfloat16", "float8_e4m3"),
+                    help="with --precision-sweep: the low precisions of the sweep (default: both)")
     a = ap.parse_args(argv)
     from .checkpoint_io import load_members
+    if a.precisions is not None and not a.precision_sweep:
+        ap.error("--precisions goes with --precision-sweep")
+    if a.precision_sweep:
+        if a.cross_play or a.fault_sweep or a.adversary_sweep or a.pgd_sweep or a.certify_sweep or a.jury or a.influence:
+            ap.error("--precision-sweep excludes --cross-play, --fault-sweep, --adversary-sweep, --pgd-sweep, --certify-sweep, --jury and --influence: "
+                     "one table per run")
+        if not a.table:
+            ap.error("--precision-sweep needs --table")
+        deltas = (0.05, 0.05) if a.jury_deltas is None else tuple(a.jury_deltas)
+        if not all(d >= 0.0 and d == d and d != float("inf") for d in deltas):
+            ap.error("--jury-deltas: two finite numbers >= 0 wanted")
+        low = ("bfloat16", "float8_e4m3") if a.precisions is None else tuple(a.precisions)
+        if len(set(low)) != len(low):
+            ap.error("--precisions: a precision twice")
+        from .precision import precision_sweep_rows
+        df = precision_sweep_rows("ippo" if a.algo == "cl" else a.algo, a.env, load_members(a.precision_sweep), precisions=("float32",) + low,
+                                  share=1.0 if a.share is None else a.share, deltas=deltas, scenes_per_cell=a.scenes_per_pair,
+                                  num_agents=a.num_agents, steps=a.steps, labels=list(a.precision_sweep))
+        df.to_csv(a.table)
+        print(df.drop(columns=["label"]).to_string())
+        return
     if (a.influence_max is not None or a.influence_deltas is not None) and not a.influence:
         ap.error("--influence-max and --influence-deltas go with --influence")
     if a.influence:

@@ -1136,6 +1136,38 @@ int copo_lin_obs_seats_f32(const copo_ppo_cfg* cfg, const float* theta, const fl
 int copo_jury_obs_seats_f32(const copo_ppo_cfg* cfg, const float* theta, const float* theta_t, int64_t member_stride,
                             int32_t n_members, const int64_t* rows, const int32_t* counts, int64_t cap, int64_t n_out,
                             const float* obs_src, float* verdict, void* stream);
+/* ---- low-precision policy forward of a seated bank (eval/precision.py; ABI 8, new symbols).  A format is
+ * COPO_LOWP_BF16 (bfloat16) or COPO_LOWP_E4M3 (OCP float8 e4m3fn: no infinities, largest value 448).  rnd rounds to nearest even into the
+ * format (e4m3: after a clamp to [-448, 448]; subnormals kept).
+ * copo_lowp_pack writes, for each of n_members members (parameters theta + k member_stride floats, the policy net of cfg), the image
+ * packed + k packed_stride BYTES: q1 [hidden][K1P] and q2 [hidden][hidden] elements of the format, output-unit-major with k contiguous,
+ * K1P = in_dim rounded up to a multiple of 32 and zero beyond in_dim; then fp32 words q3 [4][hidden], s1 [hidden], s2 [hidden], s3 [4],
+ * b1 [hidden], b2 [hidden], b3 [4].  s_l[u] is 1 for bfloat16 and, for e4m3, the smallest power of two with max_k |W_l[u][k]| / s <= 448
+ * (1 for a zero row); q_l[u][k] = rnd(W_l[u][k] / s_l[u]); the biases are fp32 as stored for e4m3 and rounded to bfloat16 for bfloat16
+ * (the places COPO_OPERAND_BF16 rounds).  packed: device, 16-byte aligned, packed_stride a multiple of 16 and at least the image's size,
+ * hidden * (K1P + hidden) * (2 or 1) + 4 * (8 * hidden + 8) bytes.  Outside captured graphs or inside, one launch.
+ * copo_lowp_forward_seats is copo_mlp_forward_seats_f32 on such images: the same lists (rows, counts, cap, n_out; a count above cap is
+ * cap, an index outside [0, n_out) is skipped, rows in no list are not written), grid ceil(cap / 16) x n_members, a workgroup past its
+ * member's count leaves before any weight load.  Per listed row with observation o: x = rnd(o); h1 = rnd(tanh(z1)), z1 = s1 (q1 x) + b1;
+ * h2 alike from h1; dist_inputs = s3 (q3 h2) + b3; for bfloat16 z1, z2 and the four outputs are themselves rounded to bfloat16, as
+ * COPO_OPERAND_BF16 does.  Both hidden layers run on the 16x16x32 matrix instruction of the format with fp32 accumulation (e4m3: one k per lane group and
+ * issue, the partial sums added in fp32 on the lanes, because the instruction's own sum over a lane's eight k is narrower), the heads in fp32
+ * on the lanes; fixed order, no atomics: two launches give the same bits.  From dist_inputs on the outputs (eps, action, logp, clipped:
+ * as copo_mlp_forward_f32) are those of copo_mlp_forward_seats_f32: equal dist_inputs bits give equal action, logp and clipped bits.
+ * One launch serves one format: members of another format get a count of 0.  NULL cfg / packed / rows / counts / obs_src, neither
+ * dist_inputs nor eps, eps without action and logp: COPO_ERR_NULL; another fmt, hidden outside {64, 128, 256, 512}, in_dim < 1, n_members
+ * outside 1..65535, cap < 1, n_out < 1, a short or misaligned image, an input so wide that the tiles pass 64 KiB of LDS: COPO_ERR_DIM.
+ * A refused call launches nothing. */
+#define COPO_LOWP_BF16 1
+#define COPO_LOWP_E4M3 2
+int copo_lowp_pack(const copo_ppo_cfg* cfg, const float* theta, int64_t member_stride, int32_t n_members, int32_t fmt, void* packed,
+                   int64_t packed_stride, void* stream);
+int copo_lowp_forward_seats(const copo_ppo_cfg* cfg, const void* packed, int64_t packed_stride, int32_t fmt, int32_t n_members,
+                            const int64_t* rows, const int32_t* counts, int64_t cap, int64_t n_out, const float* obs_src,
+                            float* dist_inputs, const float* eps, float* action, float* logp, float* clipped, void* stream);
+/* host only (tests): out[i] = rnd(in[i]) in fmt, and the e4m3 scale of a row whose largest magnitude is amax[i] -- the code the kernels run */
+int copo_debug_lowp_round(int32_t fmt, const float* in, int64_t n, float* out);
+int copo_debug_lowp_scale(const float* amax, int64_t n, float* out);
 /* The same pass over a LIST of rows: launch row m reads row rows[m] of the sources ([n_src_rows][..]) and writes
  * values[net][rows[m]] (values is [n_nets][n_src_rows]; entries of unlisted rows are left alone).  The dense postprocess
  * of a rollout buffer uses it with the rows that hold an agent -- about half of the slots. */
