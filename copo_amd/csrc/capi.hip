@@ -468,8 +468,7 @@ extern "C" int copo_gae3_f32(const float* rew, const float* val, const uint8_t* 
 extern "C" int copo_seat_tally(const uint8_t* flags, const float* rew, const int32_t* seat, const int32_t* group, int32_t E, int32_t N,
                                int32_t K, int32_t G, int64_t* out, void* stream) {
     if (!flags || !seat || !group || !out) return fail(COPO_ERR_NULL, "copo_seat_tally: NULL argument");
-    if (E < 0 || N < 1 || N > COPO_SEAT_MAX_SLOTS || K < 1 || K > 65535 || G < 1)
-        return fail(COPO_ERR_DIM, "copo_seat_tally: E=%d N=%d (1..%d) K=%d (1..65535) G=%d (>= 1)", E, N, COPO_SEAT_MAX_SLOTS, K, G);
+    if (const int rc = check_tally("copo_seat_tally", E, N, K, G)) return rc;
     if (E == 0) return COPO_OK;
     HIP_TRY(launch_seat_tally(flags, rew, seat, group, E, N, K, G, out, static_cast<hipStream_t>(stream)));
     return COPO_OK;
@@ -479,8 +478,8 @@ extern "C" int copo_certify_tally(const uint8_t* flags, const float* bounds, con
                                   const int32_t* level_of, const float* levels, int32_t E, int32_t N, int32_t K, int32_t G, int32_t L,
                                   int64_t* out, void* stream) {
     if (!flags || !bounds || !seat || !group || !level_of || !levels || !out) return fail(COPO_ERR_NULL, "copo_certify_tally: NULL argument");
-    if (E < 0 || N < 1 || N > COPO_SEAT_MAX_SLOTS || K < 1 || K > 65535 || G < 1 || L < 1)
-        return fail(COPO_ERR_DIM, "copo_certify_tally: E=%d N=%d (1..%d) K=%d (1..65535) G=%d (>= 1) L=%d (>= 1)", E, N, COPO_SEAT_MAX_SLOTS, K, G, L);
+    if (const int rc = check_tally("copo_certify_tally", E, N, K, G)) return rc;
+    if (L < 1) return fail(COPO_ERR_DIM, "copo_certify_tally: L=%d (>= 1)", L);
     if (E == 0) return COPO_OK;
     HIP_TRY(launch_certify_tally(flags, bounds, seat, group, level_of, levels, E, N, K, G, L, out, static_cast<hipStream_t>(stream)));
     return COPO_OK;
@@ -490,8 +489,7 @@ extern "C" int copo_jury_tally(const uint8_t* flags, const float* dist, const fl
                                const int32_t* judges, int32_t E, int32_t N, int32_t K, int32_t G, float delta_steer, float delta_throttle,
                                int64_t* out, void* stream) {
     if (!flags || !dist || !verdict || !seat || !group || !judges || !out) return fail(COPO_ERR_NULL, "copo_jury_tally: NULL argument");
-    if (E < 0 || N < 1 || N > COPO_SEAT_MAX_SLOTS || K < 1 || K > 65535 || G < 1)
-        return fail(COPO_ERR_DIM, "copo_jury_tally: E=%d N=%d (1..%d) K=%d (1..65535) G=%d (>= 1)", E, N, COPO_SEAT_MAX_SLOTS, K, G);
+    if (const int rc = check_tally("copo_jury_tally", E, N, K, G)) return rc;
     if (((reinterpret_cast<uintptr_t>(dist) | reinterpret_cast<uintptr_t>(verdict)) & 15) != 0)
         return fail(COPO_ERR_DIM, "copo_jury_tally: dist and verdict must be 16-byte aligned (their rows are read as one 128-bit word)");
     if (E == 0) return COPO_OK;

@@ -17,6 +17,14 @@ int fail(int code, const char* fmt, ...);
         if (_e != hipSuccess) return ::copo::fail(COPO_ERR_DEVICE, "%s: %s", #expr, hipGetErrorString(_e)); \
     } while (0)
 
+// What the four tally entries (copo_seat_tally, copo_certify_tally, copo_jury_tally, copo_influence_tally) share: the ranges of the walk
+// (seat_common.h).  A refusal is COPO_ERR_DIM in the entry point's name; E == 0 is accepted (the entry returns before its launch).
+inline int check_tally(const char* name, int32_t E, int32_t N, int32_t K, int32_t G) {
+    if (E < 0 || N < 1 || N > COPO_SEAT_MAX_SLOTS || K < 1 || K > 65535 || G < 1)
+        return fail(COPO_ERR_DIM, "%s: E=%d N=%d (1..%d) K=%d (1..65535) G=%d (>= 1)", name, E, N, COPO_SEAT_MAX_SLOTS, K, G);
+    return COPO_OK;
+}
+
 // A device buffer and its size: clears and whole-buffer copies take the byte count from here.
 template <typename T>
 struct DevBuf {

@@ -244,62 +244,40 @@ __global__ __launch_bounds__(LIST_THREADS) void influence_lists_kernel(const int
     if (tid == 0) vcounts[k] = (int32_t)total;
 }
 
+// The tally (the walk: seat_walk / SeatLane::serve, seat_common.h): a counted lane is an ego; it contributes its kept candidates' distances.
+using InfluenceWords = WordKinds<W_COUNT, W_SUM, W_SUM, W_SUM, W_SUM, W_SUM, W_MAX, W_SUM>;
+
 __global__ __launch_bounds__(256) void influence_tally_kernel(const uint8_t* __restrict__ flags, const float* __restrict__ dist,
                                                               const float* __restrict__ verdict_cf, const int32_t* __restrict__ who,
                                                               const int32_t* __restrict__ ncand, const float* __restrict__ hit,
                                                               const int32_t* __restrict__ seat, const int32_t* __restrict__ group, int32_t E,
                                                               int32_t N, int32_t K, int32_t G, int32_t M, float delta_steer,
                                                               float delta_throttle, int64_t* __restrict__ out, float* __restrict__ edges) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int e = blockIdx.x * ROWS_PER_WG + wave;
-    if (e >= E) return;                        // (the whole wave; there is no barrier in this kernel)
-    const int g = group[e];
-    if (g < 0 || g >= G) return;               // (the whole wave)
-    for (int j = 0; 64 * j < N; ++j) {
-        const int n = lane + 64 * j;
-        const size_t idx = (size_t)e * N + (n < N ? n : 0);
-        const int s = n < N ? seat[idx] : -1;
-        const bool counted = s >= 0 && s < K && ((uint32_t)flags[idx] & COPO_F_ACTED) != 0u;
-        if (!__ballot(counted)) continue;      // (uniform)
-        int64_t pairs = 0, moved = 0, q0 = 0, q1 = 0, qkl = 0, qmx = 0, trunc = 0;
+    seat_walk(seat, group, E, N, K, G, [&](const SeatLane& L) {
+        const size_t idx = L.idx;
+        const bool counted = L.seated && ((uint32_t)flags[idx] & COPO_F_ACTED) != 0u;
+        if (!__ballot(counted)) return;        // (uniform)
+        int64_t w[COPO_INFL_WORDS] = {1, 0, 0, 0, 0, 0, 0, 0};      // egos, pairs, moved, d0, d1, KL, max dev, truncated
         if (counted) {
             const float4 own = *reinterpret_cast<const float4*>(dist + idx * 4);
-            trunc = (int64_t)((uint32_t)ncand[idx] >> 16);
+            w[7] = (int64_t)((uint32_t)ncand[idx] >> 16);
             for (int c = 0; c < M; ++c) {
                 if (who[idx * M + c] < 0) continue;
-                const float4 v = *reinterpret_cast<const float4*>(verdict_cf + ((idx * M + c) * K + s) * 4);
+                const float4 v = *reinterpret_cast<const float4*>(verdict_cf + ((idx * M + c) * K + L.s) * 4);
                 const float d0 = fabsf(__fsub_rn(v.x, own.x)), d1 = fabsf(__fsub_rn(v.y, own.y));
                 const double kl = jury_kl(own, v);
-                pairs += 1;
-                moved += (d0 > delta_steer || d1 > delta_throttle) ? 1 : 0;
-                q0 += jury_q16(d0);
-                q1 += jury_q16(d1);
-                qkl += jury_q16(kl);
-                const int64_t m = jury_q16(fmaxf(d0, d1));
-                qmx = m > qmx ? m : qmx;
+                w[1] += 1;
+                w[2] += (d0 > delta_steer || d1 > delta_throttle) ? 1 : 0;
+                w[3] += q16(d0);
+                w[4] += q16(d1);
+                w[5] += q16(kl);
+                const int64_t m = q16(fmaxf(d0, d1));
+                w[6] = m > w[6] ? m : w[6];
                 if (edges) *reinterpret_cast<float4*>(edges + (idx * M + c) * 4) = make_float4(d0, d1, (float)kl, hit ? hit[idx * M + c] : 0.0f);
             }
         }
-        uint64_t todo = __ballot(counted);      // lanes with something to add; uniform over the wave
-        while (todo) {
-            const int m = __shfl(s, __ffsll((unsigned long long)todo) - 1);          // a served lane is seated: 0 <= m < K
-            const bool mine = counted && s == m;
-            todo &= ~__ballot(mine);
-            const int c_egos = __popcll(__ballot(mine));
-            const int64_t sp = wave_sum_i64(mine ? pairs : 0), sm = wave_sum_i64(mine ? moved : 0), s0 = wave_sum_i64(mine ? q0 : 0);
-            const int64_t s1 = wave_sum_i64(mine ? q1 : 0), skl = wave_sum_i64(mine ? qkl : 0), mx = wave_max_i64(mine ? qmx : 0);
-            const int64_t st = wave_sum_i64(mine ? trunc : 0);
-            if (lane < COPO_INFL_WORDS) {
-                const int64_t v = lane == 0 ? c_egos : lane == 1 ? sp : lane == 2 ? sm : lane == 3 ? s0 : lane == 4 ? s1 : lane == 5 ? skl
-                                : lane == 6 ? mx : st;
-                unsigned long long* at = reinterpret_cast<unsigned long long*>(out) + ((size_t)g * K + m) * COPO_INFL_WORDS + lane;
-                if (v != 0) {
-                    if (lane == 6) atomicMax(at, (unsigned long long)v);
-                    else atomicAdd(at, (unsigned long long)v);
-                }
-            }
-        }
-    }
+        L.serve(InfluenceWords{}, counted, w, out, [&](int m) { return (size_t)L.g * K + m; });
+    });
 }
 
 }  // namespace copo
@@ -351,13 +329,12 @@ extern "C" int copo_influence_tally(const uint8_t* flags, const float* dist, con
                                     const float* hit, const int32_t* seat, const int32_t* group, int32_t E, int32_t N, int32_t K, int32_t G,
                                     int32_t M, float delta_steer, float delta_throttle, int64_t* out, float* edges, void* stream) {
     if (!flags || !dist || !verdict_cf || !who || !ncand || !seat || !group || !out) return fail(COPO_ERR_NULL, "copo_influence_tally: NULL argument");
-    if (E < 0 || N < 1 || N > COPO_SEAT_MAX_SLOTS || K < 1 || K > 65535 || G < 1 || M < 1 || M > COPO_INFL_MAX)
-        return fail(COPO_ERR_DIM, "copo_influence_tally: E=%d N=%d (1..%d) K=%d (1..65535) G=%d (>= 1) M=%d (1..%d)", E, N, COPO_SEAT_MAX_SLOTS, K, G,
-                    M, COPO_INFL_MAX);
+    if (const int rc = check_tally("copo_influence_tally", E, N, K, G)) return rc;
+    if (M < 1 || M > COPO_INFL_MAX) return fail(COPO_ERR_DIM, "copo_influence_tally: M=%d (1..%d)", M, COPO_INFL_MAX);
     if (((reinterpret_cast<uintptr_t>(dist) | reinterpret_cast<uintptr_t>(verdict_cf) | reinterpret_cast<uintptr_t>(edges)) & 15) != 0)
         return fail(COPO_ERR_DIM, "copo_influence_tally: dist, verdict_cf and edges must be 16-byte aligned (their rows are one 128-bit word)");
     if (E == 0) return COPO_OK;
-    hipLaunchKernelGGL(influence_tally_kernel, dim3((E + ROWS_PER_WG - 1) / ROWS_PER_WG), dim3(256), 0, static_cast<hipStream_t>(stream), flags, dist,
+    hipLaunchKernelGGL(influence_tally_kernel, tally_grid(E), dim3(256), 0, static_cast<hipStream_t>(stream), flags, dist,
                        verdict_cf, who, ncand, hit, seat, group, E, N, K, G, M, delta_steer, delta_throttle, out, edges);
     HIP_TRY(hipGetLastError());
     return COPO_OK;

@@ -239,21 +239,33 @@ def tally_frame(tally, plan, labels=None):
     return pd.DataFrame(rows)
 
 
+def run_pairs(who, algo, env, weights_list, sampler, frame, *, share, scenes_per_pair, num_agents, steps, seed, labels, extra, check=None):
+    """The session of the studies on `SeatPlan.pairs` (`cross_play_rows`, `jury_rows`, `influence_rows`), as `levels.run_sweep` is the level
+    studies': the K populations `weights_list` (one layout), one bank, `sampler(t, bank, seats, use_graph)` run for `steps` env steps
+    (rounded up to whole fragments), then `frame(sampler, seats, labels)` while the session is still open.  `check`: the study's own
+    argument checks; it is called behind the member count and in front of the labels, the order the three functions always refused in."""
+    from .bank import PolicyBank
+    from .evaluate import check_labels, eval_session, graph_flag, run_steps
+    weights_list = list(weights_list)
+    K = len(weights_list)
+    if K < 1:
+        raise ValueError("%s: no members" % who)
+    if check is not None:
+        check()
+    labels = check_labels(labels, K)
+    seats = SeatPlan.pairs(K, scenes_per_pair, num_agents, share)
+    with eval_session(algo, env, seats.E, num_agents, seed, **extra) as t:
+        smp = sampler(t, PolicyBank(t.policy, weights_list), seats, graph_flag(t))
+        return frame(run_steps(smp, steps), seats, labels)
+
+
 def cross_play_rows(algo, env, weights_list, share=0.5, scenes_per_pair=4, num_agents=40, steps=1000, seed=0, labels=None, **extra):
     """Every ordered pair (focal i, partner j) of the K populations `weights_list` (one layout: one algorithm's observation) on
     `scenes_per_pair` scenes each, the same scenes for every pair: the first round(share * num_agents) slots of a scene are driven by
     i, the rest by j, for `steps` env steps (rounded up to whole fragments of the sampler).  Returns a pandas frame, one row per (pair
     group, member seated in it): `focal`, `partner`, `member`, `label`, `share`, the eight raw words of the tally (`SEAT_WORDS`),
     `success` = arrive / done, `crash_rate`, `out_rate`, `reward_per_step` = reward_q16 / 65536 / acted; NaN where a denominator is 0."""
-    from .bank import PolicyBank
-    from .evaluate import check_labels, eval_session, graph_flag, run_steps
-    weights_list = list(weights_list)
-    K = len(weights_list)
-    if K < 1:
-        raise ValueError("cross_play_rows: no members")
-    labels = check_labels(labels, K)
-    plan = SeatPlan.pairs(K, scenes_per_pair, num_agents, share)
-    with eval_session(algo, env, plan.E, num_agents, seed, **extra) as t:
-        smp = SeatSampler(t.env, t.policy, PolicyBank(t.policy, weights_list), plan, t.sampler.T, use_graph=graph_flag(t))
-        tally = run_steps(smp, steps).tally.cpu().numpy()
-    return tally_frame(tally, plan, labels)
+    return run_pairs("cross_play_rows", algo, env, weights_list,
+                     lambda t, bank, seats, use_graph: SeatSampler(t.env, t.policy, bank, seats, t.sampler.T, use_graph=use_graph),
+                     lambda smp, seats, labels: tally_frame(smp.tally.cpu().numpy(), seats, labels),
+                     share=share, scenes_per_pair=scenes_per_pair, num_agents=num_agents, steps=steps, seed=seed, labels=labels, extra=extra)

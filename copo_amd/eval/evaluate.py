@@ -11,6 +11,7 @@ checkpoints of one algorithm and scene drive their scenes of ONE simulator batch
     python -m copo_amd.eval.evaluate --root path/to/experiment --num-episodes 20 --table sweep.csv
 """
 import argparse
+import collections
 import contextlib
 import json
 
@@ -275,6 +276,75 @@ def sweep_trials(root, num_episodes=20, max_members=16, num_agents=40, seed=0, e
     return pd.concat(frames, ignore_index=True) if frames else pd.DataFrame()
 
 
+def _flag(option):
+    return "--" + option.replace("_", "-")
+
+
+def _deltas(a, option):
+    from .jury import check_deltas
+    given = getattr(a, option)
+    return check_deltas(_flag(option), (0.05, 0.05) if given is None else given)
+
+
+def _influence_args(a):
+    from .influence import check_max_others
+    return dict(max_others=check_max_others("--influence-max", 4 if a.influence_max is None else a.influence_max), deltas=_deltas(a, "influence_deltas"))
+
+
+def _precision_args(a):
+    low = ("bfloat16", "float8_e4m3") if a.precisions is None else tuple(a.precisions)
+    if len(set(low)) != len(low):
+        raise ValueError("--precisions: a precision twice")
+    return dict(precisions=("float32",) + low, deltas=_deltas(a, "jury_deltas"))
+
+
+# The studies of `main` that seat checkpoints and write one table, one entry each: the option that names the checkpoints; the module of
+# eval/ and the name of its `*_rows`, looked up when the study runs (a test may have replaced it); the option of its levels file (read by
+# the module's `load_levels`) or None; the default --share, None where the study takes none; the name of its scenes keyword; its own
+# keyword arguments from its own options (a ValueError is a usage error); the label columns left out of the print; the name of a
+# function of the module whose table of (frame, members) is printed too.
+Study = collections.namedtuple("Study", "option module rows levels share scenes extra drop epilogue",
+                               defaults=(None, None, "scenes_per_cell", lambda a: {}, ("label",), None))
+STUDIES = (
+    Study("cross_play", "crossplay", "cross_play_rows", share=0.5, scenes="scenes_per_pair"),
+    Study("fault_sweep", "faults", "fault_sweep_rows", "fault_levels", 1.0),
+    Study("adversary_sweep", "adversary", "adversary_sweep_rows", "adversary_levels", 1.0),
+    Study("pgd_sweep", "pgd", "pgd_sweep_rows", "pgd_levels", 1.0),
+    Study("certify_sweep", "certify", "certify_sweep_rows", "certify_levels", extra=lambda a: dict(method=a.certify_method)),
+    Study("jury", "jury", "jury_rows", share=0.5, scenes="scenes_per_pair", extra=lambda a: dict(plan=a.jury_plan, deltas=_deltas(a, "jury_deltas")),
+          drop=("driver_label", "judge_label"), epilogue="jury_matrix"),
+    Study("influence", "influence", "influence_rows", share=0.5, scenes="scenes_per_pair", extra=_influence_args),
+    Study("precision_sweep", "precision", "precision_sweep_rows", share=1.0, extra=_precision_args),
+)
+# the options that belong to some studies only: given (not at its default) without one of them, an option is a usage error
+GOES_WITH = dict(jury_plan=("jury",), jury_deltas=("jury", "precision_sweep"), influence_max=("influence",), influence_deltas=("influence",),
+                 precisions=("precision_sweep",), certify_method=("certify_sweep",))
+
+
+def run_study(ap, a, study):
+    """One entry of `STUDIES` from the parsed options `a`: its table written to --table and printed."""
+    import importlib
+    from .checkpoint_io import load_members
+    needs = [o for o in (study.levels, "table") if o]
+    if not all(getattr(a, o) for o in needs):
+        ap.error("%s needs %s" % (_flag(study.option), " and ".join(_flag(o) for o in needs)))
+    module = importlib.import_module("." + study.module, __package__)
+    try:
+        kw = study.extra(a)
+    except ValueError as e:
+        ap.error(str(e))
+    if study.share is not None:
+        kw["share"] = study.share if a.share is None else a.share
+    paths = getattr(a, study.option)
+    levels = [module.load_levels(getattr(a, study.levels))] if study.levels else []
+    df = getattr(module, study.rows)("ippo" if a.algo == "cl" else a.algo, a.env, load_members(paths), *levels, num_agents=a.num_agents,
+                                     steps=a.steps, labels=list(paths), **{study.scenes: a.scenes_per_pair}, **kw)
+    df.to_csv(a.table)
+    print(df.drop(columns=list(study.drop)).to_string())
+    if study.epilogue:
+        print(getattr(module, study.epilogue)(df, len(paths)).to_string())
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--root", default=None, help="experiment folder of Tune trial folders: evaluate every checkpoint of every trial "
@@ -351,122 +421,14 @@ def main(argv=None):
                     help="with --precision-sweep: the low precisions of the sweep (default: both)")
     a = ap.parse_args(argv)
     from .checkpoint_io import load_members
-    if a.precisions is not None and not a.precision_sweep:
-        ap.error("--precisions goes with --precision-sweep")
-    if a.precision_sweep:
-        if a.cross_play or a.fault_sweep or a.adversary_sweep or a.pgd_sweep or a.certify_sweep or a.jury or a.influence:
-            ap.error("--precision-sweep excludes --cross-play, --fault-sweep, --adversary-sweep, --pgd-sweep, --certify-sweep, --jury and --influence: "
-                     "one table per run")
-        if not a.table:
-            ap.error("--precision-sweep needs --table")
-        deltas = (0.05, 0.05) if a.jury_deltas is None else tuple(a.jury_deltas)
-        if not all(d >= 0.0 and d == d and d != float("inf") for d in deltas):
-            ap.error("--jury-deltas: two finite numbers >= 0 wanted")
-        low = ("bfloat16", "float8_e4m3") if a.precisions is None else tuple(a.precisions)
-        if len(set(low)) != len(low):
-            ap.error("--precisions: a precision twice")
-        from .precision import precision_sweep_rows
-        df = precision_sweep_rows("ippo" if a.algo == "cl" else a.algo, a.env, load_members(a.precision_sweep), precisions=("float32",) + low,
-                                  share=1.0 if a.share is None else a.share, deltas=deltas, scenes_per_cell=a.scenes_per_pair,
-                                  num_agents=a.num_agents, steps=a.steps, labels=list(a.precision_sweep))
-        df.to_csv(a.table)
-        print(df.drop(columns=["label"]).to_string())
-        return
-    if (a.influence_max is not None or a.influence_deltas is not None) and not a.influence:
-        ap.error("--influence-max and --influence-deltas go with --influence")
-    if a.influence:
-        if a.cross_play or a.fault_sweep or a.adversary_sweep or a.pgd_sweep or a.certify_sweep or a.jury:
-            ap.error("--influence excludes --cross-play, --fault-sweep, --adversary-sweep, --pgd-sweep, --certify-sweep and --jury: one table per run")
-        if not a.table:
-            ap.error("--influence needs --table")
-        M = 4 if a.influence_max is None else a.influence_max
-        if not 1 <= M <= 8:
-            ap.error("--influence-max: 1..8 wanted")
-        deltas = (0.05, 0.05) if a.influence_deltas is None else tuple(a.influence_deltas)
-        if not all(d >= 0.0 and d == d and d != float("inf") for d in deltas):
-            ap.error("--influence-deltas: two finite numbers >= 0 wanted")
-        from .influence import influence_rows
-        df = influence_rows("ippo" if a.algo == "cl" else a.algo, a.env, load_members(a.influence), share=0.5 if a.share is None else a.share,
-                            max_others=M, deltas=deltas, scenes_per_pair=a.scenes_per_pair, num_agents=a.num_agents, steps=a.steps,
-                            labels=list(a.influence))
-        df.to_csv(a.table)
-        print(df.drop(columns=["label"]).to_string())
-        return
-    if (a.jury_plan != "everyone" or a.jury_deltas is not None) and not a.jury:
-        ap.error("--jury-plan and --jury-deltas go with --jury")
-    if a.jury:
-        if a.cross_play or a.fault_sweep or a.adversary_sweep or a.pgd_sweep or a.certify_sweep:
-            ap.error("--jury excludes --cross-play, --fault-sweep, --adversary-sweep, --pgd-sweep and --certify-sweep: one table per run")
-        if not a.table:
-            ap.error("--jury needs --table")
-        deltas = (0.05, 0.05) if a.jury_deltas is None else tuple(a.jury_deltas)
-        if not all(d >= 0.0 and d == d and d != float("inf") for d in deltas):
-            ap.error("--jury-deltas: two finite numbers >= 0 wanted")
-        from .jury import jury_matrix, jury_rows
-        df = jury_rows("ippo" if a.algo == "cl" else a.algo, a.env, load_members(a.jury), plan=a.jury_plan, share=0.5 if a.share is None else a.share,
-                       deltas=deltas, scenes_per_pair=a.scenes_per_pair, num_agents=a.num_agents, steps=a.steps, labels=list(a.jury))
-        df.to_csv(a.table)
-        print(df.drop(columns=["driver_label", "judge_label"]).to_string())
-        print(jury_matrix(df, len(a.jury)).to_string())
-        return
-    if a.certify_method != "interval" and not a.certify_sweep:
-        ap.error("--certify-method goes with --certify-sweep")
-    if a.certify_sweep:
-        if a.cross_play or a.fault_sweep or a.adversary_sweep or a.pgd_sweep:
-            ap.error("--certify-sweep excludes --cross-play, --fault-sweep, --adversary-sweep and --pgd-sweep: one table per run")
-        if not a.table or not a.certify_levels:
-            ap.error("--certify-sweep needs --certify-levels and --table")
-        from .certify import certify_sweep_rows, load_levels
-        df = certify_sweep_rows("ippo" if a.algo == "cl" else a.algo, a.env, load_members(a.certify_sweep), load_levels(a.certify_levels),
-                                scenes_per_cell=a.scenes_per_pair, num_agents=a.num_agents, steps=a.steps, labels=list(a.certify_sweep),
-                                method=a.certify_method)
-        df.to_csv(a.table)
-        print(df.drop(columns=["label"]).to_string())
-        return
-    if a.pgd_sweep:
-        if a.cross_play or a.fault_sweep or a.adversary_sweep:
-            ap.error("--pgd-sweep excludes --cross-play, --fault-sweep and --adversary-sweep: one table per run")
-        if not a.table or not a.pgd_levels:
-            ap.error("--pgd-sweep needs --pgd-levels and --table")
-        from .pgd import load_levels, pgd_sweep_rows
-        df = pgd_sweep_rows("ippo" if a.algo == "cl" else a.algo, a.env, load_members(a.pgd_sweep), load_levels(a.pgd_levels),
-                            share=1.0 if a.share is None else a.share, scenes_per_cell=a.scenes_per_pair, num_agents=a.num_agents,
-                            steps=a.steps, labels=list(a.pgd_sweep))
-        df.to_csv(a.table)
-        print(df.drop(columns=["label"]).to_string())
-        return
-    if a.adversary_sweep:
-        if a.cross_play or a.fault_sweep:
-            ap.error("--adversary-sweep excludes --cross-play and --fault-sweep: one table per run")
-        if not a.table or not a.adversary_levels:
-            ap.error("--adversary-sweep needs --adversary-levels and --table")
-        from .adversary import adversary_sweep_rows, load_levels
-        df = adversary_sweep_rows("ippo" if a.algo == "cl" else a.algo, a.env, load_members(a.adversary_sweep), load_levels(a.adversary_levels),
-                                  share=1.0 if a.share is None else a.share, scenes_per_cell=a.scenes_per_pair, num_agents=a.num_agents,
-                                  steps=a.steps, labels=list(a.adversary_sweep))
-        df.to_csv(a.table)
-        print(df.drop(columns=["label"]).to_string())
-        return
-    if a.fault_sweep:
-        if not a.table or not a.fault_levels:
-            ap.error("--fault-sweep needs --fault-levels and --table")
-        from .faults import fault_sweep_rows, load_levels
-        df = fault_sweep_rows("ippo" if a.algo == "cl" else a.algo, a.env, load_members(a.fault_sweep), load_levels(a.fault_levels),
-                              share=1.0 if a.share is None else a.share, scenes_per_cell=a.scenes_per_pair, num_agents=a.num_agents,
-                              steps=a.steps, labels=list(a.fault_sweep))
-        df.to_csv(a.table)
-        print(df.drop(columns=["label"]).to_string())
-        return
-    if a.cross_play:
-        if not a.table:
-            ap.error("--cross-play needs --table")
-        from .crossplay import cross_play_rows
-        ws = load_members(a.cross_play)
-        df = cross_play_rows("ippo" if a.algo == "cl" else a.algo, a.env, ws, share=0.5 if a.share is None else a.share,
-                             scenes_per_pair=a.scenes_per_pair, num_agents=a.num_agents, steps=a.steps, labels=list(a.cross_play))
-        df.to_csv(a.table)
-        print(df.drop(columns=["label"]).to_string())
-        return
+    named = [s for s in STUDIES if getattr(a, s.option)]
+    if len(named) > 1:
+        ap.error("%s: one table per run" % " and ".join(_flag(s.option) for s in named))
+    for option, studies in GOES_WITH.items():
+        if getattr(a, option) != ap.get_default(option) and not any(s.option in studies for s in named):
+            ap.error("%s goes with %s" % (_flag(option), " or ".join(_flag(s) for s in studies)))
+    if named:
+        return run_study(ap, a, named[0])
     if a.root:
         if not a.table:
             ap.error("--root needs --table")

@@ -24,7 +24,7 @@ Pieces: `InfluenceBuffers`, `influence_pass`, `influence_heading`, `influence_ob
 import numpy as np
 
 from .bank import DeviceTables
-from .crossplay import SeatPlan, SeatSampler
+from .crossplay import SeatPlan, SeatSampler, run_pairs
 from .jury import Q16, check_deltas
 
 INFLUENCE_WORDS = ("egos", "pairs", "moved", "d_steer_q16", "d_throttle_q16", "kl_q16", "max_dev_q16", "truncated")
@@ -238,18 +238,9 @@ def influence_rows(algo, env, weights_list, share=0.5, max_others=4, deltas=(0.0
                    labels=None, **extra):
     """The K populations `weights_list` (one layout) on the `SeatPlan.pairs` layout of `cross_play_rows` with the influence pass, for
     `steps` env steps (rounded up to whole fragments).  Returns the `influence_frame`: one row per (pair, member)."""
-    from .bank import PolicyBank
-    from .evaluate import check_labels, eval_session, graph_flag, run_steps
-    weights_list = list(weights_list)
-    K = len(weights_list)
-    if K < 1:
-        raise ValueError("influence_rows: no members")
-    deltas = check_deltas("influence_rows", deltas)
-    M = check_max_others("influence_rows", max_others)
-    labels = check_labels(labels, K)
-    seats = SeatPlan.pairs(K, scenes_per_pair, num_agents, share)
-    with eval_session(algo, env, seats.E, num_agents, seed, **extra) as t:
-        smp = InfluenceSeatSampler(t.env, t.policy, PolicyBank(t.policy, weights_list), seats, t.sampler.T, use_graph=graph_flag(t),
-                                   max_others=M, deltas=deltas)
-        tally = run_steps(smp, steps).influence.tally.cpu().numpy()
-    return influence_frame(tally, seats, labels, deltas)
+    return run_pairs("influence_rows", algo, env, weights_list,
+                     lambda t, bank, seats, use_graph: InfluenceSeatSampler(t.env, t.policy, bank, seats, t.sampler.T, use_graph=use_graph,
+                                                                            max_others=max_others, deltas=deltas),
+                     lambda smp, seats, labels: influence_frame(smp.influence.tally.cpu().numpy(), seats, labels, smp.deltas),
+                     share=share, scenes_per_pair=scenes_per_pair, num_agents=num_agents, steps=steps, seed=seed, labels=labels, extra=extra,
+                     check=lambda: (check_deltas("influence_rows", deltas), check_max_others("influence_rows", max_others)))

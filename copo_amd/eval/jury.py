@@ -24,7 +24,7 @@ Pieces: `JuryPlan` (numpy only), `JuryBuffers`, `PolicyBank.jury_seats` / `Seate
 import numpy as np
 
 from .bank import DeviceTables
-from .crossplay import SeatPlan, SeatSampler
+from .crossplay import SeatPlan, SeatSampler, run_pairs
 
 JURY_WORDS = ("pairs", "disagree", "d_steer_q16", "d_throttle_q16", "d_logstd_q16", "kl_driver_judge_q16", "kl_judge_driver_q16", "max_dev_q16")
 VERDICT_WORDS = ("mu_steer", "mu_throttle", "logstd_steer", "logstd_throttle")
@@ -233,22 +233,17 @@ def jury_rows(algo, env, weights_list, plan="everyone", share=0.5, deltas=(0.05,
     partner) on the same `scenes_per_pair` scenes, the first round(share * num_agents) slots driven by the focal member -- with a jury:
     `plan` = "everyone" (all K members judge every row) or "seated" (focal and partner judge the rows of their pair), for `steps` env
     steps (rounded up to whole fragments).  Returns the `jury_frame`: one row per (pair, driver, judge)."""
-    from .bank import PolicyBank
-    from .evaluate import check_labels, eval_session, graph_flag, run_steps
-    weights_list = list(weights_list)
-    K = len(weights_list)
-    if K < 1:
-        raise ValueError("jury_rows: no members")
-    if plan not in PLANS:
-        raise ValueError("jury_rows: plan = %r, one of %s wanted" % (plan, ", ".join(repr(p) for p in PLANS)))
-    deltas = check_deltas("jury_rows", deltas)
-    labels = check_labels(labels, K)
-    seats = SeatPlan.pairs(K, scenes_per_pair, num_agents, share)
-    jury = JuryPlan.named(seats, plan)
-    with eval_session(algo, env, seats.E, num_agents, seed, **extra) as t:
-        smp = JurySeatSampler(t.env, t.policy, PolicyBank(t.policy, weights_list), seats, jury, t.sampler.T, use_graph=graph_flag(t), deltas=deltas)
-        tally = run_steps(smp, steps).jury_tally.cpu().numpy()
-    return jury_frame(tally, seats, jury, labels, deltas)
+    def check():
+        if plan not in PLANS:
+            raise ValueError("jury_rows: plan = %r, one of %s wanted" % (plan, ", ".join(repr(p) for p in PLANS)))
+        check_deltas("jury_rows", deltas)
+
+    return run_pairs("jury_rows", algo, env, weights_list,
+                     lambda t, bank, seats, use_graph: JurySeatSampler(t.env, t.policy, bank, seats, JuryPlan.named(seats, plan), t.sampler.T,
+                                                                       use_graph=use_graph, deltas=deltas),
+                     lambda smp, seats, labels: jury_frame(smp.jury_tally.cpu().numpy(), seats, smp.jury, labels, smp.deltas),
+                     share=share, scenes_per_pair=scenes_per_pair, num_agents=num_agents, steps=steps, seed=seed, labels=labels, extra=extra,
+                     check=check)
 
 
 def jury_verdicts(bank, obs):

@@ -294,6 +294,46 @@ def test_forward_and_fold(golden_dir):
     assert (c["ego"][r] != 0).all() and (e["other_slot"] != e["ego_slot"]).all()
 
 
+@pytest.mark.parametrize("shape", ic.TALLY_SHAPES, ids=str)
+def test_tally_alone_is_exact(shape):
+    """(4, the fold alone) `copo_influence_tally` on random tables (influence_cases.tally_tables: out-of-range groups, empty seats, a scene
+    of one member, candidate holes, truncated counts, NaN and beyond-clamp verdicts, rows without ACTED), folded twice: the integer words
+    are twice influence_numpy's, the max word is its max, the KL word within one unit per pair and fold (`test_forward_and_fold`'s bound
+    and reason: the device's exp differs from numpy's by an ulp, which can move a value across a rounding boundary of q16).  The edges of
+    the counted candidates hold the model's d0, d1 and the hit; every other edge keeps its poison."""
+    from copo_amd import _capi
+    E, N, K, G, M = shape
+    t = ic.tally_tables(shape)
+    want = inf.fold(t["flags"], t["dist"], t["verdict_cf"], t["who"], t["ncand"] >> 16, t["seat"], t["group"], K, G, ic.DELTAS)
+    assert want[..., 1].sum() > 0 and 0 < want[..., 2].sum() < want[..., 1].sum() and want[..., 7].sum() > 0 and want[..., 6].max() == 1024 * 65536
+    d = {k: _dev(v) for k, v in t.items()}
+    out = torch.zeros(G, K, 8, dtype=torch.int64, device="cuda")
+    edges = _poison(E * N, M, 4)
+    for _ in range(2):          # the tally accumulates
+        _capi.check(_capi.lib.copo_influence_tally(d["flags"].data_ptr(), d["dist"].data_ptr(), d["verdict_cf"].data_ptr(), d["who"].data_ptr(),
+                                                   d["ncand"].data_ptr(), d["hit"].data_ptr(), d["seat"].data_ptr(), d["group"].data_ptr(), E, N, K, G, M,
+                                                   ic.DELTAS[0], ic.DELTAS[1], out.data_ptr(), edges.data_ptr(), _capi.current_stream()))
+    torch.cuda.synchronize()
+    tally, edges = out.cpu().numpy(), edges.cpu().numpy()
+    exact = [0, 1, 2, 3, 4, 7]
+    off = np.abs(tally[..., 5] - 2 * want[..., 5])
+    print(shape, "egos %d pairs %d moved %d truncated %d; KL word off by at most %d units (bound %d)" % (
+        want[..., 0].sum(), want[..., 1].sum(), want[..., 2].sum(), want[..., 7].sum(), off.max(), 2 * want[..., 1].max()))
+    assert np.array_equal(tally[..., exact], 2 * want[..., exact]) and np.array_equal(tally[..., 6], want[..., 6])
+    assert (off <= 2 * want[..., 1]).all() and (tally[..., 5] % 2 == 0).all()
+    seat = t["seat"].reshape(-1)
+    ok = np.repeat((t["group"] >= 0) & (t["group"] < G), N)
+    counted = ok & (seat >= 0) & ((t["flags"] & inf.F_ACTED) != 0)
+    written = counted[:, None] & (t["who"] >= 0)
+    assert written.any() and not written.all() and (_u32(edges)[~written] == POISON).all()
+    r, c = np.nonzero(written)
+    own, v = t["dist"][r], t["verdict_cf"][r * M + c, seat[r]]
+    with np.errstate(invalid="ignore"):
+        d0, d1 = np.abs(F(v[:, 0] - own[:, 0])), np.abs(F(v[:, 1] - own[:, 1]))
+    assert np.array_equal(edges[r, c, 0], d0, equal_nan=True) and np.array_equal(edges[r, c, 1], d1, equal_nan=True)
+    assert np.array_equal(edges[r, c, 3], t["hit"][r, c]) and (np.isnan(d0) | np.isnan(d1)).any()
+
+
 def test_nobody_near(golden_dir):
     """(5) One vehicle per scene: no candidates, empty lists, words 1 .. 7 zero, obs_cf and verdict_cf untouched."""
     from copo_amd.eval.bank import PolicyBank

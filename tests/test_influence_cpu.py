@@ -147,6 +147,25 @@ def test_buffers_check_their_arguments():
             InfluenceBuffers(**dict(dict(seats=seats, O=91, L=72, max_others=4, device="cpu"), **bad))
 
 
+@pytest.mark.parametrize("shape", ic.TALLY_SHAPES, ids=str)
+def test_premise_of_the_stand_alone_fold(shape):
+    """What test_gpu_influence.py::test_tally_alone_is_exact relies on, measured on the model alone: every shape has pairs, some moved and
+    some not, truncated candidates, a max word at the clamp, out-of-range groups, empty seats, rows that did not act and candidate holes."""
+    E, N, K, G, M = shape
+    t = ic.tally_tables(shape)
+    want = inf.fold(t["flags"], t["dist"], t["verdict_cf"], t["who"], t["ncand"] >> 16, t["seat"], t["group"], K, G, ic.DELTAS)
+    pairs, moved = int(want[..., 1].sum()), int(want[..., 2].sum())
+    print(shape, "egos %d pairs %d moved %d truncated %d" % (want[..., 0].sum(), pairs, moved, want[..., 7].sum()))
+    assert pairs > 0 and 0 < moved < pairs and want[..., 7].sum() > 0 and want[..., 6].max() == 1024 * 65536
+    assert (t["seat"] == -1).any() and (t["who"] == -1).any() and not (t["flags"] & inf.F_ACTED).all() and np.isnan(t["verdict_cf"]).any()
+    if E >= 3:
+        assert len(set(t["seat"][1]) - {-1}) == 1 and 0 <= t["group"][1] < G
+        assert all(t["group"][e] == g and g in (-1, G) for e, g in ic.TALLY_BAD_GROUPS[shape].items())
+    if K >= 64:
+        assert len(set(t["seat"][0, :64])) == 64 and (t["flags"][:64] & inf.F_ACTED).all() and 0 <= t["group"][0] < G
+    assert {g for bad in ic.TALLY_BAD_GROUPS.values() for g in bad.values()} == {-1, 1, 5}          # -1 and G both occur
+
+
 def test_header_declares_the_entries_and_the_bindings_match():
     header = open(os.path.join(ROOT, "include", "copo_hip.h")).read()
     assert "#define COPO_INFL_MAX 8" in header and "#define COPO_INFL_WORDS 8" in header
