@@ -97,6 +97,10 @@ _SIGS = {
                                          C.c_void_p, C.c_int32, C.c_float, C.c_void_p]),
     "copo_jury_obs_seats_f32": (C.c_int, [C.POINTER(PpoCfg), C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p,
                                           C.c_int64, C.c_int64] + [C.c_void_p] * 3),
+    "copo_ig_obs_seats_f32": (C.c_int, [C.POINTER(PpoCfg), C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p,
+                                        C.c_int64, C.c_int64] + [C.c_void_p] * 3 + [C.c_int32] * 3 + [C.c_void_p, C.c_int32, C.c_void_p,
+                                        C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
+    "copo_attrib_tally": (C.c_int, [C.c_void_p] * 5 + [C.c_int32] * 5 + [C.c_void_p] * 3),
     "copo_jury_tally": (C.c_int, [C.c_void_p] * 6 + [C.c_int32] * 4 + [C.c_float] * 2 + [C.c_void_p, C.c_void_p]),
     "copo_lowp_pack": (C.c_int, [C.POINTER(PpoCfg), C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]),
     "copo_lowp_forward_seats": (C.c_int, [C.POINTER(PpoCfg), C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64,

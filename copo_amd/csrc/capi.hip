@@ -485,6 +485,16 @@ extern "C" int copo_certify_tally(const uint8_t* flags, const float* bounds, con
     return COPO_OK;
 }
 
+extern "C" int copo_attrib_tally(const uint8_t* flags, const float* attr, const float* heads, const int32_t* seat, const int32_t* group,
+                                 int32_t E, int32_t N, int32_t K, int32_t G, int32_t in_dim, int64_t* words, int64_t* cols, void* stream) {
+    if (!flags || !attr || !heads || !seat || !group || !words || !cols) return fail(COPO_ERR_NULL, "copo_attrib_tally: NULL argument");
+    if (const int rc = check_tally("copo_attrib_tally", E, N, K, G)) return rc;
+    if (in_dim < 1) return fail(COPO_ERR_DIM, "copo_attrib_tally: in_dim=%d (>= 1)", in_dim);
+    if (E == 0) return COPO_OK;
+    HIP_TRY(launch_attrib_tally(flags, attr, heads, seat, group, E, N, K, G, in_dim, words, cols, static_cast<hipStream_t>(stream)));
+    return COPO_OK;
+}
+
 extern "C" int copo_jury_tally(const uint8_t* flags, const float* dist, const float* verdict, const int32_t* seat, const int32_t* group,
                                const int32_t* judges, int32_t E, int32_t N, int32_t K, int32_t G, float delta_steer, float delta_throttle,
                                int64_t* out, void* stream) {

@@ -19,6 +19,7 @@
 //      learn_certify.inc: cert_obs_kernel, interval bounds of the action means over an L-infinity box of the input row
 //      learn_linbound.inc: lin_obs_kernel, linear bounds of the same means (one relaxation per tanh unit, carried backward), intersected with them
 //      learn_jury.inc: jury_obs_kernel, the forward of every JUDGE of a row into a plane of its own (a row may stand in many members' lists)
+//      learn_attrib.inc: ig_obs_kernel, integrated gradients of both action means down to the input row, all quadrature points in one resident workgroup
 //   5. LCF meta kernels: meta_lcf / meta_finish (step by step), meta_batch_fold / dot / rowstat, meta_seq (all LCF
 //      Adam steps of a pass in one workgroup)
 //   6. reduce_adam_kernel (fold of row-split partials + Adam; legacy two-net meta step), wgrad_adam_kernel (weight
@@ -50,6 +51,7 @@ namespace copo {
 #include "learn_certify.inc"
 #include "learn_linbound.inc"
 #include "learn_jury.inc"
+#include "learn_attrib.inc"
 #include "learn_meta.inc"
 #include "learn_update.inc"
 #include "learn_plan.inc"
@@ -381,6 +383,16 @@ extern "C" int copo_lin_obs_seats_f32(const copo_ppo_cfg* cfg, const float* thet
                                       int32_t n_levels, float pad, void* stream) {
     LinArgs a{COPO_SEAT_HEAD, bounds, parts, pad};
     return seat_pass_launch(cfg, a.h, bounds, pad_ok(pad), K_LIN_1_4, lin_lds_floats, LDS_LINBOUND, &a, stream);
+}
+
+extern "C" int copo_ig_obs_seats_f32(const copo_ppo_cfg* cfg, const float* theta, const float* theta_t, int64_t member_stride,
+                                     int32_t n_members, const int64_t* rows, const int32_t* counts, int64_t cap, int64_t n_out,
+                                     const float* obs_src, float* attr, float* heads, int32_t col_lo, int32_t col_hi, int32_t n_slots,
+                                     const int32_t* group, int32_t n_groups, const int32_t* level_of, const int32_t* levels,
+                                     int32_t n_levels, const float* base, int32_t max_points, void* stream) {
+    if (!heads || !base) return COPO_ERR_NULL;
+    IgArgs a{COPO_SEAT_HEAD, attr, heads, base, max_points};
+    return seat_pass_launch(cfg, a.h, attr, max_points >= 1 && max_points <= IG_MAX_POINTS, K_IG_1_4, ig_lds_floats, LDS_ROWPASS, &a, stream);
 }
 
 // The jury pass: seat mode's launch shape with a list per JUDGE; none of the level tables of the four passes above, so its checks are its own.

@@ -19,6 +19,11 @@ hipError_t launch_jury_tally(const uint8_t* flags, const float* dist, const floa
                              const int32_t* judges, int32_t E, int32_t N, int32_t K, int32_t G, float delta_steer, float delta_throttle,
                              int64_t* out, hipStream_t stream);
 
+// one step's integrated gradients folded per (scene group, bank member) into words[G][K][COPO_ATTRIB_TALLY_WORDS] and
+// cols[G][K][2][in_dim] (one launch)
+hipError_t launch_attrib_tally(const uint8_t* flags, const float* attr, const float* heads, const int32_t* seat, const int32_t* group,
+                               int32_t E, int32_t N, int32_t K, int32_t G, int32_t in_dim, int64_t* words, int64_t* cols, hipStream_t stream);
+
 // Every tally's geometry: one wave per scene, four scenes per 256-thread workgroup.
 constexpr int TALLY_SCENES_PER_WG = 4;
 inline dim3 tally_grid(int32_t E) { return dim3((E + TALLY_SCENES_PER_WG - 1) / TALLY_SCENES_PER_WG); }

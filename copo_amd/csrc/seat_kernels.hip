@@ -103,6 +103,91 @@ __global__ __launch_bounds__(256) void jury_tally_kernel(const uint8_t* __restri
     });
 }
 
+// Attribution tally (copo_attrib_tally): one step's integrated gradients (copo_ig_obs_seats_f32) folded per (scene
+// group, member).  A slot counts by the seat tally's rule for `acted`; it is attributed where heads[..][6] == 1.  Every value is
+// quantised once, q32(v) = llrint(min(|v|, 2^20) * 2^32) in float64 from the fp32 value (NaN counts as 0), so words and columns are
+// integers and the result does not depend on the order.  The eight words go through the one walk.  The columns do not: a member's rows
+// of ALL rounds of the scene are collected first (up to COPO_SEAT_MAX_SLOTS / 64 ballots), then the lanes take 64 adjacent (head,
+// column) cells at a time and walk the member's rows -- coalesced reads, a private sum per lane, and one atomic per (scene, member
+// seated in it, head, column) at the most.
+using AttribWords = WordKinds<W_COUNT, W_SUM, W_SUM, W_SUM, W_SUM, W_MAX, W_COUNT, W_COUNT>;
+constexpr int ATTRIB_ROUNDS = COPO_SEAT_MAX_SLOTS / 64;
+
+__device__ inline int64_t q32(float v) {
+    if (v != v) return 0;
+    return (int64_t)llrint(fmin(fabs((double)v), 1048576.0) * 4294967296.0);
+}
+
+__global__ __launch_bounds__(256) void attrib_tally_kernel(const uint8_t* __restrict__ flags, const float* __restrict__ attr,
+                                                           const float* __restrict__ heads, const int32_t* __restrict__ seat,
+                                                           const int32_t* __restrict__ group, int32_t E, int32_t N, int32_t K, int32_t G,
+                                                           int32_t D, int64_t* __restrict__ words, int64_t* __restrict__ cols) {
+    seat_walk(seat, group, E, N, K, G, [&](const SeatLane& L) {
+        const bool counted = L.seated && ((uint32_t)flags[L.idx] & COPO_F_ACTED) != 0u;
+        const float* h = heads + L.idx * COPO_IG_HEAD_WORDS;
+        const bool valid = counted && h[6] == 1.0f;
+        int64_t v[COPO_ATTRIB_TALLY_WORDS] = {valid, 0, 0, 0, 0, 0, !valid, 0};      // attributed, |delta| x 2, |gap| x 2, max |gap|, listed only, 0
+        if (valid) {
+            v[1] = q32(__fsub_rn(h[0], h[2]));
+            v[2] = q32(__fsub_rn(h[1], h[3]));
+            v[3] = q32(h[4]);
+            v[4] = q32(h[5]);
+            v[5] = v[3] > v[4] ? v[3] : v[4];
+        }
+        L.serve(AttribWords{}, counted, v, words, [&](int m) { return (size_t)L.g * K + m; });
+    });
+    // ---- the columns (the scene and group tests are seat_walk's: both take the whole wave) ----
+    const int lane = threadIdx.x & 63, e = blockIdx.x * TALLY_SCENES_PER_WG + (threadIdx.x >> 6);
+    if (e >= E) return;
+    const int g = group[e];
+    if (g < 0 || g >= G) return;
+    int s_j[ATTRIB_ROUNDS];
+    uint64_t todo[ATTRIB_ROUNDS];
+#pragma unroll
+    for (int j = 0; j < ATTRIB_ROUNDS; ++j) {
+        const int n = lane + 64 * j;
+        const size_t idx = (size_t)e * N + (n < N ? n : 0);
+        const int s = n < N ? seat[idx] : -1;
+        const bool ok = s >= 0 && s < K && ((uint32_t)flags[idx] & COPO_F_ACTED) != 0u && heads[idx * COPO_IG_HEAD_WORDS + 6] == 1.0f;
+        s_j[j] = ok ? s : -1;
+        todo[j] = __ballot(ok);
+    }
+    const int W = 2 * D;
+    for (;;) {
+        int m = -1;                        // the next member: the first lane of the first round that is not served yet (uniform)
+#pragma unroll
+        for (int j = 0; j < ATTRIB_ROUNDS; ++j) {
+            const int first = __shfl(s_j[j], todo[j] ? __ffsll((unsigned long long)todo[j]) - 1 : 0);
+            if (m < 0 && todo[j]) m = first;
+        }
+        if (m < 0) break;
+        uint64_t mask[ATTRIB_ROUNDS];
+#pragma unroll
+        for (int j = 0; j < ATTRIB_ROUNDS; ++j) {
+            mask[j] = __ballot(s_j[j] == m);
+            todo[j] &= ~mask[j];
+        }
+        for (int c0 = 0; c0 < W; c0 += 64) {
+            const int c = c0 + lane;
+            int64_t acc = 0;
+#pragma unroll
+            for (int j = 0; j < ATTRIB_ROUNDS; ++j)
+                for (uint64_t mk = mask[j]; mk; mk &= mk - 1) {
+                    const size_t row = (size_t)e * N + 64 * j + (__ffsll((unsigned long long)mk) - 1);
+                    if (c < W) acc += q32(attr[row * W + c]);
+                }
+            if (c < W && acc != 0)
+                atomicAdd(reinterpret_cast<unsigned long long*>(cols) + ((size_t)g * K + m) * W + c, (unsigned long long)acc);
+        }
+    }
+}
+
+hipError_t launch_attrib_tally(const uint8_t* flags, const float* attr, const float* heads, const int32_t* seat, const int32_t* group,
+                               int32_t E, int32_t N, int32_t K, int32_t G, int32_t in_dim, int64_t* words, int64_t* cols, hipStream_t stream) {
+    hipLaunchKernelGGL(attrib_tally_kernel, tally_grid(E), dim3(256), 0, stream, flags, attr, heads, seat, group, E, N, K, G, in_dim, words, cols);
+    return hipGetLastError();
+}
+
 hipError_t launch_jury_tally(const uint8_t* flags, const float* dist, const float* verdict, const int32_t* seat, const int32_t* group,
                              const int32_t* judges, int32_t E, int32_t N, int32_t K, int32_t G, float delta_steer, float delta_throttle,
                              int64_t* out, hipStream_t stream) {

@@ -164,6 +164,17 @@ class PolicyBank:
                         (("obs", obs, (n_out, int(self.cfg.pol.in_dim)), torch.float32), ("bounds", bounds, (n_out, 8), torch.float32),
                          ("parts", parts, (n_out, 8), torch.float32)), col_lo, col_hi, (bounds, parts) if linear else (bounds,), (float(pad),))
 
+    def attribute_seats(self, plan_buffers, attrib_buffers, obs, attr, heads, max_points=None):
+        """`copo_ig_obs_seats_f32` (eval/attribution.py) on the current stream: obs [n_out, O] -> attr [n_out, 2, O] and heads [n_out, 8],
+        the integrated gradients of the two action means of every seated row against the member that drives it, from the baseline and
+        with the quadrature points of the level `attrib_buffers` (`attribution.AttributionBuffers`) gives (scene group, member);
+        `max_points` defaults to the plan's.  Nothing is perturbed.  Needs the mirror (`sync_mirror`), as `act_seats`."""
+        max_points = int(attrib_buffers.max_points if max_points is None else max_points)
+        n_out, O = plan_buffers.n_out, int(self.cfg.pol.in_dim)
+        self._seat_pass("PolicyBank.attribute_seats", "copo_ig_obs_seats_f32", plan_buffers, attrib_buffers,
+                        (("obs", obs, (n_out, O), torch.float32), ("attr", attr, (n_out, 2, O), torch.float32), ("heads", heads, (n_out, 8), torch.float32),
+                         ("base", attrib_buffers.base, (attrib_buffers.L, O), torch.float32)), 0, 0, (attr, heads),
+                        (attrib_buffers.base.data_ptr(), max_points))
 
     def jury_seats(self, jury_buffers, obs, verdict):
         """`copo_jury_obs_seats_f32` (eval/jury.py) on the current stream: obs [n_out, O] -> verdict [n_out, K, 4], the four

@@ -175,6 +175,10 @@ class SeatedBank:
         """`PolicyBank.certify_seats` over the plan's own buffers (eval/certify.py)."""
         self.bank.certify_seats(self.buffers, cert_buffers, obs, bounds, col_lo, col_hi, pad, method, parts)
 
+    def attribute_seats(self, attrib_buffers, obs, attr, heads, max_points=None):
+        """`PolicyBank.attribute_seats` over the plan's own buffers (eval/attribution.py)."""
+        self.bank.attribute_seats(self.buffers, attrib_buffers, obs, attr, heads, max_points)
+
     def jury_seats(self, jury_buffers, obs, verdict):
         """`PolicyBank.jury_seats` on the rows of the plan (eval/jury.py): the judges' lists must cover the plan's [E * N] rows."""
         if jury_buffers.n_out != self.buffers.n_out:

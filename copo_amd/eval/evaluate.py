@@ -316,6 +316,10 @@ STUDIES = (
     Study("influence", "influence", "influence_rows", share=0.5, scenes="scenes_per_pair", extra=_influence_args),
     Study("precision_sweep", "precision", "precision_sweep_rows", share=1.0, extra=_precision_args),
 )
+# The ninth study: input attribution (eval/attribution.py).  It takes no --share, as certify takes none.  `STUDIES` stays the eight
+# entries that tests/test_eval_cli_cpu.py enumerates by name; `main` walks `ALL_STUDIES`, so "one table per run" and "goes with" cover
+# every entry by the same two loops.
+ALL_STUDIES = STUDIES + (Study("attribution", "attribution", "attribution_rows", "attribution_levels"),)
 # the options that belong to some studies only: given (not at its default) without one of them, an option is a usage error
 GOES_WITH = dict(jury_plan=("jury",), jury_deltas=("jury", "precision_sweep"), influence_max=("influence",), influence_deltas=("influence",),
                  precisions=("precision_sweep",), certify_method=("certify_sweep",))
@@ -419,9 +423,16 @@ def main(argv=None):
                          "per (checkpoint, precision) into --table; takes --share (default 1), --jury-deltas, --scenes-per-pair and --steps")
     ap.add_argument("--precisions", nargs="+", default=None, choices=("bfloat16", "float8_e4m3"),
                     help="with --precision-sweep: the low precisions of the sweep (default: both)")
+    ap.add_argument("--attribution", nargs="+", default=None, metavar="CKPT",
+                    help="checkpoints of --algo's layout, each attributed at every level of --attribution-levels (eval/attribution.py: "
+                         "integrated gradients of the two action means over the observation columns; nobody's driving changes): one row "
+                         "per (checkpoint, level) into --table; takes --scenes-per-pair and --steps")
+    ap.add_argument("--attribution-levels", default=None, metavar="JSON",
+                    help="with --attribution: a JSON list of {points, baseline}; baseline is \"clear_road\", \"zeros\" or a row of numbers "
+                         "in which null masks a column")
     a = ap.parse_args(argv)
     from .checkpoint_io import load_members
-    named = [s for s in STUDIES if getattr(a, s.option)]
+    named = [s for s in ALL_STUDIES if getattr(a, s.option)]
     if len(named) > 1:
         ap.error("%s: one table per run" % " and ".join(_flag(s.option) for s in named))
     for option, studies in GOES_WITH.items():

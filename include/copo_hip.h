@@ -462,6 +462,23 @@ int copo_seat_tally(const uint8_t* flags, const float* rew, const int32_t* seat,
 int copo_certify_tally(const uint8_t* flags, const float* bounds, const int32_t* seat, const int32_t* group, const int32_t* level_of,
                        const float* levels, int32_t E, int32_t N, int32_t K, int32_t G, int32_t L, int64_t* out, void* stream);
 
+/* ---- attribution tally: one step's integrated gradients (copo_ig_obs_seats_f32) folded per (scene group, bank
+ * member).  Stateless.  flags device [E][N] uint8 (the step's output), attr device [E N][2][in_dim] fp32, heads device [E N][COPO_IG_HEAD_WORDS]
+ * fp32, seat / group as copo_seat_tally, words device [G][K][COPO_ATTRIB_TALLY_WORDS] int64, cols device [G][K][2][in_dim] int64.  A slot
+ * counts exactly where copo_seat_tally counts it as acted (0 <= seat < K, 0 <= group[e] < G, flags carry COPO_F_ACTED); it is attributed
+ * where heads[..][6] == 1.  q(v) = llrint(min(|v|, 2^20) * 2^32) as int64, taken in float64 from the fp32 value, NaN as 0 (one rounding).
+ * cols[g][k][a][j] += q(attr[row][a][j]) over the attributed rows; words: [0] rows attributed; [1] / [2] the sums of q(mu_a(o) - mu_a(b))
+ * (the fp32 difference of heads[a] and heads[2 + a], rounded once); [3] / [4] the sums of q(gap_a); [5] the largest q(gap) of either head (a
+ * 64-bit atomic max); [6] rows counted but not attributed; [7] 0.  Both outputs ACCUMULATE (the caller clears them); integers only, so the
+ * result does not depend on the order.  Sums are formed inside the wave that owns the scene first: one atomic per (scene, member seated
+ * in it, head, column) at the most.  One launch on the caller's stream, no allocation, no host synchronisation; may be captured in a
+ * graph.  NULL flags / attr / heads / seat / group / words / cols: COPO_ERR_NULL; E >= 0, N in 1..COPO_SEAT_MAX_SLOTS, K in 1..65535,
+ * G >= 1, in_dim >= 1 (COPO_ERR_DIM); a refused call launches nothing. */
+#define COPO_ATTRIB_TALLY_WORDS 8
+#define COPO_IG_HEAD_WORDS 8
+int copo_attrib_tally(const uint8_t* flags, const float* attr, const float* heads, const int32_t* seat, const int32_t* group, int32_t E,
+                      int32_t N, int32_t K, int32_t G, int32_t in_dim, int64_t* words, int64_t* cols, void* stream);
+
 /* ---- jury tally: one step's verdicts (copo_jury_obs_seats_f32) against the driver's own distribution inputs,
  * folded per (scene group, driving member, judging member).  Stateless.  flags device [E][N] uint8 (the step's output), dist device
  * [E][N][4] fp32 (mu_steer, mu_throttle, logstd_steer, logstd_throttle of the member that drives the slot: the forward's dist_inputs),
@@ -1120,6 +1137,28 @@ int copo_lin_obs_seats_f32(const copo_ppo_cfg* cfg, const float* theta, const fl
                            const float* obs_src, float* bounds, float* parts, int32_t col_lo, int32_t col_hi, int32_t n_slots,
                            const int32_t* group, int32_t n_groups, const int32_t* level_of, const float* levels,
                            int32_t n_levels, float pad, void* stream);
+/* Input attribution of a seated bank (eval/attribution.py): integrated gradients of the two action MEANS of every
+ * listed row with respect to its whole observation row, against the policy that drives the row, all quadrature points in one launch.
+ * The seat-mode arguments, obs_src, n_slots, group and level_of are those of copo_adv_obs_seats_f32; col_lo / col_hi are checked as
+ * there and not read (every column is attributed).  A level is four 32-bit words: m (i32, the quadrature points), flags (i32, reserved,
+ * 0), two zeros; base (device fp32 [n_levels][in_dim]) holds a baseline row per level, a NaN entry meaning "this column keeps the row's
+ * own value".  With mm = min(m, max_points), o the TRUE row, b[j] = isnan(base[j]) ? o[j] : base[j] and d = o - b:
+ *     x_s = b + ((s - 1/2) / mm) d, s = 1 .. mm (midpoint rule);  G_a = sum_s d mu_a / d x at x_s, s ascending (a = 0 steer, 1 throttle)
+ *     attr[row][a][j] = (d[j] G_a[j]) / mm, exactly 0.0 where d[j] == 0;  gap_a = (mu_a(o) - mu_a(b)) - sum_j attr[row][a][j], j ascending
+ *     heads[row] = mu_0(o), mu_1(o), mu_0(b), mu_1(b), gap_0, gap_1, valid = 1.0, mm as bits
+ * every difference, quotient, product and sum above rounded once in fp32.  The attributions of a row sum to mu_a(o) - mu_a(b) up to the
+ * quadrature residual gap_a, which the launch reports.  A listed row whose level index or group is out of range, or whose mm <= 0, gets
+ * zeros in attr and eight zeros in heads (valid = 0); rows in no list are not written.  One launch, grid ceil(cap / 16) x n_members, the
+ * 16-row tile resident in LDS with the running sums; forward from the mirror theta_t, backward on theta as stored, the two heads one
+ * after the other behind one forward per point.  No atomics, fixed summation order: two launches give the same bits.  Refusals as
+ * copo_adv_obs_seats_f32 (NULL theta / theta_t / rows / counts / obs_src / attr / heads / base / group / level_of / levels:
+ * COPO_ERR_NULL; bad dimensions, bfloat16 operands, a hidden width outside {64, 128, 256, 512}, tiles beyond the workgroup's LDS -- hidden
+ * 512 with more than 128 input columns --: COPO_ERR_DIM), and max_points outside [1, 32]: COPO_ERR_DIM.  A refused call launches nothing. */
+int copo_ig_obs_seats_f32(const copo_ppo_cfg* cfg, const float* theta, const float* theta_t, int64_t member_stride,
+                          int32_t n_members, const int64_t* rows, const int32_t* counts, int64_t cap, int64_t n_out,
+                          const float* obs_src, float* attr, float* heads, int32_t col_lo, int32_t col_hi, int32_t n_slots,
+                          const int32_t* group, int32_t n_groups, const int32_t* level_of, const int32_t* levels,
+                          int32_t n_levels, const float* base, int32_t max_points, void* stream);
 /* The jury pass of a seated bank (eval/jury.py): the third mode of the bank's forward.  The dense bank gives every
  * member its own rows and seat mode gives a row to ONE member; here a row may be judged by many, and each judge's distribution inputs
  * land in a plane of their own.  Member j is a judge and owns the list rows[j cap .. j cap + counts[j]) of [0, n_out) (rows device
