@@ -97,6 +97,11 @@ _SIGS = {
                                          C.c_void_p, C.c_int32, C.c_float, C.c_void_p]),
     "copo_jury_obs_seats_f32": (C.c_int, [C.POINTER(PpoCfg), C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p,
                                           C.c_int64, C.c_int64] + [C.c_void_p] * 3),
+    "copo_hidden_obs_seats_f32": (C.c_int, [C.POINTER(PpoCfg), C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p,
+                                            C.c_int64, C.c_int64] + [C.c_void_p] * 3),
+    "copo_cka_accumulate": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_void_p, C.c_int32] + [C.c_void_p] * 4 +
+                            [C.c_int64, C.c_int32, C.c_int32] + [C.c_void_p] * 4),
+    "copo_cka_finish": (C.c_int, [C.c_void_p] * 3 + [C.c_int32] * 3 + [C.c_void_p] * 5),
     "copo_ig_obs_seats_f32": (C.c_int, [C.POINTER(PpoCfg), C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p,
                                         C.c_int64, C.c_int64] + [C.c_void_p] * 3 + [C.c_int32] * 3 + [C.c_void_p, C.c_int32, C.c_void_p,
                                         C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),

@@ -20,6 +20,7 @@
 //      learn_linbound.inc: lin_obs_kernel, linear bounds of the same means (one relaxation per tanh unit, carried backward), intersected with them
 //      learn_jury.inc: jury_obs_kernel, the forward of every JUDGE of a row into a plane of its own (a row may stand in many members' lists)
 //      learn_attrib.inc: ig_obs_kernel, integrated gradients of both action means down to the input row, all quadrature points in one resident workgroup
+//      learn_hidden.inc: hidden_obs_kernel, the jury's forward stopped behind layer 2: both tanh layers of every judge's rows, kept by position
 //   5. LCF meta kernels: meta_lcf / meta_finish (step by step), meta_batch_fold / dot / rowstat, meta_seq (all LCF
 //      Adam steps of a pass in one workgroup)
 //   6. reduce_adam_kernel (fold of row-split partials + Adam; legacy two-net meta step), wgrad_adam_kernel (weight
@@ -52,6 +53,7 @@ namespace copo {
 #include "learn_linbound.inc"
 #include "learn_jury.inc"
 #include "learn_attrib.inc"
+#include "learn_hidden.inc"
 #include "learn_meta.inc"
 #include "learn_update.inc"
 #include "learn_plan.inc"
@@ -410,6 +412,26 @@ extern "C" int copo_jury_obs_seats_f32(const copo_ppo_cfg* cfg, const float* the
     if (gemm_lds_attrs() != hipSuccess) return COPO_ERR_DEVICE;
     JuryArgs a{SeatHead{*cfg, theta, theta_t, member_stride, rows, counts, cap, n_out, obs_src, 0, 0, 1, nullptr, 0, nullptr, nullptr, 0, n_members},
                verdict};
+    void* args[] = {&a};
+    return launch_kernel(l, args, static_cast<hipStream_t>(stream)) == hipSuccess ? COPO_OK : COPO_ERR_DEVICE;
+}
+
+// The hidden-layer pass: the jury's launch shape and checks; the output is indexed by position in a judge's list, not by row.
+extern "C" int copo_hidden_obs_seats_f32(const copo_ppo_cfg* cfg, const float* theta, const float* theta_t, int64_t member_stride,
+                                         int32_t n_members, const int64_t* rows, const int32_t* counts, int64_t cap, int64_t n_out,
+                                         const float* obs_src, float* hidden, void* stream) {
+    int rc = check_cfg(cfg);
+    if (rc != COPO_OK) return rc;
+    if (!theta || !theta_t || !rows || !counts || !obs_src || !hidden) return COPO_ERR_NULL;
+    if (cap < 1 || n_out < 1 || n_members < 1 || n_members > 65535 || member_stride < cfg->n_params || member_stride % 4 != 0 || !aligned16(hidden))
+        return COPO_ERR_DIM;
+    Launch l;
+    rc = plan_seat_pass(*cfg, cap, n_members, aligned16(theta_t) ? FACT_MIRROR_ALIGNED : 0, K_HIDDEN_1_4,
+                        hidden_lds_floats(cfg->hidden, rowpass_k1p(cfg->pol.in_dim)), LDS_ROWPASS, &l);
+    if (rc != COPO_OK) return rc;
+    if (gemm_lds_attrs() != hipSuccess) return COPO_ERR_DEVICE;
+    HiddenArgs a{SeatHead{*cfg, theta, theta_t, member_stride, rows, counts, cap, n_out, obs_src, 0, 0, 1, nullptr, 0, nullptr, nullptr, 0, n_members},
+                 hidden};
     void* args[] = {&a};
     return launch_kernel(l, args, static_cast<hipStream_t>(stream)) == hipSuccess ? COPO_OK : COPO_ERR_DEVICE;
 }

@@ -33,7 +33,7 @@ constexpr int LDS_LINBOUND = 136 * 1024;    // lin_obs_kernel keeps 11.5 KB of s
     X(WGRAD_OT2, 64 * WG_WAVES, 80 * 1024, wgrad_adam_kernel<2>)                                                             \
     X(HEAD, 256, LDS_DEFAULT, head_kernel) X(META_FOLD, 256, LDS_DEFAULT, meta_batch_fold_kernel)                            \
     X(REDUCE_ADAM, 256, LDS_DEFAULT, reduce_adam_kernel)
-// rows behind the learner's: kernels of the evaluation side that live in this translation unit (learn_seat.inc, learn_inputgrad.inc, learn_pgd.inc, learn_certify.inc, learn_linbound.inc, learn_jury.inc, learn_attrib.inc).  They are launched
+// rows behind the learner's: kernels of the evaluation side that live in this translation unit (learn_seat.inc, learn_inputgrad.inc, learn_pgd.inc, learn_certify.inc, learn_linbound.inc, learn_jury.inc, learn_attrib.inc, learn_hidden.inc).  They are launched
 // through the same launch_kernel and get their LDS ceilings from the same loop; copo_debug_learner_kernel lists the learner's rows only
 // (ids below K_LEARNER_COUNT).  Per kernel the four shapes in shape_index order.
 #define COPO_EVAL_KERNELS(X)                                                                                                \
@@ -48,7 +48,9 @@ constexpr int LDS_LINBOUND = 136 * 1024;    // lin_obs_kernel keeps 11.5 KB of s
     X(JURY_1_4, 256, LDS_ROWPASS, jury_obs_kernel<1, 4>) X(JURY_2_4, 256, LDS_ROWPASS, jury_obs_kernel<2, 4>)                \
     X(JURY_2_8, 512, LDS_ROWPASS, jury_obs_kernel<2, 8>) X(JURY_4_8, 512, LDS_ROWPASS, jury_obs_kernel<4, 8>)                \
     X(IG_1_4, 256, LDS_ROWPASS, ig_obs_kernel<1, 4>) X(IG_2_4, 256, LDS_ROWPASS, ig_obs_kernel<2, 4>)                        \
-    X(IG_2_8, 512, LDS_ROWPASS, ig_obs_kernel<2, 8>) X(IG_4_8, 512, LDS_ROWPASS, ig_obs_kernel<4, 8>)
+    X(IG_2_8, 512, LDS_ROWPASS, ig_obs_kernel<2, 8>) X(IG_4_8, 512, LDS_ROWPASS, ig_obs_kernel<4, 8>)                        \
+    X(HIDDEN_1_4, 256, LDS_ROWPASS, hidden_obs_kernel<1, 4>) X(HIDDEN_2_4, 256, LDS_ROWPASS, hidden_obs_kernel<2, 4>)        \
+    X(HIDDEN_2_8, 512, LDS_ROWPASS, hidden_obs_kernel<2, 8>) X(HIDDEN_4_8, 512, LDS_ROWPASS, hidden_obs_kernel<4, 8>)
 struct KernelEntry { const char* name; const void* fn; int block, lds_cap; };
 #define COPO_KERNEL_ID(id, block, cap, ...) K_##id,
 #define COPO_KERNEL_ENTRY(id, block, cap, ...) {#__VA_ARGS__, reinterpret_cast<const void*>(__VA_ARGS__), block, cap},
@@ -241,7 +243,7 @@ static int plan_forward(const copo_ppo_cfg& c, int64_t n_rows, int first_net, in
 }
 
 // The four seat passes of a seated bank (copo_adv / pgd / cert / lin_obs_seats_f32; learn_inputgrad.inc, learn_pgd.inc, learn_certify.inc,
-// learn_linbound.inc), the jury pass (copo_jury_obs_seats_f32, learn_jury.inc) and the attribution pass (copo_ig_obs_seats_f32, learn_attrib.inc): the launch shape of seat mode -- `cap` rows per member at the most, the member as the grid's second dimension --
+// learn_linbound.inc), the jury pass (copo_jury_obs_seats_f32, learn_jury.inc) the attribution pass (copo_ig_obs_seats_f32, learn_attrib.inc) and the hidden-layer pass (copo_hidden_obs_seats_f32, learn_hidden.inc): the launch shape of seat mode -- `cap` rows per member at the most, the member as the grid's second dimension --
 // and always the 16-row tile, at every hidden width.  fp32 operands only.  `first_id`: the pass's hidden-64 table entry; `lds_floats`:
 // its dynamic LDS (every pass holds at least adv_obs_kernel's two h tiles, one input tile and the W3 rows: the iterate of the PGD pass is
 // a second input tile, the bound passes hold three of each); `lds_cap`: LDS_ROWPASS, or LDS_LINBOUND for the linear pass, which keeps

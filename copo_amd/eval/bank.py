@@ -191,6 +191,21 @@ class PolicyBank:
             C.byref(self.cfg), self.theta.data_ptr(), self.theta_t.data_ptr(), self.stride, self.K, jb.rows.data_ptr(), jb.counts.data_ptr(),
             jb.cap, jb.n_out, obs.data_ptr(), verdict.data_ptr(), self._capi.current_stream()))
 
+    def hidden_seats(self, jury_buffers, obs, hidden):
+        """`copo_hidden_obs_seats_f32` (eval/similarity.py) on the current stream: obs [n_out, O] -> hidden [K, cap, 2, H], both tanh
+        layers of every JUDGE j on the rows of its list in `jury_buffers`, at the POSITION of the row in the list: the bits the jury
+        pass holds before its heads.  Positions at or past a judge's count are left alone.  Needs the mirror (`sync_mirror`), as
+        `act_seats`."""
+        jb = jury_buffers
+        if jb.K != self.K:
+            raise ValueError("PolicyBank.hidden_seats: judges' lists for %d members and a bank of %d" % (jb.K, self.K))
+        for name, t, shape in (("obs", obs, (jb.n_out, int(self.cfg.pol.in_dim))), ("hidden", hidden, (self.K, jb.cap, 2, int(self.cfg.hidden)))):
+            if tuple(t.shape) != shape or not t.is_contiguous() or t.dtype != torch.float32:
+                raise ValueError("PolicyBank.hidden_seats: %s of shape %s, contiguous float32 %s wanted" % (name, tuple(t.shape), list(shape)))
+        self._capi.check(self._capi.lib.copo_hidden_obs_seats_f32(
+            C.byref(self.cfg), self.theta.data_ptr(), self.theta_t.data_ptr(), self.stride, self.K, jb.rows.data_ptr(), jb.counts.data_ptr(),
+            jb.cap, jb.n_out, obs.data_ptr(), hidden.data_ptr(), self._capi.current_stream()))
+
 
 class _BankPolicy:
     """What `VecSampler` reads of a policy, with the bank as its fused learner."""

@@ -185,6 +185,12 @@ class SeatedBank:
             raise ValueError("SeatedBank.jury_seats: judges' lists over %d rows, the plan has %d" % (jury_buffers.n_out, self.buffers.n_out))
         self.bank.jury_seats(jury_buffers, obs, verdict)
 
+    def hidden_seats(self, jury_buffers, obs, hidden):
+        """`PolicyBank.hidden_seats` on the rows of the plan (eval/similarity.py): the judges' lists must cover the plan's [E * N] rows."""
+        if jury_buffers.n_out != self.buffers.n_out:
+            raise ValueError("SeatedBank.hidden_seats: judges' lists over %d rows, the plan has %d" % (jury_buffers.n_out, self.buffers.n_out))
+        self.bank.hidden_seats(jury_buffers, obs, hidden)
+
 
 class SeatSampler(VecSampler):
     """`VecSampler` with a `SeatedBank` in the policy's place, as `BankSampler` puts a bank there, and the seat tally behind every

@@ -317,16 +317,24 @@ STUDIES = (
     Study("precision_sweep", "precision", "precision_sweep_rows", share=1.0, extra=_precision_args),
 )
 # The ninth study: input attribution (eval/attribution.py).  It takes no --share, as certify takes none.  `STUDIES` stays the eight
-# entries that tests/test_eval_cli_cpu.py enumerates by name; `main` walks `ALL_STUDIES`, so "one table per run" and "goes with" cover
-# every entry by the same two loops.
+# entries that tests/test_eval_cli_cpu.py enumerates by name; `main` walks `TABLE_STUDIES` below, which holds them all, so "one table per run" and
+# "goes with" cover every entry by the same two loops.
 ALL_STUDIES = STUDIES + (Study("attribution", "attribution", "attribution_rows", "attribution_levels"),)
+# The tenth: representation similarity (eval/similarity.py), on the scenes of --cross-play.  `ALL_STUDIES` stays the nine entries that
+# tests/test_attribution_cpu.py counts; `main` walks `TABLE_STUDIES`.
+TABLE_STUDIES = ALL_STUDIES + (
+    Study("similarity", "similarity", "similarity_rows", share=0.5, scenes="scenes_per_pair", extra=lambda a: dict(rows_of=a.similarity_rows_of),
+          drop=("label_a", "label_b"), epilogue="similarity_matrices"),)
 # the options that belong to some studies only: given (not at its default) without one of them, an option is a usage error
 GOES_WITH = dict(jury_plan=("jury",), jury_deltas=("jury", "precision_sweep"), influence_max=("influence",), influence_deltas=("influence",),
                  precisions=("precision_sweep",), certify_method=("certify_sweep",))
+# ... and with the options of `TABLE_STUDIES`' own entries: `GOES_WITH` stays the table that tests/test_eval_cli_cpu.py compares with its
+# own list of options, and `main` walks this one
+TABLE_GOES_WITH = dict(GOES_WITH, similarity_rows_of=("similarity",))
 
 
 def run_study(ap, a, study):
-    """One entry of `STUDIES` from the parsed options `a`: its table written to --table and printed."""
+    """One entry of `TABLE_STUDIES` from the parsed options `a`: its table written to --table and printed."""
     import importlib
     from .checkpoint_io import load_members
     needs = [o for o in (study.levels, "table") if o]
@@ -430,12 +438,18 @@ def main(argv=None):
     ap.add_argument("--attribution-levels", default=None, metavar="JSON",
                     help="with --attribution: a JSON list of {points, baseline}; baseline is \"clear_road\", \"zeros\" or a row of numbers "
                          "in which null masks a column")
+    ap.add_argument("--similarity", nargs="+", default=None, metavar="CKPT",
+                    help="checkpoints of --algo's layout on the scenes of --cross-play, compared by linear CKA of both hidden layers on the "
+                         "states the scenes visit (eval/similarity.py: what the checkpoints compute inside, not what they do): one row per "
+                         "(checkpoint a, checkpoint b, layer) into --table; takes --share, --scenes-per-pair and --steps")
+    ap.add_argument("--similarity-rows-of", type=int, default=None, metavar="INDEX",
+                    help="with --similarity: count only the rows that checkpoint INDEX drives (default: every acted row)")
     a = ap.parse_args(argv)
     from .checkpoint_io import load_members
-    named = [s for s in ALL_STUDIES if getattr(a, s.option)]
+    named = [s for s in TABLE_STUDIES if getattr(a, s.option)]
     if len(named) > 1:
         ap.error("%s: one table per run" % " and ".join(_flag(s.option) for s in named))
-    for option, studies in GOES_WITH.items():
+    for option, studies in TABLE_GOES_WITH.items():
         if getattr(a, option) != ap.get_default(option) and not any(s.option in studies for s in named):
             ap.error("%s goes with %s" % (_flag(option), " or ".join(_flag(s) for s in studies)))
     if named:

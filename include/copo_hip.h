@@ -1175,6 +1175,50 @@ int copo_ig_obs_seats_f32(const copo_ppo_cfg* cfg, const float* theta, const flo
 int copo_jury_obs_seats_f32(const copo_ppo_cfg* cfg, const float* theta, const float* theta_t, int64_t member_stride,
                             int32_t n_members, const int64_t* rows, const int32_t* counts, int64_t cap, int64_t n_out,
                             const float* obs_src, float* verdict, void* stream);
+/* The hidden-layer pass of a seated bank (eval/similarity.py): the fourth mode of the bank's forward, the jury pass
+ * stopped behind layer 2.  Lists, parameters and launch shape as copo_jury_obs_seats_f32.  For the row r at position p of judge j's list
+ * it writes h1 = tanh(W1 o + b1) to hidden[j][p][0][0..H) and h2 = tanh(W2 h1 + b2) to hidden[j][p][1][0..H): hidden device fp32
+ * [n_members][cap][2][hidden], unit fastest, 16-byte aligned -- indexed by POSITION in the judge's list, which is what copo_cka_accumulate
+ * stages with 128-bit loads (sixteen lanes on 256 consecutive bytes of one position).  The values are the bits the jury kernel holds in
+ * its two LDS tiles for that judge and row, whichever other rows share the tile.  Positions at or past counts[j] (the masked rows of a
+ * last, partial tile among them) and positions whose index lies outside [0, n_out) are not written; verdict[row][judge] is not
+ * written at all.  No sampling, no atomics, fixed summation order: two launches give the same bits.  Refusals as
+ * copo_jury_obs_seats_f32, with `hidden` in `verdict`'s place. */
+int copo_hidden_obs_seats_f32(const copo_ppo_cfg* cfg, const float* theta, const float* theta_t, int64_t member_stride,
+                              int32_t n_members, const int64_t* rows, const int32_t* counts, int64_t cap, int64_t n_out,
+                              const float* obs_src, float* hidden, void* stream);
+/* ---- representation similarity: linear centred kernel alignment of the hidden layers of a panel of bank members
+ * on the same rows.  Stateless.  copo_cka_accumulate, once per env step: hidden as copo_hidden_obs_seats_f32 wrote it (n_members, cap, H =
+ * the hidden width, a multiple of 64 up to COPO_CKA_MAX_HIDDEN); panel device [n_panel] int32, the members compared (n_panel in
+ * 1..COPO_CKA_MAX_PANEL; an entry outside [0, n_members) adds nothing); rows device [cap] int64 and count device [1] int32: the common
+ * list (every panel member's list is this one); flags device [n_out] uint8 (the step's output), seat device [n_out] int32; rows_of: < 0,
+ * or the member whose driven rows alone are counted.  Position p is COUNTED when p < min(count, cap), 0 <= rows[p] < n_out,
+ * flags[rows[p]] carries COPO_F_ACTED and (rows_of < 0 or seat[rows[p]] == rows_of).  With P = n_panel (n_panel + 1) / 2 pairs a <= b of
+ * panel indices, pair (a, b) at index a n_panel - a (a - 1) / 2 + (b - a), over the counted positions and both layers l:
+ *     S[r][pair][l][i][j] += sum_p h_a,l[p][i] h_b,l[p][j]     s[r][a][l][i] += sum_p h_a,l[p][i]     n[r] += counted positions
+ * S device float64 [n_planes][P][2][H][H], s device float64 [n_planes][n_panel][2][H], n device int64 [n_planes]; plane r holds the
+ * chunks r, r + n_planes, ... of COPO_CKA_CHUNK positions (n_planes in 1..COPO_CKA_MAX_PLANES is the caller's: a fixed row split that
+ * fills the chip at a small panel, a property of the plan and never of the device).  The products are accumulated in fp32 on
+ * v_mfma_f32_16x16x4_f32 and added to the float64 accumulator after every COPO_CKA_PROMOTE_ROWS positions of a plane and at the end of
+ * the launch; every accumulator element has one owner and one order, no atomics: the same sequence of launches leaves the same bits.  A
+ * position that is not counted contributes exact zeros whatever the workspace holds there.  All three outputs ACCUMULATE (the caller
+ * clears them).  copo_cka_finish: the planes summed in plane order, n = sum_r n[r], then in float64 with a fixed summation order
+ *     hsic[a][b][l] = || S[a,b,l] - s[a,l] s[b,l]^T / n ||_F^2      (hsic device float64 [n_panel][n_panel][2], both triangles)
+ *     mean[a][l][i] = s[a,l][i] / n,   var[a][l][i] = S[a,a,l][i][i] / n - mean^2      (device float64 [n_panel][2][H] each)
+ * and *n_out = n (device int64); with n < 2 every float64 output is zero.  Linear CKA is hsic[a][b] / sqrt(hsic[a][a] hsic[b][b]), the
+ * host's to form.  One launch each on the caller's stream, no allocation, no host synchronisation; both may be captured in a graph.
+ * NULL pointers: COPO_ERR_NULL; dimensions outside the ranges above, rows_of >= n_members, a hidden pointer that is not 16-byte
+ * aligned: COPO_ERR_DIM; a refused call launches nothing. */
+#define COPO_CKA_CHUNK 32
+#define COPO_CKA_PROMOTE_ROWS 128
+#define COPO_CKA_MAX_PLANES 8
+#define COPO_CKA_MAX_PANEL 255
+#define COPO_CKA_MAX_HIDDEN 512
+int copo_cka_accumulate(const float* hidden, int32_t n_members, int64_t cap, int32_t H, const int32_t* panel, int32_t n_panel,
+                        const int64_t* rows, const int32_t* count, const uint8_t* flags, const int32_t* seat, int64_t n_out,
+                        int32_t rows_of, int32_t n_planes, double* S, double* s, int64_t* n, void* stream);
+int copo_cka_finish(const double* S, const double* s, const int64_t* n, int32_t n_panel, int32_t H, int32_t n_planes, double* hsic,
+                    int64_t* n_out, double* mean, double* var, void* stream);
 /* ---- low-precision policy forward of a seated bank (eval/precision.py; ABI 8, new symbols).  A format is
  * COPO_LOWP_BF16 (bfloat16) or COPO_LOWP_E4M3 (OCP float8 e4m3fn: no infinities, largest value 448).  rnd rounds to nearest even into the
  * format (e4m3: after a clamp to [-448, 448]; subnormals kept).
