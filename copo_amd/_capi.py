@@ -102,6 +102,10 @@ _SIGS = {
     "copo_cka_accumulate": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_void_p, C.c_int32] + [C.c_void_p] * 4 +
                             [C.c_int64, C.c_int32, C.c_int32] + [C.c_void_p] * 4),
     "copo_cka_finish": (C.c_int, [C.c_void_p] * 3 + [C.c_int32] * 3 + [C.c_void_p] * 5),
+    "copo_probe_targets": (C.c_int, [C.c_void_p, C.c_int64] + [C.c_int32] * 3 + [C.c_void_p] * 5 + [C.c_int64, C.c_void_p, C.c_void_p, C.c_int32,
+                                     C.c_void_p]),
+    "copo_probe_accumulate": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int64, C.c_int32] + [C.c_void_p] * 3 + [C.c_int64] +
+                              [C.c_void_p] * 3 + [C.c_int64] + [C.c_int32] * 3 + [C.c_void_p] * 4),
     "copo_ig_obs_seats_f32": (C.c_int, [C.POINTER(PpoCfg), C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p,
                                         C.c_int64, C.c_int64] + [C.c_void_p] * 3 + [C.c_int32] * 3 + [C.c_void_p, C.c_int32, C.c_void_p,
                                         C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),

@@ -331,10 +331,16 @@ GOES_WITH = dict(jury_plan=("jury",), jury_deltas=("jury", "precision_sweep"), i
 # ... and with the options of `TABLE_STUDIES`' own entries: `GOES_WITH` stays the table that tests/test_eval_cli_cpu.py compares with its
 # own list of options, and `main` walks this one
 TABLE_GOES_WITH = dict(GOES_WITH, similarity_rows_of=("similarity",))
+# The eleventh: linear probes (eval/probes.py), on the scenes of --cross-play.  `TABLE_STUDIES` and `TABLE_GOES_WITH` stay what
+# tests/test_similarity_cpu.py compares; `main` walks `PROBE_STUDIES` and `PROBE_GOES_WITH`, which hold every entry.
+PROBE_STUDIES = TABLE_STUDIES + (
+    Study("probe", "probes", "probe_rows", share=0.5, scenes="scenes_per_pair",
+          extra=lambda a: dict(rows_of=a.probe_rows_of, ridge=1e-4 if a.probe_ridge is None else a.probe_ridge), epilogue="probe_matrix"),)
+PROBE_GOES_WITH = dict(TABLE_GOES_WITH, probe_rows_of=("probe",), probe_ridge=("probe",))
 
 
 def run_study(ap, a, study):
-    """One entry of `TABLE_STUDIES` from the parsed options `a`: its table written to --table and printed."""
+    """One entry of `PROBE_STUDIES` from the parsed options `a`: its table written to --table and printed."""
     import importlib
     from .checkpoint_io import load_members
     needs = [o for o in (study.levels, "table") if o]
@@ -444,12 +450,21 @@ def main(argv=None):
                          "(checkpoint a, checkpoint b, layer) into --table; takes --share, --scenes-per-pair and --steps")
     ap.add_argument("--similarity-rows-of", type=int, default=None, metavar="INDEX",
                     help="with --similarity: count only the rows that checkpoint INDEX drives (default: every acted row)")
+    ap.add_argument("--probe", nargs="+", default=None, metavar="CKPT",
+                    help="checkpoints of --algo's layout on the scenes of --cross-play, both hidden layers probed by ridge regressions for eight "
+                         "scene quantities (eval/probes.py: what a layer encodes; the scenes of a pair alternate between the train and the test "
+                         "fold, so --scenes-per-pair is at least 2): one row per (checkpoint, layer, quantity) and the observation's own as a "
+                         "control into --table; takes --share, --scenes-per-pair and --steps")
+    ap.add_argument("--probe-rows-of", type=int, default=None, metavar="INDEX",
+                    help="with --probe: count only the rows that checkpoint INDEX drives (default: every acted row)")
+    ap.add_argument("--probe-ridge", type=float, default=None, metavar="LAMBDA",
+                    help="with --probe: the ridge as a share of the mean feature variance (default 1e-4)")
     a = ap.parse_args(argv)
     from .checkpoint_io import load_members
-    named = [s for s in TABLE_STUDIES if getattr(a, s.option)]
+    named = [s for s in PROBE_STUDIES if getattr(a, s.option)]
     if len(named) > 1:
         ap.error("%s: one table per run" % " and ".join(_flag(s.option) for s in named))
-    for option, studies in TABLE_GOES_WITH.items():
+    for option, studies in PROBE_GOES_WITH.items():
         if getattr(a, option) != ap.get_default(option) and not any(s.option in studies for s in named):
             ap.error("%s goes with %s" % (_flag(option), " or ".join(_flag(s) for s in studies)))
     if named:

@@ -1219,6 +1219,46 @@ int copo_cka_accumulate(const float* hidden, int32_t n_members, int64_t cap, int
                         int32_t rows_of, int32_t n_planes, double* S, double* s, int64_t* n, void* stream);
 int copo_cka_finish(const double* S, const double* s, const int64_t* n, int32_t n_panel, int32_t H, int32_t n_planes, double* hsic,
                     int64_t* n_out, double* mean, double* var, void* stream);
+/* ---- linear probes (eval/probes.py; ABI 8, new symbols): the sufficient statistics of ridge regressions from feature
+ * blocks (the hidden layers copo_hidden_obs_seats_f32 keeps, the observation as a control) to per-row targets, on a train and a test fold.
+ * Stateless.  Lists as copo_cka_accumulate: rows device [cap] int64, count device [1] int32, the common list.
+ * copo_probe_targets, once per env step behind the simulator step, one wave per position p < min(count, cap) whose row r = rows[p] lies
+ * in [0, n_out): obs device fp32 [n_out][obs_dim], the observation the policy read; the LiDAR block is columns lidar_lo .. lidar_lo +
+ * num_lasers (beam 0 looks ahead, beam k is turned clockwise); trig device fp32 [num_lasers][2] = (cos, sin)(2 pi k / num_lasers), the
+ * host's float64 values rounded to fp32; flags device [n_out] uint8 and reward device fp32 [n_out], the step's outputs.  It writes
+ * targets[p][0..COPO_PROBE_PANEL): [0] nearest = the least beam (1 where no beam is below 1), [1] / [2] (1 - nearest) cos / sin of the LOWEST
+ * beam at that value (0 where no beam is below 1), [3] the share of beams below 1, [4] the least beam of the front quadrant (the beams k
+ * with ((k + n / 8) % n) 4 / n == 0; 1 at the most), [5] reward[r], [6] / [7] 1.0 where flags[r] carry COPO_F_CRASH / COPO_F_DONE, else
+ * 0.0; [COPO_PROBE_TARGETS .. 14] 0.0; [15] 1.0 -- and xobs[p][0..padded_dim) = obs[r], 0.0 beyond obs_dim (padded_dim a multiple of 64
+ * from obs_dim up to COPO_PROBE_MAX_WIDTH).  Other positions are not written.  Every fold over lanes is a total order or an integer sum:
+ * two launches give the same bits, and they are the bits of the same individually rounded fp32 operations on the host.
+ * copo_probe_accumulate, once per env step and workspace: x device fp32, x_floats floats, 16-byte aligned; block b in [0, n_blocks) is
+ * the width features at x[block_base[b] + p pos_stride ..) of every position p (block_base device [n_blocks] int64; a base that is
+ * negative, no multiple of 4 or does not hold cap positions inside x_floats adds nothing); targets device fp32 [cap][COPO_PROBE_PANEL];
+ * fold device uint8 [n_out / slots], the fold of the scene r / slots: 0 train, 1 test, COPO_PROBE_FOLD_NONE never counted.  Position p
+ * is COUNTED in fold f when copo_cka_accumulate would count it and fold[rows[p] / slots] == f.  Over the counted positions
+ *     G[r][f][b][i][j] += sum_p x_b[p][i] x_b[p][j]      (only the 64 x 64 tiles with i / 64 <= j / 64; the others are never written)
+ *     C[r][f][b][i][c] += sum_p x_b[p][i] targets[p][c]  T[r][f][c][d] += sum_p targets[p][c] targets[p][d]
+ * G device float64 [n_planes][2][n_blocks][width][width], C [n_planes][2][n_blocks][width][16], T [n_planes][2][16][16] (with column 15
+ * == 1: C[..][15] the unit sums, T[15][15] the counted rows).  Planes, fp32 v_mfma_f32_16x16x4_f32 partials, promotion every
+ * COPO_CKA_PROMOTE_ROWS positions of a plane, one owner and one order per element, masking of the operands and accumulation as
+ * copo_cka_accumulate.  One launch each on the caller's stream, grid (nt (nt + 1) / 2 + 1) x n_blocks x 2 n_planes with nt = width / 64;
+ * no allocation, no host synchronisation; both may be captured in a graph.  NULL pointers: COPO_ERR_NULL; width no multiple of 64 in
+ * 64..COPO_PROBE_MAX_WIDTH, n_blocks outside 1..COPO_PROBE_MAX_BLOCKS, n_planes outside 1..COPO_CKA_MAX_PLANES, cap or n_out < 1, n_out no
+ * multiple of slots, pos_stride below width or no multiple of 4, cap positions beyond x_floats, num_lasers < 1 or a LiDAR block outside
+ * the row, a misaligned x: COPO_ERR_DIM; a refused call launches nothing. */
+#define COPO_PROBE_TARGETS 8
+#define COPO_PROBE_PANEL 16
+#define COPO_PROBE_MAX_WIDTH 512
+#define COPO_PROBE_MAX_BLOCKS 510
+#define COPO_PROBE_FOLD_NONE 255
+int copo_probe_targets(const float* obs, int64_t n_out, int32_t obs_dim, int32_t lidar_lo, int32_t num_lasers, const float* trig,
+                       const uint8_t* flags, const float* reward, const int64_t* rows, const int32_t* count, int64_t cap, float* targets,
+                       float* xobs, int32_t padded_dim, void* stream);
+int copo_probe_accumulate(const float* x, int64_t x_floats, const int64_t* block_base, int32_t n_blocks, int64_t pos_stride, int32_t width,
+                          const float* targets, const int64_t* rows, const int32_t* count, int64_t cap, const uint8_t* flags,
+                          const int32_t* seat, const uint8_t* fold, int64_t n_out, int32_t slots, int32_t rows_of, int32_t n_planes, double* G,
+                          double* C, double* T, void* stream);
 /* ---- low-precision policy forward of a seated bank (eval/precision.py; ABI 8, new symbols).  A format is
  * COPO_LOWP_BF16 (bfloat16) or COPO_LOWP_E4M3 (OCP float8 e4m3fn: no infinities, largest value 448).  rnd rounds to nearest even into the
  * format (e4m3: after a clamp to [-448, 448]; subnormals kept).
