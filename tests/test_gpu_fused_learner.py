@@ -9,46 +9,8 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
-from copo_amd.engine import Box, Postprocessing, SampleBatch, TorchDiagGaussian  # noqa: E402
-
-
-def _make(pcls_name, fuse, odim, fused, hiddens=(256, 256), mb=512, **over):
-    from copo_amd.torch_copo import algo_ccppo as C, algo_copo as A, algo_ippo as I
-    from copo_amd.torch_copo.utils.env_wrappers import (MultiAgentIntersectionEnv, get_ccenv, get_lcf_env,
-                                                        get_rllib_compatible_env)
-    pcls, ccls = dict(copo=(A.CoPOPolicy, A.CoPOConfig), ccppo=(C.CCPPOPolicy, C.CCPPOConfig),
-                      ippo=(I.IPPOPolicy, I.IPPOConfig))[pcls_name]
-    cfg = ccls()
-    env = get_rllib_compatible_env(get_lcf_env(MultiAgentIntersectionEnv) if pcls_name == "copo"
-                                   else get_ccenv(MultiAgentIntersectionEnv))
-    cfg.update_from_dict(dict(env=env, device="cuda", use_hip_graphs=False, use_fused_learner=fused, seed=3,
-                              sgd_minibatch_size=mb, model={"fcnet_hiddens": list(hiddens)}, **over))
-    if "fuse_mode" in cfg:
-        cfg.fuse_mode = fuse
-    cfg.validate()
-    return pcls(Box(-1, 1, (odim,)), Box(-1, 1, (2,)), cfg)
-
-
-def _dense_batch(pol, R, odim, seed=0):
-    g = torch.Generator(device="cuda").manual_seed(seed)
-    rn = lambda *s: torch.randn(*s, device="cuda", generator=g)  # noqa: E731
-    b = SampleBatch()
-    b[SampleBatch.OBS] = torch.rand(R, odim, device="cuda", generator=g) * 2 - 1
-    cdim = pol.model.value_input_dim()
-    if cdim != odim:
-        b["centralized_critic_obs"] = torch.cat([b[SampleBatch.OBS], rn(R, cdim - odim) * 0.5], 1)
-    b[SampleBatch.ACTIONS] = rn(R, 2) * 0.8
-    di = torch.cat([rn(R, 2) * 0.3, rn(R, 2) * 0.2 - 0.2], 1)
-    b[SampleBatch.ACTION_DIST_INPUTS] = di
-    b[SampleBatch.ACTION_LOGP] = TorchDiagGaussian(di).logp(b[SampleBatch.ACTIONS])
-    for k, s in [(Postprocessing.ADVANTAGES, 2), (SampleBatch.VF_PREDS, 3), ("nei_advantage", 2), ("global_advantages", 1),
-                 ("nei_values", 3), ("global_values", 30), ("normalized_advantages", 1)]:
-        b[k] = rn(R) * s
-    b[Postprocessing.VALUE_TARGETS] = b[SampleBatch.VF_PREDS] + rn(R) * 2 + rn(R) * 150 * (torch.rand(R, device="cuda", generator=g) < 0.3)
-    b["nei_target"] = b["nei_values"] + rn(R) * 2
-    b["global_target"] = b["global_values"] + rn(R) * 120
-    b[SampleBatch.FLAGS] = torch.ones(R, dtype=torch.uint8, device="cuda")
-    return b
+from copo_amd.engine import SampleBatch  # noqa: E402
+from ppo_cases import dense_batch as _dense_batch, make as _make  # noqa: E402  (one copy for this file, the meta referee and the PPO referee)
 
 
 def _copy_weights(dst, src):
@@ -107,6 +69,41 @@ def test_fused_sgd_matches_torch(name, fuse, odim, over):
     scale = float(g_ref.abs().max())
     err = float((g_ref - g_fz).abs().max())
     assert err <= 1e-5 * scale + 1e-8, (err, scale)      # (both are fp32 evaluations ~1e-6 x scale from the exact gradient)
+    # ... and every tensor on its OWN scale: the value nets' gradients dwarf the policy net's
+    missed = {}
+    for (pname, p_ref), p in zip(ref.model.named_parameters(), fz.model.parameters()):
+        if p.dtype != torch.float32:
+            continue
+        g_t, g_h = p_ref.grad.reshape(-1), fz.fused.grad[off[id(p)]:off[id(p)] + p.numel()]
+        scale_t, err_t = float(g_t.abs().max()), float((g_t - g_h).abs().max())
+        if not err_t <= 1e-5 * scale_t + 1e-9:
+            missed[id(p_ref)] = (pname, err_t, scale_t, g_t.double().cpu().numpy(), g_h.double().cpu().numpy())
+    if missed:
+        # The only tensor excused from 1e-5 of its own largest element is a one-element head bias that the float64 model of the same
+        # minibatch (tests/ppo_numpy.py) shows to be a CANCELLED sum: b3 = sum over the rows of d loss / d (head output), and |b3| is
+        # at most 1 / 50 of the sum of the absolute row terms (`head_abs`).  An fp32 sum of mb terms is accurate to a few 2^-24 of the
+        # absolute terms, i.e. to 1e-5 of the sum itself only while the terms cancel by less than ~50.  Such a tensor is held to the
+        # float64 referee's rule on the model (e_hip <= 3 e_t32 + mb 2^-24 of its value) AND to 1e-5 of the uncancelled scale, and it
+        # stays under the global assertion above; every other tensor fails here.  Seen: CoPO's neighbour value net at the production
+        # shape, 446 row terms that cancel to 1e-3 of their size (b3 = 2.16e-3): torch and HIP differ by 6.0e-8 = 2.8e-5 of it; against
+        # float64 HIP is off by 2.55e-5 of it (5.5e-8, 1e-8 of the row terms' size) and torch fp32 by 2.06e-6 -- the kernel's
+        # summation order on a cancelling sum, not a wrong term.
+        import ppo_cases as PC
+        import ppo_numpy as P
+        rs = fz._row_sources
+        m = PC.minibatch(PC.host_columns(batch, dict(policy=name)), rs["rows_all"][0].cpu().numpy(), rs["w_all"][0].cpu().numpy(), float(rs["denom_all"][0]))
+        r64 = P.step(P.theta_of_nets(PC.nets_of(ref.model)), m, PC.conf_of(ref))
+        for gi, net in enumerate(PC.params_of(ref.model)):
+            for tname, p_ref in net.items():
+                if id(p_ref) not in missed:
+                    continue
+                pname, err_t, scale_t, g_t32, g_hip = missed[id(p_ref)]
+                want, uncancelled = r64["grads"][gi][tname].reshape(-1), float(r64["head_abs"][gi].max())
+                e_hip, e_t32 = np.abs(g_hip - want).max() / np.abs(want).max(), np.abs(g_t32 - want).max() / np.abs(want).max()
+                print("%s: HIP vs torch %.2e of %.2e; against float64: HIP %.2e, torch fp32 %.2e of the largest element %.2e, uncancelled %.2e" % (
+                    pname, err_t, scale_t, e_hip, e_t32, np.abs(want).max(), uncancelled))
+                assert tname == "b3" and want.size == 1 and abs(want[0]) <= uncancelled / 50.0, (pname, err_t, scale_t)
+                assert e_hip <= 3.0 * e_t32 + mb * 2.0 ** -24 and abs(g_hip[0] - want[0]) <= 1e-5 * uncancelled, (pname, e_hip, e_t32, uncancelled)
     st = ref._row_sources["stats"].tolist()          # total, policy, vf, kl, entropy, (nei, glob, adv)
     fs = fz.fused.stats.tolist()                     # total, policy, vf_ego, kl, entropy, vf_nei, vf_glob, adv
     np.testing.assert_allclose(fs[:5], st[:5], rtol=2e-4, atol=1e-5)
