@@ -7,10 +7,10 @@ using namespace copo;
 
 // what both entries ask of the accumulators' geometry; the message names the entry point
 static int cka_check(const char* who, int32_t n_panel, int32_t H, int32_t n_planes) {
-    if (n_panel < 1 || n_panel > COPO_CKA_MAX_PANEL || H < CKA_TILE || H > COPO_CKA_MAX_HIDDEN || H % CKA_TILE != 0 || n_planes < 1 ||
+    if (n_panel < 1 || n_panel > COPO_CKA_MAX_PANEL || H < GRAM_TILE || H > COPO_CKA_MAX_HIDDEN || H % GRAM_TILE != 0 || n_planes < 1 ||
         n_planes > COPO_CKA_MAX_PLANES)
         return fail(COPO_ERR_DIM, "%s: n_panel=%d (1..%d) hidden=%d (a multiple of %d up to %d) n_planes=%d (1..%d)", who, n_panel, COPO_CKA_MAX_PANEL,
-                    H, CKA_TILE, COPO_CKA_MAX_HIDDEN, n_planes, COPO_CKA_MAX_PLANES);
+                    H, GRAM_TILE, COPO_CKA_MAX_HIDDEN, n_planes, COPO_CKA_MAX_PLANES);
     return COPO_OK;
 }
 

@@ -12,8 +12,8 @@ extern "C" int copo_probe_targets(const float* obs, int64_t n_out, int32_t O, in
     if (n_out < 1 || cap < 1 || cap > INT32_MAX || O < 1 || num_lasers < 1 || lidar_lo < 0 || (int64_t)lidar_lo + num_lasers > O)
         return fail(COPO_ERR_DIM, "copo_probe_targets: n_out=%lld cap=%lld (1..2^31-1) obs_dim=%d lidar_lo=%d num_lasers=%d (>= 1, inside the row)",
                     (long long)n_out, (long long)cap, O, lidar_lo, num_lasers);
-    if (Op < O || Op > COPO_PROBE_MAX_WIDTH || Op % PROBE_TILE != 0)
-        return fail(COPO_ERR_DIM, "copo_probe_targets: padded width=%d (a multiple of %d from obs_dim=%d up to %d)", Op, PROBE_TILE, O, COPO_PROBE_MAX_WIDTH);
+    if (Op < O || Op > COPO_PROBE_MAX_WIDTH || Op % GRAM_TILE != 0)
+        return fail(COPO_ERR_DIM, "copo_probe_targets: padded width=%d (a multiple of %d from obs_dim=%d up to %d)", Op, GRAM_TILE, O, COPO_PROBE_MAX_WIDTH);
     const ProbeTargetArgs a{obs, trig, flags, reward, rows, count, cap, n_out, O, Op, lidar_lo, num_lasers, targets, xobs};
     HIP_TRY(launch_probe_targets(a, static_cast<hipStream_t>(stream)));
     return COPO_OK;
@@ -25,9 +25,9 @@ extern "C" int copo_probe_accumulate(const float* x, int64_t x_floats, const int
                                      double* C, double* T, void* stream) {
     if (!x || !block_base || !targets || !rows || !count || !flags || !seat || !fold || !G || !C || !T)
         return fail(COPO_ERR_NULL, "copo_probe_accumulate: NULL argument");
-    if (D < PROBE_TILE || D > COPO_PROBE_MAX_WIDTH || D % PROBE_TILE != 0 || n_blocks < 1 || n_blocks > COPO_PROBE_MAX_BLOCKS || n_planes < 1 ||
+    if (D < GRAM_TILE || D > COPO_PROBE_MAX_WIDTH || D % GRAM_TILE != 0 || n_blocks < 1 || n_blocks > COPO_PROBE_MAX_BLOCKS || n_planes < 1 ||
         n_planes > COPO_CKA_MAX_PLANES)
-        return fail(COPO_ERR_DIM, "copo_probe_accumulate: width=%d (a multiple of %d up to %d) n_blocks=%d (1..%d) n_planes=%d (1..%d)", D, PROBE_TILE,
+        return fail(COPO_ERR_DIM, "copo_probe_accumulate: width=%d (a multiple of %d up to %d) n_blocks=%d (1..%d) n_planes=%d (1..%d)", D, GRAM_TILE,
                     COPO_PROBE_MAX_WIDTH, n_blocks, COPO_PROBE_MAX_BLOCKS, n_planes, COPO_CKA_MAX_PLANES);
     if (cap < 1 || cap > INT32_MAX || n_out < 1 || slots < 1 || n_out % slots != 0 || pos_stride < D || pos_stride % 4 != 0 || x_floats < 1 ||
         pos_stride > x_floats / cap)

@@ -5,12 +5,9 @@
 #include <stdint.h>
 
 #include "../../include/copo_hip.h"
+#include "gram_common.h"      // GRAM_TILE: a workgroup owns a 64 x 64 tile of one S[a, b, l]
 
 namespace copo {
-
-constexpr int CKA_TILE = 64;                                  // a workgroup owns a 64 x 64 tile of one S[a, b, l]
-constexpr int CKA_CHUNK = COPO_CKA_CHUNK;                     // positions staged through LDS at a time
-constexpr int CKA_PROMOTE_CHUNKS = COPO_CKA_PROMOTE_ROWS / COPO_CKA_CHUNK;      // fp32 partial -> float64 accumulator after so many chunks
 
 struct CkaArgs {
     const float* hidden;      // [n_members][cap][2][H]

@@ -5,14 +5,12 @@
 #include <stdint.h>
 
 #include "../../include/copo_hip.h"
+#include "gram_common.h"      // GRAM_TILE: a workgroup owns a 64 x 64 tile of one G[f, b]
 
 namespace copo {
 
-constexpr int PROBE_TILE = 64;                                // a workgroup owns a 64 x 64 tile of one G[f, b]
 constexpr int PROBE_PANEL = COPO_PROBE_PANEL;                 // the columns of a target row: Q targets, zeros, the ones column
-constexpr int PROBE_CHUNK = COPO_CKA_CHUNK;                   // positions staged through LDS at a time
-constexpr int PROBE_PROMOTE_CHUNKS = COPO_CKA_PROMOTE_ROWS / COPO_CKA_CHUNK;      // fp32 partial -> float64 accumulator after so many chunks
-constexpr int PROBE_MAX_TILES = COPO_PROBE_MAX_WIDTH / PROBE_TILE;
+constexpr int PROBE_MAX_TILES = COPO_PROBE_MAX_WIDTH / GRAM_TILE;
 
 struct ProbeTargetArgs {
     const float* obs;         // [n_out][O]

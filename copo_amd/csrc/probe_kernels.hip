@@ -8,29 +8,24 @@
 // butterfly whose every step is a total order (value, then beam index) or an integer sum: the result does not depend on the order, and
 // two launches give the same bits.  cos / sin of the nearest beam come from the host's table, never from the device.
 // probe_gram_kernel, one launch per env step and feature workspace.  With x_b[p] the D features of block b at position p and the positions
-// COUNTED in fold f (p < count, the row's flags carry COPO_F_ACTED, rows_of < 0 or the row's seat is rows_of, fold[scene of the row] == f):
+// COUNTED in fold f (gram_common.h, with the fold term):
 //     G[f,b][i][j] += sum_p x_b[p][i] x_b[p][j]   (64 x 64 tiles ti <= tj)      C[f,b][i][c] += sum_p x_b[p][i] t[p][c]      T[f][c][d] += sum_p t[p][c] t[p][d]
 // Grid: (nt (nt + 1) / 2 + 1) x B x (2 folds * R planes), nt = D / 64, 256 threads.  Workgroup x < nt (nt + 1) / 2 owns the upper tile
-// (ti, tj) of G[f,b] in plane r and is cka_gram_kernel's workgroup (cka_kernels.hip) with both operands taken from one block: chunks of 32
-// positions through LDS, the next chunk's loads in flight, wave w on rows 16 w .. 16 w + 15 of the tile as four accumulators of
-// v_mfma_f32_16x16x4_f32.  The last workgroup x of a block owns C[f,b], the 16-wide target panel as one more tile column: wave w holds
-// rows 64 t + 16 w .. + 15 of every tile t as nt accumulators, operands straight from memory (16 lanes on 64 consecutive bytes of one
-// position); the one of block 0 owns T[f] as well, in wave 0.  Plane r takes chunks r, r + R, ... in ascending order; every fourth chunk
-// of its own and at the end a workgroup adds its fp32 partials to its float64 plane with a plain load-add-store.  One owner and one order
-// per accumulator element, no atomics: two runs of the same sequence of launches leave the same bits.  A position that is not counted
-// contributes exact zeros: the OPERAND is replaced by zero, whatever the workspaces hold there (not-a-numbers included).  A block whose
-// base does not fit the workspace adds nothing.
+// (ti, tj) of G[f,b] in plane r and is gram_tile (gram_common.h: the chunk walk, the staging, the matrix-core loop and the promotion to
+// float64 are described there) with both operands taken from one block and no riders.  The last workgroup x of a block owns C[f,b], the
+// 16-wide target panel as one more tile column: wave w holds rows 64 t + 16 w .. + 15 of every tile t as nt accumulators, operands
+// straight from memory (16 lanes on 64 consecutive bytes of one position); the one of block 0 owns T[f] as well, in wave 0.  It walks
+// the tile's chunks in the tile's order, promotes at the tile's interval and masks the operand as the tile does.  A block whose base does
+// not fit the workspace adds nothing.
 #include "probe_common.h"
+#include "gram_common.h"
 
 namespace copo {
-
-typedef float probe_v4f __attribute__((ext_vector_type(4)));
-constexpr int PROBE_STRIDE = 80;      // floats per staged position: 64 units + 16, so that positions p .. p + 3 start on banks 0 / 16 / 32 / 48
 
 __global__ __launch_bounds__(256) void probe_targets_kernel(ProbeTargetArgs a) {
     const int lane = threadIdx.x & 63;
     const int64_t p = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    const int64_t listed = *a.count, count = listed < 0 ? 0 : listed < a.cap ? listed : a.cap;
+    const int64_t count = gram_count(a.count, a.cap);
     if (p >= count) return;      // (uniform over the wave)
     const int64_t row = a.rows[p];
     if (row < 0 || row >= a.n_out) return;
@@ -78,30 +73,16 @@ __global__ __launch_bounds__(256) void probe_targets_kernel(ProbeTargetArgs a) {
     for (int c = lane; c < a.Op; c += 64) a.xobs[(size_t)p * a.Op + c] = c < a.O ? o[c] : 0.0f;
 }
 
-// (by value: a reference to the kernel's argument struct would put the struct on the stack)
-struct ProbeMask {
-    const int64_t* rows;
-    const uint8_t* flags;
-    const int32_t* seat;
-    const uint8_t* fold;
-    int64_t count, n_out;
-    int32_t slots, rows_of, f;
-};
-__device__ __forceinline__ bool probe_counted(const ProbeMask m, int64_t p) {
-    if (p >= m.count) return false;
-    const int64_t r = m.rows[p];
-    if (r < 0 || r >= m.n_out) return false;
-    return (m.flags[r] & COPO_F_ACTED) != 0 && (m.rows_of < 0 || m.seat[r] == m.rows_of) && m.fold[r / m.slots] == m.f;
-}
+typedef GramMask<true> ProbeMask;
 
 // the workgroup of the target panel: C[f,b] = X_b^T t of this plane's chunks, and T[f] = t^T t where own_T
 __device__ __forceinline__ void probe_panel(const ProbeArgs a, const ProbeMask mask, const float* xb, bool valid, bool own_T, int plane, int64_t n_chunks,
                                             double* C, double* T) {
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), ln = lane & 15, lj = lane >> 4;
-    const int nt = valid ? a.D / PROBE_TILE : 0;
-    probe_v4f acc[PROBE_MAX_TILES], acct = {0.f, 0.f, 0.f, 0.f};
+    const int nt = valid ? a.D / GRAM_TILE : 0;
+    gram_v4f acc[PROBE_MAX_TILES], acct = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-    for (int t = 0; t < PROBE_MAX_TILES; ++t) acc[t] = probe_v4f{0.f, 0.f, 0.f, 0.f};
+    for (int t = 0; t < PROBE_MAX_TILES; ++t) acc[t] = gram_v4f{0.f, 0.f, 0.f, 0.f};
     C += (size_t)(16 * wave + 4 * lj) * PROBE_PANEL + ln;
     T += (size_t)(4 * lj) * PROBE_PANEL + ln;
     auto promote = [&]() __attribute__((always_inline)) {
@@ -110,36 +91,36 @@ __device__ __forceinline__ void probe_panel(const ProbeArgs a, const ProbeMask m
             if (t < nt) {
 #pragma unroll
                 for (int rr = 0; rr < 4; ++rr) {
-                    double* at = C + (size_t)(PROBE_TILE * t + rr) * PROBE_PANEL;
+                    double* at = C + (size_t)(GRAM_TILE * t + rr) * PROBE_PANEL;
                     *at = *at + (double)acc[t][rr];
                 }
             }
-            acc[t] = probe_v4f{0.f, 0.f, 0.f, 0.f};
+            acc[t] = gram_v4f{0.f, 0.f, 0.f, 0.f};
         }
         if (own_T && wave == 0) {
 #pragma unroll
             for (int rr = 0; rr < 4; ++rr) T[rr * PROBE_PANEL] = T[rr * PROBE_PANEL] + (double)acct[rr];
         }
-        acct = probe_v4f{0.f, 0.f, 0.f, 0.f};
+        acct = gram_v4f{0.f, 0.f, 0.f, 0.f};
     };
     int since = 0;
     for (int64_t c = plane; c < n_chunks; c += a.R) {
-        const unsigned long long bits = __ballot(lane < PROBE_CHUNK && probe_counted(mask, c * PROBE_CHUNK + lane));      // the chunk's counted positions
+        const unsigned long long bits = __ballot(lane < GRAM_CHUNK && gram_counted(mask, c * GRAM_CHUNK + lane));      // the chunk's counted positions
 #pragma unroll 2
-        for (int ks = 0; ks < PROBE_CHUNK / 4; ++ks) {
+        for (int ks = 0; ks < GRAM_CHUNK / 4; ++ks) {
             const bool ok = (bits >> (4 * ks + lj)) & 1;
-            const size_t p = ok ? (size_t)(c * PROBE_CHUNK + 4 * ks + lj) : 0;
+            const size_t p = ok ? (size_t)(c * GRAM_CHUNK + 4 * ks + lj) : 0;
             const float tl = a.targets[p * PROBE_PANEL + ln], tv = ok ? tl : 0.f;      // the operand is masked, not the product
 #pragma unroll
             for (int t = 0; t < PROBE_MAX_TILES; ++t) {
                 if (t < nt) {
-                    const float xl = xb[p * a.pos_stride + PROBE_TILE * t + 16 * wave + ln];
+                    const float xl = xb[p * a.pos_stride + GRAM_TILE * t + 16 * wave + ln];
                     acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(ok ? xl : 0.f, tv, acc[t], 0, 0, 0);
                 }
             }
             if (own_T && wave == 0) acct = __builtin_amdgcn_mfma_f32_16x16x4f32(tv, tv, acct, 0, 0, 0);
         }
-        if (++since == PROBE_PROMOTE_CHUNKS) {
+        if (++since == GRAM_PROMOTE_CHUNKS) {
             promote();
             since = 0;
         }
@@ -148,14 +129,9 @@ __device__ __forceinline__ void probe_panel(const ProbeArgs a, const ProbeMask m
 }
 
 __global__ __launch_bounds__(256) void probe_gram_kernel(ProbeArgs a) {
-    __shared__ float4 lds_a4[PROBE_CHUNK * PROBE_STRIDE / 4], lds_b4[PROBE_CHUNK * PROBE_STRIDE / 4];
-    float* as = reinterpret_cast<float*>(lds_a4);
-    float* bs = reinterpret_cast<float*>(lds_b4);
-    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), ln = lane & 15, lj = lane >> 4;
-    const int D = a.D, nt = D / PROBE_TILE, n_upper = nt * (nt + 1) / 2, B = a.B, R = a.R;
+    const int D = a.D, nt = D / GRAM_TILE, n_upper = nt * (nt + 1) / 2, B = a.B, R = a.R;
     const int b = blockIdx.y, f = blockIdx.z / R, plane = blockIdx.z - f * R;
-    const int64_t listed = *a.count, count = listed < 0 ? 0 : listed < a.cap ? listed : a.cap;
-    const int64_t n_chunks = (count + PROBE_CHUNK - 1) / PROBE_CHUNK;
+    const int64_t count = gram_count(a.count, a.cap), n_chunks = gram_chunks(count);
     if (plane >= n_chunks) return;      // (uniform over the workgroup: this plane has no chunk in this launch)
     const ProbeMask mask{a.rows, a.flags, a.seat, a.fold, count, a.n_out, a.slots, a.rows_of, f};
     const int64_t base = a.block_base[b];
@@ -170,67 +146,10 @@ __global__ __launch_bounds__(256) void probe_gram_kernel(ProbeArgs a) {
         return;
     }
     if (!valid) return;
-    int ti = 0, tj = blockIdx.x;      // upper tiles row by row: (0, 0) .. (0, nt - 1), (1, 1) ..
-    while (tj >= nt - ti) {
-        tj -= nt - ti;
-        ++ti;
-    }
-    tj += ti;
-    const size_t pos_stride = (size_t)a.pos_stride;
-    const float* base_a = a.x + base + PROBE_TILE * ti;
-    const float* base_b = a.x + base + PROBE_TILE * tj;
-    const int sp = tid >> 4, sc = (tid & 15) * 4;      // this thread stages positions sp and sp + 16 of a chunk, units sc .. sc + 3
-    float4 reg[4];
-    auto fetch = [&](int64_t chunk) __attribute__((always_inline)) {
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            const int64_t p = chunk * PROBE_CHUNK + sp + 16 * h;
-            const bool ok = probe_counted(mask, p);
-            const size_t at = (size_t)(ok ? p : 0) * pos_stride + sc;
-            const float4 va = *reinterpret_cast<const float4*>(base_a + at), vb = *reinterpret_cast<const float4*>(base_b + at);
-            // the operand is masked, not the product (component by component: a select of two float4 objects goes through memory)
-            reg[h] = make_float4(ok ? va.x : 0.f, ok ? va.y : 0.f, ok ? va.z : 0.f, ok ? va.w : 0.f);
-            reg[2 + h] = make_float4(ok ? vb.x : 0.f, ok ? vb.y : 0.f, ok ? vb.z : 0.f, ok ? vb.w : 0.f);
-        }
-    };
-    probe_v4f acc[4];
-#pragma unroll
-    for (int t = 0; t < 4; ++t) acc[t] = probe_v4f{0.f, 0.f, 0.f, 0.f};
-    double* G = a.G + slab * D * D + (size_t)(PROBE_TILE * ti + 16 * wave + 4 * lj) * D + PROBE_TILE * tj + ln;
-    auto promote = [&]() __attribute__((always_inline)) {
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-#pragma unroll
-            for (int rr = 0; rr < 4; ++rr) {
-                double* at = G + (size_t)rr * D + 16 * t;
-                *at = *at + (double)acc[t][rr];
-            }
-            acc[t] = probe_v4f{0.f, 0.f, 0.f, 0.f};
-        }
-    };
-    int since = 0;
-    fetch(plane);
-    for (int64_t c = plane; c < n_chunks; c += R) {
-        __syncthreads();      // (the previous chunk's reads are done)
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            *reinterpret_cast<float4*>(as + (sp + 16 * h) * PROBE_STRIDE + sc) = reg[h];
-            *reinterpret_cast<float4*>(bs + (sp + 16 * h) * PROBE_STRIDE + sc) = reg[2 + h];
-        }
-        __syncthreads();
-        if (c + R < n_chunks) fetch(c + R);
-#pragma unroll
-        for (int ks = 0; ks < PROBE_CHUNK / 4; ++ks) {
-            const float av = as[(4 * ks + lj) * PROBE_STRIDE + 16 * wave + ln];
-#pragma unroll
-            for (int t = 0; t < 4; ++t) acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bs[(4 * ks + lj) * PROBE_STRIDE + 16 * t + ln], acc[t], 0, 0, 0);
-        }
-        if (++since == PROBE_PROMOTE_CHUNKS) {
-            promote();
-            since = 0;
-        }
-    }
-    if (since) promote();
+    int ti, tj;
+    gram_upper(blockIdx.x, nt, ti, tj);
+    gram_tile<false>(a.x + base + GRAM_TILE * ti, a.x + base + GRAM_TILE * tj, (size_t)a.pos_stride, mask, plane, R,
+                     a.G + slab * D * D + (size_t)(GRAM_TILE * ti) * D + GRAM_TILE * tj, (size_t)D);
 }
 
 hipError_t launch_probe_targets(const ProbeTargetArgs& a, hipStream_t stream) {
@@ -239,7 +158,7 @@ hipError_t launch_probe_targets(const ProbeTargetArgs& a, hipStream_t stream) {
 }
 
 hipError_t launch_probe_accumulate(const ProbeArgs& a, hipStream_t stream) {
-    const int nt = a.D / PROBE_TILE;
+    const int nt = a.D / GRAM_TILE;
     hipLaunchKernelGGL(probe_gram_kernel, dim3(nt * (nt + 1) / 2 + 1, a.B, 2 * a.R), dim3(256), 0, stream, a);
     return hipGetLastError();
 }

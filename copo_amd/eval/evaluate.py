@@ -315,32 +315,20 @@ STUDIES = (
           drop=("driver_label", "judge_label"), epilogue="jury_matrix"),
     Study("influence", "influence", "influence_rows", share=0.5, scenes="scenes_per_pair", extra=_influence_args),
     Study("precision_sweep", "precision", "precision_sweep_rows", share=1.0, extra=_precision_args),
-)
-# The ninth study: input attribution (eval/attribution.py).  It takes no --share, as certify takes none.  `STUDIES` stays the eight
-# entries that tests/test_eval_cli_cpu.py enumerates by name; `main` walks `TABLE_STUDIES` below, which holds them all, so "one table per run" and
-# "goes with" cover every entry by the same two loops.
-ALL_STUDIES = STUDIES + (Study("attribution", "attribution", "attribution_rows", "attribution_levels"),)
-# The tenth: representation similarity (eval/similarity.py), on the scenes of --cross-play.  `ALL_STUDIES` stays the nine entries that
-# tests/test_attribution_cpu.py counts; `main` walks `TABLE_STUDIES`.
-TABLE_STUDIES = ALL_STUDIES + (
+    Study("attribution", "attribution", "attribution_rows", "attribution_levels"),
     Study("similarity", "similarity", "similarity_rows", share=0.5, scenes="scenes_per_pair", extra=lambda a: dict(rows_of=a.similarity_rows_of),
-          drop=("label_a", "label_b"), epilogue="similarity_matrices"),)
+          drop=("label_a", "label_b"), epilogue="similarity_matrices"),
+    Study("probe", "probes", "probe_rows", share=0.5, scenes="scenes_per_pair",
+          extra=lambda a: dict(rows_of=a.probe_rows_of, ridge=1e-4 if a.probe_ridge is None else a.probe_ridge), epilogue="probe_matrix"),
+)
 # the options that belong to some studies only: given (not at its default) without one of them, an option is a usage error
 GOES_WITH = dict(jury_plan=("jury",), jury_deltas=("jury", "precision_sweep"), influence_max=("influence",), influence_deltas=("influence",),
-                 precisions=("precision_sweep",), certify_method=("certify_sweep",))
-# ... and with the options of `TABLE_STUDIES`' own entries: `GOES_WITH` stays the table that tests/test_eval_cli_cpu.py compares with its
-# own list of options, and `main` walks this one
-TABLE_GOES_WITH = dict(GOES_WITH, similarity_rows_of=("similarity",))
-# The eleventh: linear probes (eval/probes.py), on the scenes of --cross-play.  `TABLE_STUDIES` and `TABLE_GOES_WITH` stay what
-# tests/test_similarity_cpu.py compares; `main` walks `PROBE_STUDIES` and `PROBE_GOES_WITH`, which hold every entry.
-PROBE_STUDIES = TABLE_STUDIES + (
-    Study("probe", "probes", "probe_rows", share=0.5, scenes="scenes_per_pair",
-          extra=lambda a: dict(rows_of=a.probe_rows_of, ridge=1e-4 if a.probe_ridge is None else a.probe_ridge), epilogue="probe_matrix"),)
-PROBE_GOES_WITH = dict(TABLE_GOES_WITH, probe_rows_of=("probe",), probe_ridge=("probe",))
+                 precisions=("precision_sweep",), certify_method=("certify_sweep",), similarity_rows_of=("similarity",), probe_rows_of=("probe",),
+                 probe_ridge=("probe",))
 
 
 def run_study(ap, a, study):
-    """One entry of `PROBE_STUDIES` from the parsed options `a`: its table written to --table and printed."""
+    """One entry of `STUDIES` from the parsed options `a`: its table written to --table and printed."""
     import importlib
     from .checkpoint_io import load_members
     needs = [o for o in (study.levels, "table") if o]
@@ -461,10 +449,10 @@ def main(argv=None):
                     help="with --probe: the ridge as a share of the mean feature variance (default 1e-4)")
     a = ap.parse_args(argv)
     from .checkpoint_io import load_members
-    named = [s for s in PROBE_STUDIES if getattr(a, s.option)]
+    named = [s for s in STUDIES if getattr(a, s.option)]
     if len(named) > 1:
         ap.error("%s: one table per run" % " and ".join(_flag(s.option) for s in named))
-    for option, studies in PROBE_GOES_WITH.items():
+    for option, studies in GOES_WITH.items():
         if getattr(a, option) != ap.get_default(option) and not any(s.option in studies for s in named):
             ap.error("%s goes with %s" % (_flag(option), " or ".join(_flag(s) for s in studies)))
     if named:

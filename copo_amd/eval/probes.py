@@ -5,7 +5,7 @@ ridge regression from the activations of a layer to a quantity of the scene (how
 road ahead, does the step about to be taken end in a crash), fitted on the scenes of a TRAIN fold and scored by R^2 on the scenes of a TEST
 fold.  The raw observation is probed as a control: `gain` is what a layer's R^2 adds to the input's own.
 
-A `ProbePlan` is a panel of members that all read the same rows (a `JuryPlan.panel`, as `SimilarityPlan`'s) and a fold table over the
+A `ProbePlan` is a panel of members that all read the same rows (a `PanelPlan` of `panel.py`, as `SimilarityPlan` is) and a fold table over the
 scenes.  Per env step `copo_hidden_obs_seats_f32` keeps h1 and h2 of every panel member, `copo_probe_targets` (csrc/probe_kernels.hip)
 writes the step's eight targets (`TARGETS`) and the zero-padded observation row of every listed position, and `copo_probe_accumulate`
 adds the sufficient statistics of both folds to float64 accumulators -- once over the hidden blocks, once over the observation:
@@ -23,12 +23,11 @@ graph), `probe_frame` / `probe_matrix`, `probe_rows` (`evaluate --probe`) and `p
 """
 import numpy as np
 
-from .crossplay import SeatPlan, SeatSampler, run_pairs
-from .jury import JuryBuffers, JuryPlan
-from .similarity import CHUNK, FILL_WORKGROUPS, LAYERS, MAX_PANEL, MAX_PLANES, _want
+from .crossplay import SeatPlan, run_pairs
+from .panel import LAYERS, MAX_PANEL, MAX_PLANES, TILE, PanelPlan, PanelSeatSampler, every_row, hidden_activations, want
 
 TARGETS = ("nearest", "nearest_cos", "nearest_sin", "beams_hit", "front_clear", "reward", "crash", "done")
-PANEL, MAX_TARGETS, MAX_WIDTH, TILE, FOLD_NONE = 16, 15, 512, 64, 255      # include/copo_hip.h, COPO_PROBE_*
+PANEL, MAX_TARGETS, MAX_WIDTH, FOLD_NONE = 16, 15, 512, 255      # include/copo_hip.h, COPO_PROBE_*
 TRAIN, TEST = 0, 1
 OBS_LAYER = "obs"
 CONSTANT = 1e-12          # a target whose sum of squares about its mean is below this share of its sum of squares is constant on the fold
@@ -54,30 +53,17 @@ def default_folds(seats):
     return folds
 
 
-class ProbePlan:
-    """A panel of bank members probed on the seated rows of the seat plan `seats`.  `members`: the panel (default: all K; one member is
-    a panel).  `rows_of`: None, or the member whose DRIVEN rows alone are counted.  `folds`: [E] of 0 (train) / 1 (test) / 255 (never
-    counted); default `default_folds(seats)`.  A plan in which a fold has no seated scene is refused, and the message names the scene
-    groups.  Derived: `jury` (the `JuryPlan.panel` whose lists the hidden launch reads), `rows` / `count` / `cap` (the one common
-    ascending list), `blocks` = 2 M hidden blocks in (member, layer) order, `planes(D, blocks)` (the fixed row split R of an accumulator
-    set: doubled while its launch has fewer than 256 workgroups and every plane still gets a chunk of 32 rows -- a property of the plan,
-    never of the device), `accumulator_shapes(D, blocks)`, `accumulator_bytes(hidden, obs_dim)`.  `check_bytes(hidden, obs_dim)` refuses
-    accumulators beyond `max_bytes` (default 1 GiB) with the figure; it runs at construction where `hidden` is given.  Nothing here
-    touches a device."""
+class ProbePlan(PanelPlan):
+    """A `PanelPlan` of bank members probed on the seated rows of the seat plan `seats` (one member is a panel).  `folds`: [E] of 0
+    (train) / 1 (test) / 255 (never counted); default `default_folds(seats)`.  A plan in which a fold has no seated scene is refused, and
+    the message names the scene groups.  Its own: `blocks` = 2 M hidden blocks in (member, layer) order, `planes(D, blocks)` (the row
+    split R of an accumulator set: `PanelPlan.row_split` of its launch's 2 folds x blocks x (upper tiles + 1) workgroups),
+    `accumulator_shapes(D, blocks)`, `accumulator_bytes(hidden, obs_dim)`.  `check_bytes(hidden, obs_dim)` refuses accumulators beyond
+    `max_bytes` (default 1 GiB) with the figure; it runs at construction where `hidden` is given.  Nothing here touches a device."""
 
     def __init__(self, seats, members=None, rows_of=None, folds=None, hidden=None, max_bytes=1 << 30):
-        members = list(range(seats.K)) if members is None else [int(m) for m in members]
-        if len(members) > MAX_PANEL:
-            raise ValueError("ProbePlan: a panel of %d, %d at the most" % (len(members), MAX_PANEL))
-        self.jury = JuryPlan.panel(seats, members)          # (refuses an empty panel, members outside the bank and duplicates)
-        self.members, self.M, self.K = np.asarray(members, np.int32), len(members), seats.K
+        super().__init__(seats, members, rows_of, max_bytes)
         self.blocks = 2 * self.M
-        self.rows_of = -1 if rows_of is None else int(rows_of)
-        if rows_of is not None and not 0 <= self.rows_of < seats.K:
-            raise ValueError("ProbePlan: rows_of = %r of a bank of %d" % (rows_of, seats.K))
-        first = members[0]
-        self.rows, self.count, self.cap = self.jury.rows[first], int(self.jury.counts[first]), self.jury.cap
-        self.E, self.N, self.n_out, self.G = seats.E, seats.N, seats.E * seats.N, seats.n_groups
         folds = default_folds(seats) if folds is None else np.asarray(folds)
         if folds.shape != (self.E,):
             raise ValueError("ProbePlan: a fold table of shape %s, one entry per scene [%d] wanted" % (folds.shape, self.E))
@@ -90,20 +76,12 @@ class ProbePlan:
             have = set(group[seated & (self.folds == f)].tolist())
             if not have:
                 raise ValueError("ProbePlan: no seated scene in the %s fold (scene groups %s have none)" % (name, sorted(set(range(self.G)) - have)))
-        self.max_bytes = int(max_bytes)
         if hidden is not None:
             self.check_bytes(hidden)
 
-    def check(self, seats):
-        self.jury.check(seats)
-        return self
-
     def planes(self, D, blocks=None):
         nt = int(D) // TILE
-        tiles, chunks, R = 2 * (self.blocks if blocks is None else int(blocks)) * (nt * (nt + 1) // 2 + 1), -(-self.cap // CHUNK), 1
-        while R < MAX_PLANES and tiles * R < FILL_WORKGROUPS and 2 * R <= chunks:
-            R *= 2
-        return R
+        return self.row_split(2 * (self.blocks if blocks is None else int(blocks)) * (nt * (nt + 1) // 2 + 1))
 
     def accumulator_shapes(self, D, blocks=None):
         D, B = int(D), self.blocks if blocks is None else int(blocks)
@@ -111,13 +89,10 @@ class ProbePlan:
         return dict(G=(R, 2, B, D, D), C=(R, 2, B, D, PANEL), T=(R, 2, PANEL, PANEL))
 
     def accumulator_bytes(self, hidden, obs_dim=None):
-        sets = [self.accumulator_shapes(hidden)] + ([] if obs_dim is None else [self.accumulator_shapes(padded_width(obs_dim), 1)])
-        return 8 * sum(int(np.prod(shape)) for s in sets for shape in s.values())
+        return self.bytes_of(self.accumulator_shapes(hidden), *([] if obs_dim is None else [self.accumulator_shapes(padded_width(obs_dim), 1)]))
 
     def check_bytes(self, hidden, obs_dim=None):
-        H = int(hidden)
-        if H < TILE or H > MAX_WIDTH or H % TILE:
-            raise ValueError("ProbePlan: hidden = %d, a multiple of %d up to %d wanted" % (H, TILE, MAX_WIDTH))
+        H = self.check_width(hidden, MAX_WIDTH)
         if obs_dim is not None and not 1 <= int(obs_dim) <= MAX_WIDTH:
             raise ValueError("ProbePlan: an observation of %d columns, 1..%d wanted" % (int(obs_dim), MAX_WIDTH))
         need = self.accumulator_bytes(H, obs_dim)
@@ -147,14 +122,14 @@ def probe_targets(obs, lidar_lo, num_lasers, trig, flags, reward, rows, count, t
     cap, Op = int(rows.shape[0]), int(xobs.shape[1])
     if Op != padded_width(O) or Op > MAX_WIDTH:
         raise ValueError("%s: xobs of %d columns for an observation of %d: %d wanted (%d at the most)" % (who, Op, O, padded_width(O), MAX_WIDTH))
-    _want(who, "obs", obs, (n_out, O), torch.float32)
-    _want(who, "trig", trig, (n, 2), torch.float32)
-    _want(who, "flags", flags, (n_out,), torch.uint8)
-    _want(who, "reward", reward, (n_out,), torch.float32)
-    _want(who, "rows", rows, (cap,), torch.int64)
-    _want(who, "count", count, (1,), torch.int32)
-    _want(who, "targets", targets, (cap, PANEL), torch.float32)
-    _want(who, "xobs", xobs, (cap, Op), torch.float32)
+    want(who, "obs", obs, (n_out, O), torch.float32)
+    want(who, "trig", trig, (n, 2), torch.float32)
+    want(who, "flags", flags, (n_out,), torch.uint8)
+    want(who, "reward", reward, (n_out,), torch.float32)
+    want(who, "rows", rows, (cap,), torch.int64)
+    want(who, "count", count, (1,), torch.int32)
+    want(who, "targets", targets, (cap, PANEL), torch.float32)
+    want(who, "xobs", xobs, (cap, Op), torch.float32)
     _capi.check(_capi.lib.copo_probe_targets(obs.data_ptr(), n_out, O, lo, n, trig.data_ptr(), flags.data_ptr(), reward.data_ptr(), rows.data_ptr(),
                                              count.data_ptr(), cap, targets.data_ptr(), xobs.data_ptr(), Op, _capi.current_stream()))
 
@@ -191,16 +166,16 @@ def probe_accumulate(x, block_base, pos_stride, width, targets, rows, count, fla
         raise ValueError("%s: flags and seat must cover the same rows, a whole number of them per entry of fold (%s rows, a fold table of %s)" % (
             who, None if flags is None else flags.numel(), None if fold is None else tuple(fold.shape)))
     n_out, E = int(flags.numel()), int(fold.numel())
-    _want(who, "block_base", block_base, (B,), torch.int64)
-    _want(who, "targets", targets, (cap, PANEL), torch.float32)
-    _want(who, "rows", rows, (cap,), torch.int64)
-    _want(who, "count", count, (1,), torch.int32)
-    _want(who, "flags", flags, flags.shape, torch.uint8)
-    _want(who, "seat", seat, seat.shape, torch.int32)
-    _want(who, "fold", fold, (E,), torch.uint8)
-    _want(who, "G", G, (R, 2, B, D, D), torch.float64)
-    _want(who, "C", C, (R, 2, B, D, PANEL), torch.float64)
-    _want(who, "T", T, (R, 2, PANEL, PANEL), torch.float64)
+    want(who, "block_base", block_base, (B,), torch.int64)
+    want(who, "targets", targets, (cap, PANEL), torch.float32)
+    want(who, "rows", rows, (cap,), torch.int64)
+    want(who, "count", count, (1,), torch.int32)
+    want(who, "flags", flags, flags.shape, torch.uint8)
+    want(who, "seat", seat, seat.shape, torch.int32)
+    want(who, "fold", fold, (E,), torch.uint8)
+    want(who, "G", G, (R, 2, B, D, D), torch.float64)
+    want(who, "C", C, (R, 2, B, D, PANEL), torch.float64)
+    want(who, "T", T, (R, 2, PANEL, PANEL), torch.float64)
     _capi.check(_capi.lib.copo_probe_accumulate(x.data_ptr(), int(x.numel()), block_base.data_ptr(), B, stride, D, targets.data_ptr(), rows.data_ptr(),
                                                 count.data_ptr(), cap, flags.data_ptr(), seat.data_ptr(), fold.data_ptr(), n_out, n_out // E, int(rows_of), R,
                                                 G.data_ptr(), C.data_ptr(), T.data_ptr(), _capi.current_stream()))
@@ -319,45 +294,29 @@ def probe_fit(acc, ridge=1e-4, n_targets=len(TARGETS)):
     return out
 
 
-class ProbeSeatSampler(SeatSampler):
-    """`SeatSampler` with a probe panel: per env step `hidden_seats` on the observation the policy reads, the seated forward on the same
-    observation, the simulator step and the seat tally, then `probe_targets` of the step's observation, flags and reward and
+class ProbeSeatSampler(PanelSeatSampler):
+    """`PanelSeatSampler` with a probe panel: per env step `hidden_seats` on the observation the policy reads, the seated forward on the
+    same observation, the simulator step and the seat tally, then `probe_targets` of the step's observation, flags and reward and
     `probe_accumulate` once on the hidden workspace and once on the observation block -- the whole fragment is still one captured graph.
-    Actions, flags and the seat tally are a plain `SeatSampler`'s.  `acc` (`ProbeAccumulators`) accumulates until `clear_tally()`;
-    `read()` returns the two fits, `frame()` the table."""
+    `acc` (`ProbeAccumulators`) accumulates until `clear_tally()`; `read()` returns the two fits, `frame()` the table."""
 
     def __init__(self, vec_env, policy, bank, plan, probes, T, use_graph=True, ridge=1e-4):
         import torch
         from .levels import lidar_columns
-        probes.check(plan)
+        super().__init__(vec_env, policy, bank, plan, probes, T, use_graph=use_graph)
         H = int(bank.cfg.hidden)
-        super().__init__(vec_env, policy, bank, plan, T, use_graph=use_graph)
         probes.check_bytes(H, self.O)
         self.probes, self.ridge = probes, float(ridge)
-        self.jury_buffers = JuryBuffers(probes.jury, self.device)
-        self.jury_buffers.on_replace.append(self._loop.reset)
         up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(self.device)  # noqa: E731
         cap, Op = probes.cap, padded_width(self.O)
         self.lidar_lo, hi = lidar_columns(self.sim.cfg)
         self.num_lasers = hi - self.lidar_lo
         self.trig, self.fold = up(trig_table(self.num_lasers)), up(probes.folds)
-        self.hidden = torch.zeros(bank.K, cap, 2, H, dtype=torch.float32, device=self.device)
         self.block_base = up(np.array([(int(m) * cap * 2 + layer) * H for m in probes.members for layer in range(2)], np.int64))
         self.obs_base = up(np.zeros(1, np.int64))
         self.targets = torch.zeros(cap, PANEL, dtype=torch.float32, device=self.device)
         self.xobs = torch.zeros(cap, Op, dtype=torch.float32, device=self.device)
         self.acc = ProbeAccumulators(probes.M, H, probes.planes(H), Op, probes.planes(Op, 1), self.device)
-        first = int(probes.members[0])
-        self._rows, self._count = self.jury_buffers.rows[first], self.jury_buffers.counts[first:first + 1]
-
-    def clear_tally(self):
-        super().clear_tally()
-        self.acc.clear()
-
-    def _policy_obs(self, t):
-        obs = super()._policy_obs(t)
-        self.seated.hidden_seats(self.jury_buffers, obs.view(-1, self.O), self.hidden)
-        return obs
 
     def _step(self, t):
         super()._step(t)          # (it wrote obs[t + 1]; obs[t] is still what the policy read)
@@ -447,7 +406,6 @@ def probe_of(bank, obs, targets, folds, members=None, ridge=1e-4, names=None):
     (default: all), one on the zero-padded observation, and the fit.  Returns dict(frame, hidden, obs): the `probe_frame` (targets named
     `names`, default t0, t1, ...) and the two `probe_fit` results."""
     import torch
-    from .similarity import hidden_activations
     n, O = (int(v) for v in obs.shape)
     targets, folds = np.asarray(targets, np.float32), np.asarray(folds)
     if targets.ndim != 2 or targets.shape[0] != n or not 1 <= targets.shape[1] <= MAX_TARGETS:
@@ -470,8 +428,8 @@ def probe_of(bank, obs, targets, folds, members=None, ridge=1e-4, names=None):
     xobs = torch.zeros(n, Op, dtype=torch.float32, device=dev)
     xobs[:, :O] = obs
     acc = ProbeAccumulators(plan.M, H, plan.planes(H), Op, plan.planes(Op, 1), dev)
-    shared = (up(panel), up(np.arange(n, dtype=np.int64)), up(np.array([n], np.int32)), torch.ones(n, dtype=torch.uint8, device=dev),
-              torch.zeros(n, dtype=torch.int32, device=dev), up(plan.folds), -1)
+    rows, count, flags, seat, rows_of = every_row(n, dev)
+    shared = (up(panel), rows, count, flags, seat, up(plan.folds), rows_of)
     base = up(np.array([(int(m) * n * 2 + layer) * H for m in plan.members for layer in range(2)], np.int64))
     probe_accumulate(hidden, base, 2 * H, H, *shared, *acc.hidden.tensors())
     probe_accumulate(xobs, up(np.zeros(1, np.int64)), Op, Op, *shared, *acc.obs.tensors())

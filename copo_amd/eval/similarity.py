@@ -7,8 +7,8 @@ activations of two nets on the same inputs,
     cka(a, b) = hsic(a, b) / sqrt(hsic(a, a) hsic(b, b)),    hsic(a, b) = || Ha^T Hb - (1^T Ha)^T (1^T Hb) / n ||_F^2,
 is invariant to permutation, rotation and isotropic scaling of the units, which weight distance and unit-by-unit correlation are not.
 
-A `SimilarityPlan` is a panel of members that all read the same rows: the seated rows of the scene groups of a seat plan (internally a
-`JuryPlan.panel`, so every member's list is the one common ascending list).  Per env step `copo_hidden_obs_seats_f32`
+A `SimilarityPlan` is a panel of members that all read the same rows: the seated rows of the scene groups of a seat plan (a `PanelPlan`
+of `panel.py`, shared with `probes.py`: internally a `JuryPlan.panel`, so every member's list is the one common ascending list).  Per env step `copo_hidden_obs_seats_f32`
 (csrc/learn_hidden.inc, the fourth mode of the bank's forward: the jury pass stopped behind layer 2) keeps h1 and h2 of every panel member
 on those rows, and `copo_cka_accumulate` (csrc/cka_kernels.hip) adds the step's H x H cross-products of every member pair, the unit sums
 and the row count to float64 accumulators -- over the rows that ACTED in the step (the seat tally's rule), optionally only over the rows
@@ -25,77 +25,48 @@ fragment stay one captured graph; finish is issued when the frame is read), `sim
 """
 import numpy as np
 
-from .crossplay import SeatPlan, SeatSampler, run_pairs
-from .jury import JuryBuffers, JuryPlan
+from .crossplay import SeatPlan, run_pairs
+from .panel import CHUNK, FILL_WORKGROUPS, LAYERS, MAX_PANEL, MAX_PLANES, TILE, PanelPlan, PanelSeatSampler, every_row, want      # noqa: F401
+from .panel import hidden_activations      # noqa: F401  (its home is panel.py; it stays importable from here)
 
-LAYERS = ("h1", "h2")
-CHUNK, PROMOTE_ROWS, MAX_PLANES, MAX_PANEL, MAX_HIDDEN, TILE = 32, 128, 8, 255, 512, 64      # include/copo_hip.h, COPO_CKA_*
+PROMOTE_ROWS, MAX_HIDDEN = 128, 512          # include/copo_hip.h, COPO_CKA_*
 DEAD_VARIANCE, SATURATED_MEAN = 1e-8, 0.99
-FILL_WORKGROUPS = 256          # the row split stops once the Gram launch has this many workgroups: one per compute unit of the target
 
 
-class SimilarityPlan:
-    """A panel of bank members compared on the seated rows of the seat plan `seats`.  `members`: the panel, bank members in the order of
-    the tables (default: all K; otherwise at least two distinct members).  `rows_of`: None, or the member whose DRIVEN rows alone are
-    counted.  Derived: `jury`, the `JuryPlan.panel` whose lists the hidden launch reads (every panel member's list is `rows`, the one
-    common ascending list of the seated rows e * N + n of the groups in [0, G); `count`, `cap`); `pairs` int32 [P][2], the unordered
-    pairs a <= b of PANEL indices in the accumulators' order; `planes(hidden)`, the fixed row split R of the accumulators (a power of
-    two up to 8: doubled while the Gram launch has fewer than 256 workgroups and every plane still gets a chunk of 32 rows -- a property
-    of the plan, never of the device); `accumulator_bytes(hidden)`.  `check_bytes(hidden)` refuses accumulators beyond `max_bytes`
+class SimilarityPlan(PanelPlan):
+    """A `PanelPlan` of bank members compared on the seated rows of the seat plan `seats`.  `members`: default all K; otherwise at least
+    two distinct members.  Its own: `pairs` int32 [P][2], the unordered pairs a <= b of PANEL indices in the accumulators' order;
+    `planes(hidden)`, the row split R of the accumulators (`PanelPlan.row_split` of the Gram launch's P * 2 * (hidden / 64)^2
+    workgroups); `accumulator_shapes(hidden)`, `accumulator_bytes(hidden)`.  `check_bytes(hidden)` refuses accumulators beyond `max_bytes`
     (default 1 GiB) with the figure; it runs at construction where `hidden` is given.  Nothing here touches a device."""
 
     def __init__(self, seats, members=None, rows_of=None, hidden=None, max_bytes=1 << 30):
         members = list(range(seats.K)) if members is None else [int(m) for m in members]
         if members != list(range(seats.K)) and len(members) < 2:
             raise ValueError("SimilarityPlan: a panel of %d, at least two members wanted" % len(members))
-        if len(members) > MAX_PANEL:
-            raise ValueError("SimilarityPlan: a panel of %d, %d at the most" % (len(members), MAX_PANEL))
-        self.jury = JuryPlan.panel(seats, members)          # (refuses members outside the bank and duplicates)
-        self.members, self.M, self.K = np.asarray(members, np.int32), len(members), seats.K
-        self.rows_of = -1 if rows_of is None else int(rows_of)
-        if rows_of is not None and not 0 <= self.rows_of < seats.K:
-            raise ValueError("SimilarityPlan: rows_of = %r of a bank of %d" % (rows_of, seats.K))
-        first = members[0]
-        self.rows, self.count, self.cap = self.jury.rows[first], int(self.jury.counts[first]), self.jury.cap
+        super().__init__(seats, members, rows_of, max_bytes)
         self.pairs = np.array([(a, b) for a in range(self.M) for b in range(a, self.M)], np.int32)
         self.P = len(self.pairs)
-        self.E, self.N, self.n_out, self.G = seats.E, seats.N, seats.E * seats.N, seats.n_groups
-        self.max_bytes = int(max_bytes)
         if hidden is not None:
             self.check_bytes(hidden)
 
-    def check(self, seats):
-        self.jury.check(seats)
-        return self
-
     def planes(self, hidden):
-        tiles, chunks, R = self.P * 2 * (int(hidden) // TILE) ** 2, -(-self.cap // CHUNK), 1
-        while R < MAX_PLANES and tiles * R < FILL_WORKGROUPS and 2 * R <= chunks:
-            R *= 2
-        return R
+        return self.row_split(self.P * 2 * (int(hidden) // TILE) ** 2)
 
     def accumulator_shapes(self, hidden):
         H, R = int(hidden), self.planes(hidden)
         return dict(S=(R, self.P, 2, H, H), s=(R, self.M, 2, H), n=(R,))
 
     def accumulator_bytes(self, hidden):
-        return 8 * sum(int(np.prod(shape)) for shape in self.accumulator_shapes(hidden).values())
+        return self.bytes_of(self.accumulator_shapes(hidden))
 
     def check_bytes(self, hidden):
-        H = int(hidden)
-        if H < TILE or H > MAX_HIDDEN or H % TILE:
-            raise ValueError("SimilarityPlan: hidden = %d, a multiple of %d up to %d wanted" % (H, TILE, MAX_HIDDEN))
+        H = self.check_width(hidden, MAX_HIDDEN)
         need = self.accumulator_bytes(H)
         if need > self.max_bytes:
             raise ValueError("SimilarityPlan: %d pairs x 2 layers x %d x %d float64 in %d planes are %d bytes of accumulators, max_bytes = %d" % (
                 self.P, H, H, self.planes(H), need, self.max_bytes))
         return need
-
-
-def _want(who, name, t, shape, dtype):
-    if t is None or tuple(t.shape) != tuple(shape) or not t.is_contiguous() or t.dtype != dtype:
-        raise ValueError("%s: %s of shape %s and dtype %s, contiguous %s %s wanted" % (
-            who, name, None if t is None else tuple(t.shape), None if t is None else t.dtype, dtype, list(shape)))
 
 
 def cka_accumulate(hidden, panel, rows, count, flags, seat, rows_of, S, s, n):
@@ -119,15 +90,15 @@ def cka_accumulate(hidden, panel, rows, count, flags, seat, rows_of, S, s, n):
     R = int(S.shape[0])
     if flags is None or seat is None or flags.numel() != seat.numel() or flags.numel() < 1:
         raise ValueError("%s: flags and seat must cover the same rows" % who)
-    _want(who, "hidden", hidden, (K, cap, 2, H), torch.float32)
-    _want(who, "panel", panel, (M,), torch.int32)
-    _want(who, "rows", rows, (cap,), torch.int64)
-    _want(who, "count", count, (1,), torch.int32)
-    _want(who, "flags", flags, flags.shape, torch.uint8)
-    _want(who, "seat", seat, seat.shape, torch.int32)
-    _want(who, "S", S, (R, P, 2, H, H), torch.float64)
-    _want(who, "s", s, (R, M, 2, H), torch.float64)
-    _want(who, "n", n, (R,), torch.int64)
+    want(who, "hidden", hidden, (K, cap, 2, H), torch.float32)
+    want(who, "panel", panel, (M,), torch.int32)
+    want(who, "rows", rows, (cap,), torch.int64)
+    want(who, "count", count, (1,), torch.int32)
+    want(who, "flags", flags, flags.shape, torch.uint8)
+    want(who, "seat", seat, seat.shape, torch.int32)
+    want(who, "S", S, (R, P, 2, H, H), torch.float64)
+    want(who, "s", s, (R, M, 2, H), torch.float64)
+    want(who, "n", n, (R,), torch.int64)
     _capi.check(_capi.lib.copo_cka_accumulate(hidden.data_ptr(), K, cap, H, panel.data_ptr(), M, rows.data_ptr(), count.data_ptr(), flags.data_ptr(),
                                               seat.data_ptr(), int(flags.numel()), int(rows_of), R, S.data_ptr(), s.data_ptr(), n.data_ptr(),
                                               _capi.current_stream()))
@@ -143,13 +114,13 @@ def cka_finish(S, s, n, hsic, n_out, mean, var):
         raise ValueError("%s: S [R][P][2][H][H] and s [R][M][2][H] wanted" % who)
     R, P, _, H, _ = (int(v) for v in S.shape)
     M = int(s.shape[1])
-    _want(who, "S", S, (R, M * (M + 1) // 2, 2, H, H), torch.float64)
-    _want(who, "s", s, (R, M, 2, H), torch.float64)
-    _want(who, "n", n, (R,), torch.int64)
-    _want(who, "hsic", hsic, (M, M, 2), torch.float64)
-    _want(who, "n_out", n_out, (1,), torch.int64)
-    _want(who, "mean", mean, (M, 2, H), torch.float64)
-    _want(who, "var", var, (M, 2, H), torch.float64)
+    want(who, "S", S, (R, M * (M + 1) // 2, 2, H, H), torch.float64)
+    want(who, "s", s, (R, M, 2, H), torch.float64)
+    want(who, "n", n, (R,), torch.int64)
+    want(who, "hsic", hsic, (M, M, 2), torch.float64)
+    want(who, "n_out", n_out, (1,), torch.int64)
+    want(who, "mean", mean, (M, 2, H), torch.float64)
+    want(who, "var", var, (M, 2, H), torch.float64)
     _capi.check(_capi.lib.copo_cka_finish(S.data_ptr(), s.data_ptr(), n.data_ptr(), M, H, R, hsic.data_ptr(), n_out.data_ptr(), mean.data_ptr(),
                                           var.data_ptr(), _capi.current_stream()))
 
@@ -190,35 +161,20 @@ class SimilarityAccumulators:
         return dict(n=n, hsic=hsic, cka=cka_from_hsic(hsic, n), mean=self.mean.cpu().numpy(), var=self.var.cpu().numpy())
 
 
-class SimilaritySeatSampler(SeatSampler):
-    """`SeatSampler` with a similarity panel: per env step `hidden_seats` on the observation the policy reads, the seated forward on the
-    same observation, the simulator step, the seat tally and `cka_accumulate` of the step's flags -- the whole fragment is still one
-    captured graph.  Actions, flags and the seat tally are a plain `SeatSampler`'s.  `acc` (`SimilarityAccumulators`) accumulates until
-    `clear_tally()`; `read()` issues the finish and returns its numbers, `frame()` / `units()` the tables."""
+class SimilaritySeatSampler(PanelSeatSampler):
+    """`PanelSeatSampler` with a similarity panel: per env step `hidden_seats` on the observation the policy reads, the seated forward on
+    the same observation, the simulator step, the seat tally and `cka_accumulate` of the step's flags -- the whole fragment is still one
+    captured graph.  `acc` (`SimilarityAccumulators`) accumulates until `clear_tally()`; `read()` issues the finish and returns its
+    numbers, `frame()` / `units()` the tables."""
 
     def __init__(self, vec_env, policy, bank, plan, similarity, T, use_graph=True):
         import torch
-        similarity.check(plan)
         H = int(bank.cfg.hidden)
-        similarity.check_bytes(H)
-        super().__init__(vec_env, policy, bank, plan, T, use_graph=use_graph)
+        similarity.check(plan).check_bytes(H)
+        super().__init__(vec_env, policy, bank, plan, similarity, T, use_graph=use_graph)
         self.similarity = similarity
-        self.jury_buffers = JuryBuffers(similarity.jury, self.device)
-        self.jury_buffers.on_replace.append(self._loop.reset)
         self.panel = torch.from_numpy(similarity.members.copy()).to(self.device)
-        self.hidden = torch.zeros(bank.K, similarity.cap, 2, H, dtype=torch.float32, device=self.device)
         self.acc = SimilarityAccumulators(similarity.M, H, similarity.planes(H), self.device)
-        first = int(similarity.members[0])
-        self._rows, self._count = self.jury_buffers.rows[first], self.jury_buffers.counts[first:first + 1]
-
-    def clear_tally(self):
-        super().clear_tally()
-        self.acc.clear()
-
-    def _policy_obs(self, t):
-        obs = super()._policy_obs(t)
-        self.seated.hidden_seats(self.jury_buffers, obs.view(-1, self.O), self.hidden)
-        return obs
 
     def _step(self, t):
         super()._step(t)
@@ -311,19 +267,6 @@ def similarity_rows(algo, env, weights_list, rows_of=None, members=None, share=0
                      check=check)
 
 
-def hidden_activations(bank, obs):
-    """`hidden` [K][n][2][H] of every member of `bank` on every row of obs [n][O]: one launch with every member reading every row."""
-    import torch
-    n = int(obs.shape[0])
-    seats = SeatPlan(np.zeros((1, n), np.int32), bank.K)
-    jb = JuryBuffers(JuryPlan.everyone(seats), obs.device)
-    hidden = torch.zeros(bank.K, n, 2, int(bank.cfg.hidden), dtype=torch.float32, device=obs.device)
-    bank.sync_mirror()
-    bank.hidden_seats(jb, obs, hidden)
-    torch.cuda.current_stream().synchronize()          # (the plan's tables die with this call)
-    return hidden
-
-
 def cka_of(bank, obs):
     """dict(n, hsic, cka, mean, var) of every member pair of `bank` on the rows of obs [n][O] (every row counts): the hidden launch, one
     accumulate and the finish."""
@@ -333,9 +276,6 @@ def cka_of(bank, obs):
     H = int(bank.cfg.hidden)
     plan.check_bytes(H)
     hidden = hidden_activations(bank, obs)
-    dev = obs.device
-    acc = SimilarityAccumulators(plan.M, H, plan.planes(H), dev)
-    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)  # noqa: E731
-    cka_accumulate(hidden, up(plan.members), up(plan.rows), up(np.array([plan.count], np.int32)), torch.ones(n, dtype=torch.uint8, device=dev),
-                   torch.zeros(n, dtype=torch.int32, device=dev), -1, acc.S, acc.s, acc.n)
+    acc = SimilarityAccumulators(plan.M, H, plan.planes(H), obs.device)
+    cka_accumulate(hidden, torch.from_numpy(plan.members.copy()).to(obs.device), *every_row(n, obs.device), acc.S, acc.s, acc.n)
     return acc.finish()

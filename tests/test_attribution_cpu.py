@@ -154,8 +154,8 @@ def test_frame_from_hand_made_words():
 
 def test_the_command_line_entry(tmp_path, monkeypatch, capsys):
     from copo_amd.eval import checkpoint_io, evaluate
-    study = evaluate.ALL_STUDIES[-1]
-    assert len(evaluate.ALL_STUDIES) == 9 and evaluate.ALL_STUDIES[:8] == evaluate.STUDIES
+    study, = (s for s in evaluate.STUDIES if s.option == "attribution")
+    assert not any("attribution" in studies for studies in evaluate.GOES_WITH.values())          # no option of its own
     assert (study.option, study.module, study.rows, study.levels, study.share) == ("attribution", "attribution", "attribution_rows", "attribution_levels", None)
     levels = tmp_path / "levels.json"
     levels.write_text(json.dumps([dict(points=4, baseline="clear_road")]))

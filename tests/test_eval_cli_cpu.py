@@ -14,7 +14,7 @@ from copo_amd.eval.evaluate import GOES_WITH, STUDIES, main
 
 PATHS = ["a.npz", "b.npz"]
 GIVEN = dict(jury_plan=["seated"], jury_deltas=["0.1", "0.2"], influence_max=["2"], influence_deltas=["0.1", "0.2"], precisions=["bfloat16"],
-             certify_method=["linear"])          # every option of GOES_WITH away from its default
+             certify_method=["linear"], similarity_rows_of=["1"], probe_rows_of=["1"], probe_ridge=["0.01"])          # every option of GOES_WITH away from its default
 
 
 def flag(option):
@@ -30,9 +30,25 @@ def ones(*shape):
 
 
 def real_frame(study, levels, kw):
-    """A frame of the study's own frame function on a tally of ones: two checkpoints, one scene of four slots per pair or cell."""
+    """A frame of the study's own frame function on a tally of ones (hand-made numbers where the study has no tally): two checkpoints,
+    one scene of four slots per pair or cell."""
     from copo_amd.eval.crossplay import SeatPlan, tally_frame
     labels, K = kw["labels"], len(PATHS)
+    if study.option == "attribution":
+        from copo_amd.eval.attribution import AttributionPlan, attribution_frame
+        from copo_amd.sim import SimConfig
+        cfg = SimConfig(map="intersection", num_envs=2, num_agents=4)
+        seats, plan = AttributionPlan.sweep(K, levels, 1, 4)
+        O = cfg.ego_dim + cfg.navi_dim + cfg.num_lasers
+        return attribution_frame(ones(seats.n_groups, K, 8), ones(seats.n_groups, K, 2, O), ones(seats.n_groups, K, 8), seats, plan, cfg, labels)
+    if study.option == "similarity":
+        from copo_amd.eval.similarity import SimilarityPlan, similarity_frame
+        return similarity_frame(np.ones((K, K, 2)), 9, SimilarityPlan(SeatPlan.pairs(K, 1, 4, kw["share"]), rows_of=kw["rows_of"]), labels)
+    if study.option == "probe":
+        from copo_amd.eval.probes import TARGETS, probe_frame
+        fit = lambda B: dict(n_train=5, n_test=4, r2_train=np.ones((B, len(TARGETS))), r2_test=np.full((B, len(TARGETS)), 0.5),  # noqa: E731
+                             weight_norm=np.ones((B, len(TARGETS))))
+        return probe_frame(fit(2 * K), fit(1), range(K), -1 if kw["rows_of"] is None else kw["rows_of"], labels)
     if study.option in ("cross_play", "jury", "influence"):
         seats = SeatPlan.pairs(K, 1, 4, kw["share"])
         if study.option == "cross_play":
@@ -93,7 +109,8 @@ def refused(argv):
 
 def test_the_table_names_every_study_once():
     options = [s.option for s in STUDIES]
-    assert options == ["cross_play", "fault_sweep", "adversary_sweep", "pgd_sweep", "certify_sweep", "jury", "influence", "precision_sweep"]
+    assert options == ["cross_play", "fault_sweep", "adversary_sweep", "pgd_sweep", "certify_sweep", "jury", "influence", "precision_sweep",
+                       "attribution", "similarity", "probe"]
     assert len(set(s.rows for s in STUDIES)) == len(STUDIES) and all(set(studies) <= set(options) for studies in GOES_WITH.values())
     assert sorted(GOES_WITH) == sorted(GIVEN)
 
@@ -130,7 +147,8 @@ def test_a_study_wants_its_table_and_its_levels(cli, study):
 OWN_DEFAULTS = dict(cross_play=dict(share=0.5), fault_sweep=dict(share=1.0), adversary_sweep=dict(share=1.0), pgd_sweep=dict(share=1.0),
                     certify_sweep=dict(method="interval"), jury=dict(plan="everyone", deltas=(0.05, 0.05), share=0.5),
                     influence=dict(max_others=4, deltas=(0.05, 0.05), share=0.5),
-                    precision_sweep=dict(precisions=("float32", "bfloat16", "float8_e4m3"), deltas=(0.05, 0.05), share=1.0))
+                    precision_sweep=dict(precisions=("float32", "bfloat16", "float8_e4m3"), deltas=(0.05, 0.05), share=1.0), attribution=dict(),
+                    similarity=dict(rows_of=None, share=0.5), probe=dict(rows_of=None, ridge=1e-4, share=0.5))
 
 
 @pytest.mark.parametrize("study", STUDIES, ids=lambda s: s.option)
@@ -138,7 +156,7 @@ def test_the_named_rows_run_with_the_arguments_they_always_got(cli, capsys, stud
     main(cli(study, extra=["--steps", "16", "--scenes-per-pair", "3", "--num-agents", "4"]))
     (option, levels, kw, frame), = cli.called
     assert option == study.option
-    scenes = "scenes_per_pair" if study.option in ("cross_play", "jury", "influence") else "scenes_per_cell"
+    scenes = "scenes_per_pair" if study.option in ("cross_play", "jury", "influence", "similarity", "probe") else "scenes_per_cell"
     assert kw == dict(OWN_DEFAULTS[option], num_agents=4, steps=16, labels=PATHS, **{scenes: 3})
     if study.levels:
         assert levels == (module_of(study).load_levels(cli(study)[4]),)
