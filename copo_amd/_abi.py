@@ -119,3 +119,12 @@ class PetCfg(C.Structure):
 
 PET_WORDS, PET_MAX_WINDOW, PET_TYPES = 16, 4096, 3
 RECORDER_NCOL, RECORDER_MAX_SLOTS = 31, 256
+
+
+class AuditCfg(C.Structure):
+    """Mirror of `copo_audit_cfg`."""
+    _fields_ = [("E", C.c_int32), ("N", C.c_int32), ("K", C.c_int32), ("G", C.c_int32), ("heads", C.c_int32), ("bins", C.c_int32),
+                ("count_truncated", C.c_int32), ("reserved0", C.c_int32), ("gamma", C.c_double * 3), ("lo", C.c_double * 3), ("hi", C.c_double * 3)]
+
+
+AUDIT_WORDS, AUDIT_MAX_BINS, AUDIT_BIN_COUNT, AUDIT_BIN_VALUE, AUDIT_BIN_RETURN = 56, 16, 8, 24, 40

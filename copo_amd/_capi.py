@@ -114,6 +114,13 @@ _SIGS = {
     "copo_lowp_pack": (C.c_int, [C.POINTER(PpoCfg), C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]),
     "copo_lowp_forward_seats": (C.c_int, [C.POINTER(PpoCfg), C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64,
                                           C.c_int64] + [C.c_void_p] * 7),
+    "copo_value_obs_seats_f32": (C.c_int, [C.POINTER(PpoCfg), C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p,
+                                           C.c_int64, C.c_int64] + [C.c_void_p] * 4),
+    "copo_audit_create": (C.c_int, [C.POINTER(AuditCfg), C.POINTER(C.c_void_p)]),
+    "copo_audit_record": (C.c_int, [C.c_void_p] * 9),
+    "copo_audit_read": (C.c_int, [C.c_void_p] * 3),
+    "copo_audit_reset": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "copo_audit_destroy": (C.c_int, [C.c_void_p]),
     "copo_debug_lowp_round": (C.c_int, [C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]),
     "copo_debug_lowp_scale": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p]),
     "copo_influence_heading": (C.c_int, [C.c_void_p] * 4),

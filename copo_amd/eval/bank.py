@@ -37,11 +37,13 @@ class PolicyBank:
     model each member is loaded into once, as `load_policy_weights` loads it (either reference key layout), and copied out of; the
     model's own weights are put back afterwards.  Members whose shapes differ from the model's are refused.  A member is the model's
     whole flat buffer, so that the policy's own layout and `copo_transpose_weights_f32` serve it unchanged; the value nets in it
-    are never read."""
+    are never read, unless `values=True` (eval/critics.py): then every member's value nets are loaded into its slice too, from the
+    full state-dict keys `checkpoint_io.value_state_dict` finds, a member that lacks one of the model's value entries or has it in
+    another shape is refused by member and key, and `value_seats` runs them."""
 
-    def __init__(self, layout_from, weights):
+    def __init__(self, layout_from, weights, values=False):
         from .. import _capi
-        from .checkpoint_io import load_policy_state_dict, policy_state_dict
+        from .checkpoint_io import is_value_key, load_policy_state_dict, policy_state_dict, value_state_dict
         weights = list(weights)
         if not weights:
             raise ValueError("PolicyBank: no members")
@@ -52,6 +54,16 @@ class PolicyBank:
         model = layout_from.model
         own = model.state_dict()
         sds = [policy_state_dict(w) for w in weights]
+        self.has_values = bool(values)
+        if values:
+            wanted = [name for name in own if is_value_key(name)]
+            for k, w in enumerate(weights):
+                vsd = value_state_dict(w)
+                for name in wanted:
+                    if name not in vsd:
+                        raise ValueError("PolicyBank member %d: no value entry %s (a policy-only file? `load_members(paths, values=True)` keeps "
+                                         "a checkpoint's value nets)" % (k, name))
+                sds[k] = dict(sds[k], **{name: vsd[name] for name in wanted})
         for k, sd in enumerate(sds):             # every member is checked before the first is loaded
             for name, v in sd.items():
                 if name not in own or tuple(own[name].shape) != tuple(v.shape):
@@ -190,6 +202,25 @@ class PolicyBank:
         self._capi.check(self._capi.lib.copo_jury_obs_seats_f32(
             C.byref(self.cfg), self.theta.data_ptr(), self.theta_t.data_ptr(), self.stride, self.K, jb.rows.data_ptr(), jb.counts.data_ptr(),
             jb.cap, jb.n_out, obs.data_ptr(), verdict.data_ptr(), self._capi.current_stream()))
+
+    def value_seats(self, plan_buffers, obs, values, cc_obs=None):
+        """`copo_value_obs_seats_f32` (eval/critics.py) on the current stream: obs [n_out, O] -> values [n_out, n_value_heads], every
+        value net of the member that owns a row in `plan_buffers` (anything with rows [K][cap], counts [K], cap, n_out, K on the
+        device) on `cc_obs` [n_out, value input width] (None: the observation itself), the bits `FusedLearner.values(rows=...)` writes
+        for that member alone.  Rows in no list are left alone.  Needs a bank built with `values=True` and the mirror (`sync_mirror`)."""
+        pb, nv = plan_buffers, int(self.cfg.n_value_heads)
+        if not self.has_values:
+            raise ValueError("PolicyBank.value_seats: the bank was built without value nets (PolicyBank(..., values=True))")
+        if pb.K != self.K:
+            raise ValueError("PolicyBank.value_seats: lists for %d members and a bank of %d" % (pb.K, self.K))
+        src = obs if cc_obs is None else cc_obs
+        for name, t, shape in (("obs", obs, (pb.n_out, int(self.cfg.pol.in_dim))), ("values", values, (pb.n_out, nv)),
+                               ("cc_obs", src, (pb.n_out, int(self.cfg.val[0].in_dim)))):
+            if tuple(t.shape) != shape or not t.is_contiguous() or t.dtype != torch.float32:
+                raise ValueError("PolicyBank.value_seats: %s of shape %s, contiguous float32 %s wanted" % (name, tuple(t.shape), list(shape)))
+        self._capi.check(self._capi.lib.copo_value_obs_seats_f32(
+            C.byref(self.cfg), self.theta.data_ptr(), self.theta_t.data_ptr(), self.stride, self.K, pb.rows.data_ptr(), pb.counts.data_ptr(),
+            pb.cap, pb.n_out, obs.data_ptr(), None if cc_obs is None else cc_obs.data_ptr(), values.data_ptr(), self._capi.current_stream()))
 
     def hidden_seats(self, jury_buffers, obs, hidden):
         """`copo_hidden_obs_seats_f32` (eval/similarity.py) on the current stream: obs [n_out, O] -> hidden [K, cap, 2, H], both tanh

@@ -65,22 +65,43 @@ def export_policy_npz(model, path, layout="torch", policy_name="default", layer_
 
 def checkpoint_policy_weights(ckpt, policy_name="default"):
     """The policy's weights of a Tune checkpoint file, in whichever key layout it was written."""
+    return {k: v for k, v in checkpoint_weights(ckpt, policy_name).items() if "value" not in k}
+
+
+def checkpoint_weights(ckpt, policy_name="default"):
+    """Every entry of the policy's state in a Tune checkpoint file but the optimizer's: the policy net AND the value nets (the critic
+    audit, eval/critics.py, reads them; `checkpoint_policy_weights` drops them)."""
     assert os.path.isfile(ckpt), ckpt
     with open(ckpt, "rb") as f:
         blob = pickle.loads(f.read())
     weights = pickle.loads(blob.pop("worker"))["state"][policy_name]
-    return {k: v for k, v in weights.items() if k != "_optimizer_variables" and "value" not in k}
+    return {k: v for k, v in weights.items() if k != "_optimizer_variables"}
 
 
-def load_members(paths):
-    """One weights dict per path: an `.npz` population as it is, anything else as a Tune checkpoint file."""
+# state-dict prefixes of the value nets of this build's models: the ego critic (body, head), CoPO's neighbourhood and global critics
+VALUE_PREFIXES = ("_value_branch_separate.", "_value_branch.", "nei_value_network.", "global_value_network.")
+
+
+def is_value_key(name):
+    return name.startswith(VALUE_PREFIXES)
+
+
+def value_state_dict(weights):
+    """Torch state-dict entries of the value nets from a dict of full state-dict keys (a Tune-style checkpoint of this build, or an
+    `.npz` written from `model.state_dict()`): the keys under `VALUE_PREFIXES`, as float32 tensors.  Empty for a policy-only file."""
+    return {k: torch.as_tensor(np.ascontiguousarray(v), dtype=torch.float32) for k, v in weights.items() if is_value_key(k)}
+
+
+def load_members(paths, values=False):
+    """One weights dict per path: an `.npz` population as it is, anything else as a Tune checkpoint file.  `values`: keep a checkpoint
+    file's value-net entries too (an `.npz` is never filtered)."""
     ws = []
     for path in paths:
         if path.endswith(".npz"):
             with np.load(path) as f:
                 ws.append({k: f[k] for k in f.files})
         else:
-            ws.append(checkpoint_policy_weights(path))
+            ws.append(checkpoint_weights(path) if values else checkpoint_policy_weights(path))
     return ws
 
 

@@ -303,8 +303,9 @@ def _precision_args(a):
 # the module's `load_levels`) or None; the default --share, None where the study takes none; the name of its scenes keyword; its own
 # keyword arguments from its own options (a ValueError is a usage error); the label columns left out of the print; the name of a
 # function of the module whose table of (frame, members) is printed too.
-Study = collections.namedtuple("Study", "option module rows levels share scenes extra drop epilogue",
-                               defaults=(None, None, "scenes_per_cell", lambda a: {}, ("label",), None))
+# `members`: keyword arguments of `load_members` for the study's checkpoints (the critic audit keeps their value nets).
+Study = collections.namedtuple("Study", "option module rows levels share scenes extra drop epilogue members",
+                               defaults=(None, None, "scenes_per_cell", lambda a: {}, ("label",), None, {}))
 STUDIES = (
     Study("cross_play", "crossplay", "cross_play_rows", share=0.5, scenes="scenes_per_pair"),
     Study("fault_sweep", "faults", "fault_sweep_rows", "fault_levels", 1.0),
@@ -327,6 +328,27 @@ GOES_WITH = dict(jury_plan=("jury",), jury_deltas=("jury", "precision_sweep"), i
                  probe_ridge=("probe",))
 
 
+def _critic_args(a):
+    from .critics import DEFAULT_RANGE, CriticAudit
+    kw = dict(bins=8 if a.critic_bins is None else a.critic_bins, value_range=DEFAULT_RANGE if a.critic_range is None else tuple(a.critic_range),
+              pairs=bool(a.cross_play_pairs))
+    CriticAudit([1.0], kw["value_range"], kw["bins"])          # (a ValueError is a usage error)
+    if a.share is not None:          # (the study's entry names no share of its own: only the pairs layout has one)
+        if not kw["pairs"]:
+            raise ValueError("--share goes with --cross-play-pairs here: a checkpoint's own scenes have no share")
+        kw["share"] = a.share
+    return kw
+
+
+# The studies that read the VALUE nets, entries of the same kind run by the same `run_study`; a table of their own, next to their options,
+# so that STUDIES and GOES_WITH stay the list of the policy-net studies.
+CRITIC_STUDIES = (
+    Study("critic_audit", "critics", "critic_audit_rows", scenes="scenes_per_pair", extra=_critic_args, drop=("label", "head_name"),
+          epilogue="calibration_of", members=dict(values=True)),
+)
+CRITIC_GOES_WITH = dict(critic_bins=("critic_audit",), critic_range=("critic_audit",), cross_play_pairs=("critic_audit",))
+
+
 def run_study(ap, a, study):
     """One entry of `STUDIES` from the parsed options `a`: its table written to --table and printed."""
     import importlib
@@ -343,7 +365,7 @@ def run_study(ap, a, study):
         kw["share"] = study.share if a.share is None else a.share
     paths = getattr(a, study.option)
     levels = [module.load_levels(getattr(a, study.levels))] if study.levels else []
-    df = getattr(module, study.rows)("ippo" if a.algo == "cl" else a.algo, a.env, load_members(paths), *levels, num_agents=a.num_agents,
+    df = getattr(module, study.rows)("ippo" if a.algo == "cl" else a.algo, a.env, load_members(paths, **study.members), *levels, num_agents=a.num_agents,
                                      steps=a.steps, labels=list(paths), **{study.scenes: a.scenes_per_pair}, **kw)
     df.to_csv(a.table)
     print(df.drop(columns=list(study.drop)).to_string())
@@ -447,12 +469,23 @@ def main(argv=None):
                     help="with --probe: count only the rows that checkpoint INDEX drives (default: every acted row)")
     ap.add_argument("--probe-ridge", type=float, default=None, metavar="LAMBDA",
                     help="with --probe: the ridge as a share of the mean feature variance (default 1e-4)")
+    ap.add_argument("--critic-audit", nargs="+", default=None, metavar="CKPT",
+                    help="checkpoints of --algo's layout WITH their value nets (Tune-style checkpoint files of this build, or .npz files of full "
+                         "state-dict keys), every value head compared with the discounted return its agents went on to realise "
+                         "(eval/critics.py): one row per (scene group, checkpoint, head) into --table, the reliability diagram printed; takes "
+                         "--scenes-per-pair and --steps, and --share with --cross-play-pairs")
+    ap.add_argument("--critic-bins", type=int, default=None, metavar="B", help="with --critic-audit: value bins of the reliability diagram, 1..16 (default 8)")
+    ap.add_argument("--critic-range", type=float, nargs=2, default=None, metavar=("LO", "HI"),
+                    help="with --critic-audit: the value range the bins divide (default -20 20)")
+    ap.add_argument("--cross-play-pairs", action="store_true",
+                    help="with --critic-audit: the scenes of --cross-play (every ordered pair of checkpoints shares scenes) instead of scenes of "
+                         "its own per checkpoint: how a critic holds up beside every partner")
     a = ap.parse_args(argv)
     from .checkpoint_io import load_members
-    named = [s for s in STUDIES if getattr(a, s.option)]
+    named = [s for s in STUDIES + CRITIC_STUDIES if getattr(a, s.option)]
     if len(named) > 1:
         ap.error("%s: one table per run" % " and ".join(_flag(s.option) for s in named))
-    for option, studies in GOES_WITH.items():
+    for option, studies in dict(GOES_WITH, **CRITIC_GOES_WITH).items():
         if getattr(a, option) != ap.get_default(option) and not any(s.option in studies for s in named):
             ap.error("%s goes with %s" % (_flag(option), " or ".join(_flag(s) for s in studies)))
     if named:

@@ -1297,6 +1297,70 @@ int copo_debug_lowp_scale(const float* amax, int64_t n, float* out);
 int copo_mlp_forward_rows_f32(const copo_ppo_cfg* cfg, const float* theta, const float* theta_t, const float* obs_src,
                               const float* cc_src, const int64_t* rows, int64_t n_rows, int64_t n_src_rows,
                               int32_t first_net, int32_t n_nets, float* values, void* stream);
+
+/* ---- critic audit (eval/critics.py) ------------------------------------------------------------------------
+ * copo_value_obs_seats_f32: the VALUE nets of a seated bank in one launch.  rows / counts / cap / n_out are seat mode's
+ * (copo_mlp_forward_seats_f32); for every row r of member k's list and head h in [0, n_value_heads)
+ *     values[r][h] = val[h] net of member k on cc_src[r]      (cc_src NULL = obs_src; [n_out][val[h].in_dim], one width for all heads)
+ * into values [n_out][n_value_heads].  Grid ceil(cap / 16) x n_members x heads, always the 16-row tile; a workgroup past counts[k]
+ * leaves before any weight load, the last tile is masked, a row index outside [0, n_out) and rows in no list are not written.  No
+ * atomics, fixed summation order: two launches give the same bits, and member k's values hold the bits
+ * copo_mlp_forward_rows_f32(first_net = 1, n_nets = heads) writes for that member alone on its rows at the one-tile variant.  No
+ * allocation, no host synchronisation; may be captured in a graph.  NULL cfg / theta / theta_t / rows / counts / obs_src / values:
+ * COPO_ERR_NULL; bfloat16 operands, hidden outside {64, 128, 256, 512}, n_value_heads outside 1..3, cap < 1, n_out < 1, n_members
+ * outside 1..65535, a member_stride below n_params or no multiple of 4, a mirror that is not 16-byte aligned, heads of different
+ * input widths, tiles beyond the workgroup's LDS: COPO_ERR_DIM.  A refused call launches nothing. */
+int copo_value_obs_seats_f32(const copo_ppo_cfg* cfg, const float* theta, const float* theta_t, int64_t member_stride,
+                             int32_t n_members, const int64_t* rows, const int32_t* counts, int64_t cap, int64_t n_out,
+                             const float* obs_src, const float* cc_src, float* values, void* stream);
+/* copo_audit_*: V(s_t) against the discounted return that follows it, folded forward.  Per (scene, slot, head) a float64 state lives
+ * as long as the agent in the slot; head h has discount gamma[h] and the reward stream rew (0), nei_rew (1), glob_rew[e] (2).  One
+ * record per env step, after the step, with V the value of the observation the agent acted on.  A slot is audited where 0 <= seat < K
+ * and 0 <= group[e] < G.  For a row with COPO_F_ACTED, in this order, every operation individually rounded in float64:
+ *     q = gamma^2 q + 1;  c = gamma c + 1;  z = gamma z + V;  sV += V;  sVV += V^2;  n += 1
+ *     sG += r c;  sVG += r z;  sGG += r (r q + 2 gamma u);  u = gamma u + r q
+ *     per bin b: e_b = gamma e_b + [bin(V) == b];  nb_b += [..];  sVb_b += V [..];  sGb_b += r e_b
+ * so that with G_t = sum_{k >= t} gamma^(k - t) r_k up to the agent's last step (no bootstrap) sG = sum G_t, sVG = sum V_t G_t,
+ * sGG = sum G_t^2, sGb_b = sum_{t in b} G_t.  bin(V) = floor((V - lo) / (hi - lo) * bins) clamped into [0, bins - 1] (NaN: bin 0).
+ * With COPO_F_DONE on that row the agent's sums are clamped to +-2^32, quantised once to 2^-16 steps (round to nearest even) and
+ * added by 64-bit integer atomics to acc[group][member][head][COPO_AUDIT_WORDS]; `agents`, `steps` and the bin counts are plain counts.
+ * An agent that ends by COPO_F_MAXSTEP without ARRIVE / CRASH / OUT is truncated: it adds 1 to `truncated`, and its other words only
+ * when count_truncated is set.  Then -- and on COPO_F_SPAWNED or COPO_F_ENV_RESET -- the state is zeroed: a row with DONE | SPAWNED
+ * counts for the agent that acted and the new occupant starts from zero; agents still open are never counted.  The per-slot updates
+ * are independent and only the commits are atomic, on integers, so the result does not depend on scheduling.
+ * Range: |word| <= 2^48 per agent and sum (the clamp), so a cell holds 2^15 agents at the clamp; at the simulator's magnitudes (sums
+ * of squared returns near 1e7 per agent) some 1e7 agents.
+ * create: E, N, G >= 1, K in 1..65535, heads in 1..3, bins in 1..COPO_AUDIT_MAX_BINS (COPO_ERR_DIM, before the device is touched);
+ * gamma in [0, 1], lo < hi finite (COPO_ERR_CONFIG).  Allocates 8 (10 + 4 bins) E N heads + 448 G K heads bytes.
+ * record: flags [E][N] uint8, values [E N][heads], rew / nei_rew [E][N], glob_rew [E] fp32 (nei_rew with heads >= 2, glob_rew with
+ * heads = 3, else they may be NULL), seat [E][N] and group [E] int32, all on the device; one launch, may be captured in a graph.
+ * read: acc, device to device, int64 [G][K][heads][COPO_AUDIT_WORDS].  reset: state and accumulator to zero. */
+#define COPO_AUDIT_AGENTS 0
+#define COPO_AUDIT_STEPS 1
+#define COPO_AUDIT_TRUNCATED 2
+#define COPO_AUDIT_SUM_V 3
+#define COPO_AUDIT_SUM_VV 4
+#define COPO_AUDIT_SUM_G 5
+#define COPO_AUDIT_SUM_VG 6
+#define COPO_AUDIT_SUM_GG 7
+#define COPO_AUDIT_BIN_COUNT 8       /* [8, 24): rows of bin b */
+#define COPO_AUDIT_BIN_VALUE 24      /* [24, 40): sum of V over the rows of bin b, 2^-16 steps */
+#define COPO_AUDIT_BIN_RETURN 40     /* [40, 56): sum of G over the rows of bin b, 2^-16 steps */
+#define COPO_AUDIT_WORDS 56
+#define COPO_AUDIT_MAX_BINS 16
+typedef struct copo_audit_cfg {
+    int32_t E, N, K, G;        /* scenes, slots, bank members, scene groups */
+    int32_t heads, bins;
+    int32_t count_truncated, reserved0;
+    double gamma[3], lo[3], hi[3];
+} copo_audit_cfg;
+typedef struct copo_audit copo_audit;
+int copo_audit_create(const copo_audit_cfg* cfg, copo_audit** out);
+int copo_audit_record(copo_audit* h, const uint8_t* flags, const float* values, const float* rew, const float* nei_rew,
+                      const float* glob_rew, const int32_t* seat, const int32_t* group, void* stream);
+int copo_audit_read(copo_audit* h, int64_t* acc_out, void* stream);
+int copo_audit_reset(copo_audit* h, void* stream);
+int copo_audit_destroy(copo_audit* h);
 /* Adam on the flat buffers (the data-parallel path: after the gradient all-reduce); theta_t as above or NULL.
  * workspace: the workspace of the copo_ppo_fused_step_f32(apply_adam = 0, `step` given) call that produced `grad` --
  * that call published the step number and the next minibatch index there, so this one needs no trailing counter
